@@ -14,7 +14,12 @@ dense sweeps + OneGNN of step k+1 run beside the per-instance solver of step k, 
 CU per instance (32 of 256).  Every timed step still enqueues one full set of dense stages and
 one solve; the work inside the timed region is exactly K of each.
 
-Usage:  python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints one JSON line (with --dump-outputs DIR
+it first writes what the last timed step computed to DIR/*.npy).  --full adds, after the timed
+steps, what the headline does not need: the CPU baselines of the oracle pipeline (one core and
+one process per core), the parity spot-check against the oracle and the port-over-reference ratio.
+
+Usage:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -39,6 +44,28 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 N_CUS = 256
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each array (leading axis = instance) as DIR/<name>.npy, float64 (float32
+    arrays stay float32; integer results are exact in float64).  If the whole set exceeds 64 MiB, a
+    fixed, seeded subset of instances is written, the same in every run, and its indices go to
+    DIR/instances.npy."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items() if v is not None}
+    arrays = {k: (v if v.dtype == np.float32 else v.astype(np.float64)) for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    assert all(a.shape[0] == B for a in arrays.values())
+    per_instance = sum(a.nbytes // max(1, a.shape[0]) for a in arrays.values())
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    if per_instance * B > DUMP_MAX_BYTES:
+        k = max(1, DUMP_MAX_BYTES // per_instance)
+        idx = np.sort(np.random.RandomState(0).choice(B, size=k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        np.save(out_dir / "instances.npy", idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(out_dir / ("%s.npy" % name), np.ascontiguousarray(a))
 
 
 def serial_elems(stats_row, n):
@@ -200,11 +227,17 @@ def main():
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--threads-hint", type=int, default=0)
     ap.add_argument("--families", type=str, default="uniform,sparse,metric,clustered")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baselines, the parity spot-check and the "
+                         "port-over-reference ratio (off: a plain run reports the headline only)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0's x, y, ret, u, v and the assignment "
+                         "costs) to DIR/<name>.npy; inputs are seeded, so two builds can be compared file by file")
     ap.add_argument("--cpu-sample", type=int, default=32,
-                    help="instances of the same batch timed through the CPU oracle pipeline on rank 0 at N=1 "
-                         "(0 = skip); 32 x n=2048 is ~10 s of single-core work")
+                    help="with --full: instances of the same batch timed through the CPU oracle pipeline on rank 0 "
+                         "at N=1 (0 = skip); 32 x n=2048 is ~10 s of single-core work")
     ap.add_argument("--no-node-baseline", action="store_true",
-                    help="skip the one-process-per-core CPU leg (rank 0, N=1, K3 only)")
+                    help="with --full: skip the one-process-per-core CPU leg (rank 0, N=1, K3 only)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="run the stages of a step back to back on one stream (no two-stream pipelining)")
     ap.add_argument("--inflight", type=int, default=0,
@@ -223,6 +256,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.warmup is not None and args.warmup < 0:
+        raise SystemExit("--warmup must be >= 0")
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
         # no torchrun around us: become the launcher (before anything below can touch a GPU)
@@ -335,6 +372,11 @@ def run_rank(args):
 
     stats = out["stats"].cpu().numpy()
     ret = out["ret"].cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        cost = torch.gather(C, 2, out["x"].to(torch.int64).unsqueeze(2)).squeeze(2).sum(dim=1)
+        dump_outputs(args.dump_outputs, {
+            "x": out["x"].cpu().numpy(), "y": out["y"].cpu().numpy(), "ret": ret,
+            "u": out["u"].cpu().numpy(), "v": out["v"].cpu().numpy(), "cost": cost.cpu().numpy()})
     if rank == 0:
         total_instances = B * world * args.steps
         value = total_instances / elapsed
@@ -408,7 +450,7 @@ def run_rank(args):
                         "(profiles/*_pmc_traffic.txt, 2*FETCH_SIZE+WRITE_SIZE)",
             },
         }
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             k = min(args.cpu_sample, B)
             idx = [int(round(i * (B - 1) / max(1, k - 1))) for i in range(k)] if k > 1 else [0]
             idx = sorted(set(idx))
@@ -519,6 +561,8 @@ def run_rank_standin(args):
     warmup = args.warmup if args.warmup is not None else 1
     out, elapsed = run_sharded(standin_pipeline(C_host), steps, warmup, distributed=distributed,
                                gather_on_host=True)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": out["x"].numpy()})
     if rank == 0:
         gathered = out["x_all"] if distributed else out["x"]
         assert tuple(gathered.shape) == (B * world, n)

@@ -52,3 +52,28 @@ def test_failing_rank_fails_the_launcher():
     r = _run(["--gpus", "2", "--standin", "--steps", "1", "--warmup", "0"],
              env_extra={"LAPWARM_STANDIN_FAIL_RANK": "1"}, timeout=600)
     assert r.returncode != 0
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's arrays as float .npy files, identical from run to run
+    (seeded inputs); --steps sets the number of timed steps and the line carries ms_per_step."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = _run(["--standin", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _json_line(r.stdout)
+        assert line["steps"] == 3 and line["ms_per_step"] >= 0
+        x = np.load(d / "x.npy")
+        assert x.dtype == np.float64
+        dumps.append(x)
+    # the stand-in's row argmin of its seeded inputs (bench.py run_rank_standin)
+    C = np.stack([np.random.RandomState(42 + i).uniform(0, 1, (32, 32)) for i in range(4)])
+    assert np.array_equal(dumps[0], np.argmin(C, axis=2).astype(np.float64))
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_steps_must_be_positive():
+    r = _run(["--standin", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in (r.stderr + r.stdout)

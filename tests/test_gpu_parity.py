@@ -555,6 +555,44 @@ def test_pipeline_mixed_families_end_to_end(torch_cuda):
             assert np.array_equal(xo, x[b]) and np.array_equal(yo, y[b]), fams[b]
 
 
+def _bench_line(args, timeout=600):
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    proc = subprocess.run([sys.executable, str(ROOT / "bench.py")] + args, env=env, cwd=str(ROOT),
+                          capture_output=True, text=True, timeout=timeout)
+    assert proc.returncode == 0, (proc.stdout[-2000:], proc.stderr[-3000:])
+    lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{") and '"n_gpus"' in ln]
+    assert len(lines) == 1, proc.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_are_the_timed_results(tmp_path):
+    """A plain bench.py run (reduced K3 batch) reports the headline only; what --dump-outputs writes
+    is what its last timed step computed: assignments bit-exact against the oracle given the dumped
+    (u, v), costs of those assignments.  --full adds the CPU legs and the parity spot-check."""
+    from oracle import jv
+    from solvers.generators import mixed_batch
+    B, n = 4, 256
+    d = tmp_path / "dump"
+    line = _bench_line(["--batch", str(B), "--n", str(n), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(d)])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "cpu_baseline" not in line and "cpu_baseline_node" not in line and "parity_spot_check" not in line
+    got = {k: np.load(d / (k + ".npy")) for k in ("x", "y", "ret", "u", "v", "cost")}
+    assert got["u"].dtype == np.float32 and all(a.dtype == np.float64 for k, a in got.items() if k != "u")
+    Cs, _ = mixed_batch(B, n, families=("uniform", "sparse", "metric", "clustered"), seed=1234)
+    for b in range(B):
+        r, xo, yo, _ = jv.seeded_raw(Cs[b], got["u"][b].astype(np.float64), got["v"][b])
+        assert r == got["ret"][b]
+        if r == 0:
+            assert np.array_equal(xo, got["x"][b]) and np.array_equal(yo, got["y"][b])
+            assert np.isclose(got["cost"][b], Cs[b][np.arange(n), xo].sum(), rtol=1e-12, atol=0)
+    full = _bench_line(["--batch", str(B), "--n", str(n), "--steps", "1", "--warmup", "0", "--full",
+                        "--cpu-sample", "2", "--no-node-baseline"])
+    assert full["cpu_baseline"]["value"] > 0
+    assert full["parity_spot_check"] == {"instances": 2, "bit_exact": 2}
+
+
 def test_k3_config_full_size(torch_cuda):
     """BASELINE configs[2] (K3) at its stated size: batch=32, n=2048, 8 each uniform / sparse /
     metric / clustered, OneGNN H=192 L=4.  u/v within 1e-5 of the CPU forward on one instance per

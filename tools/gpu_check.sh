@@ -21,12 +21,12 @@ for s in "$@"; do
     pytest)  step pytest 900 python -m pytest tests -x -q -m gpu ;;
     parity2k) step parity2k 600 tests/native/_build/parity_driver 2048 1 ;;
     parity4k) step parity4k 900 tests/native/_build/parity_driver 4096 1 ;;
-    bench)   step bench 600 python bench.py --steps 10 --warmup 3 ;;
+    bench)   step bench 600 python bench.py --steps 10 --warmup 3 --full ;;
     bench_serial) step bench_serial 400 python bench.py --steps 5 --warmup 2 --no-overlap --cpu-sample 0 --no-node-baseline ;;
     bench_k2) step bench_k2 300 python bench.py --config K2 --steps 10 --warmup 3 --cpu-sample 0 ;;
     bench_k4) step bench_k4 400 python bench.py --config K4 --steps 3 --warmup 1 --cpu-sample 0 ;;
-    bench_k5) step bench_k5 600 python bench.py --config K5 --steps 2 --warmup 1 --cpu-sample 1 ;;
-    bench_8192) step bench_8192 300 python bench.py --config K5 --n 8192 --batch 4 --steps 2 --warmup 1 --cpu-sample 1 ;;
+    bench_k5) step bench_k5 600 python bench.py --config K5 --steps 2 --warmup 1 --full --cpu-sample 1 ;;
+    bench_8192) step bench_8192 300 python bench.py --config K5 --n 8192 --batch 4 --steps 2 --warmup 1 --full --cpu-sample 1 ;;
     prof_k5) export TMPDIR=/tmp; step prof_k5 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_k5 -o $TAG -- python3 bench.py --config K5 --steps 1 --warmup 1 --cpu-sample 0 ;;
     coop_stamps) LAPWARM_HIP_LIB=$PWD/gnn-accelerated-lap-warm-start-pipeline_amd/liblapwarm_hip_coopstamps.so DIAG_CHECK=0 step coop_stamps 300 python tools/diag_coop.py 8192 1 uniform 2 ;;
     bench_inflight) step bench_inflight 400 python bench.py --steps 5 --warmup 2 --cpu-sample 0 --no-node-baseline --inflight 8 ;;

@@ -20,7 +20,7 @@ for s in "$@"; do
     p256)  step it_p256 300 tests/native/_build/parity_driver 256 2 ;;
     p2k)   step it_p2k 400 tests/native/_build/parity_driver 2048 1 ;;
     diag)  TAILN=48 step it_diag 300 python tools/diag_k3.py 32 2048 0 ;;
-    bench) step it_bench 400 python bench.py --steps 5 --warmup 2 ;;
+    bench) step it_bench 400 python bench.py --steps 5 --warmup 2 --full ;;
     benchq) step it_benchq 300 python bench.py --steps 5 --warmup 2 --cpu-sample 0 ;;
     k2)    step it_k2 300 python bench.py --config K2 --steps 5 --warmup 2 --cpu-sample 0 ;;
     feat)  step it_feat 600 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "feature or golden or wrappers or k2_config or k3_config" ;;
