@@ -1457,17 +1457,20 @@ struct Solver {
                 v2 = kLarge;
                 j2 = -1;
             } else {
+                // A NaN in column 0 ends the serial scan at its first column below LARGE (lapjv.cpp:101-111:
+                // that column fails `c >= v1`, so v2 takes the NaN and no later `c < v2` holds): (c_js, js), (NaN, 0).
+                const bool nan0 = !(c0 == c0);
                 Top2 t2 = top2_empty();
 #pragma unroll
                 for (int r = 0; r < CH; ++r) {
                     const int j = b0 + r;
-                    if (j < n && (j == 0 || j >= js) && cs[r] == cs[r]) top2_push(t2, cs[r], j);
+                    if (j < n && (nan0 ? j == js : ((j == 0 || j >= js) && cs[r] == cs[r]))) top2_push(t2, cs[r], j);
                 }
                 t2 = bc.top2(t2);
                 v1 = t2.a1;
                 j1 = t2.i1;
-                v2 = t2.a2;
-                j2 = t2.i2;
+                v2 = nan0 ? c0 : t2.a2;
+                j2 = nan0 ? 0 : t2.i2;
             }
             // uniform reads of entries owned by other threads, then a barrier, then the
             // owners' writes: nobody may see this iteration's update while still reading.
@@ -1580,17 +1583,20 @@ struct Solver {
                     v2 = kLarge;
                     j2 = -1;
                 } else {
+                    // A NaN in column 0 ends the serial scan at its first column below LARGE (lapjv.cpp:101-111:
+                    // that column fails `c >= v1`, so v2 takes the NaN and no later `c < v2` holds): (c_js, js), (NaN, 0).
+                    const bool nan0 = !(c0 == c0);
                     Top2 t2 = top2_empty();
 #pragma unroll
                     for (int r = 0; r < CH; ++r) {
                         const int j = b0 + r;
-                        if (j < n && (j == 0 || j >= js) && cs[r] == cs[r]) top2_push(t2, cs[r], j);
+                        if (j < n && (nan0 ? j == js : ((j == 0 || j >= js) && cs[r] == cs[r]))) top2_push(t2, cs[r], j);
                     }
                     t2 = bc.top2(t2);
                     v1 = t2.a1;
                     j1 = t2.i1;
-                    v2 = t2.a2;
-                    j2 = t2.i2;
+                    v2 = nan0 ? c0 : t2.a2;
+                    j2 = nan0 ? 0 : t2.i2;
                 }
                 // uniform reads of entries owned by other threads, then a barrier, then the
                 // owners' writes: nobody may see this iteration's update while still reading.

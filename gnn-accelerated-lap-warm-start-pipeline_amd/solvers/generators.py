@@ -166,3 +166,52 @@ def mixed_instances(batch: int, n: int, indices, families=("uniform", "sparse", 
     without materialising the whole batch (32 MiB each at n = 2048)."""
     names, per = _mixed_plan(batch, families, seed)
     return [generate_family(names[i], n, per[i]) for i in indices], [names[i] for i in indices]
+
+
+# --------------------------------------------------------------------------- known-answer suite inputs
+INT64_MAX_FILL = float(np.iinfo(np.int64).max)  # 9.223372036854775807e18: masked entry of the sparse cases
+INT32_MAX_FILL = float(np.iinfo(np.int32).max)  # 2147483647: the same with a C int's maximum
+
+
+def known_answer_int_costs(n: int, cost_range: int = 100, hard: bool = False, density: float = 0.0,
+                           fill: float = INT64_MAX_FILL, seed: int = 1299821) -> np.ndarray:
+    """Integer test matrices of the `lap` package's known-answer suite, rebuilt from their description.
+
+    One legacy RandomState(seed) stream, drawn in this order:
+      1. costs randint(1, cost_range + 1) of shape (n, n);
+      2. `hard`: one offset randint(0, cost_range) per row, added to that row (rows in order), then one
+         per column, added to that column;
+      3. `density` > 0: a uniform mask rand(n, n); the entries below its percentile
+         100 * (density - 1/n), and the entries (r[k], c[k]) of two permutations r, c of range(n),
+         become `fill`.  The known-answer suite masks these (about `density` of the matrix, one perfect
+         matching among them) with a huge value; the optimum uses none of them.
+    The result is fp64.  tests/golden/lapjv_suite_cases.npz stores the sha256 of each matrix as the
+    package's own generator makes it, so the tests prove this rebuild is exact."""
+    rs = np.random.RandomState(seed)
+    C = rs.randint(1, cost_range + 1, size=(n, n)).astype(np.int64)
+    if hard:
+        for i in range(n):
+            C[i, :] += rs.randint(0, cost_range)
+        for j in range(n):
+            C[:, j] += rs.randint(0, cost_range)
+    C = C.astype(np.float64)
+    if density > 0:
+        u = rs.rand(n, n)
+        masked = u < np.percentile(u.ravel(), max(0.0, (density - 1.0 / n) * 100.0))
+        r = rs.permutation(n)
+        c = rs.permutation(n)
+        masked[r, c] = True
+        C[masked] = fill
+    return C
+
+
+def nan_costs(n: int, nan_frac: float, col0_frac: float, seed: int) -> np.ndarray:
+    """U[0,1) costs with a fraction `nan_frac` of the entries NaN, and then, where `col0_frac` > 0, the
+    column-0 entry of a further fraction `col0_frac` of the rows (the column the cold row reduction's
+    list build starts from).  One RandomState(seed) stream, drawn in that order."""
+    rs = np.random.RandomState(seed)
+    C = rs.uniform(0.0, 1.0, (n, n))
+    C[rs.uniform(size=(n, n)) < nan_frac] = np.nan
+    if col0_frac > 0:
+        C[rs.uniform(size=n) < col0_frac, 0] = np.nan
+    return C

@@ -13,6 +13,7 @@ Usage:  python tests/golden/make_golden.py          (from the repo root)
 """
 from __future__ import annotations
 
+import hashlib
 import importlib.util
 import sys
 from pathlib import Path
@@ -311,6 +312,123 @@ def make_onegnn():
     print("onegnn: done")
 
 
+# --------------------------------------------------------------------------- the reference's lapjv suite
+# LAP/lap/tests/test_lapjv.py: the matrices with inf entries (as data), the eps matrix (as data), the
+# integer matrices (too large to store: sha256 of each + our own generator, solvers/generators.py) and
+# NaN matrices of our own recipe (seeds only).  Outputs of the reference build for every case.
+INF = np.inf
+SUITE_INF = {  # label -> (matrix, known optimum, known x or None)
+    "sparse_square": ([[11., 20., INF, INF, INF], [12., INF, 12., INF, INF], [INF, 11., 10., 15., 9.],
+                       [15., INF, INF, 22., INF], [13., INF, INF, INF, 15.]], 71.0, [0, 2, 1, 3, 4]),
+    "infs_unsolvable_0": ([[0., 0., 0., INF, INF], [INF, INF, INF, 0., 0.], [INF, INF, INF, 0., 0.],
+                           [INF, INF, INF, 0., 0.], [0., 0., 0., INF, INF]], INF, None),
+    "infs_unsolvable_1": ([[19., 22., 16., INF, INF], [INF, INF, INF, 4., 13.], [INF, INF, INF, 3., 14.],
+                           [INF, INF, INF, 10., 12.], [11., 14., 13., INF, INF]], INF, None),
+    "inf_col": ([[0., INF, 0., 0., INF], [INF, INF, 0., 0., 0.], [INF, INF, INF, 0., INF],
+                 [INF, INF, INF, 0., 0.], [0., INF, 0., INF, INF]], INF, None),
+    "inf_row": ([[0., 0., 0., 0., INF], [INF, INF, 0., 0., 0.], [INF, INF, INF, INF, INF],
+                 [INF, INF, INF, 0., 0.], [0., 0., 0., INF, INF]], INF, None),
+    "all_inf": ([[INF] * 5] * 5, INF, None),
+    "inf_unique": ([[1000., 4., 1., INF], [1., 1000., 3., INF], [5., 1., 1000., INF], [INF, INF, INF, 0.]],
+                   3.0, [2, 0, 1, 3]),
+}
+# label -> (n, hard, density, fill, known optimum or nan).  "_i32" repeats a sparse case with the fill
+# test_lapjv.py itself writes (get_platform_maxint(): a C int's maximum); the plain sparse labels use
+# the int64 maximum (9.2e18).  "s4608" is the s4k recipe at a size that runs the cooperative kernel.
+I64, I32 = float(np.iinfo(np.int64).max), float(np.iinfo(np.int32).max)
+SUITE_INT = {
+    "d100": (100, False, 0.0, I64, 198.0), "d100h": (100, True, 0.0, I64, 11399.0),
+    "s100": (100, True, 0.04, I64, 11406.0), "s100_i32": (100, True, 0.04, I32, 11406.0),
+    "d1k": (1000, False, 0.0, I64, 1000.0), "d1kh": (1000, True, 0.0, I64, 101078.0),
+    "s1k": (1000, True, 0.01, I64, 101078.0), "s1k_i32": (1000, True, 0.01, I32, 101078.0),
+    "s4k": (4000, True, 0.004, I64, 402541.0), "s4k_i32": (4000, True, 0.004, I32, 402541.0),
+    "s4608": (4608, True, 0.004, I64, np.nan),
+}
+EPS_OPT = 224.8899507294651
+
+
+def suite_nan_specs():
+    """label -> (n, nan_frac, col0_frac, seed) for solvers.generators.nan_costs."""
+    out, seed = {}, 31000
+    for n in (64, 300, 700):
+        for frac in (0.001, 0.05):
+            for col0 in (0.0, 0.2):
+                seed += 1
+                out[f"nan{n}_{frac:g}" + ("_col0" if col0 else "")] = (n, frac, col0, seed)
+    return out
+
+
+def _ref_int_matrix(tu, n, hard, density, fill):
+    if density == 0.0:
+        return tu.get_dense_int(n, 100, hard=hard, seed=1299821).astype(np.float64)
+    cost, mask = tu.get_sparse_int(n, 100, density, hard=hard, seed=1299821)
+    mask = np.logical_not(mask)          # as get_sparse_*_int return it
+    cost = cost.astype(np.float64)
+    cost[~mask] = fill                   # as test_sparse_*_int do
+    return cost
+
+
+def make_reference_suite():
+    from gzip import GzipFile
+    tu = load_by_path("_ref_test_utils", REF / "LAP" / "lap" / "tests" / "test_utils.py")
+    out = {}
+    mats = {}
+    for k, (C, opt, x) in SUITE_INF.items():
+        mats[k] = np.array(C, dtype=np.float64)
+    eps_C = np.genfromtxt(GzipFile(str(REF / "LAP" / "lap" / "tests" / "cost_eps.csv.gz")), delimiter=",")
+    mats["eps"] = eps_C
+    for k, (n, hard, dens, fill, opt) in SUITE_INT.items():
+        C = _ref_int_matrix(tu, n, hard, dens, fill)
+        assert np.array_equal(C, gen.known_answer_int_costs(n, hard=hard, density=dens, fill=fill)), k
+        out[f"sha256__{k}"] = np.array(hashlib.sha256(np.ascontiguousarray(C).tobytes()).hexdigest())
+        mats[k] = C
+    nan_specs = suite_nan_specs()
+    for k, (n, frac, col0, seed) in nan_specs.items():
+        mats[k] = gen.nan_costs(n, frac, col0, seed)
+    for k, C in mats.items():
+        n = C.shape[0]
+        ret, x, y = ref_lib.dense_raw(C)
+        out[f"cold_ret__{k}"], out[f"cold_x__{k}"], out[f"cold_y__{k}"] = np.array(ret), x, y
+        seeds = {"zero": (np.zeros(n), np.zeros(n))}
+        u = C.min(1)
+        v = (C - u[:, None]).min(0)
+        if np.isfinite(u).all() and np.isfinite(v).all():
+            seeds["rowmin"] = (u, v)
+        for s, (u, v) in seeds.items():
+            ret, x, y = ref_lib.seeded_raw(C, u, v)
+            out[f"{s}_ret__{k}"] = np.array(ret)
+            out[f"{s}_x__{k}"], out[f"{s}_y__{k}"] = x.astype(np.int32), y.astype(np.int32)
+        print(f"suite {k}: n={n} cold ret {int(out[f'cold_ret__{k}'])}, seeded {sorted(seeds)}")
+    # the small inf matrices in the PackedCases layout (tests/conftest.py), cold outputs
+    inf_keys = list(SUITE_INF)
+    out["labels"] = np.array(inf_keys)
+    out["n"] = np.array([mats[k].shape[0] for k in inf_keys], dtype=np.int64)
+    out["off_vec"] = np.cumsum([0] + [mats[k].shape[0] for k in inf_keys]).astype(np.int64)
+    out["off_mat"] = np.cumsum([0] + [mats[k].size for k in inf_keys]).astype(np.int64)
+    out["C"] = np.concatenate([mats[k].ravel() for k in inf_keys])
+    out["ret"] = np.array([int(out[f"cold_ret__{k}"]) for k in inf_keys], dtype=np.int64)
+    out["x"] = np.concatenate([out[f"cold_x__{k}"] for k in inf_keys])
+    out["y"] = np.concatenate([out[f"cold_y__{k}"] for k in inf_keys])
+    # known optima of test_lapjv.py (nan: none known) and the known x where the suite asserts one
+    for k, (_, opt, x) in SUITE_INF.items():
+        out[f"opt__{k}"] = np.array(opt)
+        if x is not None:
+            out[f"known_x__{k}"] = np.array(x, dtype=np.int32)
+    for k, spec in SUITE_INT.items():
+        out[f"opt__{k}"] = np.array(spec[4])
+    out["opt__eps"] = np.array(EPS_OPT)
+    out["int_labels"] = np.array(list(SUITE_INT))
+    out["int_n"] = np.array([s[0] for s in SUITE_INT.values()], dtype=np.int64)
+    out["int_hard"] = np.array([s[1] for s in SUITE_INT.values()])
+    out["int_density"] = np.array([s[2] for s in SUITE_INT.values()])
+    out["int_fill"] = np.array([s[3] for s in SUITE_INT.values()])
+    out["nan_labels"] = np.array(list(nan_specs))
+    out["nan_spec"] = np.array([s for s in nan_specs.values()], dtype=np.float64)  # n, frac, col0, seed
+    np.savez_compressed(OUT / "lapjv_suite_cases.npz", **out)
+    # the eps matrix alone fills ~1 MB: a file of its own keeps each one under the committed-file limit
+    np.savez_compressed(OUT / "lapjv_suite_eps.npz", C=eps_C)
+
+
 if __name__ == "__main__":
     assert REF.exists(), "needs /root/reference"
     assert ref_lib.available(), "oracle/_ref/liblap_ref.so could not be built"
@@ -318,5 +436,6 @@ if __name__ == "__main__":
     make_cold()
     make_features()
     make_onegnn()
+    make_reference_suite()
     for f in sorted(OUT.glob("*.npz")):
         print(f.name, f.stat().st_size // 1024, "KiB")

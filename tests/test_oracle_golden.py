@@ -113,3 +113,68 @@ def test_onegnn_forward_matches_reference(onegnn_cases, tag):
         ub = one_gnn_ref.forward(sd, feat, torch.from_numpy(Cb).float(),
                                  torch.from_numpy(z[f"mask__{tag}__batch"])).numpy()
         np.testing.assert_allclose(ub, z[f"u__{tag}__batch"], rtol=0, atol=1e-5)
+
+
+# --------------------------------------------------------------------------- the reference's lapjv suite
+@pytest.fixture(scope="module")
+def lapjv_suite():
+    from lapjv_suite import Suite
+    return Suite()
+
+
+def test_reference_suite_integer_matrices_are_the_references(lapjv_suite):
+    """solvers.generators.known_answer_int_costs rebuilds every integer matrix of test_lapjv.py (and the
+    same recipe at n = 4608) bit for bit: sha256 of the fp64 matrix the reference's generator made."""
+    from lapjv_suite import sha256
+    assert len(lapjv_suite.int_labels) == 11
+    for label in lapjv_suite.int_labels:
+        C = lapjv_suite.matrix(label)
+        assert sha256(C) == str(lapjv_suite.z[f"sha256__{label}"]), label
+    spec = lapjv_suite.int_spec("s1k")
+    assert spec["fill"] == float(np.iinfo(np.int64).max)
+    assert (lapjv_suite.matrix("s1k") == spec["fill"]).sum() >= 1000  # a masked perfect matching at least
+
+
+def test_reference_suite_regimes(lapjv_suite):
+    """The suite reaches what the older fixtures do not: inf rows / columns, NaN (also in column 0),
+    costs far above LARGE (1e6), n up to 4608."""
+    s = lapjv_suite
+    assert np.isinf(s.matrix("all_inf")).all() and np.isinf(s.matrix("inf_row")[2]).all()
+    assert np.isinf(s.matrix("inf_col")[:, 1]).all()
+    assert s.matrix("s4k").max() > 9e18 and s.matrix("s4k_i32").max() == 2147483647.0
+    assert s.matrix("s4608").shape == (4608, 4608) and s.matrix("eps").shape == (368, 368)
+    col0 = [k for k in s.nan_labels if k.endswith("_col0")]
+    assert len(col0) == 6 and len(s.nan_labels) == 12
+    for k in s.nan_labels:
+        C = s.matrix(k)
+        assert np.isnan(C).any()
+        if k in col0:
+            assert np.isnan(C[:, 0]).sum() > np.isnan(C[:, 1:]).sum(0).max(), k
+
+
+def test_oracle_reproduces_reference_suite(lapjv_suite):
+    """The oracle (cold and seeded) reproduces every output of the reference build on the suite, and
+    the optima test_lapjv.py asserts: this pins the oracle on inf, NaN and 9.2e18 costs before the GPU
+    tests judge the kernels against it."""
+    from lapjv_suite import assert_known_optimum
+    s = lapjv_suite
+    n_seeded = 0
+    for label in s.labels:
+        C = s.matrix(label)
+        ret, x, y, _ = jv.dense_raw(C)
+        rr, rx, ry = s.cold(label)
+        assert ret == rr == 0, label
+        assert np.array_equal(x, rx) and np.array_equal(y, ry), label
+        assert_known_optimum(s, label, C[np.arange(C.shape[0]), x].sum())
+        if s.known_x(label) is not None:
+            assert np.array_equal(x, s.known_x(label)), label
+        for kind in s.seed_kinds(label):
+            u, v = s.seeds(label, kind)
+            ret, x, y, _ = jv.seeded_raw(C, u, v)
+            rr, rx, ry = s.seeded(label, kind)
+            assert ret == rr, (label, kind)
+            if ret == 0:
+                assert np.array_equal(x, rx) and np.array_equal(y, ry), (label, kind)
+                assert_known_optimum(s, label, C[np.arange(C.shape[0]), x].sum())
+            n_seeded += 1
+    assert n_seeded >= len(s.labels) + 15
