@@ -436,6 +436,77 @@ int lapwarm_reduce_costs_batched(const double *C, int batch, int n, const double
     return 0;
 }
 
+size_t lapwarm_oracle_duals_workspace_bytes(int batch, int n)
+{
+    if (batch <= 0 || n <= 0) return 0;
+    const size_t bn = (size_t)batch * n;
+    const size_t chunks = (size_t)oracle_chunks(n, batch);
+    return 3 * align_up(sizeof(int) * bn) + 3 * align_up(sizeof(double) * bn) + align_up(sizeof(int) * 2 * bn) +
+           align_up(sizeof(double) * 2 * bn) + align_up(sizeof(double) * bn * chunks) +
+           align_up(sizeof(int) * bn * chunks) + align_up(sizeof(int) * (size_t)batch * kOdInstInts) +
+           align_up(sizeof(double) * bn) + align_up(sizeof(double) * batch) + align_up(sizeof(int));
+}
+
+// Sweeps are launched in chunks (4, 8, 16, then 32 at a time) with one host synchronisation per
+// chunk to learn whether any instance still needs sweeps: not graph-capturable.
+static int oracle_duals_impl(const double *C, int batch, int n, const int *rows, const int *cols, double *u,
+                             double *v, int *ret, int *sweeps, void *workspace, size_t workspace_bytes,
+                             double tol, hipStream_t stream)
+{
+    if (int rc = check_dims(batch, n)) return rc;
+    if (workspace_bytes < lapwarm_oracle_duals_workspace_bytes(batch, n)) return -1;
+    const size_t bn = (size_t)batch * n;
+    OracleParams p;
+    p.C = C;
+    p.n = n;
+    p.batch = batch;
+    p.chunks = oracle_chunks(n, batch);
+    p.pair = (n % 2) == 0 && (reinterpret_cast<uintptr_t>(C) % 16) == 0;
+    p.rows = rows;
+    p.cols = cols;
+    Carver c{reinterpret_cast<unsigned char *>(workspace), 0};
+    p.x = c.take<int>(bn);
+    p.y = c.take<int>(bn);
+    p.pred = c.take<int>(bn);
+    p.cxx = c.take<double>(bn);
+    p.v0 = c.take<double>(bn);
+    p.v1 = c.take<double>(bn);
+    p.lrow = c.take<int>(2 * bn);
+    p.lsrc = c.take<double>(2 * bn);
+    p.pval = c.take<double>(bn * p.chunks);
+    p.parg = c.take<int>(bn * p.chunks);
+    p.inst = c.take<int>((size_t)batch * kOdInstInts);
+    double *rowpart = c.take<double>(bn);
+    double *gmin = c.take<double>((size_t)batch);
+    int *running = c.take<int>(1);
+    HIP_TRY(launch_oracle_init(p, stream));
+    const int max_s = n - 1;  // settled within n - 1 sweeps <=> at most n - 2 updating sweeps
+    int s = 0, chunk = 4;
+    for (;;) {
+        const int k = (chunk < max_s - s) ? chunk : max_s - s;
+        for (int t = 0; t < k; ++t, ++s) HIP_TRY(launch_oracle_sweep(p, s, stream));
+        const int last = s >= max_s;
+        HIP_TRY(hipMemsetAsync(running, 0, sizeof(int), stream));
+        HIP_TRY(launch_oracle_check(p, s, last, running, stream));
+        if (last) break;
+        int host_running = 0;
+        HIP_TRY(hipMemcpyAsync(&host_running, running, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (host_running == 0) break;
+        if (chunk < 32) chunk *= 2;
+    }
+    HIP_TRY(launch_oracle_finish(p, tol, u, v, rowpart, gmin, ret, sweeps, stream));
+    return 0;
+}
+
+int lapwarm_oracle_duals_batched(const double *C, int batch, int n, const int *rows, const int *cols, double *u,
+                                 double *v, int *ret, int *sweeps, void *workspace, size_t workspace_bytes,
+                                 void *stream_)
+{
+    return oracle_duals_impl(C, batch, n, rows, cols, u, v, ret, sweeps, workspace, workspace_bytes, 1e-12,
+                             reinterpret_cast<hipStream_t>(stream_));
+}
+
 // ------------------------------------------------------------------------------------------
 // Host-pointer drop-ins
 // ------------------------------------------------------------------------------------------
@@ -673,6 +744,38 @@ int lapwarm_reduce_costs(const double *C, int n, const double *u, const double *
     if (out) HIP_TRY(hipMemcpy(out, dO, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
     if (min_out) HIP_TRY(hipMemcpy(min_out, dg, sizeof(double), hipMemcpyDeviceToHost));
     return 0;
+}
+
+int lapwarm_oracle_duals(const double *C, int n, const int *rows, const int *cols, double *u, double *v,
+                         double tol)
+{
+    if (n <= 0) return -2;
+    if (n > 16384) return -5;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    const size_t ws_bytes = lapwarm_oracle_duals_workspace_bytes(1, n);
+    const size_t total = align_up(sizeof(double) * (size_t)n * n) + 2 * align_up(sizeof(int) * n) +
+                         2 * align_up(sizeof(double) * n) + align_up(sizeof(int)) + ws_bytes;
+    if (g_arena.reserve(total) != hipSuccess) return -1;
+    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
+    double *dC = c.take<double>((size_t)n * n);
+    int *dr = c.take<int>(n);
+    int *dc = c.take<int>(n);
+    double *du = c.take<double>(n);
+    double *dv = c.take<double>(n);
+    int *dret = c.take<int>(1);
+    void *ws = reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off;
+    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dr, rows, sizeof(int) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dc, cols, sizeof(int) * n, hipMemcpyHostToDevice));
+    int rc = oracle_duals_impl(dC, 1, n, dr, dc, du, dv, dret, nullptr, ws, ws_bytes, tol, nullptr);
+    if (rc) return rc;
+    int r = 0;
+    HIP_TRY(hipMemcpy(&r, dret, sizeof(int), hipMemcpyDeviceToHost));
+    if (r == 0) {
+        HIP_TRY(hipMemcpy(u, du, sizeof(double) * n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(v, dv, sizeof(double) * n, hipMemcpyDeviceToHost));
+    }
+    return r;
 }
 
 }  // extern "C"

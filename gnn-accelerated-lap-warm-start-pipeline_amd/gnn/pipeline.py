@@ -152,6 +152,32 @@ class WarmStartPipeline:
             raise RuntimeError(f"lapwarm_lapjv_duals_batched failed (code {rc}): {_hip.last_error()}")
         return x, u, v, ret
 
+    def oracle_duals_batch(self, C: torch.Tensor, x: Optional[torch.Tensor] = None):
+        """The reference's oracle duals (solvers/dual_computation.py:13-74) of a resident batch.
+        x (B,n) int32 is the matching, row i -> column x[b][i]; None: the cold lapjv_batch matching.
+        Returns x, u, v (B,n) fp64, ret (B,) int32 (0 ok, 1 negative cycle, 2 infeasible, 3 slackness,
+        4 not a permutation, 5 non-finite C) and sweeps (B,4) int32: Jacobi sweeps, hop depth, rows
+        read, replayed.  Synchronises the stream once per chunk of sweeps (not graph-capturable)."""
+        C = C.contiguous()
+        B, n, _ = C.shape
+        if x is None:
+            x, _, _, _ = self.lapjv_batch(C, want_stats=False)
+        x = x.to(device=C.device, dtype=torch.int32).contiguous()
+        rows = torch.arange(n, dtype=torch.int32, device=C.device).expand(B, n).contiguous()
+        u = torch.empty((B, n), dtype=torch.float64, device=C.device)
+        v = torch.empty((B, n), dtype=torch.float64, device=C.device)
+        ret = torch.empty((B,), dtype=torch.int32, device=C.device)
+        sweeps = torch.empty((B, 4), dtype=torch.int32, device=C.device)
+        nbytes = int(self.lib.lapwarm_oracle_duals_workspace_bytes(B, n))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=C.device)
+        stream = torch.cuda.current_stream(C.device).cuda_stream
+        rc = self.lib.lapwarm_oracle_duals_batched(C.data_ptr(), B, n, rows.data_ptr(), x.data_ptr(), u.data_ptr(),
+                                                   v.data_ptr(), ret.data_ptr(), sweeps.data_ptr(), ws.data_ptr(),
+                                                   nbytes, ct.c_void_p(stream))
+        if _hip.check(rc, "oracle_duals_batch") != 0:
+            raise RuntimeError(f"lapwarm_oracle_duals_batched failed (code {rc}): {_hip.last_error()}")
+        return x, u, v, ret, sweeps
+
     @torch.inference_mode()
     def solve_batch(self, C: torch.Tensor, eps: float = 1e-12, want_stats: bool = True) -> dict:
         """The whole hot path for a resident batch."""

@@ -31,6 +31,7 @@ SIGNATURES = {
     "lapwarm_project_feasible": (ct.c_int, [c_dp, ct.c_int, c_dp, c_dp, ct.c_int, ct.c_double]),
     "lapwarm_reduce_costs": (ct.c_int, [c_dp, ct.c_int, c_dp, c_dp, ct.c_int, c_dp, c_dp]),
     "lapwarm_warmstart_lapjv": (ct.c_int, [c_dp, ct.c_int, c_dp, c_dp, ct.c_int, c_ip, c_ip]),
+    "lapwarm_oracle_duals": (ct.c_int, [c_dp, ct.c_int, c_ip, c_ip, c_dp, c_dp, ct.c_double]),
     "lapwarm_seeded_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
     "lapwarm_lapjv_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
     "lapwarm_seeded_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, ct.c_double, c_vp, c_vp,
@@ -46,6 +47,9 @@ SIGNATURES = {
     "lapwarm_project_round_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
                                                  ct.c_size_t, c_vp]),
     "lapwarm_reduce_costs_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, ct.c_int, c_vp, c_vp,
+                                                c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_oracle_duals_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_oracle_duals_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                 c_vp, ct.c_size_t, c_vp]),
     "lapwarm_refine_aggregate_batched": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int, ct.c_int,
                                                     ct.c_int, c_vp]),

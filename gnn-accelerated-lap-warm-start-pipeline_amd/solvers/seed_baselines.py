@@ -5,9 +5,10 @@
 project_feasible) and is bit-identical to it.  `seed_noisy_optimal` keeps the reference's recipe
 (optimal duals + Gaussian noise + projection) but takes the optimal duals from the cold JV solve
 on the device instead of SciPy + Bellman-Ford (solvers/advanced_dual.py:85-113): any optimal dual
-pair is a valid starting point, so the seeds are equivalent in quality, not bit-identical.
-`seed_greedy_matching` depends on the O(n^3) difference-constraint solver
-(solvers/dual_computation.py:13-74) and is not part of the hot path.
+pair is a valid starting point, so the seeds are equivalent in quality, not bit-identical.  The
+reference's own oracle duals are `solvers.make_feasible_duals` / `compute_oracle_duals`
+(csrc/oracle_duals.hip).  `seed_greedy_matching` is not provided: a greedy matching is almost never
+optimal, and the reference's difference-constraint step raises on it.
 """
 from __future__ import annotations
 

@@ -59,6 +59,14 @@ int lapwarm_project_feasible(const double *C, int n, double *u, double *v, int m
 int lapwarm_reduce_costs(const double *C, int n, const double *u, const double *v, int shift_nonneg,
                          double *out, double *min_out);
 
+/* solvers/dual_computation.py:13-74 `dual_from_matching_diff_constraints` for a full matching
+ * (rows[k], cols[k]), k = 0..n-1, int32, in the caller's order; `tol` as the reference's.
+ * Returns 0 with u, v (n each) written, or the per-instance codes of
+ * lapwarm_oracle_duals_batched (1..5; u, v untouched), or -2 n <= 0, -5 n > 16384, -1 allocation
+ * failure, <= -1000 HIP runtime error.  The reduced-cost matrix is lapwarm_reduce_costs(.., 0, ..). */
+int lapwarm_oracle_duals(const double *C, int n, const int *rows, const int *cols, double *u, double *v,
+                         double tol);
+
 /* WarmStartLAPSolver.solve (solvers/warmstart_solver.py:31-63): C' = C - u 1^T - 1 v^T
  * (minus min(C') when negative and shift_nonneg), then the cold JV on C'.  One host-to-device
  * copy of C; the reduced matrix is formed and solved on the device; x, y [n] int32 come back. */
@@ -133,6 +141,23 @@ int lapwarm_project_round_batched(const double *C, int batch, int n, double *u, 
 int lapwarm_reduce_costs_batched(const double *C, int batch, int n, const double *u, const double *v,
                                  int shift_nonneg, double *out, double *gmin, void *workspace,
                                  size_t workspace_bytes, void *stream);
+
+/* Oracle duals (solvers/dual_computation.py:13-74 with tol = 1e-12), batched.  C [batch][n][n];
+ * rows, cols [batch][n] int32 pairs in the caller's order; u, v [batch][n] fp64 (NaN where ret != 0);
+ * ret [batch]: 0 ok, 1 negative cycle (the reference's RuntimeError), 2 dual infeasible after
+ * reconstruction, 3 complementary slackness violated on a matched edge (its two AssertionErrors),
+ * 4 the pairs are not a permutation, 5 C is not finite.  sweeps [batch][4] int32 or NULL:
+ * Jacobi sweeps run (the last changed nothing), hop depth of the shortest-path tree, rows read by
+ * the sweeps, 1 when the instance was replayed exactly.
+ * Jacobi sweeps restricted to the rows whose source changed, double-buffered; instances that do not
+ * settle within n - 1 sweeps, or whose predecessor graph has a cycle, replay the reference's
+ * Gauss-Seidel loop exactly when n <= 2048; above 2048 such instances get ret 1 without a replay.
+ * Sweeps are launched in chunks with one host synchronisation per chunk: NOT graph-capturable.
+ * Workspace: lapwarm_oracle_duals_workspace_bytes(). */
+size_t lapwarm_oracle_duals_workspace_bytes(int batch, int n);
+int lapwarm_oracle_duals_batched(const double *C, int batch, int n, const int *rows, const int *cols, double *u,
+                                 double *v, int *ret, int *sweeps, void *workspace, size_t workspace_bytes,
+                                 void *stream);
 
 /* OneGNN top-k refinement, aggregation part (gnn/one_gnn.py:139-155), float32:
  *   val_k = topk16[row][k] - u_pre[row]   (== topk(cost - u_pre): x -> x - c is monotone)
