@@ -1332,7 +1332,24 @@ hipError_t launch_cfg(const CoopParams &p, int grid, hipStream_t stream)
     return hipGetLastError();
 }
 
-}  // namespace
+// The 12 instantiations of coop_ssp_kernel: 1 or 2 granule loads per lane for every CH, then 3 (17 .. 32
+// members) for n = 8192 with 4 and n = 16384 with 8 positions per lane.
+struct CoopKernel {
+    int ch, nl;
+    hipError_t (*launch)(const CoopParams &, int, hipStream_t);
+};
+const CoopKernel kCoopKernels[] = {
+    {1, 1, launch_cfg<1, 1>},   {1, 2, launch_cfg<1, 2>},   {2, 1, launch_cfg<2, 1>}, {2, 2, launch_cfg<2, 2>},
+    {4, 1, launch_cfg<4, 1>},   {4, 2, launch_cfg<4, 2>},   {8, 1, launch_cfg<8, 1>}, {8, 2, launch_cfg<8, 2>},
+    {16, 1, launch_cfg<16, 1>}, {16, 2, launch_cfg<16, 2>}, {4, 3, launch_cfg<4, 3>}, {8, 3, launch_cfg<8, 3>},
+};
+
+const CoopKernel *coop_kernel(int ch, int nl)
+{
+    for (const CoopKernel &k : kCoopKernels)
+        if (k.ch == ch && k.nl == nl) return &k;
+    return nullptr;
+}
 
 // Positions per lane for a problem size: enough members to spread the row over many CUs, few
 // enough that one exchange stays within four granule loads per lane (G <= 32).
@@ -1358,15 +1375,9 @@ int coop_ch(int n)
     return 8;
 }
 
-int coop_members(int n)
-{
-    const int ch = coop_ch(n);
-    return (n + 64 * ch - 1) / (64 * ch);
-}
+}  // namespace
 
-size_t coop_mail_granules(int n) { return 2 * ((size_t)coop_members(n) * (kK + kKr) + kWinGran); }
-
-bool coop_enabled(int n)
+CoopConfig coop_config(int n)
 {
     static const int min_n = [] {
         const char *e = getenv("LAPWARM_COOP_MIN_N");
@@ -1378,46 +1389,47 @@ bool coop_enabled(int n)
         const char *e = getenv("LAPWARM_COOP");
         return (e && e[0] == '0') ? 0 : 1;
     }();
-    const int ch = coop_ch(n);
-    return on && n >= min_n && n <= 16384 && (ch == 1 || ch == 2 || ch == 4 || ch == 8 || ch == 16) &&
-           coop_members(n) <= 32;
-}
-
-hipError_t launch_coop(const CoopParams &p_in, hipStream_t stream)
-{
-    CoopParams p = p_in;
-    const int ch = coop_ch(p.n);
-    p.G = coop_members(p.n);
-    const int ng = p.G * kK + kWinGran;  // the largest poll: a collection's round B
     static const int xcd_stores = [] {
         const char *e = getenv("LAPWARM_COOP_XCD_STORES");
         return (e && e[0] == '0') ? 0 : 1;
     }();
-    p.xcd_stores = xcd_stores;
-    const int nl = (ng + 63) / 64;
+    static const int pairs = [] {
+        const char *e = getenv("LAPWARM_COOP_RELAUNCHES");
+        const int k = e ? atoi(e) : 96;
+        return (k >= 0 && k <= 4096) ? k : 96;
+    }();
+    CoopConfig c = {};
+    if (!on || n < min_n || n > 16384) return c;
+    const int ch = coop_ch(n);
+    const int members = (n + 64 * ch - 1) / (64 * ch);
+    const int nl = (members * kK + kWinGran + 63) / 64;  // granule loads per lane of a collection's round B
+    // (a forced geometry without an instantiation takes the one-workgroup path)
+    if (members > 32 || !coop_kernel(ch, nl)) return c;
+    c.ch = ch;
+    c.nl = nl;
+    c.members = members;
+    c.mail_granules = 2 * ((size_t)members * (kK + kKr) + kWinGran);
     // every member of an instance must be resident while the instance runs: at most 1024 single-wave
     // workgroups per launch (a quarter of what the chip holds), instances in groups of 8
-    int per_launch = (1024 / p.G) & ~7;
-    if (per_launch < 8) per_launch = 8;
-    for (int first = 0; first < p.batch; first += per_launch) {
+    c.per_launch = (1024 / members) & ~7;
+    if (c.per_launch < 8) c.per_launch = 8;
+    c.pairs = pairs;
+    c.xcd_stores = xcd_stores;
+    return c;
+}
+
+hipError_t launch_coop(const CoopParams &p_in, const CoopConfig &cfg, hipStream_t stream)
+{
+    const CoopKernel *k = coop_kernel(cfg.ch, cfg.nl);
+    if (!k) return hipErrorInvalidValue;
+    CoopParams p = p_in;
+    p.G = cfg.members;
+    p.xcd_stores = cfg.xcd_stores;
+    for (int first = 0; first < p.batch; first += cfg.per_launch) {
         p.first = first;
-        p.count = (p.batch - first < per_launch) ? p.batch - first : per_launch;
+        p.count = (p.batch - first < cfg.per_launch) ? p.batch - first : cfg.per_launch;
         const int grid = ((p.count + 7) / 8) * 8 * p.G;
-        hipError_t e = hipErrorInvalidValue;
-#define LAPWARM_COOP_CASE(CHV)                                              \
-    if (ch == CHV) {                                                        \
-        if (nl == 1) e = launch_cfg<CHV, 1>(p, grid, stream);               \
-        else if (nl == 2) e = launch_cfg<CHV, 2>(p, grid, stream);          \
-    }
-        LAPWARM_COOP_CASE(1)
-        LAPWARM_COOP_CASE(2)
-        LAPWARM_COOP_CASE(4)
-        LAPWARM_COOP_CASE(8)
-        LAPWARM_COOP_CASE(16)
-        // 17 .. 32 members (three granule loads per lane): n = 8192 with 4, n = 16384 with 8 positions per lane
-        if (nl == 3 && ch == 4) e = launch_cfg<4, 3>(p, grid, stream);
-        if (nl == 3 && ch == 8) e = launch_cfg<8, 3>(p, grid, stream);
-#undef LAPWARM_COOP_CASE
+        hipError_t e = k->launch(p, grid, stream);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -2425,6 +2425,46 @@ hipError_t launch_one(const SolverParams &p, int threads, size_t lds_bytes, hipS
     return hipGetLastError();
 }
 
+// The 61 instantiations of jv_instance_kernel: <CH, LDSL, TB, LISTS> for CH 1..16, LDS level 0..2,
+// 256 or 1024 threads, with and without candidate lists, and the large-row <16, 8, 512, false>.
+using PhaseLaunch = hipError_t (*)(const SolverParams &, int, size_t, hipStream_t);
+
+template <int CH, int TB, bool LISTS>
+PhaseLaunch by_level(int ldsl)
+{
+    if (ldsl == 2) return launch_one<CH, 2, TB, LISTS>;
+    if (ldsl == 1) return launch_one<CH, 1, TB, LISTS>;
+    return launch_one<CH, 0, TB, LISTS>;
+}
+
+template <int CH, bool LISTS>
+PhaseLaunch by_tb(int tb, int ldsl)
+{
+    return tb == 256 ? by_level<CH, 256, LISTS>(ldsl) : by_level<CH, 1024, LISTS>(ldsl);
+}
+
+template <bool LISTS>
+PhaseLaunch by_ch(int ch, int tb, int ldsl)
+{
+    if (ldsl == 8) return LISTS ? nullptr : launch_one<16, 8, 512, false>;  // large rows: seeded solves, no lists
+    switch (ch) {
+    case 1: return by_tb<1, LISTS>(tb, ldsl);
+    case 2: return by_tb<2, LISTS>(tb, ldsl);
+    case 4: return by_tb<4, LISTS>(tb, ldsl);
+    case 8: return by_tb<8, LISTS>(tb, ldsl);
+    case 16: return by_tb<16, LISTS>(tb, ldsl);
+    }
+    return nullptr;
+}
+
+hipError_t launch_phase(const PhaseConfig &k, const SolverParams &p, hipStream_t stream)
+{
+    if ((long long)k.threads * k.ch < p.n) return hipErrorInvalidValue;  // n > 16384
+    const PhaseLaunch launch = !k.lists ? by_ch<false>(k.ch, k.tb, k.ldsl) : by_ch<true>(k.ch, k.tb, k.ldsl);
+    if (!launch) return hipErrorInvalidValue;
+    return launch(p, k.threads, k.lds_bytes, stream);
+}
+
 }  // namespace
 
 bool arr_lists_enabled(int n)
@@ -2486,7 +2526,7 @@ int solver_lds_level(int n, int ch)
 
 // Picks (threads, CH) with threads*CH >= n.  `threads_hint` (0 = auto) lets the bench sweep
 // the geometry; it is rounded to a supported value.
-void solver_geometry(int n, int threads_hint, int *threads, int *ch)
+static void solver_geometry(int n, int threads_hint, int *threads, int *ch)
 {
     int t = threads_hint;
     if (t <= 0) {
@@ -2524,84 +2564,40 @@ bool solver_uses_helpers(int n)
     return want && n >= 1024 && n <= max_n && n % 2 == 0;
 }
 
-static hipError_t launch_phase(const SolverParams &p_in, int threads_hint, hipStream_t stream);
-
-// Does this launch use the instantiation with the candidate-list row reduction?  (Cold solves whose
-// caller provided the list workspace; their phase 0 or, with the cooperative shortest-path phase, phase 1.)
-static bool phase_uses_lists(const SolverParams &p)
+SolveShape solve_shape(int n, bool lists)
 {
-    return p.mode == kModeCold && p.phase == 1 && p.arr_lval && p.arr_lcol && p.arr_ltau && p.hand && p.g_x;
+    if (coop_config(n).members > 0) return SolveShape::kCoopChain;
+    return lists ? SolveShape::kListsThenPaths : SolveShape::kOneLaunch;
 }
 
-// The whole solve: one launch of jv_instance_kernel, or -- where the cooperative shortest-path phase
-// is enabled for this size (coop_ssp.hip) -- three: phase 1 (greedy / micro-ARR / cold preparation),
-// the cooperative kernel, phase 2 (whatever it left + the outputs).
-hipError_t launch_solver(const SolverParams &p_in, int threads_hint, hipStream_t stream)
+SolvePlan plan_solve(int mode, int batch, int n, int threads_hint, bool lists, int n_cus)
 {
-    if (!(coop_enabled(p_in.n) && p_in.hand && p_in.mail && p_in.cstats && p_in.g_x)) {
-        SolverParams p = p_in;
-        p.phase = 1;
-        p.mail = nullptr;
-        p.mail_granules = 0;
-        if (phase_uses_lists(p)) {
-            // cold solve with candidate lists: preparation in its own instantiation, then the shortest paths
-            hipError_t e = launch_phase(p, threads_hint, stream);
-            if (e != hipSuccess) return e;
-            p.phase = 2;
-            return launch_phase(p, threads_hint, stream);
-        }
-        p.phase = 0;
-        return launch_phase(p, threads_hint, stream);
+    SolvePlan plan = {};
+    plan.shape = solve_shape(n, lists);
+    if (plan.shape == SolveShape::kCoopChain) plan.coop = coop_config(n);
+    PhaseConfig &k = plan.paths;
+    // measured (n=2048, ARR-dominated cold solve): 512 threads 2.6 us/iteration, 1024: 3.2, 256: 3.1
+    if (threads_hint <= 0 && mode == kModeCold && n > 1024 && n <= 2048) threads_hint = 512;
+    solver_geometry(n, threads_hint, &k.threads, &k.ch);
+    // Rows that no longer fit the L1 (n > 4,427, where the state leaves LDS as well): 512 threads
+    // with n/512 positions each -- duals cached in registers (256 VGPRs per thread at this size),
+    // every head row brought into LDS by coalesced LDS-DMA (level 8).  Seeded mode only: the cold
+    // ARR loop keeps the generic geometry.
+    if (threads_hint <= 0 && mode == kModeSeeded && large_row_geometry(n, &k.threads, &k.ch)) {
+        k.ldsl = 8;
+        k.tb = 512;
+    } else {
+        k.ldsl = solver_lds_level(n, k.ch);
+        k.tb = k.threads <= 256 ? 256 : 1024;
     }
-    SolverParams p = p_in;
-    p.phase = 1;
-    p.mail_granules = (int)coop_mail_granules(p.n);
-    hipError_t e = launch_phase(p, threads_hint, stream);
-    if (e != hipSuccess) return e;
-    CoopParams c;
-    c.C = p.C;
-    c.n = p.n;
-    c.batch = p.batch;
-    c.G = 0;
-    c.first = 0;
-    c.count = p.batch;
-    c.v = p.g_v;
-    c.x = p.g_x;
-    c.y = p.g_y;
-    c.pred = p.g_pred;
-    c.fr = p.g_fr;
-    c.hand = p.hand;
-    c.cstats = p.cstats;
-    c.mail = p.mail;
-    // The cooperative kernel stops at a path it does not handle (a minima collection with a tie: rare,
-    // but seeds that went through float32 produce a few dozen per instance); jv_instance_kernel then
-    // searches that ONE path (phase 3) and the cooperative kernel carries on.  The host cannot know how
-    // often that happens, so a fixed number of (cooperative, one-path) pairs is enqueued -- a launch with
-    // nothing to do returns at once (~2 us) -- and the final phase 2 finishes whatever is left.
-    static const int pairs = [] {
-        const char *ev = getenv("LAPWARM_COOP_RELAUNCHES");
-        const int k = ev ? atoi(ev) : 96;
-        return (k >= 0 && k <= 4096) ? k : 96;
-    }();
-    for (int k = 0; k <= pairs; ++k) {
-        e = launch_coop(c, stream);
-        if (e != hipSuccess) return e;
-        if (k == pairs) break;
-        p.phase = 3;
-        e = launch_phase(p, threads_hint, stream);
-        if (e != hipSuccess) return e;
-    }
-    p.phase = 2;
-    return launch_phase(p, threads_hint, stream);
-}
-
-static hipError_t launch_phase(const SolverParams &p_in, int threads_hint, hipStream_t stream)
-{
-    SolverParams p = p_in;
+    k.lds_bytes = solver_lds_bytes(n, k.ch, k.ldsl);
+    // a cold solve whose workspace carries the candidate lists is prepared by the LISTS instantiation
+    plan.prep = k;
+    plan.prep.lists = lists;
     static const int n_helpers = [] {
         const char *e = getenv("LAPWARM_HELPERS_PER_INSTANCE");
-        const int k = e ? atoi(e) : 1;
-        return (k >= 1 && k <= 4) ? k : 1;
+        const int h = e ? atoi(e) : 1;
+        return (h >= 1 && h <= 4) ? h : 1;
     }();
     // (a helper can only help while its solver runs: with more workgroups than CUs the helpers would
     // be dispatched after the solvers they serve and leave at once -- skip them.  Assumptions, stated:
@@ -2609,64 +2605,55 @@ static hipError_t launch_phase(const SolverParams &p_in, int threads_hint, hipSt
     // helper; a helper spins until its solver's done flag or 0.5 s (60 s above n = 4096) and holds a
     // CU's LDS meanwhile, so with several launches resident -- bench.py --inflight -- helpers can delay
     // the solvers of a later launch, never deadlock them: every solver exit sets the flag.)
-    static const int n_cus = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        }
-        return cus;
-    }();
-    p.helper = (p.phase == 0 && p.mode == kModeSeeded && p.pf_ring && solver_uses_helpers(p.n) &&
-                p.batch * (1 + n_helpers) <= n_cus)
-                   ? n_helpers
-                   : 0;
-    int threads, ch;
-    // measured (n=2048, ARR-dominated cold solve): 512 threads 2.6 us/iteration, 1024: 3.2, 256: 3.1
-    if (threads_hint <= 0 && p.mode == kModeCold && p.n > 1024 && p.n <= 2048) threads_hint = 512;
-    solver_geometry(p.n, threads_hint, &threads, &ch);
-    if ((long long)threads * ch < p.n) return hipErrorInvalidValue;  // n > 16384
-    // Rows that no longer fit the L1 (n > 4,427, where the state leaves LDS as well): 512 threads
-    // with n/512 positions each -- duals cached in registers (256 VGPRs per thread at this size),
-    // every head row brought into LDS by coalesced LDS-DMA (level 8).  Seeded mode only: the cold
-    // ARR loop keeps the generic geometry.
-    if (threads_hint <= 0 && p.mode == kModeSeeded && large_row_geometry(p.n, &threads, &ch)) {
-        if (!p.g_x) return hipErrorInvalidValue;
-        const size_t lds8 = solver_lds_bytes(p.n, ch, 8);
-        return launch_one<16, 8, 512, false>(p, threads, lds8, stream);
+    if (plan.shape == SolveShape::kOneLaunch && mode == kModeSeeded && solver_uses_helpers(n) &&
+        batch * (1 + n_helpers) <= n_cus)
+        plan.helper = n_helpers;
+    return plan;
+}
+
+// Runs a plan: one launch of jv_instance_kernel, or phase 1 (greedy / micro-ARR / cold preparation),
+// the cooperative chain where the plan has one, then phase 2 (whatever is left + the outputs).
+hipError_t launch_solver(const SolvePlan &plan, const SolverParams &p_in, hipStream_t stream)
+{
+    SolverParams p = p_in;
+    p.helper = plan.helper;
+    p.mail_granules = (int)plan.coop.mail_granules;
+    if (plan.shape == SolveShape::kOneLaunch) {
+        p.phase = 0;
+        return launch_phase(plan.prep, p, stream);
     }
-    const int level = solver_lds_level(p.n, ch);
-    if (level < 2 && !p.g_x) return hipErrorInvalidValue;
-    const size_t lds = solver_lds_bytes(p.n, ch, level);
-#define LAPWARM_CASE(CHV, LISTV)                                                              \
-    case CHV:                                                                                  \
-        if (threads <= 256) {                                                                  \
-            if (level == 2) return launch_one<CHV, 2, 256, LISTV>(p, threads, lds, stream);    \
-            if (level == 1) return launch_one<CHV, 1, 256, LISTV>(p, threads, lds, stream);    \
-            return launch_one<CHV, 0, 256, LISTV>(p, threads, lds, stream);                    \
-        }                                                                                      \
-        if (level == 2) return launch_one<CHV, 2, 1024, LISTV>(p, threads, lds, stream);       \
-        if (level == 1) return launch_one<CHV, 1, 1024, LISTV>(p, threads, lds, stream);       \
-        return launch_one<CHV, 0, 1024, LISTV>(p, threads, lds, stream);
-    if (!phase_uses_lists(p)) {
-        switch (ch) {
-            LAPWARM_CASE(1, false)
-            LAPWARM_CASE(2, false)
-            LAPWARM_CASE(4, false)
-            LAPWARM_CASE(8, false)
-            LAPWARM_CASE(16, false)
-        }
-    } else {
-        switch (ch) {
-            LAPWARM_CASE(1, true)
-            LAPWARM_CASE(2, true)
-            LAPWARM_CASE(4, true)
-            LAPWARM_CASE(8, true)
-            LAPWARM_CASE(16, true)
+    p.phase = 1;
+    hipError_t e = launch_phase(plan.prep, p, stream);
+    if (e != hipSuccess) return e;
+    if (plan.shape == SolveShape::kCoopChain) {
+        CoopParams c = {};
+        c.C = p.C;
+        c.n = p.n;
+        c.batch = p.batch;
+        c.v = p.g_v;
+        c.x = p.g_x;
+        c.y = p.g_y;
+        c.pred = p.g_pred;
+        c.fr = p.g_fr;
+        c.hand = p.hand;
+        c.cstats = p.cstats;
+        c.mail = p.mail;
+        // The cooperative kernel stops at a path it does not handle (a minima collection with a tie: rare,
+        // but seeds that went through float32 produce a few dozen per instance); jv_instance_kernel then
+        // searches that ONE path (phase 3) and the cooperative kernel carries on.  The host cannot know how
+        // often that happens, so a fixed number of (cooperative, one-path) pairs is enqueued -- a launch with
+        // nothing to do returns at once (~2 us) -- and the final phase 2 finishes whatever is left.
+        for (int k = 0; k <= plan.coop.pairs; ++k) {
+            e = launch_coop(c, plan.coop, stream);
+            if (e != hipSuccess) return e;
+            if (k == plan.coop.pairs) break;
+            p.phase = 3;
+            e = launch_phase(plan.paths, p, stream);
+            if (e != hipSuccess) return e;
         }
     }
-#undef LAPWARM_CASE
-    return hipErrorInvalidValue;
+    p.phase = 2;
+    return launch_phase(plan.paths, p, stream);
 }
 
 bool solver_needs_global_state(int n)

@@ -53,7 +53,7 @@ struct SolverParams {
     int phase;
     int *hand;                 // [batch][kHandInts]
     long long *cstats;         // [batch][kCoopStats] path counters of the cooperative kernel
-    unsigned long long *mail;  // [batch][coop_mail_granules(n)] zeroed by phase 1
+    unsigned long long *mail;  // [batch][mail_granules] zeroed by phase 1
     int mail_granules;
     // candidate lists of the augmenting row reduction (cold solves, lapwarm_lapjv_*_batched):
     // [batch][n][kArrListEntries] raw costs / columns, [batch][n] thresholds; null = plain row scans
@@ -85,10 +85,42 @@ struct CoopParams {
     long long *cstats;
     unsigned long long *mail;
 };
-bool coop_enabled(int n);
-int coop_members(int n);
-size_t coop_mail_granules(int n);
-hipError_t launch_coop(const CoopParams &p, hipStream_t stream);
+
+// ---- the solve plan (jv_solver.hip: plan_solve): every host decision about how a solve runs ---------
+// The workspace layout (lapwarm_abi.hip) and the ABI queries ask the same functions.
+enum class SolveShape {
+    kOneLaunch,       // phase 0: the whole solve in one launch of jv_instance_kernel
+    kListsThenPaths,  // phase 1 with candidate lists (cold), then phase 2
+    kCoopChain,       // phase 1, (coop_ssp_kernel, phase 3) x pairs, coop_ssp_kernel, phase 2
+};
+SolveShape solve_shape(int n, bool lists);  // lists: the workspace carries candidate lists (cold solves)
+
+struct PhaseConfig {  // one launch of jv_instance_kernel<ch, ldsl, tb, lists>
+    int threads, ch, ldsl, tb;
+    bool lists;
+    size_t lds_bytes;
+};
+
+// coop_ssp_kernel<ch, nl> (coop_ssp.hip); members == 0: no cooperative path for this size
+struct CoopConfig {
+    int ch, nl, members;   // members: single-wave workgroups per instance
+    size_t mail_granules;  // per instance
+    int per_launch;        // instances per launch
+    int pairs;             // (cooperative, phase 3) pairs before the final cooperative launch
+    int xcd_stores;
+};
+CoopConfig coop_config(int n);
+hipError_t launch_coop(const CoopParams &p, const CoopConfig &cfg, hipStream_t stream);
+
+struct SolvePlan {
+    SolveShape shape;
+    PhaseConfig prep;   // phase 0, or phase 1
+    PhaseConfig paths;  // phases 2 and 3
+    int helper;         // helper workgroups per instance (phase 0 only)
+    CoopConfig coop;
+};
+SolvePlan plan_solve(int mode, int batch, int n, int threads_hint, bool lists, int n_cus);
+hipError_t launch_solver(const SolvePlan &plan, const SolverParams &p, hipStream_t stream);
 
 size_t solver_lds_bytes(int n, int ch, int level);
 int solver_lds_level(int n, int ch);
@@ -96,9 +128,7 @@ bool solver_needs_global_state(int n);
 // candidate lists for the augmenting row reduction: from the size where a row is a few times its list
 // (LAPWARM_ARR_LISTS=0 turns them off: every iteration then scans its whole row)
 bool arr_lists_enabled(int n);
-void solver_geometry(int n, int threads_hint, int *threads, int *ch);
-hipError_t launch_solver(const SolverParams &p, int threads_hint, hipStream_t stream);
-bool solver_uses_helpers(int n);  // seeded mode with a ring: one helper workgroup per instance
+bool solver_uses_helpers(int n);  // seeded mode: one helper workgroup per instance of a phase-0 launch
 
 // ---- dense sweeps (dense_sweeps.hip) ----------------------------------------------------
 struct PreludeParams {

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <stdio.h>
 #include <string.h>
+#include <tuple>
 
 #include "../../include/lapwarm_hip.h"
 #include "jv_solver.hpp"
@@ -45,66 +46,136 @@ struct Carver {
     }
 };
 
-struct SeededWs {
-    double *u_work, *v_work, *u_tight;
+// ---- workspace layouts: one function per kind; a null base measures the workspace ----------
+
+// The solver workspace of a seeded or a cold solve, laid out into the kernel argument block (the
+// caller adds C and its results).  Its size depends on neither the mode nor the threads hint: the
+// global solver state is carved whenever any geometry of this size needs it.
+struct SolverWs {
+    SolverParams sp;
+    double *u_work, *v_work, *u_tight;  // the seeded prelude's buffers
     int *viol_cnt, *tight_cnt, *flags;
     uint32_t *tight_bits;
-    double *g_dist, *g_v;
-    int *g_order, *g_pred, *g_y, *g_x, *g_fr, *g_evl, *g_tmpcol;
-    int *pf_ring;
-    int *hand;
-    long long *cstats;
-    unsigned long long *mail;
-    double *arr_lval, *arr_ltau;
-    int *arr_lcol;
+    bool lists;  // carries the candidate lists of the cold row reduction
     size_t bytes;
 };
 
-SeededWs carve_seeded(void *ws, int batch, int n, bool with_lists = false)
+SolverWs solver_layout(void *ws, int batch, int n, int mode, bool with_lists)
 {
-    SeededWs s;
+    SolverWs w;
+    SolverParams &sp = w.sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.n = n;
+    sp.batch = batch;
+    sp.mode = mode;
     Carver c{reinterpret_cast<unsigned char *>(ws), 0};
     const size_t bn = (size_t)batch * n;
     const size_t W = (size_t)(n + 31) / 32;
-    s.u_work = c.take<double>(bn);
-    s.v_work = c.take<double>(bn);
-    s.u_tight = c.take<double>(bn);
-    s.viol_cnt = c.take<int>(bn);
-    s.tight_cnt = c.take<int>(bn);
-    s.flags = c.take<int>((size_t)batch);
-    s.tight_bits = c.take<uint32_t>(bn * W);
-    s.pf_ring = c.take<int>((size_t)batch * kRingInts);
-    const bool coop = coop_enabled(n);
-    // (a cold solve with candidate lists hands its preparation over to a second launch the same way)
-    const bool two_phase = coop || (with_lists && arr_lists_enabled(n));
-    s.hand = two_phase ? c.take<int>((size_t)batch * kHandInts) : nullptr;
-    s.cstats = two_phase ? c.take<long long>((size_t)batch * kCoopStats) : nullptr;
-    s.mail = coop ? c.take<unsigned long long>((size_t)batch * coop_mail_granules(n)) : nullptr;
-    if (solver_needs_global_state(n) || two_phase) {
-        s.g_dist = c.take<double>(bn);
-        s.g_v = c.take<double>(bn);
-        s.g_order = c.take<int>(bn);
-        s.g_pred = c.take<int>(bn);
-        s.g_y = c.take<int>(bn);
-        s.g_x = c.take<int>(bn);
-        s.g_fr = c.take<int>(bn);
-        s.g_evl = c.take<int>(bn);
-        s.g_tmpcol = c.take<int>(bn + 2 * (size_t)batch);
-    } else {
-        s.g_dist = s.g_v = nullptr;
-        s.g_order = s.g_pred = s.g_y = s.g_x = s.g_fr = s.g_evl = s.g_tmpcol = nullptr;
+    w.lists = with_lists && arr_lists_enabled(n);
+    const SolveShape shape = solve_shape(n, w.lists);
+    w.u_work = c.take<double>(bn);
+    w.v_work = c.take<double>(bn);
+    w.u_tight = c.take<double>(bn);
+    w.viol_cnt = c.take<int>(bn);
+    w.tight_cnt = c.take<int>(bn);
+    w.flags = c.take<int>((size_t)batch);
+    w.tight_bits = c.take<uint32_t>(bn * W);
+    sp.pf_ring = c.take<int>((size_t)batch * kRingInts);
+    // a two-phase solve hands the state from phase 1 to the later launches through these
+    if (shape != SolveShape::kOneLaunch) {
+        sp.hand = c.take<int>((size_t)batch * kHandInts);
+        sp.cstats = c.take<long long>((size_t)batch * kCoopStats);
+    }
+    if (shape == SolveShape::kCoopChain)
+        sp.mail = c.take<unsigned long long>((size_t)batch * coop_config(n).mail_granules);
+    if (solver_needs_global_state(n) || shape != SolveShape::kOneLaunch) {
+        sp.g_dist = c.take<double>(bn);
+        sp.g_v = c.take<double>(bn);
+        sp.g_order = c.take<int>(bn);
+        sp.g_pred = c.take<int>(bn);
+        sp.g_y = c.take<int>(bn);
+        sp.g_x = c.take<int>(bn);
+        sp.g_fr = c.take<int>(bn);
+        sp.g_evl = c.take<int>(bn);
+        sp.g_tmpcol = c.take<int>(bn + 2 * (size_t)batch);
     }
     // candidate lists of the augmenting row reduction (jv_solver.hip, cold_arr_sweep): 1,544 bytes per row
-    if (with_lists && arr_lists_enabled(n)) {
-        s.arr_lval = c.take<double>(bn * kArrListEntries);
-        s.arr_lcol = c.take<int>(bn * kArrListEntries);
-        s.arr_ltau = c.take<double>(bn);
-    } else {
-        s.arr_lval = s.arr_ltau = nullptr;
-        s.arr_lcol = nullptr;
+    if (w.lists) {
+        sp.arr_lval = c.take<double>(bn * kArrListEntries);
+        sp.arr_lcol = c.take<int>(bn * kArrListEntries);
+        sp.arr_ltau = c.take<double>(bn);
     }
+    w.bytes = c.off;
+    if (mode == kModeSeeded) {  // what the prelude leaves for the solver
+        sp.u_tight = w.u_tight;
+        sp.v_work = w.v_work;
+        sp.tight_cnt = w.tight_cnt;
+        sp.tight_bits = w.tight_bits;
+        sp.inst_flags = w.flags;
+    } else {
+        sp.pf_ring = nullptr;  // a cold solve starts from C alone
+    }
+    return w;
+}
+
+// The dense sweeps: column-min partials, column minima, row partials.
+struct SweepWs {
+    double *partial, *colmin, *rowpart;
+    size_t bytes;
+};
+
+SweepWs sweep_layout(void *ws, int batch, int n)
+{
+    SweepWs s;
+    Carver c{reinterpret_cast<unsigned char *>(ws), 0};
+    const size_t bn = (size_t)batch * n;
+    s.partial = c.take<double>(bn * (size_t)colmin_chunks(n, batch));
+    s.colmin = c.take<double>(bn);
+    s.rowpart = c.take<double>(bn);
     s.bytes = c.off;
     return s;
+}
+
+// Oracle duals: the buffers of OracleParams, then the finish step's and the sweep loop's.
+struct OracleWs {
+    double *rowpart, *gmin;
+    int *running;
+    size_t bytes;
+};
+
+OracleWs oracle_layout(void *ws, int batch, int n, OracleParams *p)
+{
+    OracleWs s;
+    Carver c{reinterpret_cast<unsigned char *>(ws), 0};
+    const size_t bn = (size_t)batch * n;
+    const size_t chunks = (size_t)oracle_chunks(n, batch);
+    p->x = c.take<int>(bn);
+    p->y = c.take<int>(bn);
+    p->pred = c.take<int>(bn);
+    p->cxx = c.take<double>(bn);
+    p->v0 = c.take<double>(bn);
+    p->v1 = c.take<double>(bn);
+    p->lrow = c.take<int>(2 * bn);
+    p->lsrc = c.take<double>(2 * bn);
+    p->pval = c.take<double>(bn * chunks);
+    p->parg = c.take<int>(bn * chunks);
+    p->inst = c.take<int>((size_t)batch * kOdInstInts);
+    s.rowpart = c.take<double>(bn);
+    s.gmin = c.take<double>((size_t)batch);
+    s.running = c.take<int>(1);
+    s.bytes = c.off;
+    return s;
+}
+
+int device_cus()
+{
+    static const int cus = [] {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        const bool ok = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess;
+        return (ok && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    }();
+    return cus;
 }
 
 // grow-only device arena for the host-pointer entry points
@@ -112,15 +183,23 @@ struct Arena {
     std::mutex mu;
     void *ptr = nullptr;
     size_t cap = 0;
-    hipError_t reserve(size_t bytes)
+    // Lays out the device buffers of one host-pointer call: `layout` takes them from the Carver it is
+    // given and returns them.  It runs on a null base to measure the arena, then on the arena itself.
+    // All null: the arena could not grow.
+    template <typename Layout>
+    auto stage(Layout &&layout) -> decltype(layout(std::declval<Carver &>()))
     {
-        if (bytes <= cap) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&ptr, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
+        Carver c{nullptr, 0};
+        layout(c);
+        if (c.off > cap) {
+            if (ptr) (void)hipFree(ptr);
+            ptr = nullptr;
+            cap = 0;
+            if (hipMalloc(&ptr, c.off) != hipSuccess) return {};
+            cap = c.off;
+        }
+        c = Carver{reinterpret_cast<unsigned char *>(ptr), 0};
+        return layout(c);
     }
 };
 Arena g_arena;
@@ -205,30 +284,31 @@ int lapwarm_refine_aggregate_batched(const float *topk16, const float *u_pre, co
     return lapwarm_refine_aggregate_wsum(topk16, u_pre, w1, b1, out, nullptr, rows, H, stream_);
 }
 
-int lapwarm_solver_uses_helpers(int n) { return (solver_uses_helpers(n) && !coop_enabled(n)) ? 1 : 0; }
+int lapwarm_solver_uses_helpers(int n)
+{
+    return (solver_uses_helpers(n) && solve_shape(n, false) == SolveShape::kOneLaunch) ? 1 : 0;
+}
 
-int lapwarm_coop_members(int n) { return (n > 0 && coop_enabled(n)) ? coop_members(n) : 0; }
+int lapwarm_coop_members(int n) { return n > 0 ? coop_config(n).members : 0; }
 
 const char *lapwarm_build_info(void) { return "liblapwarm_hip gfx950 (hand-written HIP, fp64)"; }
 
 size_t lapwarm_seeded_workspace_bytes(int batch, int n)
 {
     if (check_dims(batch, n)) return 0;
-    return carve_seeded(nullptr, batch, n).bytes;
+    return solver_layout(nullptr, batch, n, kModeSeeded, false).bytes;
 }
 
 size_t lapwarm_lapjv_workspace_bytes(int batch, int n)
 {
     if (check_dims(batch, n)) return 0;
-    return carve_seeded(nullptr, batch, n, true).bytes;
+    return solver_layout(nullptr, batch, n, kModeCold, true).bytes;
 }
 
 size_t lapwarm_sweep_workspace_bytes(int batch, int n)
 {
     if (check_dims(batch, n)) return 0;
-    const size_t bn = (size_t)batch * n;
-    // column-min partials + column minima + row partials
-    return align_up(sizeof(double) * bn * (size_t)colmin_chunks(n, batch)) + 2 * align_up(sizeof(double) * bn);
+    return sweep_layout(nullptr, batch, n).bytes;
 }
 
 int lapwarm_seeded_batched(const double *C, int batch, int n, const double *u_seed,
@@ -238,12 +318,13 @@ int lapwarm_seeded_batched(const double *C, int batch, int n, const double *u_se
 {
     if (int rc = check_dims(batch, n)) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    SeededWs w = carve_seeded(workspace, batch, n);
+    SolverWs w = solver_layout(workspace, batch, n, kModeSeeded, false);
+    SolverParams &sp = w.sp;
     if (workspace_bytes < w.bytes) {
         snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
         return -1;
     }
-    HIP_TRY(launch_seed_prepare(u_seed, v_seed, w.u_work, w.v_work, (size_t)batch * n, w.flags, batch, w.pf_ring,
+    HIP_TRY(launch_seed_prepare(u_seed, v_seed, w.u_work, w.v_work, (size_t)batch * n, w.flags, batch, sp.pf_ring,
                                 batch * kRingInts, stream));
 
     PreludeParams pp;
@@ -265,44 +346,45 @@ int lapwarm_seeded_batched(const double *C, int batch, int n, const double *u_se
     pp.rerun = 1;
     HIP_TRY(launch_prelude(pp, stream));
 
-    SolverParams sp;
-    memset(&sp, 0, sizeof(sp));
     sp.C = C;
-    sp.n = n;
-    sp.batch = batch;
-    sp.mode = kModeSeeded;
-    sp.u_tight = w.u_tight;
-    sp.v_work = w.v_work;
-    sp.tight_cnt = w.tight_cnt;
-    sp.tight_bits = w.tight_bits;
-    sp.inst_flags = w.flags;
     sp.tight_eps = pp.tight_eps;
     sp.x_out = x;
     sp.y_out = y;
     sp.ret = ret;
     sp.stats = stats;
-    sp.g_dist = w.g_dist;
-    sp.g_v = w.g_v;
-    sp.g_order = w.g_order;
-    sp.g_pred = w.g_pred;
-    sp.g_y = w.g_y;
-    sp.g_x = w.g_x;
-    sp.g_fr = w.g_fr;
-    sp.g_evl = w.g_evl;
-    sp.g_tmpcol = w.g_tmpcol;
-    sp.pf_ring = w.pf_ring;
-    sp.hand = w.hand;
-    sp.cstats = w.cstats;
-    sp.mail = w.mail;
     HIP_TRY(profile_begin(stream));
-    HIP_TRY(launch_solver(sp, threads_hint, stream));
+    HIP_TRY(launch_solver(plan_solve(kModeSeeded, batch, n, threads_hint, w.lists, device_cus()), sp, stream));
     HIP_TRY(profile_end(stream));
     return 0;
 }
 
 static int lapjv_batched_impl(const double *C, int batch, int n, int *x, int *y, double *u, double *v,
                               int *ret, long long *stats, void *workspace, size_t workspace_bytes,
-                              int threads_hint, void *stream_);
+                              int threads_hint, void *stream_)
+{
+    if (int rc = check_dims(batch, n)) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    // a workspace of lapwarm_lapjv_workspace_bytes() carries the candidate lists of the row reduction;
+    // the smaller lapwarm_seeded_workspace_bytes() is still accepted (plain row scans then)
+    SolverWs w = solver_layout(workspace, batch, n, kModeCold, true);
+    if (workspace_bytes < w.bytes) w = solver_layout(workspace, batch, n, kModeCold, false);
+    if (workspace_bytes < w.bytes) {
+        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
+        return -1;
+    }
+    SolverParams &sp = w.sp;
+    sp.C = C;
+    sp.x32_out = x;
+    sp.y32_out = y;
+    sp.v_out = v;
+    sp.u_out = u;
+    sp.ret = ret;
+    sp.stats = stats;
+    HIP_TRY(profile_begin(stream));
+    HIP_TRY(launch_solver(plan_solve(kModeCold, batch, n, threads_hint, w.lists, device_cus()), sp, stream));
+    HIP_TRY(profile_end(stream));
+    return 0;
+}
 
 int lapwarm_lapjv_batched(const double *C, int batch, int n, int *x, int *y, int *ret,
                           long long *stats, void *workspace, size_t workspace_bytes,
@@ -320,59 +402,12 @@ int lapwarm_lapjv_duals_batched(const double *C, int batch, int n, int *x, int *
                               stream_);
 }
 
-static int lapjv_batched_impl(const double *C, int batch, int n, int *x, int *y, double *u, double *v,
-                              int *ret, long long *stats, void *workspace, size_t workspace_bytes,
-                              int threads_hint, void *stream_)
-{
-    if (int rc = check_dims(batch, n)) return rc;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    // a workspace of lapwarm_lapjv_workspace_bytes() carries the candidate lists of the row reduction;
-    // the smaller lapwarm_seeded_workspace_bytes() is still accepted (plain row scans then)
-    SeededWs w = carve_seeded(workspace, batch, n, true);
-    if (workspace_bytes < w.bytes) w = carve_seeded(workspace, batch, n, false);
-    if (workspace_bytes < w.bytes) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-        return -1;
-    }
-    SolverParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.C = C;
-    sp.n = n;
-    sp.batch = batch;
-    sp.mode = kModeCold;
-    sp.x32_out = x;
-    sp.y32_out = y;
-    sp.v_out = v;
-    sp.u_out = u;
-    sp.ret = ret;
-    sp.stats = stats;
-    sp.g_dist = w.g_dist;
-    sp.g_v = w.g_v;
-    sp.g_order = w.g_order;
-    sp.g_pred = w.g_pred;
-    sp.g_y = w.g_y;
-    sp.g_x = w.g_x;
-    sp.g_fr = w.g_fr;
-    sp.g_evl = w.g_evl;
-    sp.g_tmpcol = w.g_tmpcol;
-    sp.arr_lval = w.arr_lval;
-    sp.arr_lcol = w.arr_lcol;
-    sp.arr_ltau = w.arr_ltau;
-    sp.hand = w.hand;
-    sp.cstats = w.cstats;
-    sp.mail = w.mail;
-    HIP_TRY(profile_begin(stream));
-    HIP_TRY(launch_solver(sp, threads_hint, stream));
-    HIP_TRY(profile_end(stream));
-    return 0;
-}
-
 int lapwarm_colmin_batched(const double *C, int batch, int n, const double *u, double *out,
                            void *workspace, size_t workspace_bytes, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
     if (workspace_bytes < lapwarm_sweep_workspace_bytes(batch, n)) return -1;
-    HIP_TRY(launch_colmin(C, n, batch, u, out, reinterpret_cast<double *>(workspace),
+    HIP_TRY(launch_colmin(C, n, batch, u, out, sweep_layout(workspace, batch, n).partial,
                           reinterpret_cast<hipStream_t>(stream_)));
     return 0;
 }
@@ -390,16 +425,13 @@ int lapwarm_row_features_batched(const double *C, int batch, int n, const float 
     if (int rc = check_dims(batch, n)) return rc;
     if (workspace_bytes < lapwarm_sweep_workspace_bytes(batch, n)) return -1;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const size_t bn = (size_t)batch * n;
-    Carver c{reinterpret_cast<unsigned char *>(workspace), 0};
-    double *partial = c.take<double>(bn * (size_t)colmin_chunks(n, batch));
-    double *colmin = c.take<double>(bn);
-    HIP_TRY(launch_colmin(C, n, batch, nullptr, colmin, partial, stream));
+    const SweepWs w = sweep_layout(workspace, batch, n);
+    HIP_TRY(launch_colmin(C, n, batch, nullptr, w.colmin, w.partial, stream));
     FeatureParams fp;
     fp.C = C;
     fp.n = n;
     fp.batch = batch;
-    fp.colmin = colmin;
+    fp.colmin = w.colmin;
     fp.posenc = posenc;
     fp.feat = feat;
     fp.topk = topk16;
@@ -413,13 +445,10 @@ int lapwarm_project_round_batched(const double *C, int batch, int n, double *u, 
     if (int rc = check_dims(batch, n)) return rc;
     if (workspace_bytes < lapwarm_sweep_workspace_bytes(batch, n)) return -1;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const size_t bn = (size_t)batch * n;
-    Carver c{reinterpret_cast<unsigned char *>(workspace), 0};
-    double *partial = c.take<double>(bn * (size_t)colmin_chunks(n, batch));
-    double *rowpart = c.take<double>(bn);
+    const SweepWs w = sweep_layout(workspace, batch, n);
     HIP_TRY(launch_cap_rows(C, n, batch, u, v, stream));
-    HIP_TRY(launch_cap_cols(C, n, batch, u, v, partial, stream));
-    HIP_TRY(launch_reduced_min(C, n, batch, u, v, rowpart, gmin, stream));
+    HIP_TRY(launch_cap_cols(C, n, batch, u, v, w.partial, stream));
+    HIP_TRY(launch_reduced_min(C, n, batch, u, v, w.rowpart, gmin, stream));
     return 0;
 }
 
@@ -430,8 +459,7 @@ int lapwarm_reduce_costs_batched(const double *C, int batch, int n, const double
     if (int rc = check_dims(batch, n)) return rc;
     if (workspace_bytes < lapwarm_sweep_workspace_bytes(batch, n)) return -1;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    double *rowpart = reinterpret_cast<double *>(workspace);
-    HIP_TRY(launch_reduced_min(C, n, batch, u, v, rowpart, gmin, stream));
+    HIP_TRY(launch_reduced_min(C, n, batch, u, v, sweep_layout(workspace, batch, n).rowpart, gmin, stream));
     HIP_TRY(launch_reduce_costs(C, n, batch, u, v, gmin, shift_nonneg, out, stream));
     return 0;
 }
@@ -439,12 +467,8 @@ int lapwarm_reduce_costs_batched(const double *C, int batch, int n, const double
 size_t lapwarm_oracle_duals_workspace_bytes(int batch, int n)
 {
     if (batch <= 0 || n <= 0) return 0;
-    const size_t bn = (size_t)batch * n;
-    const size_t chunks = (size_t)oracle_chunks(n, batch);
-    return 3 * align_up(sizeof(int) * bn) + 3 * align_up(sizeof(double) * bn) + align_up(sizeof(int) * 2 * bn) +
-           align_up(sizeof(double) * 2 * bn) + align_up(sizeof(double) * bn * chunks) +
-           align_up(sizeof(int) * bn * chunks) + align_up(sizeof(int) * (size_t)batch * kOdInstInts) +
-           align_up(sizeof(double) * bn) + align_up(sizeof(double) * batch) + align_up(sizeof(int));
+    OracleParams p;
+    return oracle_layout(nullptr, batch, n, &p).bytes;
 }
 
 // Sweeps are launched in chunks (4, 8, 16, then 32 at a time) with one host synchronisation per
@@ -455,7 +479,6 @@ static int oracle_duals_impl(const double *C, int batch, int n, const int *rows,
 {
     if (int rc = check_dims(batch, n)) return rc;
     if (workspace_bytes < lapwarm_oracle_duals_workspace_bytes(batch, n)) return -1;
-    const size_t bn = (size_t)batch * n;
     OracleParams p;
     p.C = C;
     p.n = n;
@@ -464,21 +487,7 @@ static int oracle_duals_impl(const double *C, int batch, int n, const int *rows,
     p.pair = (n % 2) == 0 && (reinterpret_cast<uintptr_t>(C) % 16) == 0;
     p.rows = rows;
     p.cols = cols;
-    Carver c{reinterpret_cast<unsigned char *>(workspace), 0};
-    p.x = c.take<int>(bn);
-    p.y = c.take<int>(bn);
-    p.pred = c.take<int>(bn);
-    p.cxx = c.take<double>(bn);
-    p.v0 = c.take<double>(bn);
-    p.v1 = c.take<double>(bn);
-    p.lrow = c.take<int>(2 * bn);
-    p.lsrc = c.take<double>(2 * bn);
-    p.pval = c.take<double>(bn * p.chunks);
-    p.parg = c.take<int>(bn * p.chunks);
-    p.inst = c.take<int>((size_t)batch * kOdInstInts);
-    double *rowpart = c.take<double>(bn);
-    double *gmin = c.take<double>((size_t)batch);
-    int *running = c.take<int>(1);
+    const OracleWs w = oracle_layout(workspace, batch, n, &p);
     HIP_TRY(launch_oracle_init(p, stream));
     const int max_s = n - 1;  // settled within n - 1 sweeps <=> at most n - 2 updating sweeps
     int s = 0, chunk = 4;
@@ -486,16 +495,16 @@ static int oracle_duals_impl(const double *C, int batch, int n, const int *rows,
         const int k = (chunk < max_s - s) ? chunk : max_s - s;
         for (int t = 0; t < k; ++t, ++s) HIP_TRY(launch_oracle_sweep(p, s, stream));
         const int last = s >= max_s;
-        HIP_TRY(hipMemsetAsync(running, 0, sizeof(int), stream));
-        HIP_TRY(launch_oracle_check(p, s, last, running, stream));
+        HIP_TRY(hipMemsetAsync(w.running, 0, sizeof(int), stream));
+        HIP_TRY(launch_oracle_check(p, s, last, w.running, stream));
         if (last) break;
         int host_running = 0;
-        HIP_TRY(hipMemcpyAsync(&host_running, running, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&host_running, w.running, sizeof(int), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (host_running == 0) break;
         if (chunk < 32) chunk *= 2;
     }
-    HIP_TRY(launch_oracle_finish(p, tol, u, v, rowpart, gmin, ret, sweeps, stream));
+    HIP_TRY(launch_oracle_finish(p, tol, u, v, w.rowpart, w.gmin, ret, sweeps, stream));
     return 0;
 }
 
@@ -519,18 +528,11 @@ int lapjv_seeded(const double *C, int n_rows, int n_cols, long long *x, long lon
     if (n > 16384) return -5;
     std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t ws_bytes = lapwarm_seeded_workspace_bytes(1, n);
-    const size_t mat = align_up(sizeof(double) * (size_t)n * n);
-    const size_t vec = align_up(sizeof(double) * (size_t)n);
-    const size_t total = mat + 4 * vec + 256 + ws_bytes;
-    if (g_arena.reserve(total) != hipSuccess) return -1;
-    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
-    double *dC = c.take<double>((size_t)n * n);
-    double *du = c.take<double>(n);
-    double *dv = c.take<double>(n);
-    long long *dx = c.take<long long>(n);
-    long long *dy = c.take<long long>(n);
-    int *dret = c.take<int>(1);
-    void *ws = g_arena.ptr ? reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off : nullptr;
+    const auto [dC, du, dv, dx, dy, dret, ws] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>((size_t)n * n), c.take<double>(n), c.take<double>(n), c.take<long long>(n),
+                          c.take<long long>(n), c.take<int>(1), c.take<unsigned char>(ws_bytes)};
+    });
+    if (!dC) return -1;
     HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(du, u_seed, sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dv, v_seed, sizeof(double) * n, hipMemcpyHostToDevice));
@@ -546,18 +548,14 @@ int lapjv_seeded(const double *C, int n_rows, int n_cols, long long *x, long lon
 
 int lapwarm_lapjv_dense(const double *C, int n, int *x, int *y)
 {
-    if (n <= 0) return -2;
-    if (n > 16384) return -5;
+    if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t ws_bytes = lapwarm_lapjv_workspace_bytes(1, n);
-    const size_t total = align_up(sizeof(double) * (size_t)n * n) + 2 * align_up(sizeof(int) * n) + 256 + ws_bytes;
-    if (g_arena.reserve(total) != hipSuccess) return -1;
-    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
-    double *dC = c.take<double>((size_t)n * n);
-    int *dx = c.take<int>(n);
-    int *dy = c.take<int>(n);
-    int *dret = c.take<int>(1);
-    void *ws = reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off;
+    const auto [dC, dx, dy, dret, ws] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>((size_t)n * n), c.take<int>(n), c.take<int>(n), c.take<int>(1),
+                          c.take<unsigned char>(ws_bytes)};
+    });
+    if (!dC) return -1;
     HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
     int rc = lapwarm_lapjv_batched(dC, 1, n, dx, dy, dret, nullptr, ws, ws_bytes, 0, nullptr);
     if (rc) return rc;
@@ -572,27 +570,17 @@ int lapwarm_lapjv_dense(const double *C, int n, int *x, int *y)
 int lapwarm_warmstart_lapjv(const double *C, int n, const double *u, const double *v, int shift_nonneg,
                             int *x, int *y)
 {
-    if (n <= 0) return -2;
-    if (n > 16384) return -5;
+    if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t ws_sweep = lapwarm_sweep_workspace_bytes(1, n);
     const size_t ws_solve = lapwarm_lapjv_workspace_bytes(1, n);
-    const size_t mat = align_up(sizeof(double) * (size_t)n * n);
-    const size_t total = 2 * mat + 3 * align_up(sizeof(double) * n) + 2 * align_up(sizeof(int) * n) + 512 +
-                         ws_sweep + ws_solve;
-    if (g_arena.reserve(total) != hipSuccess) return -1;
-    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
-    double *dC = c.take<double>((size_t)n * n);
-    double *dR = c.take<double>((size_t)n * n);  // the reduced matrix never leaves the device
-    double *du = c.take<double>(n);
-    double *dv = c.take<double>(n);
-    double *dg = c.take<double>(1);
-    int *dx = c.take<int>(n);
-    int *dy = c.take<int>(n);
-    int *dret = c.take<int>(1);
-    void *wsA = reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off;
-    c.off += align_up(ws_sweep);
-    void *wsB = reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off;
+    // (dR, the reduced matrix, never leaves the device)
+    const auto [dC, dR, du, dv, dg, dx, dy, dret, wsA, wsB] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>((size_t)n * n), c.take<double>((size_t)n * n), c.take<double>(n),
+                          c.take<double>(n), c.take<double>(1), c.take<int>(n), c.take<int>(n), c.take<int>(1),
+                          c.take<unsigned char>(ws_sweep), c.take<unsigned char>(ws_solve)};
+    });
+    if (!dC) return -1;
     HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(du, u, sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
@@ -624,19 +612,14 @@ static void host_posenc(int n, float *out)
 
 int lapwarm_row_features(const double *C, int n, float *feat, float *topk16)
 {
-    if (n <= 0) return -2;
-    if (n > 16384) return -5;
+    if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n);
-    const size_t total = align_up(sizeof(double) * (size_t)n * n) + align_up(sizeof(float) * n * 8) +
-                         align_up(sizeof(float) * n * 21) + align_up(sizeof(float) * n * 16) + ws_bytes;
-    if (g_arena.reserve(total) != hipSuccess) return -1;
-    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
-    double *dC = c.take<double>((size_t)n * n);
-    float *dpos = c.take<float>((size_t)n * 8);
-    float *dfeat = c.take<float>((size_t)n * 21);
-    float *dtop = c.take<float>((size_t)n * 16);
-    void *ws = reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off;
+    const auto [dC, dpos, dfeat, dtop, ws] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>((size_t)n * n), c.take<float>((size_t)n * 8), c.take<float>((size_t)n * 21),
+                          c.take<float>((size_t)n * 16), c.take<unsigned char>(ws_bytes)};
+    });
+    if (!dC) return -1;
     float *pos = new float[(size_t)n * 8];
     host_posenc(n, pos);
     hipError_t e1 = hipMemcpy(dpos, pos, sizeof(float) * n * 8, hipMemcpyHostToDevice);
@@ -652,17 +635,14 @@ int lapwarm_row_features(const double *C, int n, float *feat, float *topk16)
 
 int lapwarm_min_trick(const double *C, int n, const double *u, double *v)
 {
-    if (n <= 0) return -2;
-    if (n > 16384) return -5;
+    if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n);
-    const size_t total = align_up(sizeof(double) * (size_t)n * n) + 2 * align_up(sizeof(double) * n) + ws_bytes;
-    if (g_arena.reserve(total) != hipSuccess) return -1;
-    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
-    double *dC = c.take<double>((size_t)n * n);
-    double *du = c.take<double>(n);
-    double *dv = c.take<double>(n);
-    void *ws = reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off;
+    const auto [dC, du, dv, ws] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>((size_t)n * n), c.take<double>(n), c.take<double>(n),
+                          c.take<unsigned char>(ws_bytes)};
+    });
+    if (!dC) return -1;
     HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
     if (u) HIP_TRY(hipMemcpy(du, u, sizeof(double) * n, hipMemcpyHostToDevice));
     int rc = lapwarm_colmin_batched(dC, 1, n, u ? du : nullptr, dv, ws, ws_bytes, nullptr);
@@ -673,15 +653,12 @@ int lapwarm_min_trick(const double *C, int n, const double *u, double *v)
 
 int lapwarm_row_min(const double *C, int n, const double *v, double *out)
 {
-    if (n <= 0) return -2;
-    if (n > 16384) return -5;
+    if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t total = align_up(sizeof(double) * (size_t)n * n) + 2 * align_up(sizeof(double) * n);
-    if (g_arena.reserve(total) != hipSuccess) return -1;
-    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
-    double *dC = c.take<double>((size_t)n * n);
-    double *dv = c.take<double>(n);
-    double *dout = c.take<double>(n);
+    const auto [dC, dv, dout] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>((size_t)n * n), c.take<double>(n), c.take<double>(n)};
+    });
+    if (!dC) return -1;
     HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
     if (v) HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
     int rc = lapwarm_rowmin_batched(dC, 1, n, v ? dv : nullptr, dout, nullptr);
@@ -692,18 +669,14 @@ int lapwarm_row_min(const double *C, int n, const double *v, double *out)
 
 int lapwarm_project_feasible(const double *C, int n, double *u, double *v, int max_rounds, double tol)
 {
-    if (n <= 0) return -2;
-    if (n > 16384) return -5;
+    if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n);
-    const size_t total = align_up(sizeof(double) * (size_t)n * n) + 2 * align_up(sizeof(double) * n) + 256 + ws_bytes;
-    if (g_arena.reserve(total) != hipSuccess) return -1;
-    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
-    double *dC = c.take<double>((size_t)n * n);
-    double *du = c.take<double>(n);
-    double *dv = c.take<double>(n);
-    double *dg = c.take<double>(1);
-    void *ws = reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off;
+    const auto [dC, du, dv, dg, ws] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>((size_t)n * n), c.take<double>(n), c.take<double>(n), c.take<double>(1),
+                          c.take<unsigned char>(ws_bytes)};
+    });
+    if (!dC) return -1;
     HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(du, u, sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
@@ -723,19 +696,14 @@ int lapwarm_project_feasible(const double *C, int n, double *u, double *v, int m
 int lapwarm_reduce_costs(const double *C, int n, const double *u, const double *v, int shift_nonneg,
                          double *out, double *min_out)
 {
-    if (n <= 0) return -2;
-    if (n > 16384) return -5;
+    if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n);
-    const size_t total = 2 * align_up(sizeof(double) * (size_t)n * n) + 2 * align_up(sizeof(double) * n) + 256 + ws_bytes;
-    if (g_arena.reserve(total) != hipSuccess) return -1;
-    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
-    double *dC = c.take<double>((size_t)n * n);
-    double *dO = c.take<double>((size_t)n * n);
-    double *du = c.take<double>(n);
-    double *dv = c.take<double>(n);
-    double *dg = c.take<double>(1);
-    void *ws = reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off;
+    const auto [dC, dO, du, dv, dg, ws] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>((size_t)n * n), c.take<double>((size_t)n * n), c.take<double>(n),
+                          c.take<double>(n), c.take<double>(1), c.take<unsigned char>(ws_bytes)};
+    });
+    if (!dC) return -1;
     HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(du, u, sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
@@ -749,21 +717,14 @@ int lapwarm_reduce_costs(const double *C, int n, const double *u, const double *
 int lapwarm_oracle_duals(const double *C, int n, const int *rows, const int *cols, double *u, double *v,
                          double tol)
 {
-    if (n <= 0) return -2;
-    if (n > 16384) return -5;
+    if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t ws_bytes = lapwarm_oracle_duals_workspace_bytes(1, n);
-    const size_t total = align_up(sizeof(double) * (size_t)n * n) + 2 * align_up(sizeof(int) * n) +
-                         2 * align_up(sizeof(double) * n) + align_up(sizeof(int)) + ws_bytes;
-    if (g_arena.reserve(total) != hipSuccess) return -1;
-    Carver c{reinterpret_cast<unsigned char *>(g_arena.ptr), 0};
-    double *dC = c.take<double>((size_t)n * n);
-    int *dr = c.take<int>(n);
-    int *dc = c.take<int>(n);
-    double *du = c.take<double>(n);
-    double *dv = c.take<double>(n);
-    int *dret = c.take<int>(1);
-    void *ws = reinterpret_cast<unsigned char *>(g_arena.ptr) + c.off;
+    const auto [dC, dr, dc, du, dv, dret, ws] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>((size_t)n * n), c.take<int>(n), c.take<int>(n), c.take<double>(n),
+                          c.take<double>(n), c.take<int>(1), c.take<unsigned char>(ws_bytes)};
+    });
+    if (!dC) return -1;
     HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dr, rows, sizeof(int) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dc, cols, sizeof(int) * n, hipMemcpyHostToDevice));

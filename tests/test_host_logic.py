@@ -286,3 +286,71 @@ def test_solver_geometry_and_timing_helper():
     def boom():
         raise RuntimeError("x")
     assert time_solver_rigorous(boom, 1, 2) == {"success": False, "error": "x"}
+
+
+# lapwarm_{kind}_workspace_bytes(batch, n) under default settings, recorded before the workspace layouts
+# and the solve plan were unified; the byte counts are part of the ABI contract
+WS_SIZES_N = (1, 64, 255, 256, 511, 512, 1024, 1025, 2048, 3634, 3635, 4096, 4427, 4428, 8192, 8193, 16384)
+WS_SIZES = {
+    "seeded": {
+        1: [2304, 3328, 17152, 17152, 49920, 49920, 164608, 170240, 590592, 1935360, 1935616, 2409472, 2801408,
+             2804992, 9016320, 9052160, 34804736],
+        3: [2816, 8960, 50432, 50432, 148736, 148736, 492800, 506880, 1770752, 5803264, 5804544, 7226880, 8397312,
+             8406272, 27046400, 27147008, 104411648],
+        32: [10240, 90624, 531200, 532992, 1578752, 1581568, 5251584, 5388288, 18883072, 61874176, 61892352,
+             77079296, 89541888, 89634560, 288484096, 289523200, 1113713408],
+    },
+    "lapjv": {
+        1: [2304, 3328, 17152, 17152, 49920, 863744, 1791488, 1800960, 3843584, 7546880, 7548672, 8734208, 9637376,
+             9641984, 21664768, 21702400, 60101632],
+        3: [2816, 8960, 50432, 50432, 148736, 2588928, 5372160, 5393152, 11528448, 22636800, 22642688, 26200320,
+             28904192, 28916992, 64991744, 65097216, 180302336],
+        32: [10240, 90624, 531200, 532992, 1578752, 27605760, 57293568, 57481984, 122960640, 241428992, 241496576,
+             279460608, 308277248, 308413184, 693234432, 694322944, 1923214080],
+    },
+    "sweep": {
+        1: [768, 2048, 20480, 20480, 73728, 73728, 278528, 287744, 1081344, 3372800, 3373568, 4259840, 4994048,
+             4995328, 8519680, 8062464, 8650752],
+        3: [768, 6144, 61440, 61440, 220928, 221184, 835584, 861696, 3244032, 7675392, 7677440, 8650752, 8288000,
+             8289792, 8847360, 8455680, 9437184],
+        32: [768, 65536, 652800, 655360, 2354688, 2359296, 8912896, 6297600, 9437184, 9303040, 9305600, 10485760,
+             11333120, 11335680, 12582912, 12584448, 16777216],
+    },
+    "oracle_duals": {
+        1: [3584, 6656, 42752, 42752, 133888, 133888, 463616, 478976, 1712896, 5220608, 5221632, 6570752, 7687680,
+             7689728, 13140736, 12456448, 13697792],
+        3: [3584, 18432, 126720, 126720, 399872, 400128, 1389312, 1430016, 5137152, 11994368, 11997440, 13517568,
+             13018368, 13020928, 14353152, 13767168, 16319232],
+        32: [5632, 190976, 1341184, 1346048, 4254464, 4262400, 14813696, 10892544, 17041920, 19073792, 19079424,
+             21498368, 23235840, 23240704, 30411264, 30415360, 48237056],
+    },
+}
+
+
+def test_workspace_sizes_are_unchanged():
+    import ctypes as ct
+    from lap import _hip
+    lib = _hip.load()
+    for kind, per_batch in WS_SIZES.items():
+        f = getattr(lib, f"lapwarm_{kind}_workspace_bytes")
+        f.restype, f.argtypes = ct.c_size_t, [ct.c_int, ct.c_int]
+        for batch, want in per_batch.items():
+            got = [f(batch, n) for n in WS_SIZES_N]
+            assert got == want, (kind, batch, [(n, g, w) for n, g, w in zip(WS_SIZES_N, got, want) if g != w])
+
+
+def test_forced_cooperative_geometry_without_an_instantiation_is_not_planned():
+    """LAPWARM_COOP_CH=1 at n = 2048 gives 32 members and 3 granule loads per lane: no coop_ssp_kernel<1, 3>
+    exists, so the solve takes the one-workgroup path; n = 640 (10 members, <1, 1>) stays cooperative.
+    A fresh interpreter: the library reads its settings once."""
+    import os
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from lap import _hip\n"
+            "lib = _hip.load()\n"
+            "print(lib.lapwarm_coop_members(2048), lib.lapwarm_coop_members(640))\n" % str(PKG))
+    env = dict(os.environ, LAPWARM_COOP_MIN_N="1", LAPWARM_COOP_CH="1")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split() == ["0", "10"], r.stdout
