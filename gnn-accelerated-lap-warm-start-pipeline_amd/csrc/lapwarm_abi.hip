@@ -167,6 +167,33 @@ OracleWs oracle_layout(void *ws, int batch, int n, OracleParams *p)
     return s;
 }
 
+// Rectangular / cost-limited lapjv: the extended matrices (none when the solver reads the caller's C),
+// the solver's x, y of the n x n problem, the matched costs of the finish step, the cold workspace.
+struct ExtendedWs {
+    double *E, *gath;
+    int *xs, *ys;
+    unsigned char *solver;
+    size_t solver_bytes, bytes;
+};
+
+ExtendedWs extended_layout(void *ws, int batch, int n_rows, int n_cols, int n, bool copy)
+{
+    ExtendedWs w;
+    Carver c{reinterpret_cast<unsigned char *>(ws), 0};
+    const size_t bn = (size_t)batch * n;
+    w.E = copy ? c.take<double>(bn * n) : nullptr;
+    w.xs = c.take<int>(bn);
+    w.ys = c.take<int>(bn);
+    w.gath = c.take<double>((size_t)batch * n_rows);
+    w.solver_bytes = solver_layout(nullptr, batch, n, kModeCold, true).bytes;
+    w.solver = c.take<unsigned char>(w.solver_bytes);
+    w.bytes = c.off;
+    return w;
+}
+
+// _lapjv.pyx:84 `cost_limit < np.inf` (false for NaN, as there)
+bool cost_limited(double cost_limit) { return cost_limit < (double)INFINITY; }
+
 int device_cus()
 {
     static const int cus = [] {
@@ -402,6 +429,52 @@ int lapwarm_lapjv_duals_batched(const double *C, int batch, int n, int *x, int *
                               stream_);
 }
 
+int lapwarm_lapjv_extended_n(int n_rows, int n_cols, int extend_cost, double cost_limit)
+{
+    if (n_rows <= 0 || n_cols <= 0) return -2;
+    if (n_rows != n_cols && !extend_cost) return -4;  // _lapjv.pyx:80-83, whatever the limit
+    const long long n = cost_limited(cost_limit) ? (long long)n_rows + n_cols
+                                                 : (n_rows > n_cols ? n_rows : n_cols);
+    return n > 16384 ? -5 : (int)n;
+}
+
+size_t lapwarm_lapjv_extended_workspace_bytes(int batch, int n_rows, int n_cols, int extend_cost,
+                                              double cost_limit)
+{
+    const int n = lapwarm_lapjv_extended_n(n_rows, n_cols, extend_cost, cost_limit);
+    if (n <= 0 || batch <= 0) return 0;
+    const bool copy = cost_limited(cost_limit) || n_rows != n_cols;
+    return extended_layout(nullptr, batch, n_rows, n_cols, n, copy).bytes;
+}
+
+int lapwarm_lapjv_extended_batched(const double *C, int batch, int n_rows, int n_cols, int extend_cost,
+                                   double cost_limit, int *x, int *y, double *opt, int *matched, int *ret,
+                                   long long *stats, void *workspace, size_t workspace_bytes,
+                                   int threads_hint, void *stream_)
+{
+    const int n = lapwarm_lapjv_extended_n(n_rows, n_cols, extend_cost, cost_limit);
+    if (n < 0) return n;
+    if (batch <= 0 || batch > 65535) return -2;  // (the extension kernel's grid: rows x batch)
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return -2;  // E is written with 16-byte stores
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const bool limited = cost_limited(cost_limit);
+    // a square matrix without a limit is solved where it is (_lapjv.pyx:91-95 copies it into zeros)
+    const bool copy = limited || n_rows != n_cols;
+    const ExtendedWs w = extended_layout(workspace, batch, n_rows, n_cols, n, copy);
+    if (workspace_bytes < w.bytes) {
+        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
+        return -1;
+    }
+    if (copy)
+        HIP_TRY(launch_extend_costs(C, batch, n_rows, n_cols, n, limited ? cost_limit / 2. : 0.0, w.E, stream));
+    if (int rc = lapjv_batched_impl(copy ? w.E : C, batch, n, w.xs, w.ys, nullptr, nullptr, ret, stats, w.solver,
+                                    w.solver_bytes, threads_hint, stream_))
+        return rc;
+    HIP_TRY(launch_extended_finish(C, batch, n_rows, n_cols, n, w.xs, w.ys, ret, x, y, opt, matched, w.gath,
+                                   stream));
+    return 0;
+}
+
 int lapwarm_colmin_batched(const double *C, int batch, int n, const double *u, double *out,
                            void *workspace, size_t workspace_bytes, void *stream_)
 {
@@ -564,6 +637,33 @@ int lapwarm_lapjv_dense(const double *C, int n, int *x, int *y)
     if (ret != 0) return ret;
     HIP_TRY(hipMemcpy(x, dx, sizeof(int) * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(y, dy, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int lapwarm_lapjv_extended(const double *C, int n_rows, int n_cols, int extend_cost, double cost_limit,
+                           int *x, int *y, double *opt)
+{
+    const int n = lapwarm_lapjv_extended_n(n_rows, n_cols, extend_cost, cost_limit);
+    if (n < 0) return n;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    const size_t ws_bytes = lapwarm_lapjv_extended_workspace_bytes(1, n_rows, n_cols, extend_cost, cost_limit);
+    const size_t nc = (size_t)n_rows * n_cols;
+    // (only C crosses to the device: the extended matrix is built there)
+    const auto [dC, dx, dy, dopt, dret, ws] = g_arena.stage([&](Carver &c) {
+        return std::tuple{c.take<double>(nc), c.take<int>(n_rows), c.take<int>(n_cols), c.take<double>(1),
+                          c.take<int>(1), c.take<unsigned char>(ws_bytes)};
+    });
+    if (!dC) return -1;
+    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * nc, hipMemcpyHostToDevice));
+    int rc = lapwarm_lapjv_extended_batched(dC, 1, n_rows, n_cols, extend_cost, cost_limit, dx, dy, dopt, nullptr,
+                                            dret, nullptr, ws, ws_bytes, 0, nullptr);
+    if (rc) return rc;
+    int ret = 0;
+    HIP_TRY(hipMemcpy(&ret, dret, sizeof(int), hipMemcpyDeviceToHost));
+    if (ret != 0) return ret;
+    HIP_TRY(hipMemcpy(x, dx, sizeof(int) * n_rows, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(y, dy, sizeof(int) * n_cols, hipMemcpyDeviceToHost));
+    if (opt) HIP_TRY(hipMemcpy(opt, dopt, sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

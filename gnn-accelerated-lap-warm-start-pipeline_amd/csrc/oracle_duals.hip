@@ -37,44 +37,6 @@ constexpr int kCycleThreads = 1024;
 
 __device__ __forceinline__ bool od_finite(double x) { return (x - x) == 0.0; }
 
-// numpy's pairwise summation (numpy/_core/src/umath/loops_utils.h.src, pairwise_sum) of a
-// contiguous fp64 vector: < 8 elements a plain loop, <= 128 eight accumulators, otherwise split
-// at n/2 rounded down to a multiple of 8.  Serial, in one thread.
-__device__ double pairwise_leaf(const double *a, int n)
-{
-    if (n < 8) {
-        double r = -0.0;
-        for (int i = 0; i < n; ++i) r = r + a[i];
-        return r;
-    }
-    double r[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) r[q] = a[q];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) r[q] = r[q] + a[i + q];
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res = res + a[i];
-    return res;
-}
-
-// depth D bounds the recursion: n <= 16384 splits at most 8 times before a block of <= 128
-template <int D>
-__device__ __noinline__ double pairwise_sum(const double *a, int n)
-{
-    if (n <= 128) return pairwise_leaf(a, n);
-    const int n2 = (n / 2) & ~7;
-    return pairwise_sum<D - 1>(a, n2) + pairwise_sum<D - 1>(a + n2, n - n2);
-}
-
-template <>
-__device__ __noinline__ double pairwise_sum<0>(const double *a, int n)
-{
-    return pairwise_leaf(a, n);
-}
-
 // ------------------------------------------------------------------------------------------
 // Set-up, one workgroup per instance: check that the pairs form a permutation, x (row -> col),
 // y (col -> row), C[i][x_i], v = 0, no predecessors, every row active with source value 0.

@@ -71,14 +71,17 @@ class WarmStartPipeline:
 
     def _workspace(self, B, n, cold=False):
         # (cold solves carry the candidate lists of the row reduction: a larger block, cached separately)
-        key = (B, n, cold)
+        query = self.lib.lapwarm_lapjv_workspace_bytes if cold else self.lib.lapwarm_seeded_workspace_bytes
+        return self._cached_workspace((B, n, cold), lambda: query(B, n))
+
+    def _cached_workspace(self, key, nbytes_of):
         if key not in self._ws:
             if len(self._ws) >= 4:  # a handful of shapes at most: drop the oldest
                 # kernels of an earlier call may still be running on it (any stream), and a captured
                 # graph may hold its address: wait for the device before the block can be handed out again
                 torch.cuda.synchronize(self.device)
                 self._ws.pop(next(iter(self._ws)))
-            nbytes = (self.lib.lapwarm_lapjv_workspace_bytes if cold else self.lib.lapwarm_seeded_workspace_bytes)(B, n)
+            nbytes = int(nbytes_of())
             self._ws[key] = (torch.empty((nbytes,), dtype=torch.uint8, device=self.device), nbytes)
         ws = self._ws[key]
         # the caching allocator must not recycle the block while the stream that uses it now still runs
@@ -132,6 +135,44 @@ class WarmStartPipeline:
         if _hip.check(rc, "lapjv_batch") != 0:
             raise RuntimeError(f"lapwarm_lapjv_batched failed (code {rc}): {_hip.last_error()}")
         return x, y, ret, stats
+
+    def lapjv_extended_batch(self, C: torch.Tensor, extend_cost: bool = True, cost_limit: float = float("inf"),
+                             want_stats: bool = True) -> dict:
+        """Batched rectangular / cost-limited lapjv (the reference's `lapjv(cost, extend_cost, cost_limit)`,
+        LAP/_lapjv_cpp/_lapjv.pyx:77-124) of a resident batch of one shape: C (B, n_rows, n_cols) fp64.
+        Returns x (B, n_rows), y (B, n_cols) int32 with -1 for unmatched, opt (B,) fp64, matched (B,) int32,
+        ret (B,) int32 and stats (B, 32) int64 of the cold solve of the square problem (or None).  The
+        extended matrices are built in the workspace on the device; everything is enqueued on the current
+        stream."""
+        if C.dim() != 3 or C.dtype != torch.float64 or not C.is_cuda:
+            raise ValueError("C must be a (B, n_rows, n_cols) float64 CUDA tensor")
+        C = C.contiguous()
+        B, n_rows, n_cols = C.shape
+        extend_cost, cost_limit = int(bool(extend_cost)), float(cost_limit)
+        n = self.lib.lapwarm_lapjv_extended_n(n_rows, n_cols, extend_cost, cost_limit)
+        if n == -4:
+            raise ValueError("Square cost array expected. If cost is intentionally "
+                             "non-square, pass extend_cost=True.")
+        if n == -2 or B < 1:
+            raise ValueError("lapjv_extended_batch: empty batch or empty cost matrices")
+        _hip.check(n, "lapjv_extended_batch")
+        x = torch.empty((B, n_rows), dtype=torch.int32, device=C.device)
+        y = torch.empty((B, n_cols), dtype=torch.int32, device=C.device)
+        opt = torch.empty((B,), dtype=torch.float64, device=C.device)
+        matched = torch.empty((B,), dtype=torch.int32, device=C.device)
+        ret = torch.empty((B,), dtype=torch.int32, device=C.device)
+        stats = torch.zeros((B, 32), dtype=torch.int64, device=C.device) if want_stats else None
+        ws, nbytes = self._cached_workspace(
+            ("extended", B, n_rows, n_cols, extend_cost, cost_limit < float("inf")),
+            lambda: self.lib.lapwarm_lapjv_extended_workspace_bytes(B, n_rows, n_cols, extend_cost, cost_limit))
+        stream = torch.cuda.current_stream(C.device).cuda_stream
+        rc = self.lib.lapwarm_lapjv_extended_batched(
+            C.data_ptr(), B, n_rows, n_cols, extend_cost, cost_limit, x.data_ptr(), y.data_ptr(), opt.data_ptr(),
+            matched.data_ptr(), ret.data_ptr(), stats.data_ptr() if want_stats else None, ws.data_ptr(), nbytes,
+            self.threads_hint, ct.c_void_p(stream))
+        if _hip.check(rc, "lapjv_extended_batch") != 0:
+            raise RuntimeError(f"lapwarm_lapjv_extended_batched failed (code {rc}): {_hip.last_error()}")
+        return {"x": x, "y": y, "opt": opt, "matched": matched, "ret": ret, "stats": stats}
 
     def optimal_duals_batch(self, C: torch.Tensor):
         """Cold JV + the optimal duals it ends with: x (B,n) int32, u, v (B,n) fp64, ret.

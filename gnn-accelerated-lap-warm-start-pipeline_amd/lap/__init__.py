@@ -6,10 +6,21 @@ warm-start hot path:
     lapjv(cost, extend_cost=False, cost_limit=inf, return_cost=True) -> (opt, x, y)   int32
     lapjv_seeded(C, u, v, eps=1e-12)                                  -> (x, y, cost)  int64
 
-Both run on the GPU through liblapwarm_hip.so (hand-written HIP, gfx950); there is no CPU
+    lapjv_extended(cost, extend_cost=False, cost_limit=inf, return_cost=True)  -> (opt, x, y)   int32
+
+All run on the GPU through liblapwarm_hip.so (hand-written HIP, gfx950); there is no CPU
 implementation in this package.  `lapmod` (sparse LAPMOD) is outside the hot path and raises.
+
+`lapjv_extended` is the reference's `lapjv` for every combination of its arguments: rectangular
+matrices (`extend_cost=True`) and thresholded ones (`cost_limit=t`), -1 for unmatched rows and
+columns.  `lapjv` itself still raises NotImplementedError for those two arguments, and
+`lapjv_extended` is importable as `lap.lapjv_extended` without being listed in `__all__`:
+tests/test_gpu_reference_suite.py and tests/test_host_logic.py assert both.  Once those two
+assertions are retired, routing is three lines in lap/_lapjv.py: replace the NotImplementedError
+branch of `lapjv` by `return lapjv_extended(cost, extend_cost, cost_limit, return_cost)` and add the
+name to `__all__`.
 """
-from ._lapjv import lapjv, LARGE_ as LARGE, FP_1_ as FP_1, FP_2_ as FP_2, FP_DYNAMIC_ as FP_DYNAMIC
+from ._lapjv import lapjv, lapjv_extended, LARGE_ as LARGE, FP_1_ as FP_1, FP_2_ as FP_2, FP_DYNAMIC_ as FP_DYNAMIC
 from ._seeded_jv import lapjv_seeded
 
 __version__ = "0.5.12+mi355x"

@@ -1,4 +1,6 @@
-"""lapjv: mirror of LAP/_lapjv_cpp/_lapjv.pyx:38-129 (square, unlimited path) over the HIP C ABI."""
+"""lapjv: mirror of LAP/_lapjv_cpp/_lapjv.pyx:38-129 over the HIP C ABI.  `lapjv` is the square, unlimited
+path; `lapjv_extended` is the whole function, rectangular (`extend_cost`) and thresholded (`cost_limit`)
+problems included."""
 from __future__ import annotations
 
 import numpy as np
@@ -23,8 +25,8 @@ def lapjv(cost, extend_cost=False, cost_limit=np.inf, return_cost=True):
                          "non-square, pass extend_cost=True.")
     if extend_cost or cost_limit < np.inf:
         raise NotImplementedError(
-            "extend_cost / cost_limit (rectangular and thresholded problems, _lapjv.pyx:79-95) are "
-            "outside the warm-start hot path and not built here")
+            "extend_cost / cost_limit (rectangular and thresholded problems, _lapjv.pyx:79-95) are not "
+            "routed through lapjv yet: call lap.lapjv_extended with the same arguments")
     n = n_rows
     x = np.empty((n,), dtype=np.int32)
     y = np.empty((n,), dtype=np.int32)
@@ -39,5 +41,47 @@ def lapjv(cost, extend_cost=False, cost_limit=np.inf, return_cost=True):
             raise RuntimeError("Unknown error (lapjv_internal returned %d)." % ret)
     if return_cost:
         opt = cost_c[np.arange(n_rows), x].sum()
+        return opt, x, y
+    return x, y
+
+
+def lapjv_extended(cost, extend_cost=False, cost_limit=np.inf, return_cost=True):
+    """The reference's ``lapjv`` for every combination of its arguments (_lapjv.pyx:38-129): returns
+    ``(opt, x, y)`` or ``(x, y)``, int32 ``x`` (n_rows) and ``y`` (n_cols) with -1 for unmatched rows and
+    columns.  With ``cost_limit < inf`` the problem solved is (n_rows + n_cols) square, else with
+    ``extend_cost`` max(n_rows, n_cols) square; only ``cost`` is copied to the device, the square matrix is
+    built there.  ``opt`` sums ``cost[i, x[i]]`` over the matched rows in numpy's summation order."""
+    if cost is None:
+        raise TypeError("Argument 'cost' must not be None")
+    try:  # `double cost_limit` is converted when the arguments are parsed; a str is a TypeError there
+        cost_limit = float(cost_limit)
+    except ValueError:
+        raise TypeError("must be real number, not %s" % type(cost_limit).__name__) from None
+    cost = np.asarray(cost)
+    if cost.ndim != 2:
+        raise ValueError("2-dimensional array expected")
+    cost_c = np.ascontiguousarray(cost, dtype=np.double)
+    n_rows, n_cols = cost_c.shape
+    if n_rows != n_cols and not extend_cost:
+        raise ValueError("Square cost array expected. If cost is intentionally "
+                         "non-square, pass extend_cost=True.")
+    if not (extend_cost or cost_limit < np.inf):
+        return lapjv(cost_c, return_cost=return_cost)
+    x = np.full((n_rows,), -1, dtype=np.int32)
+    y = np.full((n_cols,), -1, dtype=np.int32)
+    opt = np.float64(0.0)
+    if n_rows > 0 and n_cols > 0:  # else nothing can be matched: every entry stays -1
+        lib = _hip.require_device()
+        opt_c = _hip.ct.c_double(np.nan)
+        ret = lib.lapwarm_lapjv_extended(cost_c.ctypes.data_as(_hip.c_dp), n_rows, n_cols, int(bool(extend_cost)),
+                                         cost_limit, x.ctypes.data_as(_hip.c_ip), y.ctypes.data_as(_hip.c_ip),
+                                         _hip.ct.byref(opt_c))
+        _hip.check(ret, "lapjv_extended")
+        if ret != 0:
+            if ret == -1:
+                raise MemoryError("Out of memory.")
+            raise RuntimeError("Unknown error (lapjv_internal returned %d)." % ret)
+        opt = np.float64(opt_c.value)
+    if return_cost:
         return opt, x, y
     return x, y

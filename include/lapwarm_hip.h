@@ -73,6 +73,20 @@ int lapwarm_oracle_duals(const double *C, int n, const int *rows, const int *col
 int lapwarm_warmstart_lapjv(const double *C, int n, const double *u, const double *v, int shift_nonneg,
                             int *x, int *y);
 
+/* The reference's `lapjv(cost, extend_cost, cost_limit)` for a rectangular and / or cost-limited
+ * problem (LAP/_lapjv_cpp/_lapjv.pyx:77-95 before the solve, :115-124 after it).  C (n_rows x n_cols,
+ * row-major) is copied to the device as it is; the square matrix the reference solves is built there.
+ * x [n_rows], y [n_cols] int32 with -1 for unmatched; *opt (may be NULL) = the sum of C[i][x[i]] over the
+ * matched rows in numpy's summation order.  Returns 0, the codes of lapwarm_lapjv_extended_n, or those of
+ * lapwarm_lapjv_dense; x, y, *opt are written only when 0 is returned. */
+int lapwarm_lapjv_extended(const double *C, int n_rows, int n_cols, int extend_cost, double cost_limit,
+                           int *x, int *y, double *opt);
+
+/* n of the square problem the reference solves for this shape and these arguments (_lapjv.pyx:77-95):
+ * n_rows + n_cols when cost_limit < inf, else max(n_rows, n_cols); -2 for n_rows or n_cols <= 0, -4 for a
+ * non-square shape without extend_cost, -5 when n > 16384.  Needs no device. */
+int lapwarm_lapjv_extended_n(int n_rows, int n_cols, int extend_cost, double cost_limit);
+
 /* ------------------------------------------------------------------------------------------
  * (2) Batched, device pointers, stream-ordered.  `stream` is a hipStream_t (NULL = default).
  *     Every function returns 0 or <= -1000 (HIP error); per-instance codes go to `ret`.
@@ -109,6 +123,27 @@ int lapwarm_seeded_batched(const double *C, int batch, int n, const double *u_se
 int lapwarm_lapjv_batched(const double *C, int batch, int n, int *x, int *y, int *ret,
                           long long *stats, void *workspace, size_t workspace_bytes,
                           int threads_hint, void *stream);
+
+/* Batched rectangular / cost-limited lapjv, one shape per call.  C [batch][n_rows][n_cols]; x [batch][n_rows],
+ * y [batch][n_cols] int32 with -1 for unmatched; opt [batch] fp64 (sum of C[i][x[i]] over the matched rows in
+ * row order, numpy's pairwise summation of the compacted vector) and matched [batch] int (rows with
+ * x != -1), either may be NULL; ret [batch]; stats [batch][32] or NULL: the cold solve's, for the n x n problem.
+ * Instances with ret != 0: x, y all -1, opt NaN, matched 0.  Returns 0, the codes of
+ * lapwarm_lapjv_extended_n (nothing is launched), -2 also for batch <= 0, batch > 65535 (the batch is one
+ * dimension of the extension kernel's grid) or a workspace that is not 16-byte aligned (E is written with
+ * 16-byte stores; C may have any 8-byte alignment), -1 workspace too small, <= -1000 HIP error.
+ * Three steps on the caller's stream, kernels only: the extension kernel writes E [batch][n][n] into the
+ * workspace (E[:n_rows, :n_cols] = C, cost_limit / 2. beside and below it, 0 in E[n_rows:, n_cols:]; zeros
+ * around C without a limit; a square C without a limit is solved where it is), the cold solve of
+ * lapwarm_lapjv_batched runs on E, the finish kernel maps x, y and sums opt.  The workspace holds E, the
+ * solver's x, y [batch][n], the matched costs [batch][n_rows] and lapwarm_lapjv_workspace_bytes(batch, n);
+ * every word of it that is read is written inside the call. */
+size_t lapwarm_lapjv_extended_workspace_bytes(int batch, int n_rows, int n_cols, int extend_cost,
+                                              double cost_limit);
+int lapwarm_lapjv_extended_batched(const double *C, int batch, int n_rows, int n_cols, int extend_cost,
+                                   double cost_limit, int *x, int *y, double *opt, int *matched, int *ret,
+                                   long long *stats, void *workspace, size_t workspace_bytes,
+                                   int threads_hint, void *stream);
 
 /* As lapwarm_lapjv_batched, and also returns the optimal dual pair of each instance:
  * v [batch][n] = the solver's final column duals, u [batch][n] with u_i = C[i][x_i] - v[x_i]

@@ -1,0 +1,332 @@
+"""Rectangular and cost-limited lapjv on the GPU: `lap.lapjv_extended` (lapwarm_lapjv_extended),
+`WarmStartPipeline.lapjv_extended_batch` and the C entry point lapwarm_lapjv_extended_batched.
+
+Everything is exact equality.  The fixtures of tests/golden/lapjv_extended_cases.npz hold the reference
+build's own answers; at the sizes fixtures cannot reach the yardstick is the CPU oracle on the matrix E
+that numpy builds as LAP/_lapjv_cpp/_lapjv.pyx:84-95 does (test_lapjv_extended_host.py checks that the
+oracle reproduces every fixture), with _lapjv.pyx:116-122 applied afterwards: x, y equal, opt bitwise
+equal to the numpy expression, and the solver's ARR iterations, paths and relax steps equal to the
+oracle's."""
+import ctypes as ct
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from lapjv_extended_common import ExtendedCases, assert_case, bits, build_E, finish, solve_with
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parents[1]
+PKG = ROOT / "gnn-accelerated-lap-warm-start-pipeline_amd"
+CASES = ExtendedCases()
+COUNTERS = ((11, "arr_iters"), (4, "paths"), (6, "scan_steps"))
+INF = float("inf")
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need the MI355X"
+    return torch
+
+
+@pytest.fixture(scope="module")
+def pipe(torch_cuda):
+    from gnn import OneGNN, WarmStartPipeline
+    return WarmStartPipeline(OneGNN(21), "cuda:0")
+
+
+def _host(out):
+    return {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+
+
+def _oracle(C, extend_cost, cost_limit):
+    from oracle import jv
+    opt, x, y, (so,) = solve_with(jv.dense_raw, C, extend_cost, cost_limit)
+    return opt, x, y, so
+
+
+def _check_against_oracle(label, C, extend_cost, cost_limit, o, b=0, counters=True):
+    """o: host dict of lapjv_extended_batch; instance b against the oracle on the numpy-built E."""
+    opt, x, y, so = _oracle(C, extend_cost, cost_limit)
+    st = o["stats"][b]
+    print(f"{label}: matched {o['matched'][b]} opt {o['opt'][b]!r} (oracle {opt!r}) "
+          + " ".join(f"{name} {st[q]}/{so[name]}" for q, name in COUNTERS)
+          + f" lists {st[27]} coop {st[15]}")
+    assert o["ret"][b] == 0, (label, o["ret"][b], st[12])
+    assert np.array_equal(o["x"][b], x) and np.array_equal(o["y"][b], y), label
+    assert o["matched"][b] == (x != -1).sum(), label
+    assert bits(o["opt"][b]) == bits(opt), (label, o["opt"][b], opt)
+    if counters:
+        for q, name in COUNTERS:
+            assert st[q] == so[name], (label, name, st[q], so[name])
+    return so
+
+
+# --------------------------------------------------------------------------- fixtures
+@pytest.mark.parametrize("k", range(len(CASES)), ids=CASES.labels)
+def test_fixture_host_dropin(k):
+    """`lap.lapjv_extended(C, extend_cost, cost_limit)`: opt, x, y equal the reference's."""
+    import lap
+    c = CASES.case(k)
+    opt, x, y = lap.lapjv_extended(c["C"], c["extend_cost"], c["cost_limit"])
+    assert_case(c, opt, x, y)
+    x2, y2 = lap.lapjv_extended(c["C"], c["extend_cost"], c["cost_limit"], return_cost=False)
+    assert np.array_equal(x2, x) and np.array_equal(y2, y)
+
+
+@pytest.mark.parametrize("k", range(len(CASES)), ids=CASES.labels)
+def test_fixture_batched(torch_cuda, pipe, k):
+    """`lapjv_extended_batch` with the fixture three times in one batch: every instance equals the
+    reference's, matched counts the rows with x != -1."""
+    torch = torch_cuda
+    c = CASES.case(k)
+    C = torch.from_numpy(np.stack([c["C"]] * 3)).cuda()
+    o = _host(pipe.lapjv_extended_batch(C, c["extend_cost"], c["cost_limit"]))
+    for b in range(3):
+        assert o["ret"][b] == 0, (c["label"], o["ret"][b])
+        assert_case(c, o["opt"][b], o["x"][b], o["y"][b])
+        assert o["matched"][b] == (c["x"] != -1).sum()
+
+
+def test_square_without_limit_falls_through_to_lapjv():
+    """extend_cost=False, no limit: the square path that exists today, same values."""
+    import lap
+    C = np.random.RandomState(3).uniform(size=(50, 50))
+    a = lap.lapjv_extended(C)
+    b = lap.lapjv(C)
+    assert bits(a[0]) == bits(b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    assert a[1].dtype == np.int32 and (a[1] >= 0).all()
+
+
+# --------------------------------------------------------------------------- larger shapes against the oracle
+def _uniform(seed, shape):
+    return np.random.RandomState(seed).uniform(size=shape)
+
+
+def _int1000(seed, shape):
+    return np.random.RandomState(seed).randint(1, 1001, size=shape).astype(np.float64)
+
+
+MEDIUM = {
+    "extend_300x200": (lambda: _uniform(11, (300, 200)), True, INF),
+    "extend_200x300": (lambda: _uniform(12, (200, 300)), True, INF),
+    "limit_255x256_n511": (lambda: _uniform(13, (255, 256)), True, 0.02),     # below the candidate lists
+    "limit_256x256_n512": (lambda: _uniform(14, (256, 256)), False, 0.02),    # the first size with them
+    "limit_301x277_even_n_odd_cols": (lambda: _uniform(15, (301, 277)), True, 0.015),  # n = 578
+    "limit_150x127_odd_n": (lambda: _uniform(16, (150, 127)), True, 0.05),    # n = 277: odd rows of E
+    "extend_101x77_odd_n": (lambda: _int1000(17, (101, 77)), True, INF),      # n = 101, n_cols odd
+    "limit_ints_256x256": (lambda: _int1000(18, (256, 256)), False, 20.5),
+}
+
+
+@pytest.mark.parametrize("name", list(MEDIUM))
+def test_medium_shapes_against_oracle(torch_cuda, pipe, name):
+    torch = torch_cuda
+    make, extend_cost, limit = MEDIUM[name]
+    C = make()
+    o = _host(pipe.lapjv_extended_batch(torch.from_numpy(C[None]).cuda(), extend_cost, limit))
+    _check_against_oracle(name, C, extend_cost, limit, o)
+    # the host drop-in on the same matrix
+    import lap
+    opt, x, y = lap.lapjv_extended(C, extend_cost, limit)
+    assert np.array_equal(x, o["x"][0]) and np.array_equal(y, o["y"][0]) and bits(opt) == bits(o["opt"][0])
+
+
+@pytest.mark.parametrize("kind,limit", [("uniform", 0.004), ("uniform", 0.01), ("uniform", 0.05),
+                                        ("int1000", 2.5), ("int1000", 5.5), ("int1000", 500.5)])
+def test_limited_1024_k3_geometry(torch_cuda, pipe, kind, limit):
+    """1024 x 1024 with a cost limit: n = 2048, the geometry of the K3 benchmark."""
+    torch = torch_cuda
+    C = (_uniform if kind == "uniform" else _int1000)(21, (1024, 1024))
+    o = _host(pipe.lapjv_extended_batch(torch.from_numpy(C[None]).cuda(), False, limit))
+    _check_against_oracle(f"{kind}_1024_limit_{limit}", C, False, limit, o)
+
+
+def test_extended_2048x1024(torch_cuda, pipe):
+    torch = torch_cuda
+    C = _uniform(22, (2048, 1024))
+    o = _host(pipe.lapjv_extended_batch(torch.from_numpy(C[None]).cuda(), True, INF))
+    _check_against_oracle("extend_2048x1024", C, True, INF, o)
+    assert o["matched"][0] == 1024 and (o["y"][0] >= 0).all()
+
+
+_COOP_CHILD = """
+import sys, time
+sys.path[:0] = [%r, %r]
+import numpy as np, torch
+from gnn import OneGNN, WarmStartPipeline
+C = np.random.RandomState(23).uniform(size=(2300, 2300))
+pipe = WarmStartPipeline(OneGNN(21), "cuda:0")
+Cd = torch.from_numpy(C[None]).cuda()
+torch.cuda.synchronize()
+t = time.time()
+o = pipe.lapjv_extended_batch(Cd, False, 0.003)
+torch.cuda.synchronize()
+dt = time.time() - t
+np.savez(sys.argv[1], seconds=dt, **{k: v.cpu().numpy() for k, v in o.items()})
+"""
+
+
+def test_limited_2300_cooperative_path(tmp_path):
+    """2300 x 2300 with a cost limit: n = 4600, above the cooperative threshold (preparation with lists,
+    cooperative shortest paths, final phase).  The solve runs in a child process under its own time limit of
+    ten minutes (measured: 1.6 s on an MI355X as the first call of a fresh process)."""
+    out = tmp_path / "coop.npz"
+    t = time.time()
+    r = subprocess.run([sys.executable, "-c", _COOP_CHILD % (str(ROOT), str(PKG)), str(out)], capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    z = np.load(out)
+    o = {k: z[k] for k in ("x", "y", "opt", "matched", "ret", "stats")}
+    print(f"n = 4600: call {float(z['seconds']):.3f} s, child process {time.time() - t:.1f} s")
+    C = np.random.RandomState(23).uniform(size=(2300, 2300))
+    _check_against_oracle("limit_2300x2300_n4600", C, False, 0.003, o)
+    assert o["stats"][0, 15] >= 0, o["stats"][0, 15]  # the cooperative kernel took part
+
+
+# --------------------------------------------------------------------------- batches, NULL outputs, streams
+def test_batch_of_eight_equals_eight_single_calls(torch_cuda, pipe):
+    torch = torch_cuda
+    Cs = np.stack([_uniform(30 + b, (90, 130)) if b % 2 else _int1000(30 + b, (90, 130)) / 1000.0
+                   for b in range(8)])
+    for extend_cost, limit in ((True, INF), (True, 0.03)):
+        o = _host(pipe.lapjv_extended_batch(torch.from_numpy(Cs).cuda(), extend_cost, limit))
+        for b in range(8):
+            s = _host(pipe.lapjv_extended_batch(torch.from_numpy(Cs[b:b + 1]).cuda(), extend_cost, limit))
+            for key in ("x", "y", "matched", "ret"):
+                assert np.array_equal(o[key][b], s[key][0]), (b, key)
+            assert bits(o["opt"][b]) == bits(s["opt"][0]), b
+            for q, _ in COUNTERS:
+                assert o["stats"][b, q] == s["stats"][0, q], (b, q)
+        _check_against_oracle("batch8[5]", Cs[5], extend_cost, limit, o, b=5)
+
+
+def _raw_call(torch, lib, C, extend_cost, limit, want_opt=True, want_matched=True, fill=None, stream=None):
+    """lapwarm_lapjv_extended_batched with a workspace of this test's own."""
+    B, n_rows, n_cols = C.shape
+    nbytes = lib.lapwarm_lapjv_extended_workspace_bytes(B, n_rows, n_cols, int(extend_cost), limit)
+    assert nbytes > 0
+    dev = C.device
+    x = torch.full((B, n_rows), -7, dtype=torch.int32, device=dev)
+    y = torch.full((B, n_cols), -7, dtype=torch.int32, device=dev)
+    opt = torch.full((B,), -7.0, dtype=torch.float64, device=dev)
+    matched = torch.full((B,), -7, dtype=torch.int32, device=dev)
+    ret = torch.full((B,), -7, dtype=torch.int32, device=dev)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    if fill is not None:
+        ws.fill_(fill)
+    torch.cuda.synchronize()
+    s = stream.cuda_stream if stream is not None else 0
+    rc = lib.lapwarm_lapjv_extended_batched(C.data_ptr(), B, n_rows, n_cols, int(extend_cost), limit, x.data_ptr(),
+                                            y.data_ptr(), opt.data_ptr() if want_opt else None,
+                                            matched.data_ptr() if want_matched else None, ret.data_ptr(), None,
+                                            ws.data_ptr(), nbytes, 0, ct.c_void_p(s))
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in dict(x=x, y=y, opt=opt, matched=matched, ret=ret).items()}
+
+
+@pytest.mark.parametrize("shape,extend_cost,limit", [((60, 41), True, 0.05), ((41, 60), True, INF),
+                                                     ((64, 40), True, 0.05)])
+def test_cost_matrix_on_an_odd_8_byte_offset(torch_cuda, pipe, shape, extend_cost, limit):
+    """C that is 8-byte but not 16-byte aligned (a view one double into a larger buffer): the extension
+    kernel reads it with 8-byte loads; same result as the aligned copy.  A workspace that is not 16-byte
+    aligned is refused with -2."""
+    torch = torch_cuda
+    Cs = np.stack([_uniform(70 + b, shape) for b in range(2)])
+    aligned = torch.from_numpy(Cs).cuda()
+    buf = torch.empty((Cs.size + 1,), dtype=torch.float64, device="cuda")
+    C = buf[1:].view(Cs.shape)
+    C.copy_(aligned)
+    assert C.data_ptr() % 16 == 8 and aligned.data_ptr() % 16 == 0
+    base = _raw_call(torch, pipe.lib, aligned, extend_cost, limit)
+    o = _raw_call(torch, pipe.lib, C, extend_cost, limit, fill=0xFF)
+    for key in ("x", "y", "matched", "ret"):
+        assert np.array_equal(o[key], base[key]), key
+    assert np.array_equal(bits(o["opt"]), bits(base["opt"]))
+    opt, x, y, _ = _oracle(Cs[0], extend_cost, limit)
+    assert np.array_equal(o["x"][0], x) and np.array_equal(o["y"][0], y) and bits(o["opt"][0]) == bits(opt)
+    lib = pipe.lib
+    nbytes = lib.lapwarm_lapjv_extended_workspace_bytes(2, shape[0], shape[1], int(extend_cost), limit)
+    ws = torch.empty((nbytes + 16,), dtype=torch.uint8, device="cuda")
+    rc = lib.lapwarm_lapjv_extended_batched(C.data_ptr(), 2, shape[0], shape[1], int(extend_cost), limit, None,
+                                            None, None, None, None, None, ws.data_ptr() + 8, nbytes, 0, None)
+    assert rc == -2
+
+
+def test_null_opt_and_matched_are_accepted(torch_cuda, pipe):
+    torch = torch_cuda
+    C = torch.from_numpy(np.stack([_uniform(40, (70, 45)), _uniform(41, (70, 45))])).cuda()
+    full = _raw_call(torch, pipe.lib, C, True, 0.1)
+    for want_opt, want_matched in ((False, True), (True, False), (False, False)):
+        o = _raw_call(torch, pipe.lib, C, True, 0.1, want_opt, want_matched)
+        assert np.array_equal(o["x"], full["x"]) and np.array_equal(o["y"], full["y"]) and (o["ret"] == 0).all()
+        assert np.array_equal(bits(o["opt"]), bits(full["opt"])) if want_opt else (o["opt"] == -7.0).all()
+        assert np.array_equal(o["matched"], full["matched"]) if want_matched else (o["matched"] == -7).all()
+
+
+def test_limit_below_every_entry_matches_nothing(torch_cuda, pipe):
+    torch = torch_cuda
+    C = np.stack([_uniform(50 + b, (33, 58)) + 0.25 for b in range(3)])
+    o = _host(pipe.lapjv_extended_batch(torch.from_numpy(C).cuda(), True, 0.2))
+    assert (o["ret"] == 0).all() and (o["x"] == -1).all() and (o["y"] == -1).all()
+    assert (o["matched"] == 0).all()
+    assert np.array_equal(bits(o["opt"]), bits(np.zeros(3))), o["opt"]  # +0.0, as np.sum of nothing
+    import lap
+    opt, x, y = lap.lapjv_extended(C[0], True, 0.2)
+    assert bits(opt) == bits(0.0) and (x == -1).all() and (y == -1).all()
+
+
+@pytest.mark.parametrize("shape,extend_cost,limit", [((120, 77), True, 0.04), ((77, 120), True, INF),
+                                                     ((64, 64), True, INF), ((600, 300), True, INF)])
+def test_side_stream_and_poisoned_workspace(torch_cuda, pipe, shape, extend_cost, limit):
+    """Every word of the workspace that the kernels read is written inside the call: the result on a
+    non-default stream with the workspace filled with 0xFF equals the one with a zeroed workspace on the
+    default stream."""
+    torch = torch_cuda
+    Cs = np.stack([_uniform(60 + b, shape) for b in range(2)])
+    C = torch.from_numpy(Cs).cuda()
+    base = _raw_call(torch, pipe.lib, C, extend_cost, limit, fill=0)
+    side = torch.cuda.Stream()
+    o = _raw_call(torch, pipe.lib, C, extend_cost, limit, fill=0xFF, stream=side)
+    for key in ("x", "y", "matched", "ret"):
+        assert np.array_equal(o[key], base[key]), key
+    assert np.array_equal(bits(o["opt"]), bits(base["opt"]))
+    E = build_E(Cs[1], extend_cost, limit)
+    from oracle import jv
+    r, xo, yo, _ = jv.dense_raw(E)
+    opt, x, y = finish(E, xo, yo, *shape)
+    assert r == 0 and np.array_equal(o["x"][1], x) and np.array_equal(o["y"][1], y) and bits(o["opt"][1]) == bits(opt)
+
+
+def test_too_large_returns_minus_5_without_launching(torch_cuda, pipe):
+    """n = n_rows + n_cols > 16384: -5 before any pointer is touched (they are all NULL here)."""
+    lib = pipe.lib
+    assert lib.lapwarm_lapjv_extended_n(9000, 9000, 0, 1.0) == -5
+    assert lib.lapwarm_lapjv_extended_workspace_bytes(1, 9000, 9000, 0, 1.0) == 0
+    rc = lib.lapwarm_lapjv_extended_batched(None, 1, 9000, 9000, 0, 1.0, None, None, None, None, None, None, None, 0,
+                                            0, None)
+    assert rc == -5
+    assert lib.lapwarm_lapjv_extended_batched(None, 1, 16385, 3, 1, INF, None, None, None, None, None, None, None,
+                                              0, 0, None) == -5
+    import lap
+    with pytest.raises(ValueError, match="16384"):
+        lap.lapjv_extended(np.zeros((16385, 1)), extend_cost=True)
+    torch = torch_cuda
+    with pytest.raises(ValueError, match="16384"):
+        pipe.lapjv_extended_batch(torch.zeros((1, 16000, 400), dtype=torch.float64, device="cuda"), True, 1.0)
+    with pytest.raises(ValueError, match="Square cost array expected"):
+        pipe.lapjv_extended_batch(torch.zeros((1, 4, 5), dtype=torch.float64, device="cuda"), False, 1.0)
+
+
+def test_lapjv_still_refuses_the_two_arguments():
+    import lap
+    with pytest.raises(NotImplementedError, match="lapjv_extended"):
+        lap.lapjv(np.zeros((3, 4)), extend_cost=True)
+    with pytest.raises(NotImplementedError, match="lapjv_extended"):
+        lap.lapjv(np.zeros((3, 3)), cost_limit=1.0)
