@@ -1189,9 +1189,9 @@ __global__ void __launch_bounds__(64) coop_ssp_kernel(CoopParams p)
     const int b = p.first + grp * 8 + rem % 8;
     if (b >= p.first + p.count || b >= p.batch) return;
     int *hand = p.hand + (size_t)b * kHandInts;
-    const int nf = hand[0];
-    const int f_first = hand[1];  // > 0: relaunched behind a path that jv_instance_kernel searched
-    if (nf <= 0 || hand[2] != 0 || hand[4] != 0 || hand[3] != 0 || f_first >= nf) return;
+    const int nf = hand[kHandFreeRows];
+    const int f_first = hand[kHandPathsDone];  // > 0: relaunched behind a path that jv_instance_kernel searched
+    if (!hand_coop_may_run(hand)) return;
     const int n = p.n;
     const size_t o = (size_t)b * n;
 
@@ -1291,37 +1291,37 @@ __global__ void __launch_bounds__(64) coop_ssp_kernel(CoopParams p)
         done = f + 1;
     }
     if (g == 0 && m.lane == 0) {
-        hand[1] = done;
-        hand[2] = m.err;
-        hand[3] = m.bail_reason;
+        hand[kHandPathsDone] = done;
+        hand[kHandCoopErr] = m.err;
+        hand[kHandStopReason] = m.bail_reason;
         long long *cs = p.cstats + (size_t)b * kCoopStats;
-        cs[0] += m.paths;
-        cs[1] += m.finds;
-        cs[2] += m.scan_steps;
-        cs[3] += m.scan_elems;
-        cs[4] += m.init_elems;
-        cs[5] = ((cs[5] & 0xffffffffffll) + (long long)m.seq) | (m.same_xcd ? (1ll << 40) : 0);
+        cs[kCsPaths] += m.paths;
+        cs[kCsFinds] += m.finds;
+        cs[kCsScanSteps] += m.scan_steps;
+        cs[kCsScanElems] += m.scan_elems;
+        cs[kCsInitElems] += m.init_elems;
+        cs[kCsRounds] = ((cs[kCsRounds] & 0xffffffffffll) + (long long)m.seq) | (m.same_xcd ? (1ll << 40) : 0);
 #ifdef LAPWARM_COOP_STAMPS
-        for (int qd = 0; qd < 6; ++qd) cs[6 + qd] += m.stamps[qd];
+        for (int qd = 0; qd < 6; ++qd) cs[kCsStamp0 + qd] += m.stamps[qd];
 #endif
     }
 #ifdef LAPWARM_COOP_STAMPS
     // imbalance between the members of an instance: smallest / largest total of the poll segment and of
-    // everything else in a relax round (slots 12 .. 15; reset by phase 1)
+    // everything else in a relax round (reset by phase 1)
     if (m.lane == 0) {
         unsigned long long *cs = reinterpret_cast<unsigned long long *>(p.cstats + (size_t)b * kCoopStats);
         const unsigned long long poll_c = (unsigned long long)m.stamps[3];
         const unsigned long long work_c = (unsigned long long)(m.stamps[0] + m.stamps[1] + m.stamps[2] + m.stamps[4] +
                                                                 m.stamps[5] + m.stamps[6]);
-        atomicMax(&cs[12], poll_c);
-        atomicMax(&cs[13], work_c);
-        atomicMax(&cs[14], ~poll_c);  // (max of the complement = min)
-        atomicMax(&cs[15], ~work_c);
+        atomicMax(&cs[kCsPollMax], poll_c);
+        atomicMax(&cs[kCsWorkMax], work_c);
+        atomicMax(&cs[kCsPollMinC], ~poll_c);  // (max of the complement = min)
+        atomicMax(&cs[kCsWorkMinC], ~work_c);
     }
 #endif
     if (g != 0 && m.err && m.lane == 0) {
         // a member other than the leader saw the error first: make sure it is not lost
-        atomicMax(&hand[4], m.err);
+        atomicMax(&hand[kHandMemberErr], m.err);
     }
 }
 

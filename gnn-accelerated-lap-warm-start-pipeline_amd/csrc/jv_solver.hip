@@ -158,7 +158,7 @@ struct Solver {
     int ctrl_seen0, ctrl_seen1, ctrl_find_seq;
     int err;
 #ifdef LAPWARM_STAMPS
-    long long stamps[16];
+    long long stamps[kStampSlots];
 #endif
 
     __device__ __forceinline__ int base() const { return bc.tid * CH; }
@@ -470,9 +470,6 @@ struct Solver {
         // 2-4 tie events behind the single barrier: only with <= 4 positions per thread (with 8+
         // the extra live values of that path spill: n = 16384 went from 25 s to 55 s with it)
         constexpr bool kFastMulti = CH <= 4;
-#ifdef LAPWARM_DIAG_BARRIER
-        int diag_prev_cnt = -1;
-#endif
         bool pf_have = false;  // level 8: the current head's row sits in slot pf_slot
         int pf_slot = 0;
         double level = 0.0;
@@ -897,24 +894,12 @@ struct Solver {
             __syncthreads();
             STAMPR(tr3);
             STAMP_ADD(3, tr3, tr2);
-#ifdef LAPWARM_DIAG_BARRIER  // barrier wait by the event count of the PREVIOUS step (slots 9-12 reused)
-            if (diag_prev_cnt == 0) {
-                STAMP_ADD(9, tr3, tr2);
-                STAMP_INC(10);
-            } else if (diag_prev_cnt == 1) {
-                STAMP_ADD(11, tr3, tr2);
-                STAMP_INC(12);
-            }
-#endif
             // one LDS round trip for everything the post phase can need
             const int tot_raw = ctrl->ev_total[par];
             EventSlot sl = ctrl->rec[par][0];
             const int a_raw = ctrl->a_pub[par][0];
             const int tot = uni(tot_raw);
             const int cnt = tot - seen;
-#ifdef LAPWARM_DIAG_BARRIER
-            diag_prev_cnt = cnt;
-#endif
             if (par)
                 seen1 = tot;
             else
@@ -1859,7 +1844,7 @@ struct Solver {
     __device__ __forceinline__ int cold_prepare(double *lval, int *lcol, double *ltau)
     {
         int nf = cold_column_reduction();
-        if (LISTS && bc.tid == 0) ctrl->first_fire = 0;  // (counts the list iterations: stats slot 27)
+        if (LISTS && bc.tid == 0) ctrl->first_fire = 0;  // (counts the list iterations: kStListIters)
         if (LISTS && lval && nf > 0) {
             if (bc.tid == 0) ltau[0] = __longlong_as_double(0x7ff8000000000000LL);  // "lists not built yet"
             fence_if_global();
@@ -1935,7 +1920,7 @@ struct Solver {
         }
         if (lane == 0) ctrl->nfree = nf;
     }
-    __device__ __forceinline__ void greedy_wave0(const uint32_t *tight_bits, const int *)
+    __device__ __forceinline__ void greedy_wave0(const uint32_t *tight_bits)
     {
         constexpr int kMaxWords = (CH * TB + 31) / 32;  // the largest bitmap this instantiation can meet
         if (kMaxWords <= kWave || W <= kWave)
@@ -2148,7 +2133,7 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
     s.ctrl_seen0 = s.ctrl_seen1 = 0;
     s.ctrl_find_seq = 0;
 #ifdef LAPWARM_STAMPS
-    for (int q = 0; q < 16; ++q) s.stamps[q] = 0;
+    for (int q = 0; q < kStampSlots; ++q) s.stamps[q] = 0;
 #endif
     s.err = 0;
 
@@ -2204,15 +2189,17 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
         const size_t ng = (size_t)p.mail_granules;
         for (size_t q = tid; q < ng; q += blockDim.x) p.mail[(size_t)b * ng + q] = 0ull;
         const int *hand = p.hand + (size_t)b * kHandInts;
-        if (hand[3] == 0 || hand[2] != 0 || hand[4] != 0 || hand[1] >= hand[0]) return;  // nothing pending (uniform)
+        if (hand[kHandStopReason] == 0 || hand[kHandCoopErr] != 0 || hand[kHandMemberErr] != 0 ||
+            hand[kHandPathsDone] >= hand[kHandFreeRows])
+            return;  // nothing pending (uniform)
     }
     if (!LISTS && (p.phase == 2 || p.phase == 3)) {
         // ---- resume behind the cooperative kernel: x, y, v and the free rows come back from the
-        // global state arrays, the rows hand[1] .. hand[0] are still to be augmented
+        // global state arrays, the rows hand[kHandPathsDone] .. hand[kHandFreeRows] are still to be augmented
         const size_t o = (size_t)b * n;
         int *hand = p.hand + (size_t)b * kHandInts;
-        nf = hand[0];
-        const int f0 = hand[1];
+        nf = hand[kHandFreeRows];
+        const int f0 = hand[kHandPathsDone];
         const int f_end = (p.phase == 3) ? ((f0 + 1 < nf) ? f0 + 1 : nf) : nf;
         for (int j = tid; j < n; j += blockDim.x) {
             if (s.x != p.g_x + o) s.x[j] = p.g_x[o + j];
@@ -2220,15 +2207,16 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
             if (s.v != p.g_v + o) s.v[j] = p.g_v[o + j];
             if (s.fr != p.g_fr + o && j < nf) s.fr[j] = p.g_fr[o + j];
         }
-        branch = hand[5];
-        tight_total = hand[6];
-        free_after_greedy = hand[7];
-        s.arr_fired = hand[8];
-        s.transfer_rows = hand[9];
-        s.arr_iters = hand[10];
-        s.colred_elems = ((long long)hand[12] << 32) | (unsigned)hand[11];
-        s.err = hand[13];
-        if (hand[2] | hand[4]) s.err = 30 + ((hand[2] | hand[4]) & 31);  // the cooperative kernel failed
+        branch = hand[kHandBranch];
+        tight_total = hand[kHandTightEdges];
+        free_after_greedy = hand[kHandFreeAfterGreedy];
+        s.arr_fired = hand[kHandArrFired];
+        s.transfer_rows = hand[kHandTransferRows];
+        s.arr_iters = hand[kHandArrIters];
+        s.colred_elems = ((long long)hand[kHandColredHi] << 32) | (unsigned)hand[kHandColredLo];
+        s.err = hand[kHandPrepErr];
+        if (hand[kHandCoopErr] | hand[kHandMemberErr])  // the cooperative kernel failed
+            s.err = 30 + ((hand[kHandCoopErr] | hand[kHandMemberErr]) & 31);
         __syncthreads();
         if (!s.err && f0 >= 0 && f0 < f_end) s.augment_all(f0, f_end);
         if (p.phase == 3) {
@@ -2242,28 +2230,28 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
             }
             if (tid == 0) {
                 const int e3 = s.err | s.ctrl->err;
-                hand[1] = f_end;
-                hand[3] = 0;
-                if (e3) hand[13] = e3;
+                hand[kHandPathsDone] = f_end;
+                hand[kHandStopReason] = 0;
+                if (e3) hand[kHandPrepErr] = e3;
                 if (p.cstats) {
                     long long *cs = p.cstats + (size_t)b * kCoopStats;
-                    cs[0] += s.paths;
-                    cs[1] += s.finds;
-                    cs[2] += s.scan_steps;
-                    cs[3] += s.scan_elems;
-                    cs[4] += s.init_elems;
-                    cs[15] += 1;  // paths searched outside the cooperative kernel, one launch each
+                    cs[kCsPaths] += s.paths;
+                    cs[kCsFinds] += s.finds;
+                    cs[kCsScanSteps] += s.scan_steps;
+                    cs[kCsScanElems] += s.scan_elems;
+                    cs[kCsInitElems] += s.init_elems;
+                    cs[kCsOutsidePaths] += 1;
                 }
             }
             return;
         }
         if (p.cstats) {
             const long long *cs = p.cstats + (size_t)b * kCoopStats;
-            s.paths += (int)cs[0];
-            s.finds += (int)cs[1];
-            s.scan_steps += (int)cs[2];
-            s.scan_elems += cs[3];
-            s.init_elems += cs[4];
+            s.paths += (int)cs[kCsPaths];
+            s.finds += (int)cs[kCsFinds];
+            s.scan_steps += (int)cs[kCsScanSteps];
+            s.scan_elems += cs[kCsScanElems];
+            s.init_elems += cs[kCsInitElems];
         }
     }
     int tight_local = 0;
@@ -2302,7 +2290,7 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
         free_after_greedy = nf;
         run_paths = nf > 0;
     } else if constexpr (!LISTS) {
-        if (s.bc.wave == 0) s.greedy_wave0(p.tight_bits + (size_t)b * n * W, p.tight_cnt + (size_t)b * n);
+        if (s.bc.wave == 0) s.greedy_wave0(p.tight_bits + (size_t)b * n * W);
         __syncthreads();
         nf = s.ctrl->nfree;
         free_after_greedy = nf;
@@ -2330,24 +2318,24 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
         if (tid == 0) {
             int *hand = p.hand + (size_t)b * kHandInts;
             const int e1 = s.err | s.ctrl->err;
-            hand[0] = (run_paths && !e1) ? nf : 0;
-            hand[1] = 0;
-            hand[2] = 0;
-            hand[3] = 0;
-            hand[4] = 0;
-            hand[5] = (int)branch;
-            hand[6] = (int)tight_total;
-            hand[7] = (int)free_after_greedy;
-            hand[8] = s.arr_fired;
-            hand[9] = s.transfer_rows;
-            hand[10] = s.arr_iters;
-            hand[11] = (int)(s.colred_elems & 0xffffffffLL);
-            hand[12] = (int)(s.colred_elems >> 32);
-            hand[13] = e1;
-            hand[14] = LISTS ? s.ctrl->first_fire : 0;  // row-reduction iterations answered from the candidate lists
-            {  // this launch's duration, 10 ns ticks (phase 2 adds it to stats slot 13)
+            hand[kHandFreeRows] = (run_paths && !e1) ? nf : 0;
+            hand[kHandPathsDone] = 0;
+            hand[kHandCoopErr] = 0;
+            hand[kHandStopReason] = 0;
+            hand[kHandMemberErr] = 0;
+            hand[kHandBranch] = (int)branch;
+            hand[kHandTightEdges] = (int)tight_total;
+            hand[kHandFreeAfterGreedy] = (int)free_after_greedy;
+            hand[kHandArrFired] = s.arr_fired;
+            hand[kHandTransferRows] = s.transfer_rows;
+            hand[kHandArrIters] = s.arr_iters;
+            hand[kHandColredLo] = (int)(s.colred_elems & 0xffffffffLL);
+            hand[kHandColredHi] = (int)(s.colred_elems >> 32);
+            hand[kHandPrepErr] = e1;
+            hand[kHandListIters] = LISTS ? s.ctrl->first_fire : 0;
+            {  // this launch's duration (phase 2 adds it to kStKernelTicks)
                 const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - t_start;
-                hand[15] = (dt < 0x7fffffffull) ? (int)dt : 0x7fffffff;
+                hand[kHandPrepTicks] = (dt < 0x7fffffffull) ? (int)dt : 0x7fffffff;
             }
             if (p.cstats) {
                 for (int q = 0; q < kCoopStats; ++q) p.cstats[(size_t)b * kCoopStats + q] = 0;
@@ -2380,34 +2368,35 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
         p.ret[b] = err ? (-100 - err) : 0;
         if (p.stats) {
             long long *st = p.stats + (size_t)b * kStatsPerInstance;
-            st[0] = branch;
-            st[1] = tight_total;
-            st[2] = (branch == kBranchFallback || branch == kBranchCold) ? nf : free_after_greedy;
-            st[3] = s.arr_fired;
-            st[4] = s.paths;
-            st[5] = s.finds;
-            st[6] = s.scan_steps;
-            st[7] = s.scan_elems;
-            st[8] = s.init_elems;
-            st[9] = s.colred_elems;
-            st[10] = s.transfer_rows;
-            st[11] = s.arr_iters;
-            st[12] = err;
+            st[kStBranch] = branch;
+            st[kStTightEdges] = tight_total;
+            st[kStFreeRows] = (branch == kBranchFallback || branch == kBranchCold) ? nf : free_after_greedy;
+            st[kStArrFired] = s.arr_fired;
+            st[kStPaths] = s.paths;
+            st[kStFinds] = s.finds;
+            st[kStScanSteps] = s.scan_steps;
+            st[kStScanElems] = s.scan_elems;
+            st[kStInitElems] = s.init_elems;
+            st[kStColredElems] = s.colred_elems;
+            st[kStTransferRows] = s.transfer_rows;
+            st[kStArrIters] = s.arr_iters;
+            st[kStErr] = err;
             const unsigned long long t_end = __builtin_amdgcn_s_memrealtime();
-            st[13] = (long long)(t_end - t_start);     // whole kernel, 10 ns ticks
-            if (p.phase == 2) st[13] += p.hand[(size_t)b * kHandInts + 15];  // + the preparation launch
-            st[14] = (long long)(t_serial - t_start);  // greedy + micro-ARR part (SSP branch)
-            // paths the cooperative kernel completed | why it stopped early << 32 (-1: not used)
-            st[15] = (p.phase == 2 && p.mail) ? ((long long)p.hand[(size_t)b * kHandInts + 1] |
-                                       ((long long)p.hand[(size_t)b * kHandInts + 3] << 32))
-                                    : -1;
-            for (int q = 16; q < kStatsPerInstance; ++q) st[q] = 0;
-            if (p.phase == 2) st[27] = p.hand[(size_t)b * kHandInts + 14];  // row-reduction iterations answered from the candidate lists
+            st[kStKernelTicks] = (long long)(t_end - t_start);  // whole kernel
+            if (p.phase == 2) st[kStKernelTicks] += p.hand[(size_t)b * kHandInts + kHandPrepTicks];
+            st[kStSerialTicks] = (long long)(t_serial - t_start);
+            st[kStCoopPaths] = (p.phase == 2 && p.mail)
+                                   ? ((long long)p.hand[(size_t)b * kHandInts + kHandPathsDone] |
+                                      ((long long)p.hand[(size_t)b * kHandInts + kHandStopReason] << 32))
+                                   : -1;
+            for (int q = kStCoopReport; q < kStatsPerInstance; ++q) st[q] = 0;
+            if (p.phase == 2) st[kStListIters] = p.hand[(size_t)b * kHandInts + kHandListIters];
             if (p.phase == 2 && p.cstats) {
-                for (int q = 0; q < 11; ++q) st[16 + q] = p.cstats[(size_t)b * kCoopStats + 5 + q];  // exchange rounds; stamps
+                for (int q = 0; q < kCoopReportSlots; ++q)
+                    st[kStCoopReport + q] = p.cstats[(size_t)b * kCoopStats + kCsReport + q];
             }
 #ifdef LAPWARM_STAMPS
-            for (int q = 0; q < 16; ++q) st[16 + q] = s.stamps[q];
+            for (int q = 0; q < kStampSlots; ++q) st[kStStamps + q] = s.stamps[q];
 #endif
         }
     }
@@ -2506,7 +2495,6 @@ size_t solver_lds_bytes(int n, int ch, int level)
 {
     const int W = (n + 31) >> 5;
     const int Wpad = (W + 1) & ~1;
-    (void)ch;
     size_t bytes = sizeof(BlockExchange) + sizeof(Ctrl) + sizeof(uint32_t) * (size_t)Wpad * 5;
     if (level == 8) {  // control blocks + the row slots; all solver state in global memory
         const size_t padded = ((size_t)n + (size_t)ch * 64 - 1) / ((size_t)ch * 64) * ((size_t)ch * 64);

@@ -17,8 +17,92 @@ constexpr int kBranchAllMatched = 2;
 constexpr int kBranchFallback = 3;
 constexpr int kBranchCold = 4;
 
-constexpr int kStatsPerInstance = 32;  // 0..15 counters, 16..31 cycle stamps (diagnostic builds)
+constexpr int kStatsPerInstance = 32;
 constexpr size_t kLdsBudgetBytes = 160 * 1024;
+
+constexpr int kHandInts = 16;
+constexpr int kCoopStats = 16;
+
+// hand[]: the hand-over block of one instance, kHandInts ints: what jv_instance_kernel (phases 1, 2, 3) and
+// coop_ssp_kernel tell each other between the launches of a solve that consists of several.  Phase 1
+// writes every slot.
+enum HandSlot {
+    kHandFreeRows = 0,  // rows the shortest-path phase has to augment (0: nothing for it to do)
+    kHandPathsDone,     // resume index into the free-row list: paths completed so far
+    kHandCoopErr,       // error code of the cooperative kernel's leader
+    kHandStopReason,    // why the cooperative kernel stopped before the last path (0: it did not)
+    kHandMemberErr,     // error seen by a member other than the leader (atomicMax)
+    // what phase 1 knows and phase 2 reports
+    kHandBranch,
+    kHandTightEdges,
+    kHandFreeAfterGreedy,
+    kHandArrFired,      // micro-ARR firings
+    kHandTransferRows,  // reduction-transfer rows
+    kHandArrIters,
+    kHandColredLo,      // column-reduction elements, 64 bits in two slots
+    kHandColredHi,
+    kHandPrepErr,       // error of phase 1, or of a phase 3
+    kHandListIters,     // row-reduction iterations answered from candidate lists
+    kHandPrepTicks,     // duration of the phase-1 launch, 10 ns ticks (saturating)
+};
+static_assert(kHandPrepTicks == kHandInts - 1, "hand[] layout");
+
+// coop_ssp_kernel: may it take the next path of this instance?
+__host__ __device__ __forceinline__ bool hand_coop_may_run(const int *hand)
+{
+    return !(hand[kHandFreeRows] <= 0 || hand[kHandCoopErr] != 0 || hand[kHandMemberErr] != 0 ||
+             hand[kHandStopReason] != 0 || hand[kHandPathsDone] >= hand[kHandFreeRows]);
+}
+
+// cstats[]: kCoopStats int64 per instance, zeroed by phase 1: what the shortest-path phase counts outside
+// phase 2 (coop_ssp_kernel, and phase 3 for the paths it runs).
+enum CoopStat {
+    kCsPaths = 0,  // the path counters: phase 2 adds them to its own
+    kCsFinds,
+    kCsScanSteps,
+    kCsScanElems,
+    kCsInitElems,
+    kCsReport,               // ---- the block phase 2 copies to stats[kStCoopReport ..] starts here
+    kCsRounds = kCsReport,   // exchange rounds (low 40 bits) | all members on one XCD << 40
+    kCsStamp0,               // 6 cycle-stamp sums (-DLAPWARM_COOP_STAMPS builds)
+    kCsPollMax = kCsStamp0 + 6,  // stamp builds, over the members (atomicMax on the slot as unsigned):
+    kCsWorkMax,                  //   largest poll / work total,
+    kCsPollMinC,                 //   complement of the smallest poll total,
+    kCsWorkMinC,                 //   ... and of the smallest work total
+    kCsOutsidePaths = kCsWorkMinC,  // shipped builds: paths searched by phase 3, one launch each
+    // (as before these names existed, a COOP_STAMPS build that runs a phase 3 adds that 1 to the complement
+    // of the smallest work total: the two uses of the last slot were never separated)
+};
+constexpr int kCoopReportSlots = kCoopStats - kCsReport;
+static_assert(kCsOutsidePaths == kCoopStats - 1, "cstats layout");
+
+// stats[]: kStatsPerInstance int64 per instance.  The slot numbers are public ABI (include/lapwarm_hip.h
+// documents them; Python indexes by number); these names are for the library's own code.
+enum StatSlot {
+    kStBranch = 0,
+    kStTightEdges,
+    kStFreeRows,
+    kStArrFired,
+    kStPaths,
+    kStFinds,
+    kStScanSteps,
+    kStScanElems,
+    kStInitElems,
+    kStColredElems,
+    kStTransferRows,
+    kStArrIters,
+    kStErr,
+    kStKernelTicks,  // 10 ns ticks; a solve of several launches adds the preparation launch
+    kStSerialTicks,  // greedy + micro-ARR part (SSP branch)
+    kStCoopPaths,    // paths the cooperative kernel completed | why it stopped early << 32 (-1: not used)
+    kStCoopReport,   // kCoopReportSlots slots: cstats[kCsReport ..]
+    kStListIters = 27,          // row-reduction iterations answered from candidate lists
+    kStStamps = kStCoopReport,  // -DLAPWARM_STAMPS builds: kStampSlots cycle stamps instead (they overwrite
+                                // the cooperative report and kStListIters, as they always did)
+};
+constexpr int kStampSlots = 16;
+static_assert(kStCoopReport == 16 && kStCoopReport + kCoopReportSlots <= kStListIters, "stats layout");
+static_assert(kStStamps + kStampSlots == kStatsPerInstance, "stats layout");
 
 struct SolverParams {
     const double *C;  // [batch][n][n] row-major fp64
@@ -38,21 +122,23 @@ struct SolverParams {
     double *v_out;             // [batch][n] final column duals or null
     double *u_out;             // [batch][n] u_i = C[i][x_i] - v[x_i] or null
     int *ret;                  // [batch]
-    long long *stats;          // [batch][kStatsPerInstance] or null
+    long long *stats;          // [batch][kStatsPerInstance] (StatSlot) or null
     // per-instance state in global memory, only used when the state does not fit LDS
     double *g_dist, *g_v;
     int *g_order, *g_pred, *g_y, *g_x, *g_fr, *g_evl, *g_tmpcol;
-    // helper workgroups (EXPERIMENT, LAPWARM_HELPER=1): [batch][kRingInts] ring of upcoming head
-    // rows, zeroed by the caller; word 0 = done flag, words 2.. = (generation << 16 | row)
+    // helper workgroups (phase-0 launches of seeded solves; LAPWARM_HELPER=0 turns them off):
+    // [batch][kRingInts] ring of upcoming head rows, zeroed by the caller; word 0 = done flag,
+    // words 2.. = (generation << 16 | row)
     int *pf_ring;
-    int helper;
+    int helper;  // helper workgroups per instance (0: none)
     // cooperative shortest-path phase (coop_ssp.hip): phase 0 = the whole solve in this kernel;
     // 1 = stop before the shortest-path phase and leave x, y, v, the free-row list in the global
-    // state arrays + hand[]; 2 = take x, y, v back, run the paths the cooperative kernel left
-    // (hand[1] .. hand[0]) and write the outputs
+    // state arrays + the hand-over block; 2 = take x, y, v back, run the paths the cooperative kernel
+    // left (hand[kHandPathsDone] .. hand[kHandFreeRows]) and write the outputs; 3 = between two launches of the
+    // cooperative kernel: run the one path it stopped at
     int phase;
-    int *hand;                 // [batch][kHandInts]
-    long long *cstats;         // [batch][kCoopStats] path counters of the cooperative kernel
+    int *hand;                 // [batch][kHandInts] (HandSlot)
+    long long *cstats;         // [batch][kCoopStats] (CoopStat)
     unsigned long long *mail;  // [batch][mail_granules] zeroed by phase 1
     int mail_granules;
     // candidate lists of the augmenting row reduction (cold solves, lapwarm_lapjv_*_batched):
@@ -65,13 +151,6 @@ constexpr int kArrListEntries = 128;
 constexpr int kRingSlots = 64;
 constexpr int kRingInts = 2 + kRingSlots;
 
-// hand[]: 0 free rows, 1 paths done by the cooperative kernel (resume index), 2 its error code,
-// 3 why it stopped early, 4 error seen by a member other than the leader, 5.. what phase 1 knows
-// and phase 2 reports (14: row-reduction iterations answered from candidate lists, 15: duration of the phase-1 launch) (branch, tight edges, free rows after greedy, micro-ARR firings, transfer
-// rows, ARR iterations, column-reduction elements lo/hi, phase-1 error)
-constexpr int kHandInts = 16;
-constexpr int kCoopStats = 16;
-
 struct CoopParams {
     const double *C;
     int n, batch;
@@ -80,7 +159,7 @@ struct CoopParams {
     int xcd_stores;    // allow workgroup-scope mailbox stores when all members of an instance share an XCD
     double *v;         // [batch][n] column duals (the solver's global state arrays)
     int *x, *y, *pred;
-    const int *fr;     // [batch][n] free rows, hand[0] of them
+    const int *fr;     // [batch][n] free rows, hand[kHandFreeRows] of them
     int *hand;
     long long *cstats;
     unsigned long long *mail;

@@ -339,6 +339,37 @@ def test_workspace_sizes_are_unchanged():
             assert got == want, (kind, batch, [(n, g, w) for n, g, w in zip(WS_SIZES_N, got, want) if g != w])
 
 
+# solver_lds_bytes(n, ch, level) for n in WS_SIZES_N, recorded from the library before the kernel's LDS carving
+# and the host's byte count became one layout function.  Levels 0..2 do not depend on ch (every ch in
+# LDS_SIZES_CH gave the row below); level 8 exists for the 512 x 16 geometry of n = 8192 only.
+LDS_SIZES_CH = (1, 2, 4, 8, 16)
+LDS_SIZES = {
+    0: [
+        1816, 1816, 1936, 1936, 2096, 2096, 2416, 2456, 3056, 4056, 4056, 4336, 4576, 4576, 6896, 6936, 12016],
+    1: [
+        1860, 4128, 11124, 11160, 20500, 20536, 39288, 39364, 76792, 134888, 134924, 151800, 163956, 163992,
+        301816, 301892, 601848],
+    2: [
+        1868, 4640, 13164, 13208, 24588, 24632, 47480, 47564, 93176, 163960, 164004, 184568, 199372, 199416,
+        367352, 367436, 732920],
+}
+LDS_SIZE_LARGE_ROWS = ((8192, 16, 8), 137984)
+
+
+def test_solver_lds_sizes_are_unchanged():
+    import ctypes as ct
+    from lap import _hip
+    lib = _hip.load()
+    nbytes = lib._ZN7lapwarm16solver_lds_bytesEiii
+    nbytes.restype, nbytes.argtypes = ct.c_size_t, [ct.c_int, ct.c_int, ct.c_int]
+    for level, want in LDS_SIZES.items():
+        for ch in LDS_SIZES_CH:
+            got = [nbytes(n, ch, level) for n in WS_SIZES_N]
+            assert got == want, (level, ch, [(n, g, w) for n, g, w in zip(WS_SIZES_N, got, want) if g != w])
+    args, want = LDS_SIZE_LARGE_ROWS
+    assert nbytes(*args) == want, (args, nbytes(*args), want)
+
+
 def test_forced_cooperative_geometry_without_an_instantiation_is_not_planned():
     """LAPWARM_COOP_CH=1 at n = 2048 gives 32 members and 3 granule loads per lane: no coop_ssp_kernel<1, 3>
     exists, so the solve takes the one-workgroup path; n = 640 (10 members, <1, 1>) stays cooperative.
