@@ -18,6 +18,36 @@ namespace {
 
 constexpr int kSweepThreads = 256;
 
+// The minima of the dual utilities and of the min-trick restate NumPy expressions (np.min, np.minimum),
+// and those propagate NaN: one NaN among the operands makes the result NaN.  dmin, the reference C++'s
+// `<`, keeps whichever operand came first when the other is NaN, so the solver-side kernels (prelude,
+// projection, features) stay on dmin and the NumPy-side sweeps use nmin and the reductions built on it.
+__device__ __forceinline__ double nmin(double a, double b) { return (b < a || b != b) ? b : a; }
+
+__device__ __forceinline__ double wave_nmin(double v)
+{
+#define LAPWARM_STEP(C, M) v = nmin(v, dpp_move<C, M>(pos_inf(), v));
+    LAPWARM_DPP_REDUCE(LAPWARM_STEP)
+#undef LAPWARM_STEP
+    return readlane_f64(v, kWave - 1);
+}
+
+// BlockCtx::min_f64 with nmin
+__device__ __forceinline__ double block_nmin(BlockCtx &bc, double v)
+{
+    v = wave_nmin(v);
+    const int p = bc.parity;
+    bc.parity ^= 1;
+    if (bc.lane == 0) bc.ex->d[p][bc.wave] = v;
+    __syncthreads();
+    const int w = bc.lane & (kMaxWaves - 1);
+    double r = (w < bc.nwaves) ? bc.ex->d[p][w] : pos_inf();
+#define LAPWARM_STEP(C, M) r = nmin(r, dpp_move<C, M>(pos_inf(), r));
+    LAPWARM_DPP_ROW_REDUCE(LAPWARM_STEP)
+#undef LAPWARM_STEP
+    return readlane_f64(r, 15);
+}
+
 // ------------------------------------------------------------------------------------------
 // Seeded prelude: one workgroup per row.  Fuses four of the reference's five O(n^2) loops:
 // projection-candidate count, verify, row tightening, tight-edge bitmap + count.
@@ -160,7 +190,8 @@ projection_kernel(const double *C, int n, double *u, double *v, const int *viol_
 }
 
 // ------------------------------------------------------------------------------------------
-// Column minima: out[b][j] = min_i (C[b][i][j] - u[b][i]).  Two columns per lane (16 B loads)
+// Column minima: out[b][j] = min_i (C[b][i][j] - u[b][i]), NaN if any operand is (np.min).
+// Two columns per lane (16 B loads)
 // when n is even, a chunk of rows per workgroup, partial minima combined by a second kernel.
 // ------------------------------------------------------------------------------------------
 template <bool HAS_U, bool PAIR>
@@ -180,11 +211,11 @@ colmin_partial_kernel(const double *C, int n, const double *u, double *partial, 
         const double ui = HAS_U ? ub[i] : 0.0;
         if constexpr (PAIR) {
             const double2 c = *reinterpret_cast<const double2 *>(base + (size_t)i * n);
-            m0 = dmin(m0, HAS_U ? c.x - ui : c.x);
-            m1 = dmin(m1, HAS_U ? c.y - ui : c.y);
+            m0 = nmin(m0, HAS_U ? c.x - ui : c.x);
+            m1 = nmin(m1, HAS_U ? c.y - ui : c.y);
         } else {
             const double c = base[(size_t)i * n];
-            m0 = dmin(m0, HAS_U ? c - ui : c);
+            m0 = nmin(m0, HAS_U ? c - ui : c);
         }
     }
     double *out = partial + ((size_t)b * chunks + chunk) * n + j;
@@ -199,7 +230,7 @@ __global__ void colmin_final_kernel(const double *partial, int n, int chunks, do
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     double m = mode ? out[(size_t)b * n + j] : pos_inf();
-    for (int c = 0; c < chunks; ++c) m = dmin(m, partial[((size_t)b * chunks + c) * n + j]);
+    for (int c = 0; c < chunks; ++c) m = nmin(m, partial[((size_t)b * chunks + c) * n + j]);
     out[(size_t)b * n + j] = m;
 }
 
@@ -227,12 +258,12 @@ rowmin_kernel(const double *C, int n, const double *u, const double *v, double *
             r = (c - ui) - vb[j];
         else
             r = vb ? c - vb[j] : c;
-        m = dmin(m, r);
+        m = nmin(m, r);
     }
-    m = bc.min_f64(m);
+    m = block_nmin(bc, m);
     if (bc.tid == 0) {
         const size_t o = (size_t)b * n + i;
-        out[o] = (kind == 1) ? dmin(out[o], m) : m;
+        out[o] = (kind == 1) ? nmin(out[o], m) : m;
     }
 }
 
@@ -243,8 +274,8 @@ __global__ void __launch_bounds__(kSweepThreads) vecmin_kernel(const double *in,
     BlockCtx bc;
     bc.init(&ex);
     double m = pos_inf();
-    for (int j = bc.tid; j < n; j += kSweepThreads) m = dmin(m, in[(size_t)b * n + j]);
-    m = bc.min_f64(m);
+    for (int j = bc.tid; j < n; j += kSweepThreads) m = nmin(m, in[(size_t)b * n + j]);
+    m = block_nmin(bc, m);
     if (bc.tid == 0) out[b] = m;
 }
 

@@ -153,6 +153,10 @@ int lapwarm_lapjv_duals_batched(const double *C, int batch, int n, int *x, int *
                                 int *ret, long long *stats, void *workspace, size_t workspace_bytes,
                                 int threads_hint, void *stream);
 
+/* The sweeps below restate NumPy expressions (np.min, np.minimum) and treat NaN as NumPy does: a NaN in C,
+ * u or v makes every minimum it takes part in NaN (lapwarm_colmin_batched, lapwarm_rowmin_batched,
+ * lapwarm_project_round_batched, gmin of lapwarm_reduce_costs_batched, and the host entries built on them).
+ * The solver entry points keep the reference C++'s `<` comparisons, which pass over NaN. */
 size_t lapwarm_sweep_workspace_bytes(int batch, int n);
 
 /* out[b][j] = min_i (C[b][i][j] - u[b][i]); u may be NULL. */
