@@ -81,13 +81,6 @@ __device__ __forceinline__ void st_f64(double *p, double x)
 }
 __device__ __forceinline__ int ld_i32(const int *p) { return (int)__hip_atomic_load((gu32 *)p, LAPWARM_RLX_AGENT); }
 __device__ __forceinline__ void st_i32(int *p, int x) { __hip_atomic_store((gu32 *)p, (unsigned)x, LAPWARM_RLX_AGENT); }
-__device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ unsigned lo32(double x) { return (unsigned)(__double_as_longlong(x) & 0xffffffffLL); }
-__device__ __forceinline__ unsigned hi32(double x) { return (unsigned)((unsigned long long)__double_as_longlong(x) >> 32); }
-__device__ __forceinline__ double mk_f64(unsigned lo, unsigned hi)
-{
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 enum { kRcGo = 0, kRcTarget = 1, kRcBail = 2, kRcErr = 3 };
 

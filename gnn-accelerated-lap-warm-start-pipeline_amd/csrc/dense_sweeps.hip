@@ -18,36 +18,6 @@ namespace {
 
 constexpr int kSweepThreads = 256;
 
-// The minima of the dual utilities and of the min-trick restate NumPy expressions (np.min, np.minimum),
-// and those propagate NaN: one NaN among the operands makes the result NaN.  dmin, the reference C++'s
-// `<`, keeps whichever operand came first when the other is NaN, so the solver-side kernels (prelude,
-// projection, features) stay on dmin and the NumPy-side sweeps use nmin and the reductions built on it.
-__device__ __forceinline__ double nmin(double a, double b) { return (b < a || b != b) ? b : a; }
-
-__device__ __forceinline__ double wave_nmin(double v)
-{
-#define LAPWARM_STEP(C, M) v = nmin(v, dpp_move<C, M>(pos_inf(), v));
-    LAPWARM_DPP_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    return readlane_f64(v, kWave - 1);
-}
-
-// BlockCtx::min_f64 with nmin
-__device__ __forceinline__ double block_nmin(BlockCtx &bc, double v)
-{
-    v = wave_nmin(v);
-    const int p = bc.parity;
-    bc.parity ^= 1;
-    if (bc.lane == 0) bc.ex->d[p][bc.wave] = v;
-    __syncthreads();
-    const int w = bc.lane & (kMaxWaves - 1);
-    double r = (w < bc.nwaves) ? bc.ex->d[p][w] : pos_inf();
-#define LAPWARM_STEP(C, M) r = nmin(r, dpp_move<C, M>(pos_inf(), r));
-    LAPWARM_DPP_ROW_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    return readlane_f64(r, 15);
-}
-
 // ------------------------------------------------------------------------------------------
 // Seeded prelude: one workgroup per row.  Fuses four of the reference's five O(n^2) loops:
 // projection-candidate count, verify, row tightening, tight-edge bitmap + count.
@@ -260,7 +230,7 @@ rowmin_kernel(const double *C, int n, const double *u, const double *v, double *
             r = vb ? c - vb[j] : c;
         m = nmin(m, r);
     }
-    m = block_nmin(bc, m);
+    m = bc.min_f64<NanMinF64>(m);
     if (bc.tid == 0) {
         const size_t o = (size_t)b * n + i;
         out[o] = (kind == 1) ? nmin(out[o], m) : m;
@@ -275,7 +245,7 @@ __global__ void __launch_bounds__(kSweepThreads) vecmin_kernel(const double *in,
     bc.init(&ex);
     double m = pos_inf();
     for (int j = bc.tid; j < n; j += kSweepThreads) m = nmin(m, in[(size_t)b * n + j]);
-    m = block_nmin(bc, m);
+    m = bc.min_f64<NanMinF64>(m);
     if (bc.tid == 0) out[b] = m;
 }
 
@@ -554,30 +524,6 @@ __device__ __forceinline__ void reduce_min_max_sum(BlockCtx &bc, double &a, doub
     }
 }
 
-// sum(a), sum(b) (doubles) and sum(k) (int) behind one barrier
-__device__ __forceinline__ void reduce_sum_sum_isum(BlockCtx &bc, double &a, double &b, int &k)
-{
-    a = wave_sum_f64(a);
-    b = wave_sum_f64(b);
-    k = wave_sum_i32(k);
-    const int p = bc.parity;
-    bc.parity ^= 1;
-    if (bc.lane == 0) {
-        bc.ex->d[p][bc.wave] = a;
-        bc.ex->d[p][kMaxWaves + bc.wave] = b;
-        bc.ex->i[p][bc.wave] = k;
-    }
-    __syncthreads();
-    a = bc.ex->d[p][0];
-    b = bc.ex->d[p][kMaxWaves];
-    k = bc.ex->i[p][0];
-    for (int w = 1; w < bc.nwaves; ++w) {
-        a += bc.ex->d[p][w];
-        b += bc.ex->d[p][kMaxWaves + w];
-        k += bc.ex->i[p][w];
-    }
-}
-
 // sum(a), sum(b), sum(c) (doubles) and sum(k1), sum(k2) (ints) behind one barrier
 __device__ __forceinline__ void reduce_sum3_isum2(BlockCtx &bc, double &a, double &b, double &c, int &k1, int &k2)
 {
@@ -610,14 +556,12 @@ __device__ __forceinline__ void reduce_sum3_isum2(BlockCtx &bc, double &a, doubl
     }
 }
 
-template <bool CACHE_E>
 __global__ void __launch_bounds__(kSweepThreads, 6) row_features_kernel(FeatureParams p, int npad)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     BlockExchange *ex = reinterpret_cast<BlockExchange *>(smem);
     double *s = reinterpret_cast<double *>(smem + sizeof(BlockExchange));
-    double *ev = s + npad;  // exp(-(x - lo)), kept between the two entropy passes when it fits
-    SelectState *st = reinterpret_cast<SelectState *>(s + (CACHE_E ? 2 : 1) * (size_t)npad);
+    SelectState *st = reinterpret_cast<SelectState *>(s + npad);
     const int b = blockIdx.y, i = blockIdx.x, n = p.n;
     BlockCtx bc;
     bc.init(ex);
@@ -658,7 +602,6 @@ __global__ void __launch_bounds__(kSweepThreads, 6) row_features_kernel(FeatureP
         sq += dlt * dlt;
         const double xl = x - lo;
         const double e = exp(-xl);
-        if constexpr (CACHE_E) ev[j] = e;
         esum += e;
         if (e > 0.0) {
             tsum += e * xl;
@@ -679,7 +622,7 @@ __global__ void __launch_bounds__(kSweepThreads, 6) row_features_kernel(FeatureP
         ent = 0.0;
 #pragma unroll 2
         for (int j = bc.tid; j < n; j += kSweepThreads) {
-            const double e = CACHE_E ? ev[j] : exp(-(s[j] - lo));
+            const double e = exp(-(s[j] - lo));
             const double pj = e * rdenom;
             ent += pj * log(pj + kFeatEps);
         }
@@ -814,17 +757,11 @@ static hipError_t colmin_impl(const double *C, int n, int batch, const double *u
     const bool pair = (n % 2) == 0 && (reinterpret_cast<uintptr_t>(C) % 16) == 0;
     const int cols_per_block = kSweepThreads * (pair ? 2 : 1);
     dim3 grid((n + cols_per_block - 1) / cols_per_block, chunks, batch);
-    if (u) {
-        if (pair)
-            hipLaunchKernelGGL((colmin_partial_kernel<true, true>), grid, dim3(kSweepThreads), 0, stream, C, n, u, partial, rows_per, chunks);
-        else
-            hipLaunchKernelGGL((colmin_partial_kernel<true, false>), grid, dim3(kSweepThreads), 0, stream, C, n, u, partial, rows_per, chunks);
-    } else {
-        if (pair)
-            hipLaunchKernelGGL((colmin_partial_kernel<false, true>), grid, dim3(kSweepThreads), 0, stream, C, n, u, partial, rows_per, chunks);
-        else
-            hipLaunchKernelGGL((colmin_partial_kernel<false, false>), grid, dim3(kSweepThreads), 0, stream, C, n, u, partial, rows_per, chunks);
-    }
+    using Kernel = decltype(&colmin_partial_kernel<false, false>);
+    static constexpr Kernel kPartial[2][2] = {{colmin_partial_kernel<false, false>, colmin_partial_kernel<false, true>},
+                                              {colmin_partial_kernel<true, false>, colmin_partial_kernel<true, true>}};
+    hipLaunchKernelGGL(kPartial[u != nullptr][pair], grid, dim3(kSweepThreads), 0, stream, C, n, u, partial, rows_per,
+                       chunks);
     hipLaunchKernelGGL(colmin_final_kernel, dim3((n + 255) / 256, batch), dim3(256), 0, stream,
                        partial, n, chunks, out, final_mode);
     return hipGetLastError();
@@ -879,20 +816,15 @@ hipError_t launch_row_features(const FeatureParams &p, hipStream_t stream)
 {
     if (p.n > 16384 || p.n < 1) return hipErrorInvalidValue;
     const int npad = (p.n + 1) & ~1;
-    // exp(-(x - lo)) is no longer kept in LDS between the entropy passes: the closed form needs it
-    // once, the element-wise path recomputes it, and the 8 n bytes saved let 6-7 workgroups share a
-    // CU (measured: 1.29 -> 1.02 ms for 32 x 2048 rows together with the 6-waves-per-SIMD bound)
-    const bool cache = false;
-    const size_t lds = sizeof(BlockExchange) + sizeof(double) * (size_t)npad * (cache ? 2 : 1) + sizeof(SelectState) +
+    // exp(-(x - lo)) is not kept in LDS between the entropy passes: the closed form needs it once, the
+    // element-wise path recomputes it, and the 8 n bytes saved let 6-7 workgroups share a CU
+    // (measured: 1.29 -> 1.02 ms for 32 x 2048 rows together with the 6-waves-per-SIMD bound)
+    const size_t lds = sizeof(BlockExchange) + sizeof(double) * (size_t)npad + sizeof(SelectState) +
                        (size_t)npad;  // + one bucket byte per element
-    const void *fn = cache ? reinterpret_cast<const void *>(row_features_kernel<true>)
-                           : reinterpret_cast<const void *>(row_features_kernel<false>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(row_features_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    if (cache)
-        hipLaunchKernelGGL(row_features_kernel<true>, dim3(p.n, p.batch), dim3(kSweepThreads), lds, stream, p, npad);
-    else
-        hipLaunchKernelGGL(row_features_kernel<false>, dim3(p.n, p.batch), dim3(kSweepThreads), lds, stream, p, npad);
+    hipLaunchKernelGGL(row_features_kernel, dim3(p.n, p.batch), dim3(kSweepThreads), lds, stream, p, npad);
     return hipGetLastError();
 }
 

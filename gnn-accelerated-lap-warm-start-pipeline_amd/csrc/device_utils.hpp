@@ -22,22 +22,33 @@ constexpr int kFlagProjected = 4;       // the projection kernel changed (u,v): 
 // divergent branch that consumes it, which serialises the memory latencies of a thread's gathers.
 __device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
 
+// The two 32-bit halves of a double, and the double made of two halves: what every 32-bit lane
+// primitive (readfirstlane, readlane, DPP) and every 32-bit record field moves a double as.
+__device__ __forceinline__ int lo32(double x) { return (int)(__double_as_longlong(x) & 0xffffffffLL); }
+__device__ __forceinline__ int hi32(double x) { return (int)(__double_as_longlong(x) >> 32); }
+__device__ __forceinline__ double mk_f64(int lo, int hi)
+{
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
 // Values that are identical in every lane (read from a uniform LDS address, or the result of a
 // full butterfly) are moved to scalar registers so that the control state machine of the solver
 // runs on the scalar unit instead of being replicated on the vector ALUs of 16 waves.
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ double uni(double x)
 {
-    const long long b = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffLL));
-    const int hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+    return mk_f64(__builtin_amdgcn_readfirstlane(lo32(x)), __builtin_amdgcn_readfirstlane(hi32(x)));
 }
 
 __device__ __forceinline__ unsigned umin_u32(unsigned a, unsigned b) { return a < b ? a : b; }
 __device__ __forceinline__ double pos_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
 
 __device__ __forceinline__ double dmin(double a, double b) { return (b < a) ? b : a; }
+// The minima of the dual utilities and of the min-trick restate NumPy expressions (np.min, np.minimum),
+// and those propagate NaN: one NaN among the operands makes the result NaN.  dmin, the reference C++'s
+// `<`, keeps whichever operand came first when the other is NaN, so the solver-side kernels (prelude,
+// projection, features) stay on dmin and the NumPy-side sweeps use nmin and the reductions built on it.
+__device__ __forceinline__ double nmin(double a, double b) { return (b < a || b != b) ? b : a; }
 
 __device__ __forceinline__ bool pair_less(double a, int ia, double b, int ib)
 {
@@ -59,12 +70,12 @@ __device__ __forceinline__ int dpp_move(int old, int src)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_move(double old, double src)
 {
-    const long long o = __double_as_longlong(old), x = __double_as_longlong(src);
-    const int lo = dpp_move<CTRL, ROW_MASK>((int)(o & 0xffffffffLL), (int)(x & 0xffffffffLL));
-    const int hi = dpp_move<CTRL, ROW_MASK>((int)(o >> 32), (int)(x >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+    return mk_f64(dpp_move<CTRL, ROW_MASK>(lo32(old), lo32(src)),
+                  dpp_move<CTRL, ROW_MASK>(hi32(old), hi32(src)));
 }
 
+__device__ __forceinline__ int readlane(int x, int l) { return __builtin_amdgcn_readlane(x, l); }
+// (spelled with its own split and join: on lo32 / hi32 / mk_f64 the solver kernels schedule differently)
 __device__ __forceinline__ double readlane_f64(double x, int l)
 {
     const long long b = __double_as_longlong(x);
@@ -72,63 +83,7 @@ __device__ __forceinline__ double readlane_f64(double x, int l)
     const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
-
-// Wave64 reduction skeleton: after the six steps lane 63 holds the reduction of all lanes.
-#define LAPWARM_DPP_REDUCE(STEP)      \
-    STEP(kDppRowShr1, 0xf)            \
-    STEP(kDppRowShr2, 0xf)            \
-    STEP(kDppRowShr4, 0xf)            \
-    STEP(kDppRowShr8, 0xf)            \
-    STEP(kDppRowBcast15, 0xa)         \
-    STEP(kDppRowBcast31, 0xc)
-
-// ---- wave-level reductions (all 64 lanes must be active) --------------------------------
-__device__ __forceinline__ double wave_min(double v)
-{
-#define LAPWARM_STEP(C, M) v = dmin(v, dpp_move<C, M>(pos_inf(), v));
-    LAPWARM_DPP_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    return readlane_f64(v, kWave - 1);
-}
-
-__device__ __forceinline__ int wave_min_i32(int v)
-{
-#define LAPWARM_STEP(C, M)                                  \
-    {                                                       \
-        const int o = dpp_move<C, M>(0x7fffffff, v);        \
-        v = (o < v) ? o : v;                                \
-    }
-    LAPWARM_DPP_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    return __builtin_amdgcn_readlane(v, kWave - 1);
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-#define LAPWARM_STEP(C, M) v += dpp_move<C, M>(0, v);
-    LAPWARM_DPP_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    return __builtin_amdgcn_readlane(v, kWave - 1);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
-
-__device__ __forceinline__ double wave_max(double v)
-{
-#define LAPWARM_STEP(C, M)                                  \
-    {                                                       \
-        const double o = dpp_move<C, M>(-pos_inf(), v);     \
-        v = (o > v) ? o : v;                                \
-    }
-    LAPWARM_DPP_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    return readlane_f64(v, kWave - 1);
-}
+__device__ __forceinline__ double readlane(double x, int l) { return readlane_f64(x, l); }
 
 // Two lexicographically smallest (value, index) pairs; "empty" = (+inf, INT_MAX).
 struct Top2 {
@@ -180,27 +135,106 @@ __device__ __forceinline__ Top2 top2_merge(Top2 p, Top2 q)
     return r;
 }
 
+// ---- lane reductions (all 64 lanes must be active) ---------------------------------------
+// An operator names its value type T, the identity() that lanes without a DPP source receive, and
+// combine(moved, mine).  Results are wave-uniform.  The steps are spelled out in the body and the
+// moved value is the first argument on purpose: the optimiser orders the operands of a commutative
+// combine per function, and this is the shape that compiles to the hand-written sequence.
+
+// Wave64 reduction: after the six steps lane 63 holds the reduction of all lanes.
+template <class Op>
+__device__ __forceinline__ typename Op::T wave_reduce(typename Op::T v)
+{
+    v = Op::combine(dpp_move<kDppRowShr1, 0xf>(Op::identity(), v), v);
+    v = Op::combine(dpp_move<kDppRowShr2, 0xf>(Op::identity(), v), v);
+    v = Op::combine(dpp_move<kDppRowShr4, 0xf>(Op::identity(), v), v);
+    v = Op::combine(dpp_move<kDppRowShr8, 0xf>(Op::identity(), v), v);
+    v = Op::combine(dpp_move<kDppRowBcast15, 0xa>(Op::identity(), v), v);
+    v = Op::combine(dpp_move<kDppRowBcast31, 0xc>(Op::identity(), v), v);
+    return readlane(v, kWave - 1);
+}
+
+// 16-lane row reduction (every row of the wave holds the same 16 values): lane 15 of each row ends
+// with the result; read it from lane 15.
+template <class Op>
+__device__ __forceinline__ typename Op::T row_reduce(typename Op::T v)
+{
+    v = Op::combine(dpp_move<kDppRowShr1, 0xf>(Op::identity(), v), v);
+    v = Op::combine(dpp_move<kDppRowShr2, 0xf>(Op::identity(), v), v);
+    v = Op::combine(dpp_move<kDppRowShr4, 0xf>(Op::identity(), v), v);
+    v = Op::combine(dpp_move<kDppRowShr8, 0xf>(Op::identity(), v), v);
+    return readlane(v, 15);
+}
+
+struct MinF64 {
+    using T = double;
+    static __device__ __forceinline__ T identity() { return pos_inf(); }
+    static __device__ __forceinline__ T combine(T o, T v) { return dmin(v, o); }
+};
+struct NanMinF64 : MinF64 {
+    static __device__ __forceinline__ T combine(T o, T v) { return nmin(v, o); }
+};
+// for values that are never NaN: one v_min_f64 per step instead of a compare and two selects
+struct FminF64 : MinF64 {
+    static __device__ __forceinline__ T combine(T o, T v) { return __builtin_fmin(v, o); }
+};
+struct MaxF64 {
+    using T = double;
+    static __device__ __forceinline__ T identity() { return -pos_inf(); }
+    static __device__ __forceinline__ T combine(T o, T v) { return (o > v) ? o : v; }
+};
+struct MinI32 {
+    using T = int;
+    static __device__ __forceinline__ T identity() { return 0x7fffffff; }
+    static __device__ __forceinline__ T combine(T o, T v) { return (o < v) ? o : v; }
+};
+struct SumI32 {
+    using T = int;
+    static __device__ __forceinline__ T identity() { return 0; }
+    static __device__ __forceinline__ T combine(T o, T v) { return v + o; }
+};
+
+__device__ __forceinline__ double wave_min(double v) { return wave_reduce<MinF64>(v); }
+__device__ __forceinline__ double wave_max(double v) { return wave_reduce<MaxF64>(v); }
+__device__ __forceinline__ int wave_min_i32(int v) { return wave_reduce<MinI32>(v); }
+__device__ __forceinline__ int wave_sum_i32(int v) { return wave_reduce<SumI32>(v); }
+
+// One step of the same skeleton for Top2.  It is written by hand (by value, field by field): on the
+// generic templates the solver kernels allocate their registers differently.  The element sets merged
+// at every step are disjoint (prefix of a row / of the wave), so the merge of the two runner-up lists
+// is exact.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ Top2 top2_step(Top2 t)
+{
+    Top2 o;
+    o.a1 = dpp_move<CTRL, ROW_MASK>(pos_inf(), t.a1);
+    o.i1 = dpp_move<CTRL, ROW_MASK>(0x7fffffff, t.i1);
+    o.a2 = dpp_move<CTRL, ROW_MASK>(pos_inf(), t.a2);
+    o.i2 = dpp_move<CTRL, ROW_MASK>(0x7fffffff, t.i2);
+    return top2_merge(t, o);
+}
 __device__ __forceinline__ Top2 wave_top2(Top2 t)
 {
-    // the element sets merged at every step are disjoint (prefix of a row / of the wave), so the
-    // merge of the two runner-up lists is exact
-#define LAPWARM_STEP(C, M)                                          \
-    {                                                               \
-        Top2 o;                                                     \
-        o.a1 = dpp_move<C, M>(pos_inf(), t.a1);                     \
-        o.i1 = dpp_move<C, M>(0x7fffffff, t.i1);                    \
-        o.a2 = dpp_move<C, M>(pos_inf(), t.a2);                     \
-        o.i2 = dpp_move<C, M>(0x7fffffff, t.i2);                    \
-        t = top2_merge(t, o);                                       \
-    }
-    LAPWARM_DPP_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
+    t = top2_step<kDppRowShr1, 0xf>(t);
+    t = top2_step<kDppRowShr2, 0xf>(t);
+    t = top2_step<kDppRowShr4, 0xf>(t);
+    t = top2_step<kDppRowShr8, 0xf>(t);
+    t = top2_step<kDppRowBcast15, 0xa>(t);
+    t = top2_step<kDppRowBcast31, 0xc>(t);
     Top2 r;
     r.a1 = readlane_f64(t.a1, kWave - 1);
     r.i1 = __builtin_amdgcn_readlane(t.i1, kWave - 1);
     r.a2 = readlane_f64(t.a2, kWave - 1);
     r.i2 = __builtin_amdgcn_readlane(t.i2, kWave - 1);
     return r;
+}
+
+// fixed association order (part of the bit-exactness contract): a butterfly, not the DPP reduction
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
+    return v;
 }
 
 template <int CTRL, int ROW_MASK>
@@ -221,33 +255,13 @@ __device__ __forceinline__ void wave_excl_prefix_min_pair(double &v, int &idx, i
 {
     double iv = v;
     int ii = idx;
-#ifdef LAPWARM_NO_DPP_SCAN
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const double ov = __shfl_up(iv, off, kWave);
-        const int oi = __shfl_up(ii, off, kWave);
-        if (lane >= off && pair_less(ov, oi, iv, ii)) {
-            iv = ov;
-            ii = oi;
-        }
-    }
-    *tv = __shfl(iv, kWave - 1, kWave);
-    *ti = __shfl(ii, kWave - 1, kWave);
-    {
-        const double pv0 = __shfl_up(iv, 1, kWave);
-        const int pi0 = __shfl_up(ii, 1, kWave);
-        v = (lane == 0) ? pos_inf() : pv0;
-        idx = (lane == 0) ? 0x7fffffff : pi0;
-        return;
-    }
-#endif
     scan_step_min_pair<kDppRowShr1, 0xf>(iv, ii);
     scan_step_min_pair<kDppRowShr2, 0xf>(iv, ii);
     scan_step_min_pair<kDppRowShr4, 0xf>(iv, ii);
     scan_step_min_pair<kDppRowShr8, 0xf>(iv, ii);
     scan_step_min_pair<kDppRowBcast15, 0xa>(iv, ii);
     scan_step_min_pair<kDppRowBcast31, 0xc>(iv, ii);
-    {
+    {   // readlane_f64(iv, kWave - 1), inline: as a call the cooperative kernels order their bpermutes differently
         const long long b = __double_as_longlong(iv);
         const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), kWave - 1);
         const int hi = __builtin_amdgcn_readlane((int)(b >> 32), kWave - 1);
@@ -259,14 +273,6 @@ __device__ __forceinline__ void wave_excl_prefix_min_pair(double &v, int &idx, i
     v = (lane == 0) ? pos_inf() : pv;
     idx = (lane == 0) ? 0x7fffffff : pi;
 }
-
-// 16-lane row reduction (every row of the wave holds the same 16 values): lane 15 of each row ends
-// with the result; read it from lane 15.
-#define LAPWARM_DPP_ROW_REDUCE(STEP) \
-    STEP(kDppRowShr1, 0xf)           \
-    STEP(kDppRowShr2, 0xf)           \
-    STEP(kDppRowShr4, 0xf)           \
-    STEP(kDppRowShr8, 0xf)
 
 // ---- workgroup-level exchange through LDS ------------------------------------------------
 // Two alternating slot sets: call k writes set (k&1), one barrier, then reads it.  A thread
@@ -310,6 +316,16 @@ __device__ __forceinline__ void arr2_push(Arr2 &t, double a, int i, double vj, i
     t.y1 = first ? yj : t.y1;
 }
 
+template <int WIDTH>
+__device__ __forceinline__ double lanes_min(double v)
+{
+    static_assert(WIDTH == 64 || WIDTH == 16, "a whole wave or one row");
+    if constexpr (WIDTH == 64)
+        return wave_reduce<MinF64>(v);
+    else
+        return row_reduce<MinF64>(v);
+}
+
 // Reduce over `width` consecutive lanes holding candidates in ascending index order (width = 64:
 // whole wave via the six-step DPP reduction; width = 16: one row).  Result is wave-uniform.
 template <int WIDTH>
@@ -317,17 +333,7 @@ __device__ __forceinline__ Arr2 arr2_reduce_lanes(const Arr2 &t)
 {
     constexpr int last = WIDTH - 1;
     const unsigned long long lanes = (WIDTH == 64) ? ~0ull : 0xffffull;
-    double m1 = t.a1;
-    if constexpr (WIDTH == 64) {
-#define LAPWARM_STEP(C, M) m1 = dmin(m1, dpp_move<C, M>(pos_inf(), m1));
-        LAPWARM_DPP_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    } else {
-#define LAPWARM_STEP(C, M) m1 = dmin(m1, dpp_move<C, M>(pos_inf(), m1));
-        LAPWARM_DPP_ROW_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    }
-    m1 = readlane_f64(m1, last);
+    const double m1 = lanes_min<WIDTH>(t.a1);
     const unsigned long long k1 = __ballot(t.a1 == m1) & lanes;
     const int l1 = k1 ? __builtin_ctzll(k1) : 0;  // all +inf / NaN: any lane, values are empty
     Arr2 r;
@@ -339,17 +345,7 @@ __device__ __forceinline__ Arr2 arr2_reduce_lanes(const Arr2 &t)
     const double c2 = ((lane & last) == l1) ? t.a2 : t.a1;
     const int c2i = ((lane & last) == l1) ? t.i2 : t.i1;
     const int c2y = ((lane & last) == l1) ? t.y2 : t.y1;
-    double m2 = c2;
-    if constexpr (WIDTH == 64) {
-#define LAPWARM_STEP(C, M) m2 = dmin(m2, dpp_move<C, M>(pos_inf(), m2));
-        LAPWARM_DPP_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    } else {
-#define LAPWARM_STEP(C, M) m2 = dmin(m2, dpp_move<C, M>(pos_inf(), m2));
-        LAPWARM_DPP_ROW_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-    }
-    m2 = readlane_f64(m2, last);
+    const double m2 = lanes_min<WIDTH>(c2);
     const unsigned long long k2 = __ballot(c2 == m2) & lanes;
     const int l2 = k2 ? __builtin_ctzll(k2) : 0;
     r.a2 = readlane_f64(c2, l2);
@@ -373,22 +369,27 @@ struct BlockCtx {
         ex = e;
     }
 
+    __device__ __forceinline__ double &slot(int p, int w, double) { return ex->d[p][w]; }
+    __device__ __forceinline__ int &slot(int p, int w, int) { return ex->i[p][w]; }
+
     // Cross-wave combine without a serial LDS loop: lane l reads the slot of wave (l & 15) -- one
-    // LDS round trip -- and a 4-step butterfly over 16 lanes finishes the reduction.
-    __device__ __forceinline__ double min_f64(double v)
+    // LDS round trip -- and a 4-step row reduction over 16 lanes finishes the reduction.
+    template <class Op>
+    __device__ __forceinline__ typename Op::T reduce(typename Op::T v)
     {
-        v = wave_min(v);
+        v = wave_reduce<Op>(v);
         const int p = parity;
         parity ^= 1;
-        if (lane == 0) ex->d[p][wave] = v;
+        if (lane == 0) slot(p, wave, v) = v;
         __syncthreads();
         const int w = lane & (kMaxWaves - 1);
-        double r = (w < nwaves) ? ex->d[p][w] : pos_inf();
-#define LAPWARM_STEP(C, M) r = dmin(r, dpp_move<C, M>(pos_inf(), r));
-        LAPWARM_DPP_ROW_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-        return readlane_f64(r, 15);
+        return row_reduce<Op>((w < nwaves) ? slot(p, w, v) : Op::identity());
     }
+
+    template <class Op = MinF64>
+    __device__ __forceinline__ double min_f64(double v) { return reduce<Op>(v); }
+    __device__ __forceinline__ int min_i32(int v) { return reduce<MinI32>(v); }
+    __device__ __forceinline__ int sum_i32(int v) { return reduce<SumI32>(v); }
 
     __device__ __forceinline__ double max_f64(double v)
     {
@@ -416,40 +417,6 @@ struct BlockCtx {
         double r = ex->d[p][0];
         for (int w = 1; w < nwaves; ++w) r += ex->d[p][w];
         return r;
-    }
-
-    __device__ __forceinline__ int min_i32(int v)
-    {
-        v = wave_min_i32(v);
-        const int p = parity;
-        parity ^= 1;
-        if (lane == 0) ex->i[p][wave] = v;
-        __syncthreads();
-        const int w = lane & (kMaxWaves - 1);
-        int r = (w < nwaves) ? ex->i[p][w] : 0x7fffffff;
-#define LAPWARM_STEP(C, M)                                  \
-    {                                                       \
-        const int o = dpp_move<C, M>(0x7fffffff, r);        \
-        r = (o < r) ? o : r;                                \
-    }
-        LAPWARM_DPP_ROW_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-        return __builtin_amdgcn_readlane(r, 15);
-    }
-
-    __device__ __forceinline__ int sum_i32(int v)
-    {
-        v = wave_sum_i32(v);
-        const int p = parity;
-        parity ^= 1;
-        if (lane == 0) ex->i[p][wave] = v;
-        __syncthreads();
-        const int w = lane & (kMaxWaves - 1);
-        int r = (w < nwaves) ? ex->i[p][w] : 0;
-#define LAPWARM_STEP(C, M) r += dpp_move<C, M>(0, r);
-        LAPWARM_DPP_ROW_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-        return __builtin_amdgcn_readlane(r, 15);
     }
 
     // Workgroup-wide Arr2 reduction; *c0 (owned by thread 0) is broadcast alongside.  One barrier.
@@ -504,17 +471,10 @@ struct BlockCtx {
             r.i1 = ex->i[p][2 * w];
             r.i2 = ex->i[p][2 * w + 1];
         }
-#define LAPWARM_STEP(C, M)                                          \
-    {                                                               \
-        Top2 o;                                                     \
-        o.a1 = dpp_move<C, M>(pos_inf(), r.a1);                     \
-        o.i1 = dpp_move<C, M>(0x7fffffff, r.i1);                    \
-        o.a2 = dpp_move<C, M>(pos_inf(), r.a2);                     \
-        o.i2 = dpp_move<C, M>(0x7fffffff, r.i2);                    \
-        r = top2_merge(r, o);                                       \
-    }
-        LAPWARM_DPP_ROW_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
+        r = top2_step<kDppRowShr1, 0xf>(r);
+        r = top2_step<kDppRowShr2, 0xf>(r);
+        r = top2_step<kDppRowShr4, 0xf>(r);
+        r = top2_step<kDppRowShr8, 0xf>(r);
         Top2 out;
         out.a1 = readlane_f64(r.a1, 15);
         out.i1 = __builtin_amdgcn_readlane(r.i1, 15);
@@ -542,12 +502,8 @@ __device__ __forceinline__ void dma_request16(const double *gsrc_lane, unsigned 
                  : "v"(gsrc_lane), "s"(lds_dst_uniform)
                  : "memory");
 }
-template <int N>
-__device__ __forceinline__ void dma_wait()
-{
-    static_assert(N == 0, "only the full drain is used");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
+// every vector memory operation this wave has issued, LDS-DMA requests included, has completed
+__device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // LDS byte address of a pointer into the workgroup's LDS block
 __device__ __forceinline__ unsigned lds_address(const void *p)
 {

@@ -676,7 +676,7 @@ struct Solver {
                         col = (col < n - 2) ? col : n - 2;
                         dma_request16(row + col, sbase + (unsigned)q * (unsigned)nt * 16u);
                     }
-                    dma_wait<0>();
+                    drain();
                     __syncthreads();
                     from_slot = true;
                 }
@@ -887,7 +887,7 @@ struct Solver {
             if constexpr (PF) {
                 // every wave's pieces of the requested row have landed before the barrier releases
                 // the readers of the next step
-                if (pf_issued) dma_wait<0>();
+                if (pf_issued) drain();
                 pf_have = pf_issued;
                 pf_slot = pf_next_slot;
             }
@@ -1630,10 +1630,7 @@ struct Solver {
     // hazard recogniser does not see an asm's result feeding the next DPP move)
     __device__ __forceinline__ static double wave_min_nn(double x)
     {
-#define LAPWARM_STEP(C, M) x = __builtin_fmin(x, dpp_move<C, M>(pos_inf(), x));
-        LAPWARM_DPP_REDUCE(LAPWARM_STEP)
-#undef LAPWARM_STEP
-        return readlane_f64(x, kWave - 1);
+        return wave_reduce<FminF64>(x);
     }
 
     // The same sweep with the candidate lists in front of the row scans.
@@ -2052,7 +2049,7 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
             if (__builtin_amdgcn_s_memrealtime() - t0 > (n <= 4096 ? 50000000ull : 6000000000ull)) break;  // 0.5 s / 60 s
             __builtin_amdgcn_s_sleep(1);
         }
-        dma_wait<0>();
+        drain();
         return;
     }
     const int b = blockIdx.x;
