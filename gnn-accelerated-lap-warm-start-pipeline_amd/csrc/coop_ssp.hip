@@ -30,10 +30,9 @@
 //   mailbox buf[seq & 1]          a member publishes round r+2 (same buffer as r) only after it has
 //                                 all records of round r+1, which every member publishes after it
 //                                 finished reading round r
-#include <stdlib.h>
-
 #include "device_utils.hpp"
 #include "jv_solver.hpp"
+#include "solve_plan.hpp"  // CoopConfig
 
 namespace lapwarm {
 
@@ -1344,72 +1343,14 @@ const CoopKernel *coop_kernel(int ch, int nl)
     return nullptr;
 }
 
-// Positions per lane for a problem size: enough members to spread the row over many CUs, few
-// enough that one exchange stays within four granule loads per lane (G <= 32).
-int coop_ch(int n)
-{
-    static const int forced = [] {
-        const char *e = getenv("LAPWARM_COOP_CH");
-        return e ? atoi(e) : 0;
-    }();
-    if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16) {
-        if ((n + 64 * forced - 1) / (64 * forced) <= 32) return forced;
-    }
-    // Measured (tools/micro/hop_bench.hip, profiles/r03_hop_bench.txt): an exchange among 8 members costs
-    // 1.0-1.3 us, among 16 1.4-2.2 us (32 instances in flight), among 32 1.9-2.6 us -- the fewer members the
-    // better, as long as a lane's positions fit the register file (16 positions = ~250 VGPRs).
-    if (n <= 512) return 1;
-    if (n <= 1024) return 2;
-    // Measured with one event per member in a 2-granule relax record (a relax round polls 2G + 24 granules:
-    // one load per lane up to 20 members, two up to 32): n = 4608 x 8 467 ms with 4 positions per lane
-    // (18 members) against 508 ms with 8; n = 8192 1.13 s with 4 (32 members), 1.21 s with 8, 1.59 s with 16;
-    // n = 16384 3.88 s with 8 (32 members), 4.75 s with 16.
-    if (n <= 8192) return 4;
-    return 8;
-}
-
 }  // namespace
 
-CoopConfig coop_config(int n)
-{
-    static const int min_n = [] {
-        const char *e = getenv("LAPWARM_COOP_MIN_N");
-        // default: sizes whose solver state no longer fits one CU's LDS (solver_lds_level 0); below that the
-        // single-workgroup kernel is faster (n = 4096: 274 ms against 442 ms per 32 instances)
-        return e ? atoi(e) : 4428;
-    }();
-    static const int on = [] {
-        const char *e = getenv("LAPWARM_COOP");
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    static const int xcd_stores = [] {
-        const char *e = getenv("LAPWARM_COOP_XCD_STORES");
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    static const int pairs = [] {
-        const char *e = getenv("LAPWARM_COOP_RELAUNCHES");
-        const int k = e ? atoi(e) : 96;
-        return (k >= 0 && k <= 4096) ? k : 96;
-    }();
-    CoopConfig c = {};
-    if (!on || n < min_n || n > 16384) return c;
-    const int ch = coop_ch(n);
-    const int members = (n + 64 * ch - 1) / (64 * ch);
-    const int nl = (members * kK + kWinGran + 63) / 64;  // granule loads per lane of a collection's round B
-    // (a forced geometry without an instantiation takes the one-workgroup path)
-    if (members > 32 || !coop_kernel(ch, nl)) return c;
-    c.ch = ch;
-    c.nl = nl;
-    c.members = members;
-    c.mail_granules = 2 * ((size_t)members * (kK + kKr) + kWinGran);
-    // every member of an instance must be resident while the instance runs: at most 1024 single-wave
-    // workgroups per launch (a quarter of what the chip holds), instances in groups of 8
-    c.per_launch = (1024 / members) & ~7;
-    if (c.per_launch < 8) c.per_launch = 8;
-    c.pairs = pairs;
-    c.xcd_stores = xcd_stores;
-    return c;
-}
+bool coop_kernel_exists(int ch, int nl) { return coop_kernel(ch, nl) != nullptr; }
+
+// granule loads per lane of a collection's round B
+int coop_granule_loads(int members) { return (members * kK + kWinGran + 63) / 64; }
+
+size_t coop_mail_granules(int members) { return 2 * ((size_t)members * (kK + kKr) + kWinGran); }
 
 hipError_t launch_coop(const CoopParams &p_in, const CoopConfig &cfg, hipStream_t stream)
 {

@@ -10,7 +10,7 @@
 //   dual utilities   solvers/advanced_dual.py:14-63
 //   row features     gnn/features.py:161-243
 #include "device_utils.hpp"
-#include "jv_solver.hpp"
+#include "dense_sweeps.hpp"
 
 namespace lapwarm {
 

@@ -10,7 +10,7 @@
 //     "unmatched", the number of matched rows and opt = sum of C[i][x_i] over the matched rows in
 //     row order, summed as numpy sums the compacted vector (pairwise_sum, device_utils.hpp).
 #include "device_utils.hpp"
-#include "jv_solver.hpp"
+#include "extend_costs.hpp"
 
 namespace lapwarm {
 

@@ -36,16 +36,13 @@
 //     the solver announces through a ring in global memory -- columns joining the SCAN list, the
 //     winner of a minima collection, the next path's start row -- into the L2 both share.  It writes
 //     nothing the solver reads.  DESIGN.md section 4 has the measurements and the happens-before table.
-#include <stdlib.h>
 #include <string.h>
 
 #include "device_utils.hpp"
 #include "jv_solver.hpp"
+#include "solve_plan.hpp"  // PhaseConfig
 
 namespace lapwarm {
-
-__host__ __device__ int solver_row_slots(int n, int ch);  // LDS level 8, defined with solver_lds_bytes
-bool large_row_geometry(int n, int *threads, int *ch);
 
 namespace {
 
@@ -2443,23 +2440,14 @@ PhaseLaunch by_ch(int ch, int tb, int ldsl)
     return nullptr;
 }
 
+}  // namespace
+
 hipError_t launch_phase(const PhaseConfig &k, const SolverParams &p, hipStream_t stream)
 {
     if ((long long)k.threads * k.ch < p.n) return hipErrorInvalidValue;  // n > 16384
     const PhaseLaunch launch = !k.lists ? by_ch<false>(k.ch, k.tb, k.ldsl) : by_ch<true>(k.ch, k.tb, k.ldsl);
     if (!launch) return hipErrorInvalidValue;
     return launch(p, k.threads, k.lds_bytes, stream);
-}
-
-}  // namespace
-
-bool arr_lists_enabled(int n)
-{
-    static const int on = [] {
-        const char *e = getenv("LAPWARM_ARR_LISTS");
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return on && n >= 512;
 }
 
 // LDS levels: 2 = position-owned search, every array in LDS; 1 = x and the free-row list in global
@@ -2476,18 +2464,6 @@ __host__ __device__ int solver_row_slots(int n, int ch)
     return 0;
 }
 
-// n = 8192 -> 512 threads x 16 positions, two row slots.  Measured (uniform instance, ms per solve):
-// n = 8192: 2,278 here against 2,658 with 1024 x 8 and the state in global memory (level 0);
-// n = 16384 (512 x 32, one slot): 51 s against 25 s for 1024 x 16 at level 0 -- the step time grows
-// with the positions per thread, so K5 stays on the generic path.
-bool large_row_geometry(int n, int *threads, int *ch)
-{
-    if (n != 8192) return false;
-    *threads = 512;
-    *ch = n / 512;
-    return solver_row_slots(n, *ch) >= 1;
-}
-
 size_t solver_lds_bytes(int n, int ch, int level)
 {
     const int W = (n + 31) >> 5;
@@ -2500,157 +2476,6 @@ size_t solver_lds_bytes(int n, int ch, int level)
     if (level >= 1) bytes += (size_t)n * (2 * sizeof(double) + 5 * sizeof(int)) + 2 * sizeof(int);
     if (level >= 2) bytes += (size_t)n * 2 * sizeof(int);
     return bytes;
-}
-
-int solver_lds_level(int n, int ch)
-{
-    if (solver_lds_bytes(n, ch, 2) <= kLdsBudgetBytes) return 2;
-    if (solver_lds_bytes(n, ch, 1) <= kLdsBudgetBytes) return 1;
-    return 0;
-}
-
-// Picks (threads, CH) with threads*CH >= n.  `threads_hint` (0 = auto) lets the bench sweep
-// the geometry; it is rounded to a supported value.
-static void solver_geometry(int n, int threads_hint, int *threads, int *ch)
-{
-    int t = threads_hint;
-    if (t <= 0) {
-        // measured on MI355X (K3, n=2048): 1024 threads 107 ms, 512: 128 ms, 256: 180 ms --
-        // the per-step fixed latency dominates, so use as many lanes as there are columns
-        if (n <= 64) t = 64;
-        else if (n <= 128) t = 128;
-        else if (n <= 256) t = 256;
-        else if (n <= 512) t = 512;
-        else t = 1024;
-    }
-    t = ((t + 63) / 64) * 64;
-    if (t > 1024) t = 1024;
-    if (t < 64) t = 64;
-    int c = 1;
-    while ((long long)t * c < n && c < 16) c <<= 1;
-    while ((long long)t * c < n && t < 1024) t += 64;
-    *threads = t;
-    *ch = c;
-}
-
-// Helper workgroups: rows of 8-64 KiB (n = 1024 .. 8192, even).  Measured on the same box, solver
-// kernel per launch: K3 79.6 -> 73.2 ms, K4 slice 327.8 -> 276.0 ms, n = 8192 2.28 -> 2.09 s,
-// K2 (n = 512) no change, n = 16384 worse.
-bool solver_uses_helpers(int n)
-{
-    static const int want = [] {
-        const char *e = getenv("LAPWARM_HELPER");
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    static const int max_n = [] {
-        const char *e = getenv("LAPWARM_HELPER_MAX_N");
-        return e ? atoi(e) : 8192;  // n = 16384: 29.3 s with a helper against 25.6 s without
-    }();
-    return want && n >= 1024 && n <= max_n && n % 2 == 0;
-}
-
-SolveShape solve_shape(int n, bool lists)
-{
-    if (coop_config(n).members > 0) return SolveShape::kCoopChain;
-    return lists ? SolveShape::kListsThenPaths : SolveShape::kOneLaunch;
-}
-
-SolvePlan plan_solve(int mode, int batch, int n, int threads_hint, bool lists, int n_cus)
-{
-    SolvePlan plan = {};
-    plan.shape = solve_shape(n, lists);
-    if (plan.shape == SolveShape::kCoopChain) plan.coop = coop_config(n);
-    PhaseConfig &k = plan.paths;
-    // measured (n=2048, ARR-dominated cold solve): 512 threads 2.6 us/iteration, 1024: 3.2, 256: 3.1
-    if (threads_hint <= 0 && mode == kModeCold && n > 1024 && n <= 2048) threads_hint = 512;
-    solver_geometry(n, threads_hint, &k.threads, &k.ch);
-    // Rows that no longer fit the L1 (n > 4,427, where the state leaves LDS as well): 512 threads
-    // with n/512 positions each -- duals cached in registers (256 VGPRs per thread at this size),
-    // every head row brought into LDS by coalesced LDS-DMA (level 8).  Seeded mode only: the cold
-    // ARR loop keeps the generic geometry.
-    if (threads_hint <= 0 && mode == kModeSeeded && large_row_geometry(n, &k.threads, &k.ch)) {
-        k.ldsl = 8;
-        k.tb = 512;
-    } else {
-        k.ldsl = solver_lds_level(n, k.ch);
-        k.tb = k.threads <= 256 ? 256 : 1024;
-    }
-    k.lds_bytes = solver_lds_bytes(n, k.ch, k.ldsl);
-    // a cold solve whose workspace carries the candidate lists is prepared by the LISTS instantiation
-    plan.prep = k;
-    plan.prep.lists = lists;
-    static const int n_helpers = [] {
-        const char *e = getenv("LAPWARM_HELPERS_PER_INSTANCE");
-        const int h = e ? atoi(e) : 1;
-        return (h >= 1 && h <= 4) ? h : 1;
-    }();
-    // (a helper can only help while its solver runs: with more workgroups than CUs the helpers would
-    // be dispatched after the solvers they serve and leave at once -- skip them.  Assumptions, stated:
-    // workgroups are dispatched in index order, so every solver of THIS launch is resident before its
-    // helper; a helper spins until its solver's done flag or 0.5 s (60 s above n = 4096) and holds a
-    // CU's LDS meanwhile, so with several launches resident -- bench.py --inflight -- helpers can delay
-    // the solvers of a later launch, never deadlock them: every solver exit sets the flag.)
-    if (plan.shape == SolveShape::kOneLaunch && mode == kModeSeeded && solver_uses_helpers(n) &&
-        batch * (1 + n_helpers) <= n_cus)
-        plan.helper = n_helpers;
-    return plan;
-}
-
-// Runs a plan: one launch of jv_instance_kernel, or phase 1 (greedy / micro-ARR / cold preparation),
-// the cooperative chain where the plan has one, then phase 2 (whatever is left + the outputs).
-hipError_t launch_solver(const SolvePlan &plan, const SolverParams &p_in, hipStream_t stream)
-{
-    SolverParams p = p_in;
-    p.helper = plan.helper;
-    p.mail_granules = (int)plan.coop.mail_granules;
-    if (plan.shape == SolveShape::kOneLaunch) {
-        p.phase = 0;
-        return launch_phase(plan.prep, p, stream);
-    }
-    p.phase = 1;
-    hipError_t e = launch_phase(plan.prep, p, stream);
-    if (e != hipSuccess) return e;
-    if (plan.shape == SolveShape::kCoopChain) {
-        CoopParams c = {};
-        c.C = p.C;
-        c.n = p.n;
-        c.batch = p.batch;
-        c.v = p.g_v;
-        c.x = p.g_x;
-        c.y = p.g_y;
-        c.pred = p.g_pred;
-        c.fr = p.g_fr;
-        c.hand = p.hand;
-        c.cstats = p.cstats;
-        c.mail = p.mail;
-        // The cooperative kernel stops at a path it does not handle (a minima collection with a tie: rare,
-        // but seeds that went through float32 produce a few dozen per instance); jv_instance_kernel then
-        // searches that ONE path (phase 3) and the cooperative kernel carries on.  The host cannot know how
-        // often that happens, so a fixed number of (cooperative, one-path) pairs is enqueued -- a launch with
-        // nothing to do returns at once (~2 us) -- and the final phase 2 finishes whatever is left.
-        for (int k = 0; k <= plan.coop.pairs; ++k) {
-            e = launch_coop(c, plan.coop, stream);
-            if (e != hipSuccess) return e;
-            if (k == plan.coop.pairs) break;
-            p.phase = 3;
-            e = launch_phase(plan.paths, p, stream);
-            if (e != hipSuccess) return e;
-        }
-    }
-    p.phase = 2;
-    return launch_phase(plan.paths, p, stream);
-}
-
-bool solver_needs_global_state(int n)
-{
-    // a threads_hint may pick another CH: be conservative for every supported geometry.
-    // Level 2 keeps everything in LDS; 0, 1 and 8 use the global workspace.
-    for (int c = 1; c <= 16; c <<= 1) {
-        if (solver_lds_level(n, c) < 2) return true;
-    }
-    int t, c;
-    if (large_row_geometry(n, &t, &c)) return true;
-    return false;
 }
 
 }  // namespace lapwarm

@@ -1,5 +1,5 @@
-// jv_solver.hpp -- host-visible interface of the per-instance solver kernel (jv_solver.hip)
-// and of the dense sweep kernels (dense_sweeps.hip).  Internal to the shared library; the
+// jv_solver.hpp -- host-visible interface of the solver kernels: the per-instance kernel (jv_solver.hip)
+// and the cooperative shortest-path kernel (coop_ssp.hip).  Internal to the shared library; the
 // public C ABI is include/lapwarm_hip.h.
 #pragma once
 
@@ -165,153 +165,19 @@ struct CoopParams {
     unsigned long long *mail;
 };
 
-// ---- the solve plan (jv_solver.hip: plan_solve): every host decision about how a solve runs ---------
-// The workspace layout (lapwarm_abi.hip) and the ABI queries ask the same functions.
-enum class SolveShape {
-    kOneLaunch,       // phase 0: the whole solve in one launch of jv_instance_kernel
-    kListsThenPaths,  // phase 1 with candidate lists (cold), then phase 2
-    kCoopChain,       // phase 1, (coop_ssp_kernel, phase 3) x pairs, coop_ssp_kernel, phase 2
-};
-SolveShape solve_shape(int n, bool lists);  // lists: the workspace carries candidate lists (cold solves)
+// ---- launchers (the plan they run is solve_plan.hpp's; the launch tables are private to the kernel files) ----
+struct PhaseConfig;
+struct CoopConfig;
+hipError_t launch_phase(const PhaseConfig &k, const SolverParams &p, hipStream_t stream);  // jv_instance_kernel
+hipError_t launch_coop(const CoopParams &p, const CoopConfig &cfg, hipStream_t stream);    // coop_ssp_kernel
 
-struct PhaseConfig {  // one launch of jv_instance_kernel<ch, ldsl, tb, lists>
-    int threads, ch, ldsl, tb;
-    bool lists;
-    size_t lds_bytes;
-};
-
-// coop_ssp_kernel<ch, nl> (coop_ssp.hip); members == 0: no cooperative path for this size
-struct CoopConfig {
-    int ch, nl, members;   // members: single-wave workgroups per instance
-    size_t mail_granules;  // per instance
-    int per_launch;        // instances per launch
-    int pairs;             // (cooperative, phase 3) pairs before the final cooperative launch
-    int xcd_stores;
-};
-CoopConfig coop_config(int n);
-hipError_t launch_coop(const CoopParams &p, const CoopConfig &cfg, hipStream_t stream);
-
-struct SolvePlan {
-    SolveShape shape;
-    PhaseConfig prep;   // phase 0, or phase 1
-    PhaseConfig paths;  // phases 2 and 3
-    int helper;         // helper workgroups per instance (phase 0 only)
-    CoopConfig coop;
-};
-SolvePlan plan_solve(int mode, int batch, int n, int threads_hint, bool lists, int n_cus);
-hipError_t launch_solver(const SolvePlan &plan, const SolverParams &p, hipStream_t stream);
-
+// the LDS carving of jv_instance_kernel (jv_solver.hip): bytes of a level, row slots of level 8
 size_t solver_lds_bytes(int n, int ch, int level);
-int solver_lds_level(int n, int ch);
-bool solver_needs_global_state(int n);
-// candidate lists for the augmenting row reduction: from the size where a row is a few times its list
-// (LAPWARM_ARR_LISTS=0 turns them off: every iteration then scans its whole row)
-bool arr_lists_enabled(int n);
-bool solver_uses_helpers(int n);  // seeded mode: one helper workgroup per instance of a phase-0 launch
+__host__ __device__ int solver_row_slots(int n, int ch);
 
-// ---- dense sweeps (dense_sweeps.hip) ----------------------------------------------------
-struct PreludeParams {
-    const double *C;
-    int n, batch;
-    const double *u;  // [batch][n] duals the verify step uses (seed, or projected)
-    const double *v;  // [batch][n]
-    double eps, tight_eps;
-    int rerun;        // 0: first pass; 1: only instances whose duals were projected
-    double *u_tight;
-    int *viol_cnt;    // [batch][n] candidates of the projection per row (first pass only)
-    int *tight_cnt;
-    uint32_t *tight_bits;
-    int *inst_flags;
-};
-hipError_t launch_prelude(const PreludeParams &p, hipStream_t stream);
-hipError_t launch_seed_prepare(const double *u_seed, const double *v_seed, double *u_work, double *v_work,
-                               size_t count, int *flags, int n_flags, int *ring, int n_ring, hipStream_t stream);
-
-// Gauss-Seidel projection of (u, v) for the instances flagged kFlagHasViolation; in place.
-hipError_t launch_projection(const double *C, int n, int batch, double *u, double *v,
-                             const int *viol_cnt, int *inst_flags, double eps, hipStream_t stream);
-
-// out[b][j] = min_i (C[b][i][j] - (u ? u[b][i] : 0)); `partial` holds batch*chunks*n doubles.
-int colmin_chunks(int n, int batch);
-hipError_t launch_colmin(const double *C, int n, int batch, const double *u, double *out,
-                         double *partial, hipStream_t stream);
-
-// out[b][i] = min_j (C[b][i][j] - (v ? v[b][j] : 0))
-hipError_t launch_rowmin(const double *C, int n, int batch, const double *v, double *out,
-                         hipStream_t stream);
-
-// R[b][i][j] = (C - u_i) - v_j - shift[b] ; gmin[b] = min_ij ((C - u_i) - v_j)
-hipError_t launch_reduced_min(const double *C, int n, int batch, const double *u, const double *v,
-                              double *gmin_partial, double *gmin, hipStream_t stream);
-hipError_t launch_reduce_costs(const double *C, int n, int batch, const double *u, const double *v,
-                               const double *gmin, int shift_nonneg, double *out, hipStream_t stream);
-// one round of project_feasible's u/v caps: u = min(u, rowmin(C - v)) ; v = min(v, colmin(C - u))
-hipError_t launch_cap_rows(const double *C, int n, int batch, double *u, const double *v,
-                           hipStream_t stream);
-hipError_t launch_cap_cols(const double *C, int n, int batch, const double *u, double *v,
-                           double *partial, hipStream_t stream);
-
-// 13 row statistics + 8 positional encodings (float32) and the 16 smallest costs per row.
-struct FeatureParams {
-    const double *C;
-    int n, batch;
-    const double *colmin;  // [batch][n]
-    const float *posenc;   // [n][8] host-computed table
-    float *feat;           // [batch][n][21]
-    float *topk;           // [batch][n][16] ascending, +inf padded, or null
-};
-hipError_t launch_row_features(const FeatureParams &p, hipStream_t stream);
-
-// ---- oracle duals (oracle_duals.hip) ----------------------------------------------------
-constexpr int kOracleMaxN = 16384;
-constexpr int kOracleReplayMaxN = 2048;  // largest n whose unsettled instances are replayed exactly
-// per-instance results (the ret codes of lapwarm_oracle_duals_batched) and internal states
-constexpr int kOracleOk = 0, kOracleNegativeCycle = 1, kOracleInfeasible = 2, kOracleSlackness = 3,
-              kOracleNotPermutation = 4, kOracleNonFinite = 5;
-constexpr int kOracleDone = 100, kOracleReplay = 101;  // status 0: still sweeping
-// per-instance int slots of the workspace
-constexpr int kOdStatus = 0, kOdCount0 = 1, kOdCount1 = 2, kOdSweeps = 3, kOdDepth = 4, kOdRowsRead = 5,
-              kOdReplayed = 6, kOdSlackBad = 7, kOdInstInts = 16;
-struct OracleParams {
-    const double *C;
-    int n, batch, chunks, pair;
-    const int *rows, *cols;  // [batch][n] pairs in the caller's order
-    int *x, *y;              // [batch][n] row -> col, col -> row
-    double *cxx;             // [batch][n] C[i][x_i]
-    double *v0, *v1;         // [batch][n] the two Jacobi buffers
-    int *pred;               // [batch][n] row that last lowered v_j, or -1
-    int *lrow;               // [2][batch][n] active rows of the current / next sweep
-    double *lsrc;            // [2][batch][n] their source values v[x_i]
-    double *pval;            // [batch][chunks][n] partial column minima
-    int *parg;               // [batch][chunks][n] their rows
-    int *inst;               // [batch][kOdInstInts]
-};
-int oracle_chunks(int n, int batch);
-hipError_t launch_oracle_init(const OracleParams &p, hipStream_t stream);
-// sweep s (0-based, the same for every instance of the batch)
-hipError_t launch_oracle_sweep(const OracleParams &p, int s, hipStream_t stream);
-// after s sweeps: stop the converged, find predecessor cycles; `last` hands the unsettled to the
-// replay; `running` (zeroed by the caller) receives the number of instances that go on sweeping
-hipError_t launch_oracle_check(const OracleParams &p, int s, int last, int *running, hipStream_t stream);
-// replay (n <= kOracleReplayMaxN), u/v with the gauge, reduced-cost minimum, ret and counters
-hipError_t launch_oracle_finish(const OracleParams &p, double tol, double *u, double *v, double *rowpart,
-                                double *gmin, int *ret, int *sweeps, hipStream_t stream);
-
-// ---- rectangular / cost-limited lapjv (extend_costs.hip) -----------------------------------
-// E [batch][n][n] = C [batch][n_rows][n_cols] in the top left corner, `fill` beside and below it,
-// 0 in E[n_rows:, n_cols:] (LAP/_lapjv_cpp/_lapjv.pyx:84-95; fill = 0 without a cost limit)
-hipError_t launch_extend_costs(const double *C, int batch, int n_rows, int n_cols, int n, double fill, double *E,
-                               hipStream_t stream);
-// _lapjv.pyx:115-122: xs, ys [batch][n] of the solve on E -> x [batch][n_rows], y [batch][n_cols] with -1
-// for unmatched, matched [batch] and opt [batch] (either may be null); gath [batch][n_rows] scratch.
-// Instances with ret != 0: x, y all -1, opt NaN, matched 0.
-hipError_t launch_extended_finish(const double *C, int batch, int n_rows, int n_cols, int n, const int *xs,
-                                  const int *ys, const int *ret, int *x, int *y, double *opt, int *matched,
-                                  double *gath, hipStream_t stream);
-
-// OneGNN refinement aggregation (onegnn_refine.hip)
-hipError_t launch_refine_aggregate(const float *topk16, const float *u_pre, const float *w1,
-                                   const float *b1, float *out, float *wsum, int rows, int H,
-                                   hipStream_t stream);
+// what the plan needs from coop_ssp.hip's private record sizes, per member count of an instance
+bool coop_kernel_exists(int ch, int nl);  // is there a coop_ssp_kernel<ch, nl>
+int coop_granule_loads(int members);      // granule loads per lane (nl)
+size_t coop_mail_granules(int members);   // mailbox granules per instance
 
 }  // namespace lapwarm

@@ -12,7 +12,12 @@
 #include <tuple>
 
 #include "../../include/lapwarm_hip.h"
+#include "dense_sweeps.hpp"
+#include "extend_costs.hpp"
 #include "jv_solver.hpp"
+#include "onegnn_refine.hpp"
+#include "oracle_duals.hpp"
+#include "solve_plan.hpp"
 
 using namespace lapwarm;
 

@@ -6,7 +6,7 @@
 // kernel emits the (B, n, H) aggregate and the GEMM runs once per row (16x fewer flops, no
 // 16x intermediate in HBM).  float32 throughout, exact-erf GELU as torch's default.
 #include "device_utils.hpp"
-#include "jv_solver.hpp"
+#include "onegnn_refine.hpp"
 
 namespace lapwarm {
 namespace {

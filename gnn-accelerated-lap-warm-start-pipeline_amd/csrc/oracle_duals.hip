@@ -23,7 +23,8 @@
 //     np.mean, the matched |reduced cost| maximum; the reduced-cost minimum is the dense
 //     launch_reduced_min sweep ((C - u_i) - v_j, the reference's order).
 #include "device_utils.hpp"
-#include "jv_solver.hpp"
+#include "dense_sweeps.hpp"  // colmin_chunks, launch_reduced_min
+#include "oracle_duals.hpp"
 
 namespace lapwarm {
 

@@ -1,0 +1,50 @@
+// solve_plan.hpp -- the solve plan (solve_plan.hip): every host decision about how a solve runs.
+// The workspace layout (lapwarm_abi.hip) and the ABI queries ask the same functions.  Host only: the
+// kernels and their launch tables are behind jv_solver.hpp.
+#pragma once
+
+#include "jv_solver.hpp"
+
+namespace lapwarm {
+
+enum class SolveShape {
+    kOneLaunch,       // phase 0: the whole solve in one launch of jv_instance_kernel
+    kListsThenPaths,  // phase 1 with candidate lists (cold), then phase 2
+    kCoopChain,       // phase 1, (coop_ssp_kernel, phase 3) x pairs, coop_ssp_kernel, phase 2
+};
+SolveShape solve_shape(int n, bool lists);  // lists: the workspace carries candidate lists (cold solves)
+
+struct PhaseConfig {  // one launch of jv_instance_kernel<ch, ldsl, tb, lists>
+    int threads, ch, ldsl, tb;
+    bool lists;
+    size_t lds_bytes;
+};
+
+// coop_ssp_kernel<ch, nl> (coop_ssp.hip); members == 0: no cooperative path for this size
+struct CoopConfig {
+    int ch, nl, members;   // members: single-wave workgroups per instance
+    size_t mail_granules;  // per instance
+    int per_launch;        // instances per launch
+    int pairs;             // (cooperative, phase 3) pairs before the final cooperative launch
+    int xcd_stores;
+};
+CoopConfig coop_config(int n);
+
+struct SolvePlan {
+    SolveShape shape;
+    PhaseConfig prep;   // phase 0, or phase 1
+    PhaseConfig paths;  // phases 2 and 3
+    int helper;         // helper workgroups per instance (phase 0 only)
+    CoopConfig coop;
+};
+SolvePlan plan_solve(int mode, int batch, int n, int threads_hint, bool lists, int n_cus);
+hipError_t launch_solver(const SolvePlan &plan, const SolverParams &p, hipStream_t stream);
+
+int solver_lds_level(int n, int ch);
+bool solver_needs_global_state(int n);
+// candidate lists for the augmenting row reduction: from the size where a row is a few times its list
+// (LAPWARM_ARR_LISTS=0 turns them off: every iteration then scans its whole row)
+bool arr_lists_enabled(int n);
+bool solver_uses_helpers(int n);  // seeded mode: one helper workgroup per instance of a phase-0 launch
+
+}  // namespace lapwarm

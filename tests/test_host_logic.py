@@ -339,9 +339,10 @@ def test_workspace_sizes_are_unchanged():
             assert got == want, (kind, batch, [(n, g, w) for n, g, w in zip(WS_SIZES_N, got, want) if g != w])
 
 
-# solver_lds_bytes(n, ch, level) for n in WS_SIZES_N, recorded from the library before the kernel's LDS carving
-# and the host's byte count became one layout function.  Levels 0..2 do not depend on ch (every ch in
-# LDS_SIZES_CH gave the row below); level 8 exists for the 512 x 16 geometry of n = 8192 only.
+# solver_lds_bytes(n, ch, level) for n in WS_SIZES_N, recorded from the library before the records the solver
+# kernels share were named.  The kernel's LDS carving and the host's byte count are still two pieces of code
+# that have to agree: solver_lds_bytes sits next to the carving in jv_solver.hip.  Levels 0..2 do not depend
+# on ch (every ch in LDS_SIZES_CH gave the row below); level 8 exists for the 512 x 16 geometry of n = 8192 only.
 LDS_SIZES_CH = (1, 2, 4, 8, 16)
 LDS_SIZES = {
     0: [
@@ -385,3 +386,52 @@ def test_forced_cooperative_geometry_without_an_instantiation_is_not_planned():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout.split() == ["0", "10"], r.stdout
+
+
+# ---- the solve plan (csrc/solve_plan.hip) against tests/golden/solve_plans.json, recorded from the library
+# before the planner moved out of the kernel files: a wrong threads / ch / ldsl / tb / helper / cooperative
+# decision still solves correctly, so only a table catches it
+
+def _golden_plans(key):
+    import json
+    return json.loads((ROOT / "tests" / "golden" / "solve_plans.json").read_text())[key]
+
+
+def _assert_same_plans(got, want, points, where):
+    for args, g, w in zip(points, got["index"], want["index"]):
+        assert got["plans"][g] == want["plans"][w], (where, "mode, batch, n, hint, lists, cus", args,
+                                                     got["plans"][g], want["plans"][w])
+    assert len(got["index"]) == len(want["index"]) == len(points)
+    assert got["queries"] == want["queries"], where
+
+
+def test_solve_plan_table_is_unchanged():
+    """Every field of lapwarm::plan_solve over mode x WS_SIZES_N x threads_hint x lists x (batch, n_cus), default
+    environment; (128, 256) and (129, 256) sit on either side of the helper guard batch * 2 <= n_cus."""
+    import solve_plan_common as spc
+    from lap import _hip
+    assert spc.GRID_N == WS_SIZES_N
+    points = list(spc.grid())
+    assert len(points) == 2 * len(WS_SIZES_N) * 5 * 2 * 4
+    want = _golden_plans("default")
+    _assert_same_plans(spc.record(_hip.load(), points), want, points, "default")
+    helpers = {p[13] for p in want["plans"]}
+    shapes = {p[0] for p in want["plans"]}
+    assert helpers == {0, 1} and shapes == {0, 1, 2}  # the table does cover the decisions it is there for
+
+
+@pytest.mark.parametrize("setting", ["LAPWARM_COOP_MIN_N=1", "LAPWARM_HELPER=0", "LAPWARM_ARR_LISTS=0"])
+def test_solve_plan_table_under_a_knob_is_unchanged(setting):
+    """The same for n in (64, 640, 2048, 4428, 8192) with one knob off its default, plus what the workspace
+    layout asks beside the plan.  A fresh interpreter: the library reads its settings once."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import solve_plan_common as spc
+    name, value = setting.split("=")
+    r = subprocess.run([sys.executable, spc.__file__], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, **{name: value}))
+    assert r.returncode == 0, r.stderr[-2000:]
+    want = _golden_plans(setting)
+    _assert_same_plans(json.loads(r.stdout), want, list(spc.env_grid()), setting)
