@@ -74,7 +74,22 @@ __device__ __forceinline__ double dpp_move(double old, double src)
                   dpp_move<CTRL, ROW_MASK>(hi32(old), hi32(src)));
 }
 
+// a 64-bit word moves as its two halves, like a double
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long dpp_move(unsigned long long old, unsigned long long src)
+{
+    const unsigned lo = (unsigned)dpp_move<CTRL, ROW_MASK>((int)(unsigned)old, (int)(unsigned)src);
+    const unsigned hi = (unsigned)dpp_move<CTRL, ROW_MASK>((int)(old >> 32), (int)(src >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
 __device__ __forceinline__ int readlane(int x, int l) { return __builtin_amdgcn_readlane(x, l); }
+__device__ __forceinline__ unsigned long long readlane(unsigned long long x, int l)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(x >> 32), l);
+    return ((unsigned long long)hi << 32) | lo;
+}
 // (spelled with its own split and join: on lo32 / hi32 / mk_f64 the solver kernels schedule differently)
 __device__ __forceinline__ double readlane_f64(double x, int l)
 {
@@ -193,6 +208,22 @@ struct SumI32 {
     static __device__ __forceinline__ T identity() { return 0; }
     static __device__ __forceinline__ T combine(T o, T v) { return v + o; }
 };
+// A (value, index) pair packed as (f32_key(value) << 32) | index: the minimum is the smallest value and,
+// among equal values, the smallest index.
+struct MinU64 {
+    using T = unsigned long long;
+    static __device__ __forceinline__ T identity() { return ~0ull; }
+    static __device__ __forceinline__ T combine(T o, T v) { return (o < v) ? o : v; }
+};
+// Order-preserving map of a float32 onto unsigned integers: -0.0 and +0.0 share one key, and every NaN,
+// whatever its sign bit, has the largest key (after +inf).
+__device__ __forceinline__ unsigned f32_key(float x)
+{
+    if (x != x) return 0xffffffffu;
+    unsigned b = __float_as_uint(x);
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
 
 __device__ __forceinline__ double wave_min(double v) { return wave_reduce<MinF64>(v); }
 __device__ __forceinline__ double wave_max(double v) { return wave_reduce<MaxF64>(v); }
@@ -371,6 +402,10 @@ struct BlockCtx {
 
     __device__ __forceinline__ double &slot(int p, int w, double) { return ex->d[p][w]; }
     __device__ __forceinline__ int &slot(int p, int w, int) { return ex->i[p][w]; }
+    __device__ __forceinline__ unsigned long long &slot(int p, int w, unsigned long long)
+    {
+        return reinterpret_cast<unsigned long long &>(ex->d[p][w]);
+    }
 
     // Cross-wave combine without a serial LDS loop: lane l reads the slot of wave (l & 15) -- one
     // LDS round trip -- and a 4-step row reduction over 16 lanes finishes the reduction.

@@ -18,6 +18,7 @@
 #include "onegnn_refine.hpp"
 #include "oracle_duals.hpp"
 #include "solve_plan.hpp"
+#include "train_loss.hpp"
 
 using namespace lapwarm;
 
@@ -170,6 +171,24 @@ OracleWs oracle_layout(void *ws, int batch, int n, OracleParams *p)
     s.running = c.take<int>(1);
     s.bytes = c.off;
     return s;
+}
+
+// Training loss: the column-pass partials, the integer counts the backward reads (K, R, cnt, ksum), the row
+// minima of the reduced costs and the hinge partial sums.  The plan fields of *p must be filled.
+size_t train_loss_layout(void *ws, TrainLossParams *p)
+{
+    Carver c{reinterpret_cast<unsigned char *>(ws), 0};
+    const size_t bn = (size_t)p->batch * p->n;
+    p->pval = c.take<float>(bn * p->chunks);
+    p->parg = c.take<int>(bn * p->chunks);
+    p->K = c.take<int>(bn);
+    p->R = c.take<int>(bn);
+    p->cnt = c.take<int>(bn);
+    p->ksum = c.take<int>(bn);
+    p->mkey = c.take<unsigned>(bn);
+    p->mj = c.take<int>(bn);
+    p->hpart = c.take<double>((size_t)p->batch * p->hparts);
+    return c.off;
 }
 
 // Rectangular / cost-limited lapjv: the extended matrices (none when the solver reads the caller's C),
@@ -592,6 +611,60 @@ int lapwarm_oracle_duals_batched(const double *C, int batch, int n, const int *r
 {
     return oracle_duals_impl(C, batch, n, rows, cols, u, v, ret, sweeps, workspace, workspace_bytes, 1e-12,
                              reinterpret_cast<hipStream_t>(stream_));
+}
+
+size_t lapwarm_train_loss_workspace_bytes(int batch, int n)
+{
+    if (check_dims(batch, n) || batch > 65535) return 0;
+    TrainLossParams p{};
+    p.n = n;
+    p.batch = batch;
+    train_loss_plan(&p);
+    return train_loss_layout(nullptr, &p);
+}
+
+int lapwarm_train_loss_forward(const float *C, int batch, int n, const int *sizes, const float *u_pred,
+                               const float *u_target, float *v_proj, int *argmin_row, int *assign, float *terms,
+                               int *ret, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_dims(batch, n)) return rc;
+    if (batch > 65535) return -2;  // the batch is one dimension of every grid
+    if (workspace_bytes < lapwarm_train_loss_workspace_bytes(batch, n)) return -1;
+    TrainLossParams p{};
+    p.C = C;
+    p.n = n;
+    p.batch = batch;
+    p.sizes = sizes;
+    p.u = u_pred;
+    p.ut = u_target;
+    p.v = v_proj;
+    p.arow = argmin_row;
+    p.assign = assign;
+    p.terms = terms;
+    p.ret = ret;
+    train_loss_plan(&p);
+    train_loss_layout(workspace, &p);
+    HIP_TRY(launch_train_loss_forward(p, reinterpret_cast<hipStream_t>(stream_)));
+    return 0;
+}
+
+int lapwarm_train_loss_backward(int batch, int n, const int *sizes, const float *u_pred, const float *u_target,
+                                const float *weights, float grad_scale, float *grad_u, const void *workspace,
+                                size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_dims(batch, n)) return rc;
+    if (batch > 65535) return -2;
+    if (workspace_bytes < lapwarm_train_loss_workspace_bytes(batch, n)) return -1;
+    TrainLossParams p{};
+    p.n = n;
+    p.batch = batch;
+    p.sizes = sizes;
+    p.u = u_pred;
+    p.ut = u_target;
+    train_loss_plan(&p);
+    train_loss_layout(const_cast<void *>(workspace), &p);  // the kernel only reads it
+    HIP_TRY(launch_train_loss_backward(p, weights, grad_scale, grad_u, reinterpret_cast<hipStream_t>(stream_)));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -58,6 +58,11 @@ SIGNATURES = {
     "lapwarm_oracle_duals_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
     "lapwarm_oracle_duals_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                 c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_train_loss_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_train_loss_forward": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_train_loss_backward": (ct.c_int, [ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, ct.c_float, c_vp, c_vp,
+                                               ct.c_size_t, c_vp]),
     "lapwarm_refine_aggregate_batched": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int, ct.c_int,
                                                     ct.c_int, c_vp]),
     "lapwarm_refine_aggregate_wsum": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int, ct.c_int, c_vp]),

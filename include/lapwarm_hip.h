@@ -198,6 +198,39 @@ int lapwarm_oracle_duals_batched(const double *C, int batch, int n, const int *r
                                  double *v, int *ret, int *sweeps, void *workspace, size_t workspace_bytes,
                                  void *stream);
 
+/* The OneGNN training loss, gnn/train_one_gnn.py:180-226 `compute_loss` with its host greedy
+ * `greedy_primal_upper` (:137-177), float32 terms and fp64 sums.  C [batch][n][n] float32, padded to the batch
+ * maximum n; sizes [batch] int32 = n_b, the valid rows and columns of instance b are the prefix 0..n_b-1
+ * (`collate`, :72-91); u_pred, u_target [batch][n].  Outputs: v_proj [batch][n] with v_j = min_i (C_ij - u_i)
+ * (:189-193; 0 on padded columns); argmin_row [batch][n] int32, the row attaining v_j (-1 on padded columns);
+ * assign [batch][n] int32, the greedy's column of row i (:143-152; -1 on padded rows); terms [batch][4] =
+ * dual_lower (:195), feas (:197-201), u_reg (:212), primal_upper (:176), each an fp64 sum of the reference's
+ * float32 terms rounded once; ret [batch]: 0, or 2 for sizes[b] outside 1..n (terms NaN, assign -1, v_proj 0).
+ * Ties go to the lowest index (the row attaining a column minimum, the greedy's row order by min_j reduced_ij,
+ * the column a row takes); the reference leaves them to np.argsort's unstable default (:145, :148).  A NaN in C
+ * or u_pred reaches v_proj and feas as in torch.min / torch.relu; in the greedy a NaN reduced cost, of either
+ * sign bit, ranks after +inf when a row chooses its column and is left out of the row minimum that orders the rows.
+ * Returns 0, -2 for n <= 0, batch <= 0 or batch > 65535, -5 for n > 16384, -1 workspace too small,
+ * <= -1000 HIP error.  Four kernels on the caller's stream, no host synchronisation; every workspace word
+ * that is read is written inside the call.  The workspace keeps what the backward needs. */
+size_t lapwarm_train_loss_workspace_bytes(int batch, int n);
+int lapwarm_train_loss_forward(const float *C, int batch, int n, const int *sizes, const float *u_pred,
+                               const float *u_target, float *v_proj, int *argmin_row, int *assign, float *terms,
+                               int *ret, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Gradient of  w0 (primal_upper - dual_lower) + w1 feas + w2 u_reg  of every instance with respect to u_pred,
+ * times grad_scale (1 / batch for the reference's batch means, :215-219; primal_upper is a constant, :176-177):
+ *   grad_u[b][i] = grad_scale [ w0 (cnt_i - 1) + w1 (R_i - sum_{j: a_j = i} K_j) / n_b^2
+ *                               + w2 2 (u_i - u_target_i) / n_b ]
+ * with cnt_i = #{j: a_j = i}, R_i = #{j: h_ij > 0}, K_j = #{i: h_ij > 0}, h_ij = (u_i + v_j) - C_ij: what
+ * autograd returns for :189-201 and :212 when no column minimum is tied.  Evaluated in fp64, rounded once;
+ * 0 on padded rows and for instances with ret 2.  weights [3] float32 on the device (the reference: 1, 1, 0.1);
+ * workspace: the one the forward call of the same batch, n, sizes, u_pred and u_target wrote; it is only read.
+ * Returns as the forward. */
+int lapwarm_train_loss_backward(int batch, int n, const int *sizes, const float *u_pred, const float *u_target,
+                                const float *weights, float grad_scale, float *grad_u, const void *workspace,
+                                size_t workspace_bytes, void *stream);
+
 /* OneGNN top-k refinement, aggregation part (gnn/one_gnn.py:139-155), float32:
  *   val_k = topk16[row][k] - u_pre[row]   (== topk(cost - u_pre): x -> x - c is monotone)
  *   w     = softmax(-val) over the finite entries (0 elsewhere)

@@ -1,0 +1,153 @@
+#!/usr/bin/env python3
+"""Generate tests/golden/train_loss_cases.npz FROM THE REFERENCE.
+
+Runs only where the reference repository exists (REF below).  It loads the reference's gnn/train_one_gnn.py by
+file path (imported, never copied; an empty stand-in module answers its `import h5py`, which only the dataset
+reader uses), calls its `compute_loss` on the CPU with `u_pred.requires_grad_()` and stores data only:
+
+  * the inputs: cost (B, n, n), u_pred, u_target (B, n) float32, sizes (B,);
+  * the reference's per-instance v_proj, dual_lower, feas, u_reg, primal_upper (the locals of `compute_loss`
+    when it returns) and its grad_u;
+  * dual64, feas64, ureg64: the same sums over the same float32 terms in float64; g64: the closed-form gradient
+    in float64 from the integer counts; the stable-order greedy's assign and primal_upper: all from
+    tests/train_loss_common.py;
+  * per case, whether the reference's primal_upper equals the stable-order one in every instance.  np.argsort's
+    default sort is unstable and the reference always sorts ties, so this depends on the numpy build; the count
+    is printed, not asserted.  (With numpy >= 2 the reference's `sum()` of float32 scalars also stays float32,
+    where numpy 1.x promoted it to float64.)
+
+It asserts that no valid column of a gradient case has two rows attaining its minimum (the reference's `min`
+backward is unspecified there), and that the reference's float32 sums and grad_u lie within the recursive-summation
+bound of the float64 values (train_loss_common.reference_bounds).
+
+Usage:  python tests/golden/make_train_loss.py          (from the repo root)
+"""
+from __future__ import annotations
+
+import importlib.util
+import json
+import sys
+import types
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[2]
+REF = Path("/root/reference")
+OUT = Path(__file__).resolve().parent / "train_loss_cases.npz"
+
+sys.path.insert(0, str(ROOT / "tests"))
+import train_loss_common as tl  # noqa: E402
+
+sys.modules.setdefault("h5py", types.ModuleType("h5py"))
+_spec = importlib.util.spec_from_file_location("_ref_train_one_gnn", str(REF / "gnn" / "train_one_gnn.py"))
+ref = importlib.util.module_from_spec(_spec)
+sys.modules["_ref_train_one_gnn"] = ref
+_spec.loader.exec_module(ref)
+
+CAPTURED = ("v_proj", "dual_lower", "feas", "u_reg", "primal_upper")
+
+
+def reference_loss(cost, u_pred, u_target, sizes):
+    """compute_loss of the reference on the CPU: its per-instance locals and grad_u."""
+    B, n = u_pred.shape
+    mask = torch.arange(n)[None, :] < torch.from_numpy(sizes.astype(np.int64))[:, None]
+    batch = ref.Batch(cost=torch.from_numpy(cost), u=torch.from_numpy(u_target), v=torch.zeros(B, n),
+                      row_feat=torch.zeros(B, n, 1), mask=mask)
+    u = torch.from_numpy(u_pred.copy()).requires_grad_()
+    seen = {}
+
+    def grab(frame, event, arg):
+        if event == "return" and frame.f_code is ref.compute_loss.__code__:
+            seen.update({k: frame.f_locals[k].detach().clone() for k in CAPTURED})
+
+    sys.setprofile(grab)
+    try:
+        loss, _ = ref.compute_loss(batch, {"u": u})
+    finally:
+        sys.setprofile(None)
+    loss.backward()
+    out = {k: seen[k].numpy().astype(np.float32) for k in CAPTURED}
+    out["grad_u"] = u.grad.numpy().astype(np.float32)
+    return out
+
+
+def uniform_case(rng, B, n, sizes):
+    """Costs uniform in [0, 1), u_pred = u_target + noise with |u| up to 4: u + v then rounds more coarsely than
+    C, which leaves the positive hinge residue the loss has to reproduce.  From n = 257 the costs are
+    tl.cost_from_grid(q) of 12-bit integers q, and q is what the file stores, so that it stays small.  Finite
+    rubbish in the padding, which no valid entry may depend on."""
+    if n < 257:
+        cost = rng.random(size=(B, n, n), dtype=np.float32)
+    else:
+        cost = tl.cost_from_grid(rng.integers(0, 1 << 12, size=(B, n, n)).astype(np.uint16))
+    u_target = rng.uniform(-4.0, 4.0, size=(B, n)).astype(np.float32)
+    u_pred = (u_target + 0.05 * rng.standard_normal((B, n))).astype(np.float32)
+    return pad(cost, u_pred, u_target, sizes)
+
+
+def integer_case(rng, B, n, sizes):
+    """Small-integer costs with integer u: ties in every column and every row."""
+    cost = rng.integers(0, 6, size=(B, n, n)).astype(np.float32)
+    u_target = rng.integers(-2, 3, size=(B, n)).astype(np.float32)
+    u_pred = (u_target + rng.integers(-1, 2, size=(B, n))).astype(np.float32)
+    return pad(cost, u_pred, u_target, sizes)
+
+
+def pad(cost, u_pred, u_target, sizes):
+    for b, nb in enumerate(sizes):
+        cost[b, nb:, :] = -7.0
+        cost[b, :, nb:] = -7.0
+        u_pred[b, nb:] = 3.0
+        u_target[b, nb:] = -3.0
+    return cost, u_pred, u_target
+
+
+def main():
+    rng = np.random.default_rng(20240611)
+    specs = []
+    for n in (1, 2, 7, 63, 64, 65, 257):
+        for B in (1, 3):
+            specs.append(("uniform", f"uniform-n{n}-B{B}", B, n, [n] * B))
+    specs.append(("uniform", "uniform-n65-mixed", 4, 65, [65, 64, 1, 33]))
+    for n in (2, 7, 64, 65):
+        specs.append(("integer", f"integer-n{n}-B3", 3, n, [n] * 3))
+    specs.append(("integer", "integer-n65-mixed", 4, 65, [65, 64, 1, 33]))
+
+    arrays, meta, agree = {}, [], 0
+    for k, (kind, label, B, n, sizes) in enumerate(specs):
+        sizes = np.asarray(sizes, dtype=np.int32)
+        cost, u_pred, u_target = (uniform_case if kind == "uniform" else integer_case)(rng, B, n, sizes)
+        got = reference_loss(cost, u_pred, u_target, sizes)
+        r = tl.restate(cost, u_pred, u_target, sizes)
+        assert tl.bits_equal32(got["v_proj"], r["v"]), label
+        if kind == "uniform":
+            for b in range(B):
+                nb = int(sizes[b])
+                cm = cost[b, :nb, :nb] - u_pred[b, :nb, None]
+                assert ((cm == cm.min(axis=0)).sum(axis=0) == 1).all(), (label, b, "tied column minimum")
+            bound = tl.reference_bounds(r, sizes)
+            assert (np.abs(got["dual_lower"] - r["dual64"]) <= bound["dual"]).all(), label
+            assert (np.abs(got["feas"] - r["feas64"]) <= bound["feas"]).all(), label
+            assert (np.abs(got["u_reg"] - r["ureg64"]) <= bound["ureg"]).all(), label
+            assert (np.abs(got["grad_u"] - r["g64"]) <= bound["grad"]).all(), label
+        if kind == "uniform":
+            assert (r["feas64"][sizes > 2] > 0).all(), (label, "no positive hinge residue")
+        primal_equal = bool(tl.bits_equal32(got["primal_upper"], r["primal_upper"]))
+        agree += primal_equal
+        meta.append(dict(label=label, kind=kind, B=B, n=n, primal_equal=primal_equal))
+        store = dict(cost=cost, u_pred=u_pred, u_target=u_target, sizes=sizes, ref_v=got["v_proj"],
+                     ref_dual=got["dual_lower"], ref_feas=got["feas"], ref_ureg=got["u_reg"],
+                     ref_primal=got["primal_upper"], ref_grad=got["grad_u"], dual64=r["dual64"], feas64=r["feas64"],
+                     ureg64=r["ureg64"], g64=r["g64"], assign=r["assign"], primal_stable=r["primal_upper"])
+        if kind == "uniform" and n >= 257:
+            store["cost_q"] = tl.grid_from_cost(store.pop("cost"))
+        arrays.update({f"c{k}_{name}": a for name, a in store.items()})
+    np.savez_compressed(OUT, meta=np.array(json.dumps(meta)), **arrays)
+    print(f"{OUT.name}: {len(meta)} cases, {OUT.stat().st_size} bytes; reference primal_upper equals the "
+          f"stable-order one in {agree} of {len(meta)} cases (numpy {np.__version__})")
+
+
+if __name__ == "__main__":
+    main()
