@@ -335,6 +335,24 @@ int lapwarm_refine_aggregate_batched(const float *topk16, const float *u_pre, co
     return lapwarm_refine_aggregate_wsum(topk16, u_pre, w1, b1, out, nullptr, rows, H, stream_);
 }
 
+size_t lapwarm_refine_backward_workspace_bytes(int rows, int H)
+{
+    return refine_backward_workspace_bytes(rows, H);
+}
+
+int lapwarm_refine_backward(const float *topk16, const float *u_pre, const float *w1, const float *b1,
+                            const float *grad_out, const float *grad_wsum, float *grad_u, float *grad_w1,
+                            float *grad_b1, int rows, int H, void *ws, size_t ws_bytes, void *stream_)
+{
+    if (rows < 0 || H < 1) return -2;
+    if (rows == 0) return 0;
+    if (!topk16 || !u_pre || !w1 || !b1 || !grad_out || !grad_u || !grad_w1 || !grad_b1 || !ws) return -2;
+    if (ws_bytes < refine_backward_workspace_bytes(rows, H)) return -2;
+    HIP_TRY(launch_refine_backward(topk16, u_pre, w1, b1, grad_out, grad_wsum, grad_u, grad_w1, grad_b1, rows, H, ws,
+                                   reinterpret_cast<hipStream_t>(stream_)));
+    return 0;
+}
+
 int lapwarm_solver_uses_helpers(int n)
 {
     return (solver_uses_helpers(n) && solve_shape(n, false) == SolveShape::kOneLaunch) ? 1 : 0;

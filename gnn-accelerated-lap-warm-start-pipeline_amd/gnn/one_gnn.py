@@ -12,7 +12,10 @@ the MI355X:
     instead of before it -- 16x fewer flops and no (B, n, 16, H) tensor in HBM.  The aggregation
     sum_k w_k GELU(w1 val_k + b1) is a hand-written HIP kernel (onegnn_refine.hip); the H x H
     GEMMs stay with PyTorch-ROCm (rocBLAS/hipBLASLt on the MFMA units);
-  * training mode keeps the reference's op order (dropout placement).
+  * the fused aggregation is differentiable: its backward is a second HIP kernel that recomputes the
+    weights and the GELU from the 64 bytes of a row (lapwarm_refine_backward), so a gradient taken through
+    an eval-mode model reaches u_pre and the first edge-MLP layer;
+  * training mode keeps the reference's op order (dropout placement) unless `fused_refine_training` is set.
 """
 from __future__ import annotations
 
@@ -22,6 +25,65 @@ from typing import Optional
 import torch
 from torch import nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
+
+
+class _RefineAggregate(torch.autograd.Function):
+    """agg[r] = sum_k w_k GELU(w1 val_k + b1) and wsum[r] = sum_k w_k with val = base[r] - u_pre[r] and
+    w = softmax(-val) over the finite entries: lapwarm_refine_aggregate_wsum forward, one
+    lapwarm_refine_backward call on the current stream backward.
+
+    base (rows, 16) float32 contiguous, the ascending top-16 costs, is a constant: its gradient is None.
+    u_pre (rows,), w1 (H, 1) or (H,) and b1 (H,) are taken as float32 (half precision is upcast) and
+    receive their gradients in their own dtype.  The backward saves the inputs only, nothing of size
+    rows x 16 x H, and is not itself differentiable."""
+
+    @staticmethod
+    def forward(ctx, base, u_pre, w1, b1):
+        from lap import _hip
+        rows, H = base.shape[0], b1.shape[0]
+        up = u_pre.detach().to(torch.float32).contiguous().view(rows)
+        w1f = w1.detach().to(torch.float32).contiguous().view(-1)
+        b1f = b1.detach().to(torch.float32).contiguous()
+        agg = torch.empty((rows, H), dtype=torch.float32, device=base.device)
+        wsum = torch.empty((rows,), dtype=torch.float32, device=base.device)
+        lib = _hip.require_device()
+        stream = torch.cuda.current_stream(base.device).cuda_stream
+        rc = lib.lapwarm_refine_aggregate_wsum(base.data_ptr(), up.data_ptr(), w1f.data_ptr(), b1f.data_ptr(),
+                                               agg.data_ptr(), wsum.data_ptr(), rows, H, ct.c_void_p(stream))
+        if _hip.check(rc, "refine_aggregate") != 0:
+            raise RuntimeError(f"refine_aggregate failed (code {rc})")
+        ctx.save_for_backward(base, up, w1f, b1f)
+        ctx.meta = (u_pre.shape, u_pre.dtype, w1.shape, w1.dtype, b1.dtype)
+        ctx.set_materialize_grads(False)
+        return agg, wsum
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_agg, grad_wsum):
+        from lap import _hip
+        base, up, w1f, b1f = ctx.saved_tensors
+        u_shape, u_dtype, w1_shape, w1_dtype, b1_dtype = ctx.meta
+        rows, H = base.shape[0], b1f.shape[0]
+        if grad_agg is None:
+            grad_agg = torch.zeros((rows, H), dtype=torch.float32, device=base.device)
+        grad_agg = grad_agg.to(torch.float32).contiguous()
+        if grad_wsum is not None:
+            grad_wsum = grad_wsum.to(torch.float32).contiguous()
+        grad_u = torch.empty((rows,), dtype=torch.float32, device=base.device)
+        grad_w1 = torch.empty((H,), dtype=torch.float32, device=base.device)
+        grad_b1 = torch.empty((H,), dtype=torch.float32, device=base.device)
+        lib = _hip.require_device()
+        nbytes = int(lib.lapwarm_refine_backward_workspace_bytes(rows, H))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=base.device)
+        stream = torch.cuda.current_stream(base.device).cuda_stream
+        rc = lib.lapwarm_refine_backward(base.data_ptr(), up.data_ptr(), w1f.data_ptr(), b1f.data_ptr(),
+                                         grad_agg.data_ptr(), None if grad_wsum is None else grad_wsum.data_ptr(),
+                                         grad_u.data_ptr(), grad_w1.data_ptr(), grad_b1.data_ptr(), rows, H,
+                                         ws.data_ptr(), nbytes, ct.c_void_p(stream))
+        if _hip.check(rc, "refine_backward") != 0:
+            raise RuntimeError(f"lapwarm_refine_backward failed (code {rc}): {_hip.last_error()}")
+        return (None, grad_u.view(u_shape).to(u_dtype), grad_w1.view(w1_shape).to(w1_dtype), grad_b1.to(b1_dtype))
 
 
 class ResidualBlock(nn.Module):
@@ -40,6 +102,12 @@ class ResidualBlock(nn.Module):
 
 
 class OneGNN(nn.Module):
+    # Training mode on the GPU with topk = 16 also takes the fused refinement (HIP forward and backward, second
+    # edge-MLP layer after the weighted sum, message_dropout on the message before message_norm, where the
+    # reference has it too) when this is True.  False: training mode is the reference's op order.  A plain
+    # attribute: no constructor argument, not in the state dict.
+    fused_refine_training = False
+
     def __init__(self, in_dim: int, hidden: int = 64, layers: int = 2, dropout: float = 0.1,
                  topk: int = 16) -> None:
         super().__init__()
@@ -97,7 +165,7 @@ class OneGNN(nn.Module):
                 base = base.unsqueeze(0)
         else:
             base, _ = torch.topk(cost, k=k, dim=-1, largest=False)
-        if self.training or not h.is_cuda or k != 16:
+        if (self.training and not self.fused_refine_training) or not h.is_cuda or k != 16:
             return self._refine_reference_order(h, base, u_pre, mask_rows)
         return self._refine_fused(h, base.contiguous(), u_pre, mask_rows)
 
@@ -117,26 +185,16 @@ class OneGNN(nn.Module):
         return self.message_norm(self.message_dropout(msg))
 
     def _refine_fused(self, h, base, u_pre, mask_rows):
-        from lap import _hip
         B, N, H = h.shape
         rows = B * N
-        up = u_pre.contiguous().view(rows)
         if mask_rows is not None:
             # masked rows: every value becomes +inf -> zero weights -> zero message
             base = base.masked_fill(~mask_rows, float("inf")).contiguous()
-        agg = torch.empty((rows, H), dtype=torch.float32, device=h.device)
-        wsum = torch.empty((rows,), dtype=torch.float32, device=h.device)
         lin1, lin2 = self.edge_mlp[0], self.edge_mlp[2]
-        lib = _hip.require_device()
-        stream = torch.cuda.current_stream(h.device).cuda_stream
-        rc = lib.lapwarm_refine_aggregate_wsum(
-            base.data_ptr(), up.data_ptr(), lin1.weight.contiguous().view(-1).data_ptr(),
-            lin1.bias.contiguous().data_ptr(), agg.data_ptr(), wsum.data_ptr(), rows, H,
-            ct.c_void_p(stream))
-        if _hip.check(rc, "refine_aggregate") != 0:
-            raise RuntimeError(f"refine_aggregate failed (code {rc})")
+        agg, wsum = _RefineAggregate.apply(base.view(rows, 16), u_pre.reshape(rows), lin1.weight, lin1.bias)
         msg = F.linear(agg, lin2.weight) + wsum.unsqueeze(-1) * lin2.bias
         msg = msg.view(B, N, H)
         if mask_rows is not None:
             msg = msg * mask_rows
-        return self.message_norm(msg)
+        # identity in eval mode; in training (fused_refine_training) the reference's dropout on the message
+        return self.message_norm(self.message_dropout(msg))

@@ -244,6 +244,24 @@ int lapwarm_refine_aggregate_batched(const float *topk16, const float *u_pre, co
 int lapwarm_refine_aggregate_wsum(const float *topk16, const float *u_pre, const float *w1,
                                   const float *b1, float *out, float *wsum, int rows, int H, void *stream);
 
+/* Backward of lapwarm_refine_aggregate_wsum.  With G = grad_out [rows][H] = dL/dout and s = grad_wsum [rows] =
+ * dL/dwsum (NULL: zero), x_kh = w1[h] val_k + b1[h] and GELU'(x) = Phi(x) + x phi(x):
+ *   Q_k = sum_h G_h GELU(x_kh) + s,   D_k = sum_h G_h w1_h GELU'(x_kh)
+ *   dval_k = w_k D_k - w_k (Q_k - sum_m w_m Q_m)   (0 where val_k is not finite)
+ *   grad_u[row] = -sum_k dval_k
+ *   grad_w1[h] = sum_row sum_k G_h w_k GELU'(x_kh) val_k,   grad_b1[h] = sum_row sum_k G_h w_k GELU'(x_kh)
+ * topk16 is a constant: it has no gradient.  val, w and GELU are recomputed from the inputs; nothing of size
+ * rows x 16 x H is stored.  float32 terms; the sums over rows are accumulated in fp64 in a fixed order (per
+ * workgroup into the workspace, then by a second kernel) and rounded once, without atomics: equal inputs give
+ * equal bits.  A row without a finite value gives grad_u == 0 and adds nothing to grad_w1 / grad_b1.
+ * Two kernels on the caller's stream, no allocation, no host synchronisation; every workspace word that is read
+ * is written inside the call.  Returns 0 (rows == 0: nothing is launched), -2 for rows < 0, H < 1, a NULL pointer
+ * other than grad_wsum or ws_bytes below lapwarm_refine_backward_workspace_bytes(rows, H), <= -1000 HIP error. */
+size_t lapwarm_refine_backward_workspace_bytes(int rows, int H);
+int lapwarm_refine_backward(const float *topk16, const float *u_pre, const float *w1, const float *b1,
+                            const float *grad_out, const float *grad_wsum, float *grad_u, float *grad_w1,
+                            float *grad_b1, int rows, int H, void *ws, size_t ws_bytes, void *stream);
+
 /* Profiling hook for bench.py: when enabled, lapwarm_seeded_batched / lapwarm_lapjv_batched
  * bracket the per-instance solver kernel with HIP events on the caller's stream;
  * lapwarm_profile_last_solver_ms() waits for the last bracket and returns its duration. */
