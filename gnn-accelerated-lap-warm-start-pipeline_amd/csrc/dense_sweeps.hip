@@ -11,6 +11,7 @@
 //   row features     gnn/features.py:161-243
 #include "device_utils.hpp"
 #include "dense_sweeps.hpp"
+#include "ragged_batch.hpp"
 
 namespace lapwarm {
 
@@ -556,18 +557,33 @@ __device__ __forceinline__ void reduce_sum3_isum2(BlockCtx &bc, double &a, doubl
     }
 }
 
-__global__ void __launch_bounds__(kSweepThreads, 6) row_features_kernel(FeatureParams p, int npad)
+// What one workgroup gets for one row of an n x n instance.
+struct FeatureRow {
+    const double *row;  // its n costs
+    const double *cm;   // the n column minima of its instance
+    const float *pos;   // its 8 positional encodings
+    float *feat;        // 21
+    float *topk;        // 16, or null
+    float *cost32;      // CAST: n floats, (float)row, or null
+    int n;
+};
+
+// The row body of both feature kernels: the uniform batch (row_features_kernel) and the ragged one
+// (row_features_ragged_kernel) differ only in where a row and its outputs are.  `npad` doubles of LDS are
+// staged (npad >= n, even); CAST also writes the row as float32 while it is in registers on its way to LDS.
+template <bool CAST>
+__device__ __forceinline__ void row_features_body(const FeatureRow &r, int npad)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     BlockExchange *ex = reinterpret_cast<BlockExchange *>(smem);
     double *s = reinterpret_cast<double *>(smem + sizeof(BlockExchange));
     SelectState *st = reinterpret_cast<SelectState *>(s + npad);
-    const int b = blockIdx.y, i = blockIdx.x, n = p.n;
+    const int n = r.n;
     BlockCtx bc;
     bc.init(ex);
     int par = 0;
-    const double *row = p.C + ((size_t)b * n + i) * n;
-    const double *cm = p.colmin + (size_t)b * n;
+    const double *row = r.row;
+    const double *cm = r.cm;
 
     double lo = pos_inf(), hi = -pos_inf(), sum = 0.0;
 #pragma unroll 4
@@ -577,6 +593,9 @@ __global__ void __launch_bounds__(kSweepThreads, 6) row_features_kernel(FeatureP
         hi = (x > hi) ? x : hi;
         sum += x;
         s[j] = x;
+        if constexpr (CAST) {
+            if (r.cost32) r.cost32[j] = (float)x;
+        }
     }
     reduce_min_max_sum(bc, lo, hi, sum);
     const double mean = sum / n;
@@ -647,9 +666,8 @@ __global__ void __launch_bounds__(kSweepThreads, 6) row_features_kernel(FeatureP
             a2 += dq * dq;
         }
         kstd = sqrt(a2 / kk);
-        if (p.topk) {
-            float *tk = p.topk + ((size_t)b * n + i) * 16;
-            for (int q = 0; q < 16; ++q) tk[q] = (float)st->top[q];  // +inf beyond n
+        if (r.topk) {
+            for (int q = 0; q < 16; ++q) r.topk[q] = (float)st->top[q];  // +inf beyond n
         }
     }
     // median absolute deviation: the same selection on |x - median|, which lies in [0, dmax]
@@ -669,7 +687,7 @@ __global__ void __launch_bounds__(kSweepThreads, 6) row_features_kernel(FeatureP
             difficulty = 1.0 / ((hi - lo) / (double)(n - 1) + kFeatEps);
         }
         const double m = (n > 1) ? (double)n : 1.0;
-        float *f = p.feat + ((size_t)b * n + i) * 21;
+        float *f = r.feat;
         f[0] = (float)lo;
         f[1] = (float)hi;
         f[2] = (float)mean;
@@ -683,8 +701,55 @@ __global__ void __launch_bounds__(kSweepThreads, 6) row_features_kernel(FeatureP
         f[10] = (float)difficulty;
         f[11] = (float)((double)(cnts & 0xffff) / m);
         f[12] = (float)((double)(cnts >> 16) / m);
-        for (int q = 0; q < 8; ++q) f[13 + q] = p.posenc[(size_t)i * 8 + q];
+        for (int q = 0; q < 8; ++q) f[13 + q] = r.pos[q];
     }
+}
+
+__global__ void __launch_bounds__(kSweepThreads, 6) row_features_kernel(FeatureParams p, int npad)
+{
+    const int b = blockIdx.y, i = blockIdx.x, n = p.n;
+    const size_t o = (size_t)b * n + i;
+    FeatureRow r;
+    r.row = p.C + o * n;
+    r.cm = p.colmin + (size_t)b * n;
+    r.pos = p.posenc + (size_t)i * 8;
+    r.feat = p.feat + o * 21;
+    r.topk = p.topk ? p.topk + o * 16 : nullptr;
+    r.cost32 = nullptr;
+    r.n = n;
+    row_features_body<false>(r, npad);
+}
+
+// Ragged batch (ragged_batch.hpp): workgroup (i, b) owns row i of the padded [N] rows of instance b.
+// A row of the prefix runs the body above at n = n_b; a padded row (i >= n_b, or every row of an
+// instance whose size is outside 1..N) writes its zeros and +inf and leaves before the first barrier.
+// The exit depends on blockIdx and sizes[b] only: workgroup-uniform.
+__global__ void __launch_bounds__(kSweepThreads, 6) row_features_ragged_kernel(RaggedBatch g, RaggedFeatureOut o,
+                                                                               int npad)
+{
+    const int b = blockIdx.y, i = blockIdx.x, N = g.N, tid = threadIdx.x;
+    const int n = ragged_size(g, b);
+    const size_t orow = (size_t)b * N + i;
+    if (i == 0 && tid == 0) o.ret[b] = n ? 0 : 2;
+    if (tid == 0 && o.mask) o.mask[orow] = i < n;
+    if (o.cost32) {  // the zeros right of the prefix, or the whole padded row
+        float *c = o.cost32 + orow * N;
+        for (int j = (i < n ? n : 0) + tid; j < N; j += kSweepThreads) c[j] = 0.0f;
+    }
+    if (i >= n) {
+        if (tid < 21) o.feat[orow * 21 + tid] = 0.0f;
+        if (tid < 16 && o.topk) o.topk[orow * 16 + tid] = __builtin_inff();
+        return;
+    }
+    FeatureRow r;
+    r.row = g.C + g.offsets[b] + (size_t)i * (g.ld ? g.ld : n);
+    r.cm = o.colmin + (size_t)b * N;
+    r.pos = o.posenc + ((size_t)o.pos_off[b] + i) * 8;
+    r.feat = o.feat + orow * 21;
+    r.topk = o.topk ? o.topk + orow * 16 : nullptr;
+    r.cost32 = o.cost32 ? o.cost32 + orow * N : nullptr;
+    r.n = n;
+    row_features_body<true>(r, npad);
 }
 
 }  // namespace
@@ -812,19 +877,37 @@ hipError_t launch_reduce_costs(const double *C, int n, int batch, const double *
     return hipGetLastError();
 }
 
+// exp(-(x - lo)) is not kept in LDS between the entropy passes: the closed form needs it once, the
+// element-wise path recomputes it, and the 8 n bytes saved let 6-7 workgroups share a CU
+// (measured: 1.29 -> 1.02 ms for 32 x 2048 rows together with the 6-waves-per-SIMD bound)
+static size_t row_features_lds(int npad)
+{
+    return sizeof(BlockExchange) + sizeof(double) * (size_t)npad + sizeof(SelectState) +
+           (size_t)npad;  // + one bucket byte per element
+}
+
 hipError_t launch_row_features(const FeatureParams &p, hipStream_t stream)
 {
     if (p.n > 16384 || p.n < 1) return hipErrorInvalidValue;
     const int npad = (p.n + 1) & ~1;
-    // exp(-(x - lo)) is not kept in LDS between the entropy passes: the closed form needs it once, the
-    // element-wise path recomputes it, and the 8 n bytes saved let 6-7 workgroups share a CU
-    // (measured: 1.29 -> 1.02 ms for 32 x 2048 rows together with the 6-waves-per-SIMD bound)
-    const size_t lds = sizeof(BlockExchange) + sizeof(double) * (size_t)npad + sizeof(SelectState) +
-                       (size_t)npad;  // + one bucket byte per element
+    const size_t lds = row_features_lds(npad);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(row_features_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(row_features_kernel, dim3(p.n, p.batch), dim3(kSweepThreads), lds, stream, p, npad);
+    return hipGetLastError();
+}
+
+// LDS is sized for N: the rows of one launch share one size, whatever their instance's n_b.
+hipError_t launch_row_features_ragged(const RaggedBatch &g, const RaggedFeatureOut &o, hipStream_t stream)
+{
+    if (g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+    const int npad = (g.N + 1) & ~1;
+    const size_t lds = row_features_lds(npad);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(row_features_ragged_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(row_features_ragged_kernel, dim3(g.N, g.batch), dim3(kSweepThreads), lds, stream, g, o, npad);
     return hipGetLastError();
 }
 

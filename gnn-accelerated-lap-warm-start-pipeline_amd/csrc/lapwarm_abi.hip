@@ -17,6 +17,7 @@
 #include "jv_solver.hpp"
 #include "onegnn_refine.hpp"
 #include "oracle_duals.hpp"
+#include "ragged_batch.hpp"
 #include "solve_plan.hpp"
 #include "train_loss.hpp"
 
@@ -551,6 +552,48 @@ int lapwarm_row_features_batched(const double *C, int batch, int n, const float 
     fp.feat = feat;
     fp.topk = topk16;
     HIP_TRY(launch_row_features(fp, stream));
+    return 0;
+}
+
+// ---- ragged batches: B instances of different sizes behind one offset and one size per instance ----
+static int check_ragged(const void *C, const void *offsets, const void *sizes, int ld, int batch, int N)
+{
+    if (N <= 0 || batch <= 0 || batch > 65535 || ld < 0) return -2;  // the batch is one dimension of every grid
+    if (N > 16384) return -5;
+    if (!C || !offsets || !sizes) return -2;
+    return 0;
+}
+
+size_t lapwarm_ragged_workspace_bytes(int batch, int N)
+{
+    if (N <= 0 || batch <= 0 || batch > 65535 || N > 16384) return 0;
+    return align_up(sizeof(double) * (size_t)batch * N);  // the column minima the feature kernel compares with
+}
+
+int lapwarm_colmin_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                          const double *u, double *out, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!out || !workspace) return -2;
+    if (workspace_bytes < lapwarm_ragged_workspace_bytes(batch, N)) return -1;
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    HIP_TRY(launch_colmin_ragged(g, u, out, reinterpret_cast<hipStream_t>(stream_)));
+    return 0;
+}
+
+int lapwarm_row_features_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                const float *posenc, const int *pos_off, float *feat, float *topk16, float *cost32,
+                                unsigned char *mask, int *ret, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!posenc || !pos_off || !feat || !ret || !workspace) return -2;
+    if (workspace_bytes < lapwarm_ragged_workspace_bytes(batch, N)) return -1;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    double *colmin = reinterpret_cast<double *>(workspace);
+    HIP_TRY(launch_colmin_ragged(g, nullptr, colmin, stream));
+    const RaggedFeatureOut o{colmin, posenc, pos_off, feat, topk16, cost32, mask, ret};
+    HIP_TRY(launch_row_features_ragged(g, o, stream));
     return 0;
 }
 

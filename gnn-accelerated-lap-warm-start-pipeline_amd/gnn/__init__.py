@@ -6,6 +6,7 @@ OneGNN and the two row-feature functions are the hot path and run on the device.
 `compute_features` (the O(n^2)-edge model and its features, SURVEY.md section 2: out of scope) are
 importable names that raise NotImplementedError when USED, so that the harness' import line
 succeeds and its OneGNN branch runs; a DualGNN checkpoint is reported, not silently mishandled."""
+from .collate import DeviceBatch, collate_device
 from .features import compute_row_features, compute_row_features_torch, positional_encodings, ROW_FEATURE_DIM
 from .one_gnn import OneGNN, ResidualBlock
 from .pipeline import GNNPredictor, WarmStartPipeline, load_checkpoint
@@ -25,4 +26,4 @@ def compute_features(*args, **kwargs):
 
 __all__ = ["OneGNN", "ResidualBlock", "DualGNN", "compute_features", "compute_row_features",
            "compute_row_features_torch", "positional_encodings", "ROW_FEATURE_DIM", "GNNPredictor",
-           "WarmStartPipeline", "load_checkpoint"]
+           "WarmStartPipeline", "load_checkpoint", "collate_device", "DeviceBatch"]

@@ -96,6 +96,173 @@ def row_features_device(C, return_topk: bool = True):
     return (feat, topk) if return_topk else feat
 
 
+MAX_N = 16384       # LDS of the row kernels
+MAX_BATCH = 65535   # the batch is one grid dimension
+
+_RAGGED_POSENC_CACHE = {}
+
+
+def _ragged_posenc(distinct, device):
+    """The (n, 8) tables of the sizes in `distinct` (sorted), one after the other, on the device, and the first
+    row of each: built on the host from positional_encodings, so bit-identical to the per-n tables; kept per
+    set of sizes (the newest 32 sets)."""
+    import torch
+    key = (distinct, str(device))
+    if key not in _RAGGED_POSENC_CACHE:
+        if len(_RAGGED_POSENC_CACHE) >= 32:
+            _RAGGED_POSENC_CACHE.pop(next(iter(_RAGGED_POSENC_CACHE)))
+        first = dict(zip(distinct, np.concatenate(([0], np.cumsum(distinct)[:-1])).tolist()))
+        table = np.concatenate([positional_encodings(n) for n in distinct], axis=0)
+        _RAGGED_POSENC_CACHE[key] = (torch.from_numpy(table).to(device), first)
+    return _RAGGED_POSENC_CACHE[key]
+
+
+class RaggedFeatures:
+    """What one ragged call returns, padded to N = the largest size: feat (B, N, 21) f32, topk (B, N, 16) f32
+    or None, cost32 (B, N, N) f32 or None, mask (B, N) bool, sizes (B,) int32 and ret (B,) int32 (0, or 2
+    for a size outside 1..N), all on the device."""
+    __slots__ = ("feat", "topk", "cost32", "mask", "sizes", "ret")
+
+    def __init__(self, feat, topk, cost32, mask, sizes, ret):
+        self.feat, self.topk, self.cost32, self.mask, self.sizes, self.ret = feat, topk, cost32, mask, sizes, ret
+
+
+class RaggedPack:
+    """A ragged batch on the device, as the C ABI takes it: C fp64, offsets (B,) int64, sizes and pos_off (B,)
+    int32 (views of one uploaded block), posenc (rows, 8) f32, ld (0: packed), N, and the sizes on the host."""
+    __slots__ = ("C", "offsets", "sizes", "pos_off", "posenc", "ld", "N", "host_sizes")
+
+    def __init__(self, C, offsets, sizes, pos_off, posenc, ld, N, host_sizes):
+        self.C, self.offsets, self.sizes, self.pos_off, self.posenc = C, offsets, sizes, pos_off, posenc
+        self.ld, self.N, self.host_sizes = ld, N, host_sizes
+
+
+def _check_ragged_sizes(sizes, n_max=MAX_N):
+    if len(sizes) < 1:
+        raise ValueError("at least one cost matrix expected")
+    if len(sizes) > MAX_BATCH:
+        raise ValueError(f"at most {MAX_BATCH} instances per call, not {len(sizes)}")
+    for n in sizes:
+        if n < 1:
+            raise ValueError("square, non-empty cost matrices expected")
+        if n > n_max:
+            raise ValueError(f"n exceeds the {n_max} limit of this call: {n}")
+
+
+def ragged_pack(costs, device="cuda:0", sizes=None):
+    """Host-side half of a ragged call: validates, packs and uploads.  `costs` is a sequence of square fp64
+    matrices (NumPy: packed on the host into one buffer, one H2D copy; CUDA tensors: packed on the device), or,
+    with `sizes`, one padded (B, N, N) fp64 array or CUDA tensor whose instance b is the prefix [:n_b, :n_b].
+    Returns a RaggedPack.  Raises ValueError before any device work."""
+    import torch
+    if sizes is not None:
+        shape = tuple(costs.shape)
+        if len(shape) != 3 or shape[1] != shape[2]:
+            raise ValueError(f"a padded batch must be (B, N, N), not {shape}")
+        host_sizes = [int(n) for n in sizes]
+        if len(host_sizes) != shape[0]:
+            raise ValueError(f"{shape[0]} instances but {len(host_sizes)} sizes")
+        N, ld = shape[1], shape[1]
+        if N > MAX_N:
+            raise ValueError(f"n exceeds the {MAX_N} limit of this build: {N}")
+        _check_ragged_sizes(host_sizes, N)
+        offsets = np.arange(len(host_sizes), dtype=np.int64) * (N * N)
+        on_device = isinstance(costs, torch.Tensor) and costs.is_cuda
+        mats = None
+    else:
+        mats = list(costs)
+        on_device = bool(mats) and all(isinstance(c, torch.Tensor) and c.is_cuda for c in mats)
+        if not on_device:
+            mats = [np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float64) for c in mats]
+        for c in mats:
+            if c.ndim != 2 or c.shape[0] != c.shape[1]:
+                raise ValueError(f"square cost matrices expected, not {tuple(c.shape)}")
+            if on_device and c.dtype != torch.float64:
+                raise ValueError("CUDA cost matrices must be float64")
+        host_sizes = [int(c.shape[0]) for c in mats]
+        _check_ragged_sizes(host_sizes)
+        N, ld = max(host_sizes), 0
+        sq = np.asarray(host_sizes, dtype=np.int64) ** 2
+        offsets = np.concatenate(([0], np.cumsum(sq)[:-1])).astype(np.int64)
+    if on_device and sizes is not None and costs.dtype != torch.float64:
+        raise ValueError("a padded CUDA batch must be float64")
+    _hip.require_device()
+    device = torch.device(device)
+    if sizes is not None:
+        C = costs if on_device else torch.from_numpy(np.ascontiguousarray(costs, dtype=np.float64)).to(device)
+        C = C.contiguous()
+    elif on_device:
+        device = mats[0].device
+        C = torch.cat([c.reshape(-1) for c in mats])
+    else:
+        buf = np.empty(int(offsets[-1]) + host_sizes[-1] ** 2, dtype=np.float64)
+        for c, o in zip(mats, offsets.tolist()):
+            buf[o:o + c.size] = c.reshape(-1)
+        C = torch.from_numpy(buf).to(device)
+    device = C.device
+    B = len(host_sizes)
+    posenc, first = _ragged_posenc(tuple(sorted(set(host_sizes))), device)
+    meta = np.empty(2 * B, dtype=np.int64)  # offsets, then sizes and pos_off as int32: one copy
+    meta[:B] = offsets
+    m32 = meta[B:].view(np.int32)
+    m32[:B] = host_sizes
+    m32[B:] = [first[n] for n in host_sizes]
+    meta_d = torch.from_numpy(meta).to(device)
+    d32 = meta_d[B:].view(torch.int32)
+    return RaggedPack(C, meta_d[:B], d32[:B], d32[B:], posenc, ld, N, host_sizes)
+
+
+def row_features_ragged(costs, return_topk: bool = True, want_cost32: bool = False, device="cuda:0", sizes=None):
+    """Row features of B cost matrices of different sizes in one call (two kernels): a RaggedFeatures padded to
+    the largest size.  feat[b, :n_b] and topk[b, :n_b] are bit for bit what row_features_device gives for
+    instance b alone; padded rows are 0 / +inf.  `costs`, `device`, `sizes`: see ragged_pack.  Enqueued on the
+    current torch stream; nothing is read back."""
+    return row_features_packed(ragged_pack(costs, device, sizes), return_topk, want_cost32)
+
+
+def row_features_packed(pack: RaggedPack, return_topk: bool = True, want_cost32: bool = False):
+    """row_features_ragged of a batch that is packed already."""
+    import torch
+    lib = _hip.require_device()
+    dev, B, N = pack.C.device, len(pack.host_sizes), pack.N
+    feat = torch.empty((B, N, ROW_FEATURE_DIM), dtype=torch.float32, device=dev)
+    topk = torch.empty((B, N, TOPK), dtype=torch.float32, device=dev) if return_topk else None
+    cost32 = torch.empty((B, N, N), dtype=torch.float32, device=dev) if want_cost32 else None
+    mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    ret = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws_bytes = lib.lapwarm_ragged_workspace_bytes(B, N)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.lapwarm_row_features_ragged(
+        pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), pack.ld, B, N, pack.posenc.data_ptr(),
+        pack.pos_off.data_ptr(), feat.data_ptr(), topk.data_ptr() if return_topk else None,
+        cost32.data_ptr() if want_cost32 else None, mask.data_ptr(), ret.data_ptr(), ws.data_ptr(), ws_bytes,
+        ct.c_void_p(stream))
+    if _hip.check(rc, "row_features_ragged") != 0:
+        raise RuntimeError(f"row_features_ragged failed (code {rc})")
+    return RaggedFeatures(feat, topk, cost32, mask.view(torch.bool), pack.sizes, ret)
+
+
+def min_trick_ragged(pack: RaggedPack, u=None):
+    """v (B, N) f64 with v[b][j] = min_{i < n_b} (C_b[i][j] - u[b][i]) and 0 beyond n_b; u (B, N) f64 on the
+    device, or None for the plain column minima."""
+    import torch
+    lib = _hip.require_device()
+    B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
+    if u is not None and (u.dtype != torch.float64 or tuple(u.shape) != (B, N) or not u.is_contiguous()):
+        raise ValueError(f"u must be a contiguous float64 ({B}, {N}) tensor")
+    v = torch.empty((B, N), dtype=torch.float64, device=dev)
+    ws_bytes = lib.lapwarm_ragged_workspace_bytes(B, N)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.lapwarm_colmin_ragged(pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), pack.ld, B, N,
+                                   u.data_ptr() if u is not None else None, v.data_ptr(), ws.data_ptr(), ws_bytes,
+                                   ct.c_void_p(stream))
+    if _hip.check(rc, "min_trick_ragged") != 0:
+        raise RuntimeError(f"min_trick_ragged failed (code {rc})")
+    return v
+
+
 def compute_row_features_torch(cost):
     """Device-resident variant: CUDA tensor (n, n) of any float dtype -> (n, 21) float32 on the
     same device.  float32 inputs are widened exactly to float64 before the sweep."""

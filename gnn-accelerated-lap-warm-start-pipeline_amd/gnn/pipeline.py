@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from lap import _hip
-from .features import ROW_FEATURE_DIM, min_trick_device, row_features_device
+from .features import (ROW_FEATURE_DIM, min_trick_device, min_trick_ragged, ragged_pack, row_features_device,
+                       row_features_packed)
 from .one_gnn import OneGNN
 
 STATS_FIELDS = ("branch", "tight_edges", "free_rows", "arr_fired", "paths", "finds", "scan_steps",
@@ -225,6 +226,47 @@ class WarmStartPipeline:
         u, v = self.predict_batch(C)
         x, y, ret, stats = self.seeded_batch(C, u, v, eps, want_stats)
         return {"x": x, "y": y, "ret": ret, "stats": stats, "u": u, "v": v}
+
+    def _predict_ragged(self, costs):
+        pack = ragged_pack(costs, self.device)
+        r = row_features_packed(pack)
+        u = self.model(r.feat, mask=r.mask, topk_values=r.topk)["u"].to(torch.float64)
+        # OneGNN centres u over the padded width (masked rows included, as the reference's forward does), which
+        # shifts every instance shorter than the batch maximum; centred over its own rows an instance gets
+        # what the model gives it alone
+        count = pack.sizes.to(torch.float64).unsqueeze(1)
+        u = ((u - u.sum(dim=1, keepdim=True) / count) * r.mask).contiguous()
+        return pack, u, min_trick_ragged(pack, u)
+
+    @torch.inference_mode()
+    def predict_ragged(self, costs):
+        """costs: square fp64 matrices of different sizes (NumPy, or CUDA tensors) -> a list of (u_hat, v_hat),
+        fp64 device tensors of length n_b, what predict_batch gives each instance alone: ragged features and
+        top-16, one masked OneGNN forward over the padded batch, then the fp64 min-trick of u_hat per instance
+        (lapwarm_colmin_ragged)."""
+        pack, u, v = self._predict_ragged(costs)
+        return [(u[b, :n], v[b, :n]) for b, n in enumerate(pack.host_sizes)]
+
+    @torch.inference_mode()
+    def solve_many(self, costs, eps: float = 1e-12, want_stats: bool = True):
+        """The whole hot path for instances of different sizes: predict_ragged, then seeded_batch once per
+        group of equal size.  Returns one dict per instance, in input order: x, y (n_b,) int64, ret, stats,
+        u, v -- the rows of what solve_batch returns for a batch of that size."""
+        pack, u, v = self._predict_ragged(costs)
+        off = pack.offsets.tolist()
+        groups = {}
+        for b, n in enumerate(pack.host_sizes):
+            groups.setdefault(n, []).append(b)
+        out = [None] * len(pack.host_sizes)
+        for n, members in groups.items():
+            C = torch.stack([pack.C[off[b]:off[b] + n * n].view(n, n) for b in members])
+            idx = torch.tensor(members, device=self.device)
+            ug, vg = u[idx, :n], v[idx, :n]
+            x, y, ret, stats = self.seeded_batch(C, ug, vg, eps, want_stats)
+            for k, b in enumerate(members):
+                out[b] = {"x": x[k], "y": y[k], "ret": ret[k], "stats": stats[k] if want_stats else None,
+                          "u": ug[k], "v": vg[k]}
+        return out
 
     # ---- two-stream software pipeline: the dense sweeps + OneGNN of batch k+1 run beside the
     # per-instance solver of batch k.  The solver occupies one CU per instance (32 of the 256 at

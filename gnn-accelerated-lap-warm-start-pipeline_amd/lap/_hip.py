@@ -51,7 +51,12 @@ SIGNATURES = {
     "lapwarm_colmin_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
     "lapwarm_row_features_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
                                                 ct.c_size_t, c_vp]),
-    "lapwarm_project_round_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
+    "lapwarm_ragged_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_colmin_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, c_vp,
+                                         ct.c_size_t, c_vp]),
+    "lapwarm_row_features_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, c_vp,
+                                               c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_project_round_batched":(ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
                                                  ct.c_size_t, c_vp]),
     "lapwarm_reduce_costs_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, ct.c_int, c_vp, c_vp,
                                                 c_vp, ct.c_size_t, c_vp]),

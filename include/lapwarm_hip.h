@@ -171,6 +171,37 @@ int lapwarm_rowmin_batched(const double *C, int batch, int n, const double *v, d
 int lapwarm_row_features_batched(const double *C, int batch, int n, const float *posenc, float *feat,
                                  float *topk16, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Ragged batches: `batch` square fp64 matrices of different sizes in one device buffer C.  offsets [batch]
+ * int64 (device) is the element offset of instance b, a multiple of 8 bytes and no more; sizes [batch] int32
+ * (device) is n_b; ld is the row stride in elements, 0 for n_b (packed, instances back to back), ld > 0 for a
+ * common stride (the padded [batch][N][N] layout of `collate`, gnn/train_one_gnn.py:72-91, has ld = N and
+ * offsets[b] = b N N).  N, 1..16384, is the padded width of every output; batch is 1..65535.  An instance with
+ * sizes[b] outside 1..N (or above ld > 0) is treated as empty: padded outputs everywhere, ret[b] = 2, the code
+ * of lapwarm_train_loss_forward.  Both entries return 0, -2 for N <= 0, batch outside 1..65535, ld < 0 or a
+ * NULL pointer that may not be NULL, -5 for N > 16384, -1 workspace too small, <= -1000 HIP error.  Kernels
+ * on the caller's stream only: no memset, allocation or host synchronisation, so a call can be captured into
+ * a graph; every word of every output, and every workspace word that is read, is written inside the call. */
+size_t lapwarm_ragged_workspace_bytes(int batch, int N);
+
+/* out [batch][N]: out[b][j] = min_{i < n_b} (C_b[i][j] - u[b][i]) for j < n_b, 0 for j >= n_b; u [batch][N]
+ * fp64 or NULL; NaN as np.min, like lapwarm_colmin_batched.  One kernel.  An instance whose base address and
+ * row stride are multiples of 16 bytes is read with 16-byte loads, any other with 8-byte loads; the kernel
+ * decides per instance.  The workspace is not used by this entry; its size is checked all the same. */
+int lapwarm_colmin_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                          const double *u, double *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The row features, top-16, float32 costs and mask of a padded OneGNN batch in two kernels (column minima,
+ * then one workgroup per padded row).  posenc [rows][8] float32 holds the tables of gnn/features.py:21-31 of
+ * the distinct sizes, one after the other, and pos_off [batch] int32 (device) the first table row of instance
+ * b.  feat [batch][N][21]: rows i < n_b are what lapwarm_row_features_batched gives for the n_b x n_b instance
+ * alone, bit for bit; rows i >= n_b are 0.  topk16 [batch][N][16] or NULL: ascending, +inf beyond n_b and on
+ * padded rows.  cost32 [batch][N][N] or NULL: (float)C on the prefix, 0 elsewhere, written while the row is
+ * read for its features.  mask [batch][N] uint8 or NULL: 1 for i < n_b.  ret [batch]: 0 or 2. */
+int lapwarm_row_features_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch,
+                                int N, const float *posenc, const int *pos_off, float *feat, float *topk16,
+                                float *cost32, unsigned char *mask, int *ret, void *workspace,
+                                size_t workspace_bytes, void *stream);
+
 /* One round of project_feasible: u = min(u, rowmin(C-v)); v = min(v, colmin(C-u));
  * gmin[b] = min((C-u)-v).  The host loop decides when to stop. */
 int lapwarm_project_round_batched(const double *C, int batch, int n, double *u, double *v,
