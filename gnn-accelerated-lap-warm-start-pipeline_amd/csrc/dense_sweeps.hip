@@ -11,6 +11,7 @@
 //   row features     gnn/features.py:161-243
 #include "device_utils.hpp"
 #include "dense_sweeps.hpp"
+#include "jv_solver.hpp"
 #include "ragged_batch.hpp"
 
 namespace lapwarm {
@@ -25,12 +26,23 @@ constexpr int kSweepThreads = 256;
 // ------------------------------------------------------------------------------------------
 // EPT > 0: the row (and v) stay in registers between the two passes (n <= EPT * kSweepThreads), so C
 // is read from HBM exactly once; EPT == 0: rows of any length, second pass re-reads (L2).
-template <int EPT>
-__global__ void __launch_bounds__(kSweepThreads) prelude_kernel(PreludeParams p)
+// One body, two entries.  prelude_kernel: row i of instance b of a uniform batch.  RAGGED (prelude_ragged_kernel,
+// ragged_batch.hpp): workgroup (i, b) owns row i of the padded [N] rows of instance b and leaves at once beyond
+// n_b (workgroup-uniform: blockIdx and sizes[b] only); n_b is loaded once into a scalar; p.n is N, the stride of
+// every [batch][.] array, and the bitmap of instance b is its n_b rows of ceil(n_b / 32) words, back to back, at
+// b * N * ceil(N / 32) -- the layout the solver reads for an instance of that size alone.
+template <int EPT, bool RAGGED>
+__device__ __forceinline__ void prelude_body(const PreludeParams &p, const RaggedBatch &g)
 {
     __shared__ BlockExchange ex;
     __shared__ uint32_t bits[512];  // n <= 16384
-    const int b = blockIdx.y, i = blockIdx.x, n = p.n;
+    const int b = blockIdx.y, i = blockIdx.x;
+    int n_b = p.n;
+    if constexpr (RAGGED) {
+        n_b = __builtin_amdgcn_readfirstlane(ragged_size(g, b));
+        if (i >= n_b) return;
+    }
+    const int n = n_b;
     if (p.rerun && !(p.inst_flags[b] & kFlagProjected)) return;
     BlockCtx bc;
     bc.init(&ex);
@@ -38,9 +50,10 @@ __global__ void __launch_bounds__(kSweepThreads) prelude_kernel(PreludeParams p)
     for (int w = bc.tid; w < W; w += kSweepThreads) bits[w] = 0;
 
     const size_t rowoff = ((size_t)b * n + i) * n;
-    const double *row = p.C + rowoff;
-    const double *vb = p.v + (size_t)b * n;
-    const double ui = p.u[(size_t)b * n + i];
+    const double *row = RAGGED ? g.C + g.offsets[b] + (size_t)i * (g.ld ? g.ld : n) : p.C + rowoff;
+    const int pn = p.n;  // stride of the [batch][.] arrays: n, or N
+    const double *vb = p.v + (size_t)b * pn;
+    const double ui = p.u[(size_t)b * pn + i];
     const double eps = p.eps;
     const bool first = !p.rerun;
 
@@ -91,7 +104,8 @@ __global__ void __launch_bounds__(kSweepThreads) prelude_kernel(PreludeParams p)
     }
     __syncthreads();
     int cnt = 0;
-    uint32_t *out_bits = p.tight_bits + ((size_t)b * n + i) * W;
+    uint32_t *out_bits = RAGGED ? p.tight_bits + (size_t)b * pn * ((pn + 31) >> 5) + (size_t)i * W
+                                : p.tight_bits + ((size_t)b * n + i) * W;
     for (int w = bc.tid; w < W; w += kSweepThreads) {
         const uint32_t word = bits[w];
         out_bits[w] = word;
@@ -99,7 +113,7 @@ __global__ void __launch_bounds__(kSweepThreads) prelude_kernel(PreludeParams p)
     }
     cnt = bc.sum_i32(cnt);
     if (bc.tid == 0) {
-        const size_t o = (size_t)b * n + i;
+        const size_t o = (size_t)b * pn + i;
         p.u_tight[o] = u_new;
         p.tight_cnt[o] = cnt;
         const int viol = counts & 0xffff, bad = counts >> 16;
@@ -113,28 +127,34 @@ __global__ void __launch_bounds__(kSweepThreads) prelude_kernel(PreludeParams p)
     }
 }
 
+template <int EPT>
+__global__ void __launch_bounds__(kSweepThreads) prelude_kernel(PreludeParams p)
+{
+    prelude_body<EPT, false>(p, RaggedBatch{});
+}
+
+template <int EPT>
+__global__ void __launch_bounds__(kSweepThreads) prelude_ragged_kernel(PreludeParams p, RaggedBatch g)
+{
+    prelude_body<EPT, true>(p, g);
+}
+
 // ------------------------------------------------------------------------------------------
 // Projection (slow path, one workgroup per flagged instance).  u and v only ever decrease, and
 // fl(fl(u+v)-C) is monotone in both, so an entry that is not a candidate under the seed duals
 // can never fire: rows without candidates are skipped, the others replay the serial scan as
 // "find the next firing column given the current u_i" with a workgroup-wide first-index search.
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kSweepThreads)
-projection_kernel(const double *C, int n, double *u, double *v, const int *viol_cnt,
-                  int *inst_flags, double eps)
+// The body: row i of the instance is Cb + (row0 + i) * ldc; ub / vb / vc are its n duals and candidate counts.
+__device__ __forceinline__ void project_instance(BlockExchange *ex, const double *Cb, size_t row0, size_t ldc, int n,
+                                                 double *ub, double *vb, const int *vc, int *inst_flags, int b,
+                                                 int flags, double eps)
 {
-    __shared__ BlockExchange ex;
-    const int b = blockIdx.x;
-    const int flags = inst_flags[b];
-    if (!(flags & kFlagHasViolation)) return;
     BlockCtx bc;
-    bc.init(&ex);
-    double *ub = u + (size_t)b * n;
-    double *vb = v + (size_t)b * n;
-    const int *vc = viol_cnt + (size_t)b * n;
+    bc.init(ex);
     for (int i = 0; i < n; ++i) {
         if (vc[i] == 0) continue;
-        const double *row = C + ((size_t)b * n + i) * n;
+        const double *row = Cb + (row0 + i) * ldc;
         double ui = ub[i];
         int jstart = 0;
         for (int guard = 0; guard <= n; ++guard) {
@@ -158,6 +178,33 @@ projection_kernel(const double *C, int n, double *u, double *v, const int *viol_
         if (bc.tid == 0) ub[i] = ui;
     }
     if (bc.tid == 0) inst_flags[b] = (flags | kFlagProjected) & ~kFlagInfeasible;
+}
+
+__global__ void __launch_bounds__(kSweepThreads)
+projection_kernel(const double *C, int n, double *u, double *v, const int *viol_cnt,
+                  int *inst_flags, double eps)
+{
+    __shared__ BlockExchange ex;
+    const int b = blockIdx.x;
+    const int flags = inst_flags[b];
+    if (!(flags & kFlagHasViolation)) return;
+    const size_t ob = (size_t)b * n;
+    project_instance(&ex, C, ob, n, n, u + ob, v + ob, viol_cnt + ob, inst_flags, b, flags, eps);
+}
+
+// Ragged batch: u, v, viol_cnt [batch][N]; the matrix of instance b from its offset and size.
+__global__ void __launch_bounds__(kSweepThreads)
+projection_ragged_kernel(RaggedBatch g, double *u, double *v, const int *viol_cnt, int *inst_flags, double eps)
+{
+    __shared__ BlockExchange ex;
+    const int b = blockIdx.x;
+    const int n = __builtin_amdgcn_readfirstlane(ragged_size(g, b));
+    if (n == 0) return;
+    const int flags = inst_flags[b];
+    if (!(flags & kFlagHasViolation)) return;
+    const size_t ob = (size_t)b * g.N;
+    project_instance(&ex, g.C + g.offsets[b], 0, g.ld ? g.ld : n, n, u + ob, v + ob, viol_cnt + ob, inst_flags, b,
+                     flags, eps);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -783,6 +830,41 @@ hipError_t launch_seed_prepare(const double *u_seed, const double *v_seed, doubl
     return hipGetLastError();
 }
 
+// The same for a ragged batch, [batch][N] throughout: the seeds of the prefix of every instance (the padding
+// is never read), the flags, and the results an instance keeps when no solver launch takes it -- x, y -1
+// everywhere (the solver writes the prefix), ret 2 (a size outside 1..N), stats 0.
+__global__ void __launch_bounds__(kSweepThreads)
+seed_prepare_ragged_kernel(RaggedBatch g, const double *u_seed, const double *v_seed, double *u_work, double *v_work,
+                           int *flags, long long *x, long long *y, int *ret, long long *stats)
+{
+    const int b = blockIdx.y, j = blockIdx.x * kSweepThreads + threadIdx.x, N = g.N;
+    const int n = ragged_size(g, b);
+    const size_t o = (size_t)b * N + j;
+    if (j < n) {
+        u_work[o] = u_seed[o];
+        v_work[o] = v_seed[o];
+    }
+    if (j < N) {
+        x[o] = -1;
+        y[o] = -1;
+    }
+    if (j == 0) {
+        flags[b] = 0;
+        ret[b] = 2;
+    }
+    if (stats && j < kStatsPerInstance) stats[(size_t)b * kStatsPerInstance + j] = 0;
+}
+
+hipError_t launch_seed_prepare_ragged(const RaggedBatch &g, const double *u_seed, const double *v_seed, double *u_work,
+                                      double *v_work, int *flags, long long *x, long long *y, int *ret,
+                                      long long *stats, hipStream_t stream)
+{
+    if (g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(seed_prepare_ragged_kernel, dim3((g.N + kSweepThreads - 1) / kSweepThreads, g.batch),
+                       dim3(kSweepThreads), 0, stream, g, u_seed, v_seed, u_work, v_work, flags, x, y, ret, stats);
+    return hipGetLastError();
+}
+
 hipError_t launch_prelude(const PreludeParams &p, hipStream_t stream)
 {
     if (p.n > 16384) return hipErrorInvalidValue;
@@ -801,6 +883,29 @@ hipError_t launch_projection(const double *C, int n, int batch, double *u, doubl
 {
     hipLaunchKernelGGL(projection_kernel, dim3(batch), dim3(kSweepThreads), 0, stream, C, n, u, v,
                        viol_cnt, inst_flags, eps);
+    return hipGetLastError();
+}
+
+// p.n == g.N, p.batch == g.batch; p.C is not read.  The register-resident variant is chosen by N.
+hipError_t launch_prelude_ragged(const PreludeParams &p, const RaggedBatch &g, hipStream_t stream)
+{
+    if (g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535 || p.n != g.N) return hipErrorInvalidValue;
+    const dim3 grid(g.N, g.batch), block(kSweepThreads);
+    if (g.N <= 8 * kSweepThreads)
+        hipLaunchKernelGGL(prelude_ragged_kernel<8>, grid, block, 0, stream, p, g);
+    else if (g.N <= 16 * kSweepThreads)
+        hipLaunchKernelGGL(prelude_ragged_kernel<16>, grid, block, 0, stream, p, g);
+    else
+        hipLaunchKernelGGL(prelude_ragged_kernel<0>, grid, block, 0, stream, p, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_projection_ragged(const RaggedBatch &g, double *u, double *v, const int *viol_cnt, int *inst_flags,
+                                    double eps, hipStream_t stream)
+{
+    if (g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(projection_ragged_kernel, dim3(g.batch), dim3(kSweepThreads), 0, stream, g, u, v, viol_cnt,
+                       inst_flags, eps);
     return hipGetLastError();
 }
 

@@ -28,6 +28,17 @@ hipError_t launch_seed_prepare(const double *u_seed, const double *v_seed, doubl
 hipError_t launch_projection(const double *C, int n, int batch, double *u, double *v,
                              const int *viol_cnt, int *inst_flags, double eps, hipStream_t stream);
 
+// The three stages in front of a ragged seeded solve (ragged_batch.hpp): every [batch][.] array has the padded
+// stride N, and the tight-edge bitmap of instance b is n_b rows of ceil(n_b / 32) words at b * N * ceil(N / 32).
+// The prepare step also leaves x, y = -1, ret = 2 and stats = 0 for the solver launches to overwrite.
+struct RaggedBatch;
+hipError_t launch_seed_prepare_ragged(const RaggedBatch &g, const double *u_seed, const double *v_seed, double *u_work,
+                                      double *v_work, int *flags, long long *x, long long *y, int *ret,
+                                      long long *stats, hipStream_t stream);
+hipError_t launch_prelude_ragged(const PreludeParams &p, const RaggedBatch &g, hipStream_t stream);  // p.n = g.N
+hipError_t launch_projection_ragged(const RaggedBatch &g, double *u, double *v, const int *viol_cnt, int *inst_flags,
+                                    double eps, hipStream_t stream);
+
 // out[b][j] = min_i (C[b][i][j] - (u ? u[b][i] : 0)); `partial` holds batch*chunks*n doubles.
 int colmin_chunks(int n, int batch);
 hipError_t launch_colmin(const double *C, int n, int batch, const double *u, double *out,

@@ -116,7 +116,8 @@ __device__ __forceinline__ unsigned long long stamp_now()
 #define STAMP_INC(slot)
 #endif
 
-template <int CH, int LDSL, int TB>
+// RAGGED: the instance is one of a ragged batch (jv_instance_kernel<.., true>): the rows of C are ldc apart, not n.
+template <int CH, int LDSL, int TB, bool RAGGED = false>
 struct Solver {
     // LDS levels: 2 = all solver state in LDS, 1 = x and the free-row list in global memory,
     // 0 = all state in global memory, 8 = as 0 with the head rows staged in LDS (below)
@@ -132,6 +133,7 @@ struct Solver {
     // problem
     const double *C;
     int n, W;
+    int ldc;  // row stride of C where RAGGED (it is n otherwise, and this is not set)
     // state
     double *dist, *v;
     int *order, *pred, *y, *x, *fr;
@@ -424,7 +426,7 @@ struct Solver {
         {
             // every load is issued before the first use: indices are clamped instead of
             // branching, so the CH gathers of a thread are all in flight together
-            const double *row = C + (size_t)start * n;
+            const double *row = C + (size_t)start * (RAGGED ? ldc : n);
             double c0[CH];
 #pragma unroll
             for (int r = 0; r < CH; ++r) {
@@ -656,7 +658,7 @@ struct Solver {
                 err = 6;
                 break;
             }
-            const double *row = C + (size_t)head_i * n;
+            const double *row = C + (size_t)head_i * (RAGGED ? ldc : n);
             double c[CH];
             double c_head;
             bool from_slot = false;
@@ -744,7 +746,7 @@ struct Solver {
                 const int ri = uni(nq_i);
                 if (queued && (unsigned)ri < (unsigned)n && nslots > 1) {
                     pf_next_slot = from_slot ? (pf_slot ^ 1) : 0;
-                    const double *nrow = C + (size_t)ri * n;
+                    const double *nrow = C + (size_t)ri * (RAGGED ? ldc : n);
                     const unsigned sbase = lds_address(slots) + (unsigned)pf_next_slot * (unsigned)slot_bytes +
                                            (unsigned)bc.wave * 1024u;
                     const int nt = (int)blockDim.x;
@@ -1215,7 +1217,7 @@ struct Solver {
             double c[RU][CH];
 #pragma unroll
             for (int q = 0; q < RU; ++q) {
-                const double *row = C + (size_t)(i + q) * n;
+                const double *row = C + (size_t)(i + q) * (RAGGED ? ldc : n);
 #pragma unroll
                 for (int r = 0; r < CH; ++r) c[q][r] = row[jc[r]];
             }
@@ -1236,7 +1238,7 @@ struct Solver {
             }
         }
         for (; i < n; ++i) {
-            const double *row = C + (size_t)i * n;
+            const double *row = C + (size_t)i * (RAGGED ? ldc : n);
 #pragma unroll
             for (int r = 0; r < CH; ++r) {
                 const double c = row[jc[r]];
@@ -1283,7 +1285,7 @@ struct Solver {
                 if (bc.tid == 0) fr[nf] = i;
                 ++nf;
             } else if (pred[i] == 1) {
-                const double *row = C + (size_t)i * n;
+                const double *row = C + (size_t)i * (RAGGED ? ldc : n);
                 double m = kLarge;
                 double ct[CH];
 #pragma unroll
@@ -1328,7 +1330,7 @@ struct Solver {
     __device__ __forceinline__ void arr_build_list(int i, double *lval, int *lcol, double *ltau)
     {
         const int lane = bc.lane;
-        const double *row = C + (size_t)i * n;
+        const double *row = C + (size_t)i * (RAGGED ? ldc : n);
         double a0 = pos_inf(), a1 = pos_inf(), a2 = pos_inf(), r0 = 0.0, r1 = 0.0;
         int j0 = -1, j1 = -1;
         bool nan0 = false;
@@ -1384,7 +1386,7 @@ struct Solver {
         const int free_i = (fwd >= 0) ? fwd : fr[current];
         fwd = -1;
         current++;
-        const double *row = C + (size_t)free_i * n;
+        const double *row = C + (size_t)free_i * (RAGGED ? ldc : n);
         double v1, v2;
         int j1, j2;
         // Normal regime (column 0 not above the sentinel): the two smallest (value, index)
@@ -1510,7 +1512,7 @@ struct Solver {
             const int free_i = (fwd >= 0) ? fwd : fr[current];
             fwd = -1;
             current++;
-            const double *row = C + (size_t)free_i * n;
+            const double *row = C + (size_t)free_i * (RAGGED ? ldc : n);
             double v1, v2;
             int j1, j2;
             // Normal regime (column 0 not above the sentinel): the two smallest (value, index)
@@ -1939,7 +1941,7 @@ struct Solver {
             for (int f = start + bc.wave; f < n_free; f += bc.nwaves) {
                 const int i = fr[f];
                 const double ui = u_tight[i];
-                const double *row = C + (size_t)i * n;
+                const double *row = C + (size_t)i * (RAGGED ? ldc : n);
                 Top2 t = top2_empty();
                 for (int j = bc.lane; j < n; j += kWave) {
                     const double r = (row[j] - ui) - v[j];
@@ -1958,7 +1960,7 @@ struct Solver {
             {
                 const int i = fr[ff];
                 const double ui = u_tight[i];
-                const double *row = C + (size_t)i * n;
+                const double *row = C + (size_t)i * (RAGGED ? ldc : n);
                 Top2 t = top2_empty();
                 for (int j = bc.tid; j < n; j += blockDim.x) {
                     const double r = (row[j] - ui) - v[j];
@@ -1995,12 +1997,25 @@ struct Solver {
 //    (ret -106 / -103 / wrong x) -- the same source that is exact in the plain instantiation.  Not explained
 //    (the instantiation spills 87 VGPRs there against 30); avoided by not compiling those loops in here.
 // The seeded launches keep the plain row scans for their fallbacks: the code, and the timing, of round 2.
-template <int CH, int LDSL, int TB, bool LISTS>
+// RAGGED = true: instance b of a ragged batch (lapwarm_seeded_ragged; seeded, phase 0, LDS level 2, no
+// helper workgroups) -- n = rg_sizes[b], loaded once into a scalar register; the matrix at rg_offsets[b] with
+// row stride rg_ld; the seeded inputs and the outputs, [batch][.] arrays, with the padded stride rg_N.  The
+// workgroup leaves at once unless n is in [rg_n_lo, rg_n_hi], the sizes this launch's instantiation and
+// dynamic LDS were chosen for.  Every use of the flag is a compile-time branch: the uniform instantiations
+// are what they were without it.
+template <int CH, int LDSL, int TB, bool LISTS, bool RAGGED = false>
 __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
 {
+    static_assert(!RAGGED || (LDSL == 2 && !LISTS), "ragged launches: all state in LDS, no candidate lists");
     extern __shared__ __align__(16) unsigned char smem[];
-    const int n = p.n;
-    if (blockIdx.x >= (unsigned)p.batch) {
+    int n_b = p.n;
+    if constexpr (RAGGED) {
+        n_b = __builtin_amdgcn_readfirstlane(p.rg_sizes[blockIdx.x]);
+        if (n_b < p.rg_n_lo || n_b > p.rg_n_hi) return;  // (uniform)
+    }
+    const int n = n_b;
+    const int pn = RAGGED ? p.rg_N : n;  // stride of the [batch][.] arrays a ragged launch touches
+    if (!RAGGED && blockIdx.x >= (unsigned)p.batch) {
         // ---- helper workgroup of instance blockIdx.x - batch (same XCD when batch % 8 == 0: the
         // dispatcher deals workgroups to the 8 XCDs round robin): wave 0 pulls the announced rows
         // towards the shared L2 with LDS-DMA requests into a dummy area; nothing reads them here.
@@ -2053,7 +2068,7 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
     const int W = (n + 31) >> 5;
     const int Wpad = (W + 1) & ~1;
 
-    Solver<CH, LDSL, TB> s;
+    Solver<CH, LDSL, TB, RAGGED> s;
     unsigned char *cur = smem;
     s.slots = smem;
     s.slot_bytes = 0;
@@ -2116,7 +2131,12 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
         s.fr = p.g_fr + o;
     }
     s.bc.init(ex);
-    s.C = p.C + (size_t)b * n * n;
+    if constexpr (RAGGED) {
+        s.C = p.C + p.rg_offsets[b];
+        s.ldc = p.rg_ld ? p.rg_ld : n;
+    } else {
+        s.C = p.C + (size_t)b * n * n;
+    }
     s.n = n;
     s.W = W;
     s.ring = (p.helper && p.pf_ring) ? p.pf_ring + (size_t)b * kRingInts : nullptr;
@@ -2176,7 +2196,7 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
     long long tight_total = 0;
     long long free_after_greedy = 0;
     int nf = 0;
-    if (p.phase == 3) {
+    if (!RAGGED && p.phase == 3) {
         // ---- between two launches of the cooperative kernel: its mailbox starts from zero again (its
         // round tags restart with every launch), and if it stopped at a path it does not handle, THAT
         // ONE path is searched here; the cooperative kernel carries on behind it
@@ -2187,7 +2207,7 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
             hand[kHandPathsDone] >= hand[kHandFreeRows])
             return;  // nothing pending (uniform)
     }
-    if (!LISTS && (p.phase == 2 || p.phase == 3)) {
+    if (!LISTS && !RAGGED && (p.phase == 2 || p.phase == 3)) {
         // ---- resume behind the cooperative kernel: x, y, v and the free rows come back from the
         // global state arrays, the rows hand[kHandPathsDone] .. hand[kHandFreeRows] are still to be augmented
         const size_t o = (size_t)b * n;
@@ -2254,8 +2274,8 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
             s.x[j] = -1;
             s.y[j] = -1;
             if (p.mode == kModeSeeded) {
-                s.v[j] = p.v_work[(size_t)b * n + j];
-                tight_local += p.tight_cnt[(size_t)b * n + j];
+                s.v[j] = p.v_work[(size_t)b * pn + j];
+                tight_local += p.tight_cnt[(size_t)b * pn + j];
             }
         }
     }
@@ -2284,7 +2304,8 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
         free_after_greedy = nf;
         run_paths = nf > 0;
     } else if constexpr (!LISTS) {
-        if (s.bc.wave == 0) s.greedy_wave0(p.tight_bits + (size_t)b * n * W);
+        // (ragged: n rows of W words at b * N * ceil(N / 32), as prelude_ragged_kernel leaves them)
+        if (s.bc.wave == 0) s.greedy_wave0(p.tight_bits + (size_t)b * pn * (RAGGED ? (pn + 31) >> 5 : W));
         __syncthreads();
         nf = s.ctrl->nfree;
         free_after_greedy = nf;
@@ -2292,12 +2313,12 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
             branch = kBranchAllMatched;
         } else {
             branch = kBranchSsp;
-            s.micro_arr(nf, p.u_tight + (size_t)b * n, p.tight_eps);
+            s.micro_arr(nf, p.u_tight + (size_t)b * pn, p.tight_eps);
             t_serial = __builtin_amdgcn_s_memrealtime();
             run_paths = true;
         }
     }
-    if (p.phase == 1) {
+    if (!RAGGED && p.phase == 1) {
         // ---- hand over to the cooperative kernel: state to the global arrays, mailbox zeroed
         __syncthreads();
         const size_t o = (size_t)b * n;
@@ -2343,8 +2364,8 @@ __global__ void __launch_bounds__(TB) jv_instance_kernel(SolverParams p)
     const int err = s.err | s.ctrl->err;
     for (int j = tid; j < n; j += blockDim.x) {
         if (p.x_out) {
-            p.x_out[(size_t)b * n + j] = s.x[j];
-            p.y_out[(size_t)b * n + j] = s.y[j];
+            p.x_out[(size_t)b * pn + j] = s.x[j];
+            p.y_out[(size_t)b * pn + j] = s.y[j];
         }
         if (p.x32_out) {
             p.x32_out[(size_t)b * n + j] = s.x[j];
@@ -2408,7 +2429,7 @@ hipError_t launch_one(const SolverParams &p, int threads, size_t lds_bytes, hipS
     return hipGetLastError();
 }
 
-// The 61 instantiations of jv_instance_kernel: <CH, LDSL, TB, LISTS> for CH 1..16, LDS level 0..2,
+// The 61 uniform instantiations of jv_instance_kernel: <CH, LDSL, TB, LISTS> for CH 1..16, LDS level 0..2,
 // 256 or 1024 threads, with and without candidate lists, and the large-row <16, 8, 512, false>.
 using PhaseLaunch = hipError_t (*)(const SolverParams &, int, size_t, hipStream_t);
 
@@ -2440,7 +2461,34 @@ PhaseLaunch by_ch(int ch, int tb, int ldsl)
     return nullptr;
 }
 
+template <int CH, int TB>
+hipError_t launch_one_ragged(const SolverParams &p, int threads, size_t lds_bytes, hipStream_t stream)
+{
+    auto kern = jv_instance_kernel<CH, 2, TB, false, true>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(p.batch), dim3(threads), lds_bytes, stream, p);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+// The 4 ragged instantiations: the (CH, TB) that plan_solve gives a seeded solve at LDS level 2.
+hipError_t launch_phase_ragged(const PhaseConfig &k, const SolverParams &p, hipStream_t stream)
+{
+    if (k.ldsl != 2 || k.lists || p.mode != kModeSeeded || p.phase != 0 || p.helper != 0) return hipErrorInvalidValue;
+    if (!p.rg_offsets || !p.rg_sizes || p.rg_ld < 0 || p.rg_n_lo < 1 || p.rg_n_hi > p.rg_N ||
+        (p.rg_ld > 0 && p.rg_n_hi > p.rg_ld))
+        return hipErrorInvalidValue;
+    if ((long long)k.threads * k.ch < p.rg_n_hi || solver_lds_bytes(p.rg_n_hi, k.ch, 2) > k.lds_bytes)
+        return hipErrorInvalidValue;
+    if (k.ch == 1 && k.tb == 256) return launch_one_ragged<1, 256>(p, k.threads, k.lds_bytes, stream);
+    if (k.ch == 1 && k.tb == 1024) return launch_one_ragged<1, 1024>(p, k.threads, k.lds_bytes, stream);
+    if (k.ch == 2 && k.tb == 1024) return launch_one_ragged<2, 1024>(p, k.threads, k.lds_bytes, stream);
+    if (k.ch == 4 && k.tb == 1024) return launch_one_ragged<4, 1024>(p, k.threads, k.lds_bytes, stream);
+    return hipErrorInvalidValue;
+}
 
 hipError_t launch_phase(const PhaseConfig &k, const SolverParams &p, hipStream_t stream)
 {

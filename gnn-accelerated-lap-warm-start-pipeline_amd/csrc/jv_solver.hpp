@@ -146,6 +146,13 @@ struct SolverParams {
     // (last: a member in the middle moved the kernel arguments behind it and cost the seeded kernel 12 SGPR spills)
     double *arr_lval, *arr_ltau;
     int *arr_lcol;
+    // a launch of the ragged seeded solve (launch_phase_ragged; appended for the same reason): a grid of `batch`
+    // workgroups, workgroup b runs instance b when rg_n_lo <= rg_sizes[b] <= rg_n_hi.  n is not read then.
+    const long long *rg_offsets;  // [batch] element offset of the matrix in C, device
+    const int *rg_sizes;          // [batch] n_b, device
+    int rg_ld;                    // row stride, 0: n_b
+    int rg_N;                     // stride of the [batch][.] seeded inputs and outputs
+    int rg_n_lo, rg_n_hi;
 };
 constexpr int kArrListEntries = 128;
 constexpr int kRingSlots = 64;
@@ -169,6 +176,7 @@ struct CoopParams {
 struct PhaseConfig;
 struct CoopConfig;
 hipError_t launch_phase(const PhaseConfig &k, const SolverParams &p, hipStream_t stream);  // jv_instance_kernel
+hipError_t launch_phase_ragged(const PhaseConfig &k, const SolverParams &p, hipStream_t stream);  // its RAGGED form
 hipError_t launch_coop(const CoopParams &p, const CoopConfig &cfg, hipStream_t stream);    // coop_ssp_kernel
 
 // the LDS carving of jv_instance_kernel (jv_solver.hip): bytes of a level, row slots of level 8

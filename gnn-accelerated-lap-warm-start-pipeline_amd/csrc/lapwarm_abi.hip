@@ -125,6 +125,32 @@ SolverWs solver_layout(void *ws, int batch, int n, int mode, bool with_lists)
     return w;
 }
 
+// The seeded solve of a ragged batch: the prelude's buffers with the padded stride N.  The tight-edge bitmap
+// of instance b is n_b rows of ceil(n_b / 32) words at b * N * ceil(N / 32).  Nothing else: an instance this
+// entry takes keeps its solver state in LDS and has no helper ring.
+struct RaggedSolverWs {
+    double *u_work, *v_work, *u_tight;
+    int *viol_cnt, *tight_cnt, *flags;
+    uint32_t *tight_bits;
+    size_t bytes;
+};
+
+RaggedSolverWs ragged_solver_layout(void *ws, int batch, int N)
+{
+    RaggedSolverWs w;
+    Carver c{reinterpret_cast<unsigned char *>(ws), 0};
+    const size_t bn = (size_t)batch * N;
+    w.u_work = c.take<double>(bn);
+    w.v_work = c.take<double>(bn);
+    w.u_tight = c.take<double>(bn);
+    w.viol_cnt = c.take<int>(bn);
+    w.tight_cnt = c.take<int>(bn);
+    w.flags = c.take<int>((size_t)batch);
+    w.tight_bits = c.take<uint32_t>(bn * ((size_t)(N + 31) / 32));
+    w.bytes = c.off;
+    return w;
+}
+
 // The dense sweeps: column-min partials, column minima, row partials.
 struct SweepWs {
     double *partial, *colmin, *rowpart;
@@ -594,6 +620,94 @@ int lapwarm_row_features_ragged(const double *C, const long long *offsets, const
     HIP_TRY(launch_colmin_ragged(g, nullptr, colmin, stream));
     const RaggedFeatureOut o{colmin, posenc, pos_off, feat, topk16, cost32, mask, ret};
     HIP_TRY(launch_row_features_ragged(g, o, stream));
+    return 0;
+}
+
+size_t lapwarm_seeded_ragged_workspace_bytes(int batch, int N)
+{
+    if (N <= 0 || batch <= 0 || batch > 65535 || N > 16384) return 0;
+    return ragged_solver_layout(nullptr, batch, N).bytes;
+}
+
+int lapwarm_seeded_ragged_groups(const int *sizes, int batch, int *group_of)
+{
+    if (!sizes || !group_of || batch <= 0) return -2;
+    RaggedGroup groups[kMaxRaggedGroups];
+    return plan_ragged_groups(sizes, batch, group_of, groups);
+}
+
+int lapwarm_seeded_ragged(const double *C, const long long *offsets, const int *sizes, const int *host_sizes, int ld,
+                          int batch, int N, const double *u_seed, const double *v_seed, double eps, long long *x,
+                          long long *y, int *ret, long long *stats, void *workspace, size_t workspace_bytes,
+                          void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!host_sizes || !u_seed || !v_seed || !x || !y || !ret || !workspace) return -2;
+    for (int b = 0; b < batch; ++b) {
+        if (host_sizes[b] < 1 || host_sizes[b] > N || (ld > 0 && host_sizes[b] > ld)) return -2;
+    }
+    RaggedGroup groups[kMaxRaggedGroups];
+    const int n_groups = plan_ragged_groups(host_sizes, batch, nullptr, groups);
+    if (n_groups < 0) {
+        snprintf(g_err, sizeof(g_err), "lapwarm_seeded_ragged: an instance is outside the one-launch, all-LDS class");
+        return -6;
+    }
+    const RaggedSolverWs w = ragged_solver_layout(workspace, batch, N);
+    if (workspace_bytes < w.bytes) {
+        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
+        return -1;
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    HIP_TRY(launch_seed_prepare_ragged(g, u_seed, v_seed, w.u_work, w.v_work, w.flags, x, y, ret, stats, stream));
+
+    PreludeParams pp;
+    pp.C = C;
+    pp.n = N;
+    pp.batch = batch;
+    pp.u = w.u_work;
+    pp.v = w.v_work;
+    pp.eps = eps;
+    pp.tight_eps = (eps < 1e-9) ? 1e-9 : eps;  // std::max(eps, 1e-9), lapjv_seeded.cpp:76
+    pp.rerun = 0;
+    pp.u_tight = w.u_tight;
+    pp.viol_cnt = w.viol_cnt;
+    pp.tight_cnt = w.tight_cnt;
+    pp.tight_bits = w.tight_bits;
+    pp.inst_flags = w.flags;
+    HIP_TRY(launch_prelude_ragged(pp, g, stream));
+    HIP_TRY(launch_projection_ragged(g, w.u_work, w.v_work, w.viol_cnt, w.flags, eps, stream));
+    pp.rerun = 1;
+    HIP_TRY(launch_prelude_ragged(pp, g, stream));
+
+    SolverParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.C = C;
+    sp.n = N;
+    sp.batch = batch;
+    sp.mode = kModeSeeded;
+    sp.u_tight = w.u_tight;
+    sp.v_work = w.v_work;
+    sp.tight_cnt = w.tight_cnt;
+    sp.tight_bits = w.tight_bits;
+    sp.inst_flags = w.flags;
+    sp.tight_eps = pp.tight_eps;
+    sp.x_out = x;
+    sp.y_out = y;
+    sp.ret = ret;
+    sp.stats = stats;
+    sp.rg_offsets = offsets;
+    sp.rg_sizes = sizes;
+    sp.rg_ld = ld;
+    sp.rg_N = N;
+    // one launch per kernel configuration; the launches are independent and each workgroup picks its own
+    HIP_TRY(profile_begin(stream));  // (the bracket of lapwarm_profile_enable: all solver launches of the call)
+    for (int k = 0; k < n_groups; ++k) {
+        sp.rg_n_lo = groups[k].n_lo;
+        sp.rg_n_hi = groups[k].n_hi;
+        HIP_TRY(launch_phase_ragged(groups[k].k, sp, stream));
+    }
+    HIP_TRY(profile_end(stream));
     return 0;
 }
 

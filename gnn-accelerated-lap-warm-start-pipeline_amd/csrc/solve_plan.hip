@@ -248,6 +248,44 @@ hipError_t launch_solver(const SolvePlan &plan, const SolverParams &p_in, hipStr
     return launch_phase(plan.paths, p, stream);
 }
 
+bool ragged_solve_eligible(int n)
+{
+    if (n < 1 || n > 16384) return false;
+    return solve_shape(n, false) == SolveShape::kOneLaunch && !solver_uses_helpers(n) && !solver_needs_global_state(n);
+}
+
+int plan_ragged_groups(const int *sizes, int batch, int *group_of, RaggedGroup *groups)
+{
+    int count = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int n = sizes[b];
+        if (!ragged_solve_eligible(n)) return -1;
+        // (batch and the CU count only decide about helpers, which an eligible size does not have)
+        const PhaseConfig k = plan_solve(kModeSeeded, batch, n, 0, false, 0).prep;
+        int g = 0;
+        for (; g < count; ++g) {
+            const PhaseConfig &q = groups[g].k;
+            if (q.threads == k.threads && q.ch == k.ch && q.ldsl == k.ldsl && q.tb == k.tb && q.lists == k.lists) break;
+        }
+        if (g == count) {
+            if (count == kMaxRaggedGroups) return -1;
+            groups[count++] = RaggedGroup{k, n, n};
+        } else {
+            RaggedGroup &r = groups[g];
+            if (k.lds_bytes > r.k.lds_bytes) r.k.lds_bytes = k.lds_bytes;
+            if (n < r.n_lo) r.n_lo = n;
+            if (n > r.n_hi) r.n_hi = n;
+        }
+        if (group_of) group_of[b] = g;
+    }
+    for (int g = 0; g < count; ++g) {
+        for (int h = g + 1; h < count; ++h) {
+            if (groups[g].n_lo <= groups[h].n_hi && groups[h].n_lo <= groups[g].n_hi) return -1;
+        }
+    }
+    return count;
+}
+
 bool solver_needs_global_state(int n)
 {
     // a threads_hint may pick another CH: be conservative for every supported geometry.

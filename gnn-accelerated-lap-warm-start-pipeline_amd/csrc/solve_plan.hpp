@@ -40,6 +40,25 @@ struct SolvePlan {
 SolvePlan plan_solve(int mode, int batch, int n, int threads_hint, bool lists, int n_cus);
 hipError_t launch_solver(const SolvePlan &plan, const SolverParams &p, hipStream_t stream);
 
+// ---- seeded solves of a ragged batch (lapwarm_seeded_ragged): one launch per kernel configuration ----
+// An instance is eligible when its own plan is one launch without helper workgroups and with all state in
+// LDS: solve_shape kOneLaunch, solver_uses_helpers and solver_needs_global_state both false.
+bool ragged_solve_eligible(int n);
+// Instances share a launch when their plans have the same PhaseConfig template arguments and workgroup size
+// (threads, ch, ldsl, tb, lists); the launch's dynamic LDS is the largest of the group.  Every rule of the plan
+// is monotone in n, so a group is the eligible sizes of an interval [n_lo, n_hi]: that is how a workgroup
+// tells, from sizes[b] alone, whether a launch is its own (plan_ragged_groups checks that the intervals of
+// one call are disjoint).
+struct RaggedGroup {
+    PhaseConfig k;
+    int n_lo, n_hi;  // smallest and largest size of the call in this group
+};
+constexpr int kMaxRaggedGroups = 16;
+// Groups in the order of their first instance; group_of [batch] (may be null) receives each instance's group.
+// Returns the number of groups, -1 when an instance is not eligible (or there are more than
+// kMaxRaggedGroups configurations, or two intervals overlap: neither happens with the rules above).
+int plan_ragged_groups(const int *sizes, int batch, int *group_of, RaggedGroup *groups);
+
 int solver_lds_level(int n, int ch);
 bool solver_needs_global_state(int n);
 // candidate lists for the augmenting row reduction: from the size where a row is a few times its list

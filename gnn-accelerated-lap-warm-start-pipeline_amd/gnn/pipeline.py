@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 from lap import _hip
-from .features import (ROW_FEATURE_DIM, min_trick_device, min_trick_ragged, ragged_pack, row_features_device,
-                       row_features_packed)
+from .features import (ROW_FEATURE_DIM, RaggedPack, min_trick_device, min_trick_ragged, ragged_pack,
+                       row_features_device, row_features_packed)
 from .one_gnn import OneGNN
 
 STATS_FIELDS = ("branch", "tight_edges", "free_rows", "arr_fired", "paths", "finds", "scan_steps",
@@ -69,6 +69,7 @@ class WarmStartPipeline:
         self.model = model.to(self.device).eval()
         self.threads_hint = int(threads_hint)
         self._ws = {}
+        self._ragged_ok = {}  # size -> does seeded_ragged take it
 
     def _workspace(self, B, n, cold=False):
         # (cold solves carry the candidate lists of the row reduction: a larger block, cached separately)
@@ -247,17 +248,75 @@ class WarmStartPipeline:
         pack, u, v = self._predict_ragged(costs)
         return [(u[b, :n], v[b, :n]) for b, n in enumerate(pack.host_sizes)]
 
+    def seeded_ragged(self, pack: RaggedPack, u: torch.Tensor, v: torch.Tensor, eps: float = 1e-12,
+                      want_stats: bool = True):
+        """lapjv_seeded of every instance of a ragged batch in one call (lapwarm_seeded_ragged): one solver
+        launch per kernel configuration, not per size, and `pack.C` is read where it is.  `pack` is a
+        ragged_pack result, u, v (B, N) fp64 (read on each instance's prefix).  Returns x, y (B, N) int64 with -1
+        beyond n_b, ret (B,) int32, stats (B, 32) int64 or None; row b is what seeded_batch gives instance b
+        alone with threads_hint 0: the launches follow the automatic plan, and this pipeline's threads_hint does not
+        apply here (solve_many keeps the per-size path when one is set).  Every size must be in the class
+        `ragged_solve_eligible` describes."""
+        B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
+        for name, t in (("u", u), ("v", v)):
+            if t.dtype != torch.float64 or tuple(t.shape) != (B, N) or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{name} must be a contiguous float64 ({B}, {N}) tensor on {dev}")
+        x = torch.empty((B, N), dtype=torch.int64, device=dev)
+        y = torch.empty((B, N), dtype=torch.int64, device=dev)
+        ret = torch.empty((B,), dtype=torch.int32, device=dev)
+        stats = torch.empty((B, 32), dtype=torch.int64, device=dev) if want_stats else None
+        ws, nbytes = self._cached_workspace(("seeded_ragged", B, N),
+                                            lambda: self.lib.lapwarm_seeded_ragged_workspace_bytes(B, N))
+        host_sizes = (ct.c_int * B)(*pack.host_sizes)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lapwarm_seeded_ragged(
+            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), host_sizes, pack.ld, B, N,
+            u.data_ptr(), v.data_ptr(), float(eps), x.data_ptr(), y.data_ptr(), ret.data_ptr(),
+            stats.data_ptr() if want_stats else None, ws.data_ptr(), nbytes, ct.c_void_p(stream))
+        if _hip.check(rc, "seeded_ragged") != 0:
+            raise RuntimeError(f"lapwarm_seeded_ragged failed (code {rc}): {_hip.last_error()}")
+        return x, y, ret, stats
+
+    def ragged_solve_eligible(self, n: int) -> bool:
+        """Does seeded_ragged take an instance of this size?  Those whose own solve plan is one launch with
+        all solver state in LDS and no helper workgroup: every n < 1024 and the odd n up to 3631 with
+        the default settings (the library decides, from the plan)."""
+        known = self._ragged_ok
+        if n not in known:
+            one = (ct.c_int * 1)(int(n))
+            known[n] = self.lib.lapwarm_seeded_ragged_groups(one, 1, (ct.c_int * 1)()) == 1
+        return known[n]
+
     @torch.inference_mode()
     def solve_many(self, costs, eps: float = 1e-12, want_stats: bool = True):
-        """The whole hot path for instances of different sizes: predict_ragged, then seeded_batch once per
-        group of equal size.  Returns one dict per instance, in input order: x, y (n_b,) int64, ret, stats,
-        u, v -- the rows of what solve_batch returns for a batch of that size."""
+        """The whole hot path for instances of different sizes: predict_ragged, then seeded_ragged for every
+        instance it takes (one solver launch per kernel configuration, the packed costs read in place) and
+        seeded_batch once per size for the rest (helper or global-state sizes, the cooperative chain; every
+        instance when this pipeline has a threads_hint).
+        Returns one dict per instance, in input order: x, y (n_b,) int64, ret, stats, u, v -- the rows of what
+        solve_batch returns for a batch of that size."""
         pack, u, v = self._predict_ragged(costs)
-        off = pack.offsets.tolist()
+        sizes = pack.host_sizes
+        out = [None] * len(sizes)
+        # (a threads_hint picks another geometry than the plan the ragged launches are grouped by: per-size path)
+        ragged = [b for b, n in enumerate(sizes) if self.threads_hint == 0 and self.ragged_solve_eligible(n)]
+        if ragged:
+            sub, us, vs = pack, u, v
+            if len(ragged) < len(sizes):  # the eligible instances only: their offsets and sizes, C as it is
+                idx = torch.tensor(ragged, device=self.device)
+                sub = RaggedPack(pack.C, pack.offsets[idx], pack.sizes[idx], None, None, pack.ld, pack.N,
+                                 [sizes[b] for b in ragged])
+                us, vs = u[idx], v[idx]
+            x, y, ret, stats = self.seeded_ragged(sub, us, vs, eps, want_stats)
+            for k, b in enumerate(ragged):
+                n = sizes[b]
+                out[b] = {"x": x[k, :n], "y": y[k, :n], "ret": ret[k], "stats": stats[k] if want_stats else None,
+                          "u": us[k, :n], "v": vs[k, :n]}
         groups = {}
-        for b, n in enumerate(pack.host_sizes):
-            groups.setdefault(n, []).append(b)
-        out = [None] * len(pack.host_sizes)
+        for b, n in enumerate(sizes):
+            if out[b] is None:
+                groups.setdefault(n, []).append(b)
+        off = pack.offsets.tolist() if groups else None
         for n, members in groups.items():
             C = torch.stack([pack.C[off[b]:off[b] + n * n].view(n, n) for b in members])
             idx = torch.tensor(members, device=self.device)

@@ -56,6 +56,10 @@ SIGNATURES = {
                                          ct.c_size_t, c_vp]),
     "lapwarm_row_features_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, c_vp,
                                                c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_seeded_ragged_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_seeded_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_ip, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp,
+                                         ct.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_seeded_ragged_groups": (ct.c_int, [c_ip, ct.c_int, c_ip]),
     "lapwarm_project_round_batched":(ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
                                                  ct.c_size_t, c_vp]),
     "lapwarm_reduce_costs_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, ct.c_int, c_vp, c_vp,

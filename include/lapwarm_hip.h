@@ -202,6 +202,35 @@ int lapwarm_row_features_ragged(const double *C, const long long *offsets, const
                                 float *cost32, unsigned char *mask, int *ret, void *workspace,
                                 size_t workspace_bytes, void *stream);
 
+/* lapjv_seeded of every instance of a ragged batch (C, offsets, sizes, ld, batch, N as above) in one call:
+ * u_seed, v_seed [batch][N] fp64, read on the prefix of each instance only; x, y [batch][N] int64 with -1 beyond
+ * n_b; ret [batch]; stats [batch][32] or NULL.  x, y, ret and stats of instance b are what
+ * lapwarm_seeded_batched gives it alone (batch 1), the time slots 13, 14 and 16.. of stats apart: the
+ * instance runs under the kernel instantiation it would get alone.  Instances whose solve plans have the same
+ * kernel configuration (workgroup size, positions per lane, LDS level, register bound) share ONE launch, so
+ * the call makes one prepare, two prelude, one projection launch and one solver launch per distinct
+ * configuration -- at most seven -- whatever the number of distinct sizes.  host_sizes [batch] is a HOST copy
+ * of sizes: the launches are planned from it and the stream is never synchronised (kernels only: the call
+ * can be captured into a graph).  Every instance must be in the class whose plan is one launch with all
+ * solver state in LDS and no helper workgroup: lapwarm_solver_uses_helpers(n_b) == 0, lapwarm_coop_members(n_b)
+ * == 0 and n_b small enough for the state to fit LDS (with the default settings every n < 1024 and the odd n up to 3631).  A
+ * launch takes the instances whose size ON THE DEVICE lies between the smallest and the largest host size of its
+ * group, so an instance whose device size is not the host's is solved only if some launch of the call covers that
+ * size (safely: the launch's threads and LDS hold for every n up to its largest); otherwise it stays as the prepare
+ * step leaves it: x, y -1, ret 2, stats 0.  Returns 0, -2 (N <= 0, batch outside 1..65535, ld < 0, a NULL pointer other than stats, a host
+ * size outside 1..N or above ld > 0), -5 (N > 16384), -6 (an instance outside the class: solve it with
+ * lapwarm_seeded_batched), -1 (workspace too small), <= -1000 HIP error; only the last follows device work. */
+size_t lapwarm_seeded_ragged_workspace_bytes(int batch, int N);
+int lapwarm_seeded_ragged(const double *C, const long long *offsets, const int *sizes, const int *host_sizes, int ld,
+                          int batch, int N, const double *u_seed, const double *v_seed, double eps, long long *x,
+                          long long *y, int *ret, long long *stats, void *workspace, size_t workspace_bytes,
+                          void *stream);
+/* Host only, no device needed: group_of [batch] receives the launch of every instance of `sizes` (HOST,
+ * [batch]), numbered from 0 in the order of first appearance; two instances share a launch exactly when their
+ * solve plans have the same kernel configuration.  Returns the number of launches, -1 when an instance is
+ * outside the class above, -2 for batch <= 0 or a NULL pointer. */
+int lapwarm_seeded_ragged_groups(const int *sizes, int batch, int *group_of);
+
 /* One round of project_feasible: u = min(u, rowmin(C-v)); v = min(v, colmin(C-u));
  * gmin[b] = min((C-u)-v).  The host loop decides when to stop. */
 int lapwarm_project_round_batched(const double *C, int batch, int n, double *u, double *v,
@@ -293,8 +322,8 @@ int lapwarm_refine_backward(const float *topk16, const float *u_pre, const float
                             const float *grad_out, const float *grad_wsum, float *grad_u, float *grad_w1,
                             float *grad_b1, int rows, int H, void *ws, size_t ws_bytes, void *stream);
 
-/* Profiling hook for bench.py: when enabled, lapwarm_seeded_batched / lapwarm_lapjv_batched
- * bracket the per-instance solver kernel with HIP events on the caller's stream;
+/* Profiling hook for bench.py: when enabled, lapwarm_seeded_batched / lapwarm_lapjv_batched /
+ * lapwarm_seeded_ragged bracket their solver launches with HIP events on the caller's stream;
  * lapwarm_profile_last_solver_ms() waits for the last bracket and returns its duration. */
 void lapwarm_profile_enable(int on);
 double lapwarm_profile_last_solver_ms(void);
