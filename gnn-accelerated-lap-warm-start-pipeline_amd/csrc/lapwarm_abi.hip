@@ -743,25 +743,14 @@ size_t lapwarm_oracle_duals_workspace_bytes(int batch, int n)
     return oracle_layout(nullptr, batch, n, &p).bytes;
 }
 
-// Sweeps are launched in chunks (4, 8, 16, then 32 at a time) with one host synchronisation per
-// chunk to learn whether any instance still needs sweeps: not graph-capturable.
-static int oracle_duals_impl(const double *C, int batch, int n, const int *rows, const int *cols, double *u,
-                             double *v, int *ret, int *sweeps, void *workspace, size_t workspace_bytes,
-                             double tol, hipStream_t stream)
+// Init, the sweeps and the finish of a uniform or a ragged call.  Sweeps are launched in chunks (4, 8, 16, then
+// 32 at a time) up to max_s, with one host synchronisation per chunk to learn whether any instance still needs
+// sweeps: not graph-capturable.  The one place that knows the schedule: a ragged instance is bit-equal to the
+// uniform call because both are checked at the same sweep numbers.
+static int oracle_run(const OracleParams &p, const OracleWs &w, int max_s, double tol, double *u, double *v, int *ret,
+                      int *sweeps, hipStream_t stream)
 {
-    if (int rc = check_dims(batch, n)) return rc;
-    if (workspace_bytes < lapwarm_oracle_duals_workspace_bytes(batch, n)) return -1;
-    OracleParams p;
-    p.C = C;
-    p.n = n;
-    p.batch = batch;
-    p.chunks = oracle_chunks(n, batch);
-    p.pair = (n % 2) == 0 && (reinterpret_cast<uintptr_t>(C) % 16) == 0;
-    p.rows = rows;
-    p.cols = cols;
-    const OracleWs w = oracle_layout(workspace, batch, n, &p);
     HIP_TRY(launch_oracle_init(p, stream));
-    const int max_s = n - 1;  // settled within n - 1 sweeps <=> at most n - 2 updating sweeps
     int s = 0, chunk = 4;
     for (;;) {
         const int k = (chunk < max_s - s) ? chunk : max_s - s;
@@ -780,12 +769,72 @@ static int oracle_duals_impl(const double *C, int batch, int n, const int *rows,
     return 0;
 }
 
+static int oracle_duals_impl(const double *C, int batch, int n, const int *rows, const int *cols, double *u,
+                             double *v, int *ret, int *sweeps, void *workspace, size_t workspace_bytes,
+                             double tol, hipStream_t stream)
+{
+    if (int rc = check_dims(batch, n)) return rc;
+    if (workspace_bytes < lapwarm_oracle_duals_workspace_bytes(batch, n)) return -1;
+    OracleParams p;
+    p.C = C;
+    p.n = n;
+    p.batch = batch;
+    p.chunks = oracle_chunks(n, batch);
+    p.pair = (n % 2) == 0 && (reinterpret_cast<uintptr_t>(C) % 16) == 0;
+    p.rows = rows;
+    p.cols = cols;
+    const OracleWs w = oracle_layout(workspace, batch, n, &p);
+    // settled within n - 1 sweeps <=> at most n - 2 updating sweeps
+    return oracle_run(p, w, n - 1, tol, u, v, ret, sweeps, stream);
+}
+
 int lapwarm_oracle_duals_batched(const double *C, int batch, int n, const int *rows, const int *cols, double *u,
                                  double *v, int *ret, int *sweeps, void *workspace, size_t workspace_bytes,
                                  void *stream_)
 {
     return oracle_duals_impl(C, batch, n, rows, cols, u, v, ret, sweeps, workspace, workspace_bytes, 1e-12,
                              reinterpret_cast<hipStream_t>(stream_));
+}
+
+size_t lapwarm_oracle_duals_ragged_workspace_bytes(int batch, int N)
+{
+    if (N <= 0 || batch <= 0 || batch > 65535 || N > kOracleMaxN) return 0;
+    OracleParams p;
+    return oracle_layout(nullptr, batch, N, &p).bytes;  // the uniform slots with the padded stride N
+}
+
+// One init and one chain of sweep chunks for all instances: the chunk schedule of oracle_run is shared and runs to
+// the largest budget, max_b (n_b - 1), taken from the host sizes; the kernels keep every instance to its own
+// budget.  As many host synchronisations as one uniform call of the largest size: not graph-capturable.
+int lapwarm_oracle_duals_ragged(const double *C, const long long *offsets, const int *sizes, const int *host_sizes,
+                                int ld, int batch, int N, const int *rows, const int *cols, double *u, double *v,
+                                int *ret, int *sweeps, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!host_sizes || !rows || !cols || !u || !v || !ret || !workspace) return -2;
+    OracleParams p;
+    p.C = C;
+    p.n = N;
+    p.batch = batch;
+    p.chunks = oracle_chunks(N, batch);
+    p.pair = 0;  // chosen per instance on the device
+    p.offsets = offsets;
+    p.sizes = sizes;
+    p.ld = ld;
+    p.rows = rows;
+    p.cols = cols;
+    const OracleWs w = oracle_layout(workspace, batch, N, &p);
+    if (workspace_bytes < w.bytes) {
+        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
+        return -1;
+    }
+    int max_s = 0;  // a host size the device would treat as empty asks for no sweeps
+    for (int b = 0; b < batch; ++b) {
+        const int n = host_sizes[b];
+        if (n >= 1 && n <= N && (ld == 0 || n <= ld) && n - 1 > max_s) max_s = n - 1;
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    return oracle_run(p, w, max_s, 1e-12, u, v, ret, sweeps, stream);
 }
 
 size_t lapwarm_train_loss_workspace_bytes(int batch, int n)

@@ -22,9 +22,13 @@
 //   * finish: u from the matched pairs, the gauge shift with numpy's pairwise-sum order of
 //     np.mean, the matched |reduced cost| maximum; the reduced-cost minimum is the dense
 //     launch_reduced_min sweep ((C - u_i) - v_j, the reference's order).
+//
+// A ragged batch (ragged_batch.hpp) runs the same kernel bodies with a per-instance view: one init, one shared
+// chain of sweeps, and each instance keeps the sweep budget and the check points it has alone.
 #include "device_utils.hpp"
 #include "dense_sweeps.hpp"  // colmin_chunks, launch_reduced_min
 #include "oracle_duals.hpp"
+#include "ragged_batch.hpp"
 
 namespace lapwarm {
 
@@ -38,14 +42,49 @@ constexpr int kCycleThreads = 1024;
 
 __device__ __forceinline__ bool od_finite(double x) { return (x - x) == 0.0; }
 
+// One body per kernel, two addressings.  Every per-instance array has the row stride p.n in both: that is n
+// in a uniform batch and the padded width N in a ragged one, where instance b uses the prefix n_b of its row.
+// Uniform: instance b is the n x n block at C + b * n * n, and the pair load is the host's choice for the
+// whole batch.  RAGGED (ragged_batch.hpp): n_b x n_b at C + offsets[b] with row stride ld, or n_b when
+// packed; the 16-byte pair load is taken when n_b and the row stride are even and the base is 16-byte
+// aligned (offsets are multiples of 8 bytes only), decided here per instance, workgroup-uniform.
+struct OdInstance {
+    int n;
+    size_t ld;        // row stride of C
+    const double *C;
+    bool pair;
+};
+
+template <bool RAGGED>
+__device__ __forceinline__ OdInstance od_instance(const OracleParams &p, int b)
+{
+    OdInstance t;
+    if constexpr (RAGGED) {
+        const RaggedBatch g{p.C, p.offsets, p.sizes, p.ld, p.batch, p.n};
+        t.n = __builtin_amdgcn_readfirstlane(ragged_size(g, b));
+        t.ld = p.ld ? (size_t)p.ld : (size_t)t.n;
+        t.C = p.C + p.offsets[b];
+        t.pair = (t.n % 2) == 0 && (t.ld % 2) == 0 && (reinterpret_cast<uintptr_t>(t.C) % 16) == 0;
+    } else {
+        t.n = p.n;
+        t.ld = (size_t)p.n;
+        t.C = p.C + (size_t)b * p.n * p.n;
+        t.pair = p.pair != 0;
+    }
+    return t;
+}
+
 // ------------------------------------------------------------------------------------------
 // Set-up, one workgroup per instance: check that the pairs form a permutation, x (row -> col),
 // y (col -> row), C[i][x_i], v = 0, no predecessors, every row active with source value 0.
 // ------------------------------------------------------------------------------------------
+// A ragged instance that is treated as empty (ragged_size) gets kOracleEmpty here and no kernel touches it again.
+template <bool RAGGED>
 __global__ void __launch_bounds__(kOdThreads) od_init_kernel(OracleParams p)
 {
-    const int b = blockIdx.x, n = p.n, tid = threadIdx.x;
-    const size_t bn = (size_t)b * n;
+    const OdInstance t = od_instance<RAGGED>(p, blockIdx.x);
+    const int b = blockIdx.x, n = t.n, tid = threadIdx.x;
+    const size_t bn = (size_t)b * p.n;
     int *x = p.x + bn, *y = p.y + bn;
     for (int i = tid; i < n; i += kOdThreads) {
         x[i] = -1;
@@ -66,7 +105,7 @@ __global__ void __launch_bounds__(kOdThreads) od_init_kernel(OracleParams p)
     int nonfinite = 0;
     if (!bad) {
         for (int i = tid; i < n; i += kOdThreads) {
-            const double c = p.C[(bn + i) * n + x[i]];
+            const double c = t.C[(size_t)i * t.ld + x[i]];
             nonfinite |= !od_finite(c);
             p.cxx[bn + i] = c;
             p.lrow[bn + i] = i;
@@ -79,6 +118,7 @@ __global__ void __launch_bounds__(kOdThreads) od_init_kernel(OracleParams p)
     if (tid == 0) {
         int *st = p.inst + (size_t)b * kOdInstInts;
         st[kOdStatus] = bad ? kOracleNotPermutation : (nonfinite ? kOracleNonFinite : 0);
+        if (RAGGED && n == 0) st[kOdStatus] = kOracleEmpty;
         st[kOdCount0] = n;
         st[kOdCount1] = 0;
         st[kOdSweeps] = 0;
@@ -93,7 +133,9 @@ __global__ void __launch_bounds__(kOdThreads) od_init_kernel(OracleParams p)
 // One frontier sweep, part 1: grid (column tiles, chunks, batch).  Chunk c takes an equal share
 // of the active list (at least kOdRowsPerChunk entries), 2 columns per lane, and writes its
 // column minima with the row that gave them (ties: the smallest row).  The first sweep reads
-// every element of C and checks it is finite.
+// every element of C and checks it is finite.  RAGGED: the sweep number is the batch's, the budget the
+// instance's own -- an instance that has made its n_b - 1 sweeps is skipped, so at every check its state is
+// what it is alone; blocks and lanes right of the prefix leave at once.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ int od_chunks_used(int cnt, int chunks)
 {
@@ -101,13 +143,17 @@ __device__ __forceinline__ int od_chunks_used(int cnt, int chunks)
     return c < chunks ? c : chunks;
 }
 
+template <bool RAGGED>
 __global__ void __launch_bounds__(kOdThreads) od_sweep_partial_kernel(OracleParams p, int s)
 {
-    const int b = blockIdx.z, chunk = blockIdx.y, n = p.n;
+    const int b = blockIdx.z, chunk = blockIdx.y;
     int *st = p.inst + (size_t)b * kOdInstInts;
     const int cur = s & 1;
     const int cnt = st[kOdCount0 + cur];
+    const OdInstance t = od_instance<RAGGED>(p, b);
     if (st[kOdStatus] != 0) return;
+    const int n = t.n;
+    if (RAGGED && s >= n - 1) return;
     if (cnt == 0) {
         if (blockIdx.x == 0 && chunk == 0 && threadIdx.x == 0) st[kOdStatus] = kOracleDone;
         return;
@@ -121,11 +167,11 @@ __global__ void __launch_bounds__(kOdThreads) od_sweep_partial_kernel(OraclePara
     const int j = (blockIdx.x * kOdThreads + threadIdx.x) * 2;
     if (j >= n) return;
     const bool two = (j + 1) < n;
-    const size_t bn = (size_t)b * n;
-    const size_t lo = (size_t)cur * p.batch * n + bn;
+    const size_t bn = (size_t)b * p.n;
+    const size_t lo = (size_t)cur * p.batch * p.n + bn;
     const int *lrow = p.lrow + lo;
     const double *lsrc = p.lsrc + lo;
-    const double *Cb = p.C + bn * n;
+    const double *Cb = t.C;
     double m0 = pos_inf(), m1 = pos_inf();
     int a0 = 0x7fffffff, a1 = 0x7fffffff;
     int nonfinite = 0;
@@ -135,9 +181,9 @@ __global__ void __launch_bounds__(kOdThreads) od_sweep_partial_kernel(OraclePara
         const int i = lrow[q];
         const double src = lsrc[q];
         const double base = p.cxx[bn + i];
-        const double *row = Cb + (size_t)i * n + j;
+        const double *row = Cb + (size_t)i * t.ld + j;
         double c0, c1;
-        if (p.pair) {
+        if (t.pair) {
             const double2 c = *reinterpret_cast<const double2 *>(row);
             c0 = c.x;
             c1 = c.y;
@@ -158,7 +204,7 @@ __global__ void __launch_bounds__(kOdThreads) od_sweep_partial_kernel(OraclePara
         }
     }
     if (first && nonfinite) atomicCAS(&st[kOdStatus], 0, kOracleNonFinite);
-    const size_t po = ((size_t)b * p.chunks + chunk) * n + j;
+    const size_t po = ((size_t)b * p.chunks + chunk) * p.n + j;
     p.pval[po] = m0;
     p.parg[po] = a0;
     if (two) {
@@ -170,27 +216,30 @@ __global__ void __launch_bounds__(kOdThreads) od_sweep_partial_kernel(OraclePara
 // Part 2: grid (column blocks, batch).  Combine the chunks, apply the strict update into the
 // other v buffer, record the predecessor row, and append the row matched to every changed column
 // (with its new source value) to the next active list.
+template <bool RAGGED>
 __global__ void __launch_bounds__(kOdThreads) od_sweep_final_kernel(OracleParams p, int s)
 {
-    const int b = blockIdx.y, n = p.n;
+    const int b = blockIdx.y;
     int *st = p.inst + (size_t)b * kOdInstInts;
     const int cur = s & 1;
     const int cnt = st[kOdCount0 + cur];
+    const int n = od_instance<RAGGED>(p, b).n;
     if (st[kOdStatus] != 0 || cnt == 0) return;
+    if (RAGGED && s >= n - 1) return;
     const int j = blockIdx.x * kOdThreads + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         st[kOdSweeps] = s + 1;
         st[kOdRowsRead] += cnt;
     }
     if (j >= n) return;
-    const size_t bn = (size_t)b * n;
+    const size_t bn = (size_t)b * p.n;
     const double *vo = (cur ? p.v1 : p.v0) + bn;
     double *vn = (cur ? p.v0 : p.v1) + bn;
     const int used = od_chunks_used(cnt, p.chunks);
     double m = pos_inf();
     int arg = 0x7fffffff;
     for (int c = 0; c < used; ++c) {
-        const size_t po = ((size_t)b * p.chunks + c) * n + j;
+        const size_t po = ((size_t)b * p.chunks + c) * p.n + j;
         const double t = p.pval[po];
         const int a = p.parg[po];
         if (t < m || (t == m && a < arg)) {
@@ -204,7 +253,7 @@ __global__ void __launch_bounds__(kOdThreads) od_sweep_final_kernel(OracleParams
         p.pred[bn + j] = arg;
         const int i = p.y[bn + j];
         const int q = atomicAdd(&st[kOdCount0 + (cur ^ 1)], 1);
-        const size_t lo = (size_t)(cur ^ 1) * p.batch * n + bn;
+        const size_t lo = (size_t)(cur ^ 1) * p.batch * p.n + bn;
         p.lrow[lo + q] = i;
         p.lsrc[lo + q] = m;
         st[kOdDepth] = s + 1;  // every writer stores the same value
@@ -217,20 +266,30 @@ __global__ void __launch_bounds__(kOdThreads) od_sweep_final_kernel(OracleParams
 // After a chunk of sweeps, one workgroup per running instance: stop the converged ones, detect a
 // cycle in the predecessor graph (column j -> column x[pred[j]]) by pointer doubling in LDS, and
 // at the end of the sweep budget hand the unsettled ones to the replay.  `running` counts the
-// instances that still need sweeps.
+// instances that still need sweeps.  RAGGED: s is the batch's sweep number; the instance has made
+// min(s, n_b - 1) sweeps -- that is the parity of its lists -- and its budget ends at s >= n_b - 1, or with the
+// host's `last` (a device size above every host size: the schedule ends before the instance's own budget).
 // ------------------------------------------------------------------------------------------
+template <bool RAGGED>
 __global__ void __launch_bounds__(kCycleThreads) od_check_kernel(OracleParams p, int s, int last, int *running)
 {
     extern __shared__ int q[];
-    const int b = blockIdx.x, n = p.n, tid = threadIdx.x;
+    const int b = blockIdx.x, tid = threadIdx.x;
     int *st = p.inst + (size_t)b * kOdInstInts;
+    const int n = od_instance<RAGGED>(p, b).n;
     if (st[kOdStatus] != 0) return;
+    if constexpr (RAGGED) {  // the host's `last` still ends an instance whose budget lies beyond the host's
+        if (s >= n - 1) {
+            last = 1;
+            s = n - 1;
+        }
+    }
     const int cnt = st[kOdCount0 + (s & 1)];
     if (cnt == 0) {
         if (tid == 0) st[kOdStatus] = kOracleDone;
         return;
     }
-    const size_t bn = (size_t)b * n;
+    const size_t bn = (size_t)b * p.n;
     for (int j = tid; j < n; j += kCycleThreads) {
         const int pr = p.pred[bn + j];
         q[j] = pr < 0 ? -1 : p.x[bn + pr];
@@ -275,14 +334,18 @@ __global__ void __launch_bounds__(kCycleThreads) od_check_kernel(OracleParams p,
 // (only the self-edge, weight 0, touches v[a], and it never fires), so one pair is one
 // workgroup-wide step.  Then the tol check of the `for ... else` clause.
 // ------------------------------------------------------------------------------------------
+template <bool RAGGED>
 __global__ void __launch_bounds__(kReplayThreads) od_replay_kernel(OracleParams p, double tol)
 {
     __shared__ double vl[kOracleReplayMaxN];
-    const int b = blockIdx.x, n = p.n, tid = threadIdx.x;
+    const int b = blockIdx.x, tid = threadIdx.x;
     int *st = p.inst + (size_t)b * kOdInstInts;
     if (st[kOdStatus] != kOracleReplay) return;
-    const size_t bn = (size_t)b * n;
-    const double *Cb = p.C + bn * n;
+    const OdInstance inst = od_instance<RAGGED>(p, b);
+    const int n = inst.n;
+    const size_t ld = inst.ld;
+    const size_t bn = (size_t)b * p.n;
+    const double *Cb = inst.C;
     const int *rows = p.rows + bn, *cols = p.cols + bn;
     for (int j = tid; j < n; j += kReplayThreads) vl[j] = 0.0;
     __syncthreads();
@@ -291,7 +354,7 @@ __global__ void __launch_bounds__(kReplayThreads) od_replay_kernel(OracleParams 
         int upd = 0;
         double c[kReplayEpt];
         {
-            const double *row = Cb + (size_t)rows[0] * n;
+            const double *row = Cb + (size_t)rows[0] * ld;
 #pragma unroll
             for (int e = 0; e < kReplayEpt; ++e) {
                 const int j = tid + e * kReplayThreads;
@@ -300,10 +363,10 @@ __global__ void __launch_bounds__(kReplayThreads) od_replay_kernel(OracleParams 
         }
         for (int k = 0; k < n; ++k) {
             const int a = cols[k];
-            const double base = Cb[(size_t)rows[k] * n + a];
+            const double base = Cb[(size_t)rows[k] * ld + a];
             const double va = vl[a];
             double cn[kReplayEpt];
-            const double *nrow = Cb + (size_t)rows[(k + 1 < n) ? k + 1 : k] * n;
+            const double *nrow = Cb + (size_t)rows[(k + 1 < n) ? k + 1 : k] * ld;
 #pragma unroll
             for (int e = 0; e < kReplayEpt; ++e) {
                 const int j = tid + e * kReplayThreads;
@@ -331,7 +394,7 @@ __global__ void __launch_bounds__(kReplayThreads) od_replay_kernel(OracleParams 
     int neg = 0;
     if (!broke) {
         for (int k = 0; k < n; ++k) {
-            const double *row = Cb + (size_t)rows[k] * n;
+            const double *row = Cb + (size_t)rows[k] * ld;
             const int a = cols[k];
             const double base = row[a];
             const double va = vl[a];
@@ -352,14 +415,24 @@ __global__ void __launch_bounds__(kReplayThreads) od_replay_kernel(OracleParams 
 // ------------------------------------------------------------------------------------------
 // Finish, one workgroup per instance: u_r = C[r][x_r] - v[x_r]; shift = (mean(u) + mean(v)) / 2;
 // u -= shift, v += shift; max over matched edges of |(C - u) - v|.  Instances that failed get NaN.
+// RAGGED: all of this on the prefix n_b; u and v are 0 beyond it.
 // ------------------------------------------------------------------------------------------
+template <bool RAGGED>
 __global__ void __launch_bounds__(kOdThreads) od_finish_kernel(OracleParams p, double *u_out, double *v_out)
 {
     __shared__ double sh[2];
-    const int b = blockIdx.x, n = p.n, tid = threadIdx.x;
+    const int b = blockIdx.x, tid = threadIdx.x;
     int *st = p.inst + (size_t)b * kOdInstInts;
-    const size_t bn = (size_t)b * n;
+    const size_t bn = (size_t)b * p.n;
     double *u = u_out + bn, *v = v_out + bn;
+    int n = p.n;
+    if constexpr (RAGGED) {
+        n = od_instance<true>(p, b).n;
+        for (int j = n + tid; j < p.n; j += kOdThreads) {
+            u[j] = 0.0;
+            v[j] = 0.0;
+        }
+    }
     if (st[kOdStatus] != kOracleDone) {
         const double qnan = __longlong_as_double(0x7ff8000000000000LL);
         for (int j = tid; j < n; j += kOdThreads) {
@@ -424,36 +497,53 @@ int oracle_chunks(int n, int batch) { return colmin_chunks(n, batch); }
 
 hipError_t launch_oracle_init(const OracleParams &p, hipStream_t stream)
 {
-    hipLaunchKernelGGL(od_init_kernel, dim3(p.batch), dim3(kOdThreads), 0, stream, p);
+    if (p.sizes)
+        hipLaunchKernelGGL(od_init_kernel<true>, dim3(p.batch), dim3(kOdThreads), 0, stream, p);
+    else
+        hipLaunchKernelGGL(od_init_kernel<false>, dim3(p.batch), dim3(kOdThreads), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launch_oracle_sweep(const OracleParams &p, int s, hipStream_t stream)
 {
     const dim3 g1((p.n + 2 * kOdThreads - 1) / (2 * kOdThreads), p.chunks, p.batch);
-    hipLaunchKernelGGL(od_sweep_partial_kernel, g1, dim3(kOdThreads), 0, stream, p, s);
     const dim3 g2((p.n + kOdThreads - 1) / kOdThreads, p.batch);
-    hipLaunchKernelGGL(od_sweep_final_kernel, g2, dim3(kOdThreads), 0, stream, p, s);
+    if (p.sizes) {
+        hipLaunchKernelGGL(od_sweep_partial_kernel<true>, g1, dim3(kOdThreads), 0, stream, p, s);
+        hipLaunchKernelGGL(od_sweep_final_kernel<true>, g2, dim3(kOdThreads), 0, stream, p, s);
+    } else {
+        hipLaunchKernelGGL(od_sweep_partial_kernel<false>, g1, dim3(kOdThreads), 0, stream, p, s);
+        hipLaunchKernelGGL(od_sweep_final_kernel<false>, g2, dim3(kOdThreads), 0, stream, p, s);
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_oracle_check(const OracleParams &p, int s, int last, int *running, hipStream_t stream)
 {
     const size_t lds = sizeof(int) * (size_t)p.n;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(od_check_kernel),
+    auto *kernel = p.sizes ? od_check_kernel<true> : od_check_kernel<false>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(od_check_kernel, dim3(p.batch), dim3(kCycleThreads), lds, stream, p, s, last, running);
+    hipLaunchKernelGGL(kernel, dim3(p.batch), dim3(kCycleThreads), lds, stream, p, s, last, running);
     return hipGetLastError();
 }
 
 hipError_t launch_oracle_finish(const OracleParams &p, double tol, double *u, double *v, double *rowpart,
                                 double *gmin, int *ret, int *sweeps, hipStream_t stream)
 {
-    if (p.n <= kOracleReplayMaxN)
-        hipLaunchKernelGGL(od_replay_kernel, dim3(p.batch), dim3(kReplayThreads), 0, stream, p, tol);
-    hipLaunchKernelGGL(od_finish_kernel, dim3(p.batch), dim3(kOdThreads), 0, stream, p, u, v);
-    hipError_t e = launch_reduced_min(p.C, p.n, p.batch, u, v, rowpart, gmin, stream);
+    hipError_t e;
+    if (p.sizes) {  // the replay serves n_b <= kOracleReplayMaxN: the check kernel flags no other instance
+        hipLaunchKernelGGL(od_replay_kernel<true>, dim3(p.batch), dim3(kReplayThreads), 0, stream, p, tol);
+        hipLaunchKernelGGL(od_finish_kernel<true>, dim3(p.batch), dim3(kOdThreads), 0, stream, p, u, v);
+        const RaggedBatch g{p.C, p.offsets, p.sizes, p.ld, p.batch, p.n};
+        e = launch_reduced_min_ragged(g, u, v, rowpart, gmin, stream);
+    } else {
+        if (p.n <= kOracleReplayMaxN)
+            hipLaunchKernelGGL(od_replay_kernel<false>, dim3(p.batch), dim3(kReplayThreads), 0, stream, p, tol);
+        hipLaunchKernelGGL(od_finish_kernel<false>, dim3(p.batch), dim3(kOdThreads), 0, stream, p, u, v);
+        e = launch_reduced_min(p.C, p.n, p.batch, u, v, rowpart, gmin, stream);
+    }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(od_verdict_kernel, dim3((p.batch + 255) / 256), dim3(256), 0, stream, p, gmin, ret, sweeps);
     return hipGetLastError();

@@ -1,4 +1,5 @@
-// ragged_batch.hip -- column minima of a batch of cost matrices of different sizes, gfx950.
+// ragged_batch.hip -- column minima and the reduced-cost minimum of a batch of cost matrices of different sizes,
+// gfx950.
 //
 // Reference behaviour reproduced (paths relative to /root/reference): the column minima of
 // gnn/features.py:218 and the min-trick of scripts/gnn_benchmark.py:262, per instance of a batch laid out
@@ -70,7 +71,51 @@ __global__ void __launch_bounds__(kColminThreads) colmin_ragged_kernel(RaggedBat
     }
 }
 
+constexpr int kRowThreads = 256;
+
+// rowpart[b][i] = min_{j < n_b} ((C_b[i][j] - u_i) - v_j): workgroup (i, b), gone at once beyond the prefix.
+__global__ void __launch_bounds__(kRowThreads)
+reduced_rowmin_ragged_kernel(RaggedBatch g, const double *u, const double *v, double *rowpart)
+{
+    __shared__ BlockExchange ex;
+    const int b = blockIdx.y, i = blockIdx.x;
+    const int n = __builtin_amdgcn_readfirstlane(ragged_size(g, b));
+    if (i >= n) return;
+    BlockCtx bc;
+    bc.init(&ex);
+    const double *row = g.C + g.offsets[b] + (size_t)i * (g.ld ? g.ld : n);
+    const double *vb = v + (size_t)b * g.N;
+    const double ui = u[(size_t)b * g.N + i];
+    double m = pos_inf();
+    for (int j = bc.tid; j < n; j += kRowThreads) m = nmin(m, (row[j] - ui) - vb[j]);
+    m = bc.min_f64<NanMinF64>(m);
+    if (bc.tid == 0) rowpart[(size_t)b * g.N + i] = m;
+}
+
+__global__ void __launch_bounds__(kRowThreads) vecmin_ragged_kernel(RaggedBatch g, const double *in, double *out)
+{
+    __shared__ BlockExchange ex;
+    const int b = blockIdx.x;
+    const int n = ragged_size(g, b);
+    BlockCtx bc;
+    bc.init(&ex);
+    double m = pos_inf();
+    for (int j = bc.tid; j < n; j += kRowThreads) m = nmin(m, in[(size_t)b * g.N + j]);
+    m = bc.min_f64<NanMinF64>(m);
+    if (bc.tid == 0) out[b] = m;
+}
+
 }  // namespace
+
+hipError_t launch_reduced_min_ragged(const RaggedBatch &g, const double *u, const double *v, double *rowpart,
+                                     double *gmin, hipStream_t stream)
+{
+    if (g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(reduced_rowmin_ragged_kernel, dim3(g.N, g.batch), dim3(kRowThreads), 0, stream, g, u, v,
+                       rowpart);
+    hipLaunchKernelGGL(vecmin_ragged_kernel, dim3(g.batch), dim3(kRowThreads), 0, stream, g, rowpart, gmin);
+    return hipGetLastError();
+}
 
 hipError_t launch_colmin_ragged(const RaggedBatch &g, const double *u, double *out, hipStream_t stream)
 {

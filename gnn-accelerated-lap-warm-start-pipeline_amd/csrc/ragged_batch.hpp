@@ -29,6 +29,11 @@ __device__ __forceinline__ int ragged_size(const RaggedBatch &g, int b)
 // u, out [batch][N].  One kernel.
 hipError_t launch_colmin_ragged(const RaggedBatch &g, const double *u, double *out, hipStream_t stream);
 
+// gmin[b] = min_{i, j < n_b} ((C_b[i][j] - u[b][i]) - v[b][j]), NaN as np.min, +inf for an instance treated as
+// empty: launch_reduced_min per instance.  u, v, rowpart [batch][N]; gmin [batch].  Two kernels.
+hipError_t launch_reduced_min_ragged(const RaggedBatch &g, const double *u, const double *v, double *rowpart,
+                                     double *gmin, hipStream_t stream);
+
 struct RaggedFeatureOut {
     const double *colmin;  // [batch][N] from launch_colmin_ragged(g, nullptr, ...)
     const float *posenc;   // [rows][8]: the per-n tables of the distinct sizes, one after the other

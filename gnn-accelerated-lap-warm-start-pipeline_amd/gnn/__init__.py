@@ -7,7 +7,8 @@ OneGNN and the two row-feature functions are the hot path and run on the device.
 importable names that raise NotImplementedError when USED, so that the harness' import line
 succeeds and its OneGNN branch runs; a DualGNN checkpoint is reported, not silently mishandled."""
 from .collate import DeviceBatch, collate_device
-from .features import compute_row_features, compute_row_features_torch, positional_encodings, ROW_FEATURE_DIM
+from .features import (compute_row_features, compute_row_features_torch, positional_encodings, ragged_pack,
+                       RaggedPack, ROW_FEATURE_DIM)
 from .one_gnn import OneGNN, ResidualBlock
 from .pipeline import GNNPredictor, WarmStartPipeline, load_checkpoint
 
@@ -26,4 +27,4 @@ def compute_features(*args, **kwargs):
 
 __all__ = ["OneGNN", "ResidualBlock", "DualGNN", "compute_features", "compute_row_features",
            "compute_row_features_torch", "positional_encodings", "ROW_FEATURE_DIM", "GNNPredictor",
-           "WarmStartPipeline", "load_checkpoint", "collate_device", "DeviceBatch"]
+           "WarmStartPipeline", "load_checkpoint", "collate_device", "DeviceBatch", "ragged_pack", "RaggedPack"]

@@ -117,6 +117,32 @@ def _ragged_posenc(distinct, device):
     return _RAGGED_POSENC_CACHE[key]
 
 
+_RAGGED_META_CACHE = {}
+
+
+def _ragged_meta(host_sizes, ld, offsets, device):
+    """offsets (B,) int64, sizes and pos_off (B,) int32 and the positional-encoding tables on the device.  They
+    depend on the sizes and the layout alone and nothing writes to them, so they are kept per (sizes, ld, device),
+    the newest 32: a batch of a shape seen before uploads nothing and waits for nothing."""
+    import torch
+    key = (host_sizes, ld, str(device))
+    hit = _RAGGED_META_CACHE.get(key)
+    if hit is None:
+        if len(_RAGGED_META_CACHE) >= 32:
+            _RAGGED_META_CACHE.pop(next(iter(_RAGGED_META_CACHE)))
+        B = len(host_sizes)
+        posenc, first = _ragged_posenc(tuple(sorted(set(host_sizes))), device)
+        meta = np.empty(2 * B, dtype=np.int64)  # offsets, then sizes and pos_off as int32: one copy
+        meta[:B] = offsets
+        m32 = meta[B:].view(np.int32)
+        m32[:B] = host_sizes
+        m32[B:] = [first[n] for n in host_sizes]
+        meta_d = torch.from_numpy(meta).to(device)
+        d32 = meta_d[B:].view(torch.int32)
+        hit = _RAGGED_META_CACHE[key] = (meta_d[:B], d32[:B], d32[B:], posenc)
+    return hit
+
+
 class RaggedFeatures:
     """What one ragged call returns, padded to N = the largest size: feat (B, N, 21) f32, topk (B, N, 16) f32
     or None, cost32 (B, N, N) f32 or None, mask (B, N) bool, sizes (B,) int32 and ret (B,) int32 (0, or 2
@@ -129,7 +155,8 @@ class RaggedFeatures:
 
 class RaggedPack:
     """A ragged batch on the device, as the C ABI takes it: C fp64, offsets (B,) int64, sizes and pos_off (B,)
-    int32 (views of one uploaded block), posenc (rows, 8) f32, ld (0: packed), N, and the sizes on the host."""
+    int32 (views of one uploaded block), posenc (rows, 8) f32, ld (0: packed), N, and the sizes on the host.
+    offsets, sizes, pos_off and posenc are shared by every pack of the same sizes and layout: read-only."""
     __slots__ = ("C", "offsets", "sizes", "pos_off", "posenc", "ld", "N", "host_sizes")
 
     def __init__(self, C, offsets, sizes, pos_off, posenc, ld, N, host_sizes):
@@ -199,17 +226,8 @@ def ragged_pack(costs, device="cuda:0", sizes=None):
         for c, o in zip(mats, offsets.tolist()):
             buf[o:o + c.size] = c.reshape(-1)
         C = torch.from_numpy(buf).to(device)
-    device = C.device
-    B = len(host_sizes)
-    posenc, first = _ragged_posenc(tuple(sorted(set(host_sizes))), device)
-    meta = np.empty(2 * B, dtype=np.int64)  # offsets, then sizes and pos_off as int32: one copy
-    meta[:B] = offsets
-    m32 = meta[B:].view(np.int32)
-    m32[:B] = host_sizes
-    m32[B:] = [first[n] for n in host_sizes]
-    meta_d = torch.from_numpy(meta).to(device)
-    d32 = meta_d[B:].view(torch.int32)
-    return RaggedPack(C, meta_d[:B], d32[:B], d32[B:], posenc, ld, N, host_sizes)
+    offs_d, sizes_d, pos_off_d, posenc = _ragged_meta(tuple(host_sizes), ld, offsets, C.device)
+    return RaggedPack(C, offs_d, sizes_d, pos_off_d, posenc, ld, N, host_sizes)
 
 
 def row_features_ragged(costs, return_topk: bool = True, want_cost32: bool = False, device="cuda:0", sizes=None):

@@ -10,6 +10,7 @@ Two entry points:
 from __future__ import annotations
 
 import ctypes as ct
+from collections.abc import Sequence
 from pathlib import Path
 from typing import Optional, Tuple
 
@@ -56,6 +57,25 @@ def load_checkpoint(path, device="cpu") -> Tuple[OneGNN, dict]:
     model.load_state_dict(state)
     model.to(device).eval()
     return model, info
+
+
+class RaggedDuals(Sequence):
+    """What oracle_duals_many returns: entry b is (x, u, v, ret, sweeps) of instance b, sliced to n_b.  The
+    entries are views of the padded device tensors x, u, v (B, N), ret (B,) and sweeps (B, 4), which are the
+    fields; a view is made when its entry is read, so a caller that wants the padded batch pays for none."""
+    __slots__ = ("x", "u", "v", "ret", "sweeps", "sizes")
+
+    def __init__(self, x, u, v, ret, sweeps, sizes):
+        self.x, self.u, self.v, self.ret, self.sweeps, self.sizes = x, u, v, ret, sweeps, sizes
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def __getitem__(self, b):
+        if isinstance(b, slice):
+            return [self[k] for k in range(*b.indices(len(self)))]
+        n = self.sizes[b]  # (IndexError ends an iteration)
+        return self.x[b, :n], self.u[b, :n], self.v[b, :n], self.ret[b], self.sweeps[b]
 
 
 class WarmStartPipeline:
@@ -221,6 +241,116 @@ class WarmStartPipeline:
             raise RuntimeError(f"lapwarm_oracle_duals_batched failed (code {rc}): {_hip.last_error()}")
         return x, u, v, ret, sweeps
 
+    def oracle_duals_ragged(self, pack: RaggedPack, x: torch.Tensor):
+        """oracle_duals_batch of every instance of a ragged batch in one call (lapwarm_oracle_duals_ragged): one
+        init and one shared chain of sweep launches, `pack.C` read where it is.  `pack` is a ragged_pack result;
+        x (B, N) int32 or int64 on the device of the pack is the matching, row i -> column x[b][i] on the prefix
+        of each instance (anything beyond it is ignored).  Returns u, v (B, N) fp64 (0 beyond the prefix; NaN
+        on the prefix of an instance with ret 1, 4 or 5), ret (B,) int32 with the codes of oracle_duals_batch
+        (and 6 for a size the device treats as empty) and sweeps (B, 4) int32; row b is, bit for bit, what
+        oracle_duals_batch gives instance b alone.  Synchronises the stream once per chunk of sweeps (not
+        graph-capturable).  Raises ValueError before any device work."""
+        B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
+        if pack.C.dtype != torch.float64:
+            raise ValueError(f"the packed costs must be float64, not {pack.C.dtype}")
+        if not isinstance(x, torch.Tensor) or x.dtype not in (torch.int32, torch.int64):
+            raise ValueError("x must be an int32 or int64 tensor")
+        if tuple(x.shape) != (B, N):
+            raise ValueError(f"x must be ({B}, {N}), not {tuple(x.shape)}")
+        if x.device != dev:
+            raise ValueError(f"x must be on {dev}, not {x.device}")
+        cols = x.to(torch.int32).contiguous()
+        rows = torch.arange(N, dtype=torch.int32, device=dev).expand(B, N).contiguous()
+        u = torch.empty((B, N), dtype=torch.float64, device=dev)
+        v = torch.empty((B, N), dtype=torch.float64, device=dev)
+        ret = torch.empty((B,), dtype=torch.int32, device=dev)
+        sweeps = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        ws, nbytes = self._cached_workspace(("oracle_ragged", B, N),
+                                            lambda: self.lib.lapwarm_oracle_duals_ragged_workspace_bytes(B, N))
+        host_sizes = (ct.c_int * B)(*pack.host_sizes)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lapwarm_oracle_duals_ragged(
+            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), host_sizes, pack.ld, B, N,
+            rows.data_ptr(), cols.data_ptr(), u.data_ptr(), v.data_ptr(), ret.data_ptr(), sweeps.data_ptr(),
+            ws.data_ptr(), nbytes, ct.c_void_p(stream))
+        if _hip.check(rc, "oracle_duals_ragged") != 0:
+            raise RuntimeError(f"lapwarm_oracle_duals_ragged failed (code {rc}): {_hip.last_error()}")
+        return u, v, ret, sweeps
+
+    def _matching_packed(self, pack, r=None):
+        """x (B, N), -1 beyond n_b: the assignment the seeded solve of every instance ends at.  One
+        seeded_ragged call where it takes every instance: x stays the padded tensor the solver wrote."""
+        with torch.no_grad():
+            pack, u, v = self._predict_packed(pack, r)
+            if self.threads_hint == 0 and all(self.ragged_solve_eligible(n) for n in set(pack.host_sizes)):
+                return self.seeded_ragged(pack, u, v, want_stats=False)[0]
+            sol = self._solve_packed(pack, u, v, want_stats=False)
+        return torch.nn.utils.rnn.pad_sequence([o["x"] for o in sol], batch_first=True, padding_value=-1)
+
+    def _padded_matching(self, x, sizes, N, dev):
+        """The caller's matchings as one (B, N) integer tensor on the device, -1 beyond n_b: a (B, N) tensor on
+        the device is used as it is; a sequence of B vectors is padded on the device when every one is a tensor
+        there, of one integer type, and otherwise on the host (one upload)."""
+        B = len(sizes)
+        if isinstance(x, torch.Tensor) and x.ndim == 2:
+            if tuple(x.shape) != (B, N) or x.device != dev:
+                raise ValueError(f"a padded x must be ({B}, {N}) on {dev}, not {tuple(x.shape)} on {x.device}")
+            return x
+        x = list(x)
+        if len(x) != B:
+            raise ValueError(f"{B} instances but {len(x)} matchings")
+        on_device = all(isinstance(xb, torch.Tensor) and xb.device == dev and xb.dtype == x[0].dtype for xb in x)
+        if not on_device:
+            x = [np.asarray(xb.cpu() if isinstance(xb, torch.Tensor) else xb) for xb in x]
+        for b, (xb, n) in enumerate(zip(x, sizes)):
+            if tuple(xb.shape) != (n,):
+                raise ValueError(f"matching {b} has shape {tuple(xb.shape)} for an instance of size {n}")
+        if on_device:
+            return torch.nn.utils.rnn.pad_sequence(x, batch_first=True, padding_value=-1)
+        xh = np.full((B, N), -1, dtype=np.int32)
+        for b, (xb, n) in enumerate(zip(x, sizes)):
+            xh[b, :n] = xb
+        return torch.from_numpy(xh).to(dev)
+
+    def oracle_duals_many(self, costs, x=None):
+        """The oracle duals of instances of different sizes: ragged_pack, then one oracle_duals_ragged call.
+        costs: a sequence of square fp64 matrices, or one (B, n, n) float64 CUDA tensor of B instances of one
+        size, which is read where it is.  x: one matching per instance (n_b values each, row i -> column), or
+        one (B, N) integer tensor on the device, or None for the matching of solve_many.
+        A seeded solve ends at an optimal assignment whatever the model predicts; where the optimum is unique
+        that is the `lap.lapjv` matching and the duals have the reference's bits, and where costs tie another
+        optimal matching may be chosen: the duals are then still optimal (feasible, tight on that matching) but
+        need not be the ones the reference computes from its own matching.
+        Returns a sequence with one (x, u, v, ret, sweeps) per instance, in input order, sliced to n_b: views of
+        the padded results (its fields x, u, v, ret, sweeps), made when an entry is read."""
+        if isinstance(costs, torch.Tensor) and costs.ndim == 3:
+            pack = ragged_pack(costs, self.device, sizes=[costs.shape[1]] * costs.shape[0])
+        else:
+            pack = ragged_pack(costs, self.device)
+        host_sizes, N = pack.host_sizes, pack.N
+        xd = self._matching_packed(pack) if x is None else self._padded_matching(x, host_sizes, N, pack.C.device)
+        u, v, ret, sweeps = self.oracle_duals_ragged(pack, xd)
+        return RaggedDuals(xd, u, v, ret, sweeps, host_sizes)
+
+    def training_batch(self, costs):
+        """costs of different sizes -> a labelled DeviceBatch (gnn/collate.py) with no per-instance host work
+        (where seeded_ragged takes every size; other sizes are solved per size, as in solve_many):
+        one ragged_pack (the only upload of the costs), one ragged feature call (features, top-16, float32
+        costs, mask), the matching of the seeded solve from this pipeline's model, and the ragged oracle duals
+        of that matching as the float32 targets u, v (0 on padded rows).  Raises RuntimeError naming the first
+        instance whose oracle duals fail, with its code."""
+        from .collate import DeviceBatch
+        pack = ragged_pack(costs, self.device)
+        r = row_features_packed(pack, return_topk=True, want_cost32=True)
+        x = self._matching_packed(pack, r)
+        u, v, ret, _ = self.oracle_duals_ragged(pack, x)
+        bad = torch.nonzero(ret).reshape(-1).tolist()
+        if bad:
+            raise RuntimeError(f"training_batch: oracle duals of instance {bad[0]} (n = {pack.host_sizes[bad[0]]}) "
+                               f"failed with code {int(ret[bad[0]])}")
+        return DeviceBatch(cost=r.cost32, u=u.to(torch.float32), v=v.to(torch.float32), row_feat=r.feat,
+                           topk=r.topk, mask=r.mask, sizes=r.sizes)
+
     @torch.inference_mode()
     def solve_batch(self, C: torch.Tensor, eps: float = 1e-12, want_stats: bool = True) -> dict:
         """The whole hot path for a resident batch."""
@@ -229,8 +359,12 @@ class WarmStartPipeline:
         return {"x": x, "y": y, "ret": ret, "stats": stats, "u": u, "v": v}
 
     def _predict_ragged(self, costs):
-        pack = ragged_pack(costs, self.device)
-        r = row_features_packed(pack)
+        return self._predict_packed(ragged_pack(costs, self.device))
+
+    def _predict_packed(self, pack, r=None):
+        """(pack, u_hat, v_hat) of a packed batch; `r`: its row features, where the caller has them already."""
+        if r is None:
+            r = row_features_packed(pack)
         u = self.model(r.feat, mask=r.mask, topk_values=r.topk)["u"].to(torch.float64)
         # OneGNN centres u over the padded width (masked rows included, as the reference's forward does), which
         # shifts every instance shorter than the batch maximum; centred over its own rows an instance gets
@@ -295,7 +429,10 @@ class WarmStartPipeline:
         instance when this pipeline has a threads_hint).
         Returns one dict per instance, in input order: x, y (n_b,) int64, ret, stats, u, v -- the rows of what
         solve_batch returns for a batch of that size."""
-        pack, u, v = self._predict_ragged(costs)
+        return self._solve_packed(*self._predict_ragged(costs), eps, want_stats)
+
+    def _solve_packed(self, pack, u, v, eps=1e-12, want_stats=True):
+        """solve_many behind the prediction: the seeded solves of a packed batch from u, v (B, N) fp64."""
         sizes = pack.host_sizes
         out = [None] * len(sizes)
         # (a threads_hint picks another geometry than the plan the ragged launches are grouped by: per-size path)

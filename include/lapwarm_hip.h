@@ -258,6 +258,26 @@ int lapwarm_oracle_duals_batched(const double *C, int batch, int n, const int *r
                                  double *v, int *ret, int *sweeps, void *workspace, size_t workspace_bytes,
                                  void *stream);
 
+/* lapwarm_oracle_duals_batched of every instance of a ragged batch (C, offsets, sizes, ld, batch, N as above) in
+ * one call.  rows, cols [batch][N] int32: the pairs of instance b, in the caller's order, on the prefix n_b.
+ * u, v [batch][N] fp64: on the prefix what the uniform call writes (NaN for ret 1, 4 and 5), 0 beyond it.
+ * ret [batch]: the codes of lapwarm_oracle_duals_batched, and 6 for an instance that is treated as empty (size
+ * outside 1..N, or wider than ld > 0): it gets no work, u and v all 0, sweeps 0.  sweeps [batch][4] or NULL.
+ * u, v, ret and sweeps of instance b are what lapwarm_oracle_duals_batched gives it alone (batch 1), bit for bit.
+ * One init and one chain of sweep launches for all instances.  The chunk schedule is shared and runs to the
+ * largest budget max_b (n_b - 1), taken from host_sizes [batch], a HOST copy of sizes (an entry the device would
+ * treat as empty counts as 0); every instance keeps its own budget of n_b - 1 sweeps and its own check points on
+ * the device.  As many host synchronisations as one uniform call of size max n_b: NOT graph-capturable.
+ * An instance whose device size is larger than every host size makes only the sweeps of the host's budget; if it
+ * has not settled by then, the last check hands it to the replay (n_b <= 2048: exact u, v and ret, with the
+ * replayed counter set) or reports ret 1 (larger n_b).  Never a fault, and never ret 0 without duals.
+ * Returns 0, -2 (N <= 0, batch outside 1..65535, ld < 0, a NULL pointer other than sweeps), -5 (N > 16384),
+ * -1 (workspace too small), <= -1000 HIP error. */
+size_t lapwarm_oracle_duals_ragged_workspace_bytes(int batch, int N);
+int lapwarm_oracle_duals_ragged(const double *C, const long long *offsets, const int *sizes, const int *host_sizes,
+                                int ld, int batch, int N, const int *rows, const int *cols, double *u, double *v,
+                                int *ret, int *sweeps, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The OneGNN training loss, gnn/train_one_gnn.py:180-226 `compute_loss` with its host greedy
  * `greedy_primal_upper` (:137-177), float32 terms and fp64 sums.  C [batch][n][n] float32, padded to the batch
  * maximum n; sizes [batch] int32 = n_b, the valid rows and columns of instance b are the prefix 0..n_b-1
