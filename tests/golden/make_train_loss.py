@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/train_loss_cases.npz FROM THE REFERENCE.
+"""Generate tests/golden/train_loss_cases.npz and tests/golden/train_loss_large_ref.npz FROM THE REFERENCE.
 
 Runs only where the reference repository exists (REF below).  It loads the reference's gnn/train_one_gnn.py by
 file path (imported, never copied; an empty stand-in module answers its `import h5py`, which only the dataset
@@ -15,6 +15,11 @@ reader uses), calls its `compute_loss` on the CPU with `u_pred.requires_grad_()`
     default sort is unstable and the reference always sorts ties, so this depends on the numpy build; the count
     is printed, not asserted.  (With numpy >= 2 the reference's `sum()` of float32 scalars also stays float32,
     where numpy 1.x promoted it to float64.)
+
+The inputs come from the recipes of tests/train_loss_common.py (uniform_case, integer_case, sparse_inf_case),
+which the GPU tests draw from as well.  train_loss_large_ref.npz holds no inputs: for the two n = 1028 cases of
+tl.LARGE_REF_LABELS it stores the reference's v_proj, dual_lower, feas, u_reg and grad_u, the seed the inputs are
+regenerated from and a CRC32 of their bytes.
 
 It asserts that no valid column of a gradient case has two rows attaining its minimum (the reference's `min`
 backward is unspecified there), and that the reference's float32 sums and grad_u lie within the recursive-summation
@@ -39,6 +44,8 @@ OUT = Path(__file__).resolve().parent / "train_loss_cases.npz"
 
 sys.path.insert(0, str(ROOT / "tests"))
 import train_loss_common as tl  # noqa: E402
+
+OUT_LARGE = tl.LARGE_REF
 
 sys.modules.setdefault("h5py", types.ModuleType("h5py"))
 _spec = importlib.util.spec_from_file_location("_ref_train_one_gnn", str(REF / "gnn" / "train_one_gnn.py"))
@@ -73,35 +80,38 @@ def reference_loss(cost, u_pred, u_target, sizes):
     return out
 
 
-def uniform_case(rng, B, n, sizes):
-    """Costs uniform in [0, 1), u_pred = u_target + noise with |u| up to 4: u + v then rounds more coarsely than
-    C, which leaves the positive hinge residue the loss has to reproduce.  From n = 257 the costs are
-    tl.cost_from_grid(q) of 12-bit integers q, and q is what the file stores, so that it stays small.  Finite
-    rubbish in the padding, which no valid entry may depend on."""
-    if n < 257:
-        cost = rng.random(size=(B, n, n), dtype=np.float32)
-    else:
-        cost = tl.cost_from_grid(rng.integers(0, 1 << 12, size=(B, n, n)).astype(np.uint16))
-    u_target = rng.uniform(-4.0, 4.0, size=(B, n)).astype(np.float32)
-    u_pred = (u_target + 0.05 * rng.standard_normal((B, n))).astype(np.float32)
-    return pad(cost, u_pred, u_target, sizes)
+def check_against_restatement(label, m, got, r):
+    """The assertions every gradient case has to pass: v bit-equal to the restatement, no tied column minimum,
+    the reference's float32 sums and grad_u within the recursive-summation bound of the float64 values."""
+    cost, u_pred, sizes = m["cost"], m["u_pred"], m["sizes"]
+    assert tl.bits_equal32(got["v_proj"], r["v"]), label
+    for b in range(len(sizes)):
+        nb = int(sizes[b])
+        cm = cost[b, :nb, :nb] - u_pred[b, :nb, None]
+        assert ((cm == cm.min(axis=0)).sum(axis=0) == 1).all(), (label, b, "tied column minimum")
+    bound = tl.reference_bounds(r, sizes)
+    assert (np.abs(got["dual_lower"] - r["dual64"]) <= bound["dual"]).all(), label
+    assert (np.abs(got["feas"] - r["feas64"]) <= bound["feas"]).all(), label
+    assert (np.abs(got["u_reg"] - r["ureg64"]) <= bound["ureg"]).all(), label
+    assert (np.abs(got["grad_u"] - r["g64"]) <= bound["grad"]).all(), label
+    assert (r["feas64"][sizes > 2] > 0).all(), (label, "no positive hinge residue")
 
 
-def integer_case(rng, B, n, sizes):
-    """Small-integer costs with integer u: ties in every column and every row."""
-    cost = rng.integers(0, 6, size=(B, n, n)).astype(np.float32)
-    u_target = rng.integers(-2, 3, size=(B, n)).astype(np.float32)
-    u_pred = (u_target + rng.integers(-1, 2, size=(B, n))).astype(np.float32)
-    return pad(cost, u_pred, u_target, sizes)
-
-
-def pad(cost, u_pred, u_target, sizes):
-    for b, nb in enumerate(sizes):
-        cost[b, nb:, :] = -7.0
-        cost[b, :, nb:] = -7.0
-        u_pred[b, nb:] = 3.0
-        u_target[b, nb:] = -3.0
-    return cost, u_pred, u_target
+def write_large():
+    """train_loss_large_ref.npz: recorded results of the reference for the cases of tl.LARGE_REF_LABELS, whose
+    inputs tl.large_case() regenerates; primal_upper is left out (it depends on an unstable sort)."""
+    arrays, meta = {}, []
+    for k, label in enumerate(tl.LARGE_REF_LABELS):
+        m = tl.large_case(label)
+        got = reference_loss(m["cost"], m["u_pred"], m["u_target"], m["sizes"])
+        r = tl.restate(m["cost"], m["u_pred"], m["u_target"], m["sizes"])
+        check_against_restatement(label, m, got, r)
+        meta.append(dict(label=label, kind=m["kind"], B=m["B"], n=m["n"], seed=m["seed"], crc=tl.input_crc(m)))
+        store = dict(ref_v=got["v_proj"], ref_dual=got["dual_lower"], ref_feas=got["feas"], ref_ureg=got["u_reg"],
+                     ref_grad=got["grad_u"])
+        arrays.update({f"c{k}_{name}": a for name, a in store.items()})
+    np.savez_compressed(OUT_LARGE, meta=np.array(json.dumps(meta)), **arrays)
+    print(f"{OUT_LARGE.name}: {len(meta)} cases, {OUT_LARGE.stat().st_size} bytes")
 
 
 def main():
@@ -118,22 +128,12 @@ def main():
     arrays, meta, agree = {}, [], 0
     for k, (kind, label, B, n, sizes) in enumerate(specs):
         sizes = np.asarray(sizes, dtype=np.int32)
-        cost, u_pred, u_target = (uniform_case if kind == "uniform" else integer_case)(rng, B, n, sizes)
+        cost, u_pred, u_target = tl.RECIPES[kind](rng, B, n, sizes)
         got = reference_loss(cost, u_pred, u_target, sizes)
         r = tl.restate(cost, u_pred, u_target, sizes)
         assert tl.bits_equal32(got["v_proj"], r["v"]), label
         if kind == "uniform":
-            for b in range(B):
-                nb = int(sizes[b])
-                cm = cost[b, :nb, :nb] - u_pred[b, :nb, None]
-                assert ((cm == cm.min(axis=0)).sum(axis=0) == 1).all(), (label, b, "tied column minimum")
-            bound = tl.reference_bounds(r, sizes)
-            assert (np.abs(got["dual_lower"] - r["dual64"]) <= bound["dual"]).all(), label
-            assert (np.abs(got["feas"] - r["feas64"]) <= bound["feas"]).all(), label
-            assert (np.abs(got["u_reg"] - r["ureg64"]) <= bound["ureg"]).all(), label
-            assert (np.abs(got["grad_u"] - r["g64"]) <= bound["grad"]).all(), label
-        if kind == "uniform":
-            assert (r["feas64"][sizes > 2] > 0).all(), (label, "no positive hinge residue")
+            check_against_restatement(label, dict(cost=cost, u_pred=u_pred, sizes=sizes), got, r)
         primal_equal = bool(tl.bits_equal32(got["primal_upper"], r["primal_upper"]))
         agree += primal_equal
         meta.append(dict(label=label, kind=kind, B=B, n=n, primal_equal=primal_equal))
@@ -151,3 +151,4 @@ def main():
 
 if __name__ == "__main__":
     main()
+    write_large()

@@ -19,25 +19,43 @@ LABELS = CASES.labels()
 MIXED = LABELS.index("uniform-n65-mixed")
 
 
-def run_abi(m, sizes=None, stream=None, ws=None):
-    """lapwarm_train_loss_forward and _backward on case m; everything back as NumPy arrays."""
+SENTINEL = 0x5AA55AA5  # what run_abi(tail=True) pre-fills every output with, as int32 bits
+
+
+def run_abi(m, sizes=None, stream=None, ws=None, tail=False, cost_offset=0):
+    """lapwarm_train_loss_forward and _backward on case m; everything back as NumPy arrays.
+
+    tail: v, arow, assign and grad get n more elements and terms and ret one more row, everything pre-filled
+    with SENTINEL; the extra elements must come back untouched.  cost_offset: cost starts that many bytes (a
+    multiple of 4) into its allocation."""
     import torch
 
     from lap import _hip
     lib = _hip.require_device()
     dev = torch.device("cuda:0")
     B, n = m["u_pred"].shape
-    cost = torch.from_numpy(m["cost"]).to(dev)
+    assert cost_offset % 4 == 0
+    buf = torch.empty((B * n * n + cost_offset // 4,), dtype=torch.float32, device=dev)
+    cost = buf[cost_offset // 4:].view(B, n, n)
+    cost.copy_(torch.from_numpy(m["cost"]))
+    assert buf.data_ptr() % 16 == 0 and cost.data_ptr() == buf.data_ptr() + cost_offset
     u = torch.from_numpy(m["u_pred"]).to(dev)
     t = torch.from_numpy(m["u_target"]).to(dev)
     sz = torch.from_numpy(np.asarray(m["sizes"] if sizes is None else sizes, dtype=np.int32)).to(dev)
     w = torch.tensor(tl.WEIGHTS, dtype=torch.float32, device=dev)
-    v = torch.empty((B, n), dtype=torch.float32, device=dev)
-    arow = torch.empty((B, n), dtype=torch.int32, device=dev)
-    assign = torch.empty((B, n), dtype=torch.int32, device=dev)
-    terms = torch.empty((B, 4), dtype=torch.float32, device=dev)
-    ret = torch.empty((B,), dtype=torch.int32, device=dev)
-    grad = torch.empty((B, n), dtype=torch.float32, device=dev)
+
+    def output(count, extra, dtype):
+        if not tail:
+            return torch.empty((count,), dtype=dtype, device=dev)
+        return torch.full((count + extra,), SENTINEL, dtype=torch.int32, device=dev).view(dtype)
+
+    flat = dict(v=output(B * n, n, torch.float32), arow=output(B * n, n, torch.int32),
+                assign=output(B * n, n, torch.int32), terms=output(B * 4, 4, torch.float32),
+                ret=output(B, 1, torch.int32), grad=output(B * n, n, torch.float32))
+    counts = dict(v=B * n, arow=B * n, assign=B * n, terms=B * 4, ret=B, grad=B * n)
+    shapes = dict(v=(B, n), arow=(B, n), assign=(B, n), terms=(B, 4), ret=(B,), grad=(B, n))
+    v, arow, assign, terms, ret, grad = (flat[k][:counts[k]].view(shapes[k])
+                                         for k in ("v", "arow", "assign", "terms", "ret", "grad"))
     nbytes = int(lib.lapwarm_train_loss_workspace_bytes(B, n))
     assert nbytes > 0
     if ws is None:
@@ -53,6 +71,10 @@ def run_abi(m, sizes=None, stream=None, ws=None):
                                          grad.data_ptr(), ws.data_ptr(), ws.numel(), ct.c_void_p(s.cuda_stream))
     assert rc == 0, (rc, _hip.last_error())
     s.synchronize()
+    if tail:
+        for key, x in flat.items():
+            beyond = x[counts[key]:].view(torch.int32).cpu().numpy()
+            assert (beyond == SENTINEL).all(), (key, "written beyond its end at", np.flatnonzero(beyond != SENTINEL)[:8])
     out = dict(v=v, arow=arow, assign=assign, terms=terms, ret=ret, grad=grad)
     out = {k: x.cpu().numpy() for k, x in out.items()}
     out["ws"] = ws

@@ -1,6 +1,8 @@
 """The training-loss fixtures (tests/golden/train_loss_cases.npz, written from the reference by
 tests/golden/make_train_loss.py) against the NumPy restatement of train_loss_common.py, the C header and the
-argument checks of gnn.losses.  No GPU."""
+argument checks of gnn.losses; and the restatement at n = 1028, on inputs regenerated from their seeds, against the
+reference's recorded results in tests/golden/train_loss_large_ref.npz.  No GPU."""
+import json
 import re
 from pathlib import Path
 
@@ -56,6 +58,53 @@ def test_reference_sums_and_gradient_within_the_summation_bound(k):
     # the reference's gradient is 0 on padded rows, and so is the closed form
     for b, nb in enumerate(m["sizes"]):
         assert (m["ref_grad"][b, nb:] == 0).all() and (r["g64"][b, nb:] == 0).all()
+
+
+def test_large_specs_reach_the_paths_they_are_there_for():
+    """The shapes of the cases above n = 1024, restated from csrc/train_loss.hip's launch arithmetic."""
+    def plan(B, n):
+        rows = max(1, -(-n * B // 8192))
+        p2 = 1 << (n - 1).bit_length()
+        return dict(rows_per_wave=rows, hparts=-(-n // (rows * 4)) * 4, p2=p2, lds=8 * p2 + 4 * -(-n // 32))
+    spec = tl.LARGE_SPECS
+    assert plan(8, 1025)["rows_per_wave"] == 2 and plan(8, 1028)["rows_per_wave"] == 2
+    assert plan(3, 4100)["rows_per_wave"] == 2 and plan(128, 65)["rows_per_wave"] == 2
+    one = plan(1, 4097)
+    assert one == dict(rows_per_wave=1, hparts=4100, p2=8192, lds=66052)
+    assert spec["uniform-n4097-B1"][2:4] == (1, 4097) and spec["uniform-n4100-mixed"][2:4] == (3, 4100)
+    assert spec["uniform-n1028-mixed"][4] == [1028, 1025, 1, 513, 1024, 64, 1027, 1000]
+    assert spec["uniform-n4100-mixed"][4] == [4100, 4097, 2049]
+    assert len({s[1] for s in spec.values()}) == len(spec)  # a seed of its own each
+    for label in tl.LARGE_REF_LABELS:
+        assert spec[label][2:] == (2, 1028, [1028, 1025])
+
+
+@pytest.mark.parametrize("label", tl.LARGE_REF_LABELS)
+def test_restatement_against_the_reference_at_n1028(label):
+    """restate() is the expected value of every test of test_gpu_train_loss_large.py: here it meets what the
+    reference computed at n = 1028, uniform and with isolated +inf entries."""
+    z = np.load(tl.LARGE_REF, allow_pickle=False)
+    meta = json.loads(str(z["meta"]))
+    k = [m["label"] for m in meta].index(label)
+    m = tl.large_case(label)
+    assert meta[k]["seed"] == m["seed"] and (meta[k]["B"], meta[k]["n"]) == m["u_pred"].shape
+    assert tl.input_crc(m) == meta[k]["crc"], (
+        "the regenerated inputs differ from the ones the fixture was recorded on: this NumPy's random stream "
+        f"(numpy {np.__version__}) differs, not the kernel or the restatement")
+    if m["kind"] == "inf":
+        frac = np.mean([np.isinf(m["cost"][b, :nb, :nb]).mean() for b, nb in enumerate(m["sizes"])])
+        assert 0.09 < frac < 0.11
+    r = tl.restate(m["cost"], m["u_pred"], m["u_target"], m["sizes"])
+    assert tl.bits_equal32(r["v"], z[f"c{k}_ref_v"])
+    bound = tl.reference_bounds(r, m["sizes"])
+    assert (np.abs(z[f"c{k}_ref_dual"] - r["dual64"]) <= bound["dual"]).all()
+    assert (np.abs(z[f"c{k}_ref_feas"] - r["feas64"]) <= bound["feas"]).all()
+    assert (np.abs(z[f"c{k}_ref_ureg"] - r["ureg64"]) <= bound["ureg"]).all()
+    assert (np.abs(z[f"c{k}_ref_grad"] - r["g64"]) <= bound["grad"]).all()
+    assert np.isfinite(r["v"]).all() and np.isfinite(r["g64"]).all() and (r["feas64"] > 0).all()
+    for b, nb in enumerate(m["sizes"]):
+        assert (z[f"c{k}_ref_grad"][b, nb:] == 0).all() and (r["g64"][b, nb:] == 0).all()
+        assert sorted(r["assign"][b, :nb].tolist()) == list(range(nb))
 
 
 def test_integer_cases_are_tied():

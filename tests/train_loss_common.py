@@ -1,5 +1,10 @@
-"""Reader of tests/golden/train_loss_cases.npz and a NumPy restatement of the OneGNN training loss (shared by
-tests/golden/make_train_loss.py, test_train_loss_fixtures.py and test_gpu_train_loss.py).
+"""Reader of tests/golden/train_loss_cases.npz, the input recipes of the training-loss cases and a NumPy
+restatement of the OneGNN training loss (shared by tests/golden/make_train_loss.py, test_train_loss_fixtures.py,
+test_gpu_train_loss.py and test_gpu_train_loss_large.py).
+
+The cases above n = 257 are never stored: large_case() regenerates them from np.random.default_rng(seed) with
+the fixed seeds of LARGE_SPECS, and tests/golden/train_loss_large_ref.npz holds, for two of them, what the
+reference computed and a CRC32 of the input bytes.
 
 The restatement is written from the definition of the loss, not from the reference's code.  Per instance with
 n_b valid rows and columns (a prefix of the padded matrix), all terms float32:
@@ -12,11 +17,13 @@ n_b valid rows and columns (a prefix of the padded matrix), all terms float32:
     g_i = (1/B) [ w0 (cnt_i - 1) + w1 (R_i - sum_{a_j = i} K_j) / n_b^2 + w2 2 (u_i - t_i) / n_b ]
 """
 import json
+import zlib
 from pathlib import Path
 
 import numpy as np
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "train_loss_cases.npz"
+LARGE_REF = Path(__file__).resolve().parent / "golden" / "train_loss_large_ref.npz"
 WEIGHTS = (1.0, 1.0, 0.1)
 F32_EPS = 2.0 ** -24  # unit roundoff of float32
 GRID_SCALE = np.float32(0.7310586)  # no power of two: the products below use the whole mantissa
@@ -31,6 +38,84 @@ def grid_from_cost(cost):
     q = np.rint(cost.astype(np.float64) / float(GRID_SCALE) * 4096).astype(np.uint16)
     assert np.array_equal(cost_from_grid(q).view(np.int32), np.ascontiguousarray(cost).view(np.int32))
     return q
+
+
+def uniform_case(rng, B, n, sizes):
+    """Costs uniform in [0, 1), u_pred = u_target + noise with |u| up to 4: u + v then rounds more coarsely than
+    C, which leaves the positive hinge residue the loss has to reproduce.  From n = 257 the costs are
+    cost_from_grid(q) of 12-bit integers q, and q is what the golden file stores, so that it stays small.
+    Finite rubbish in the padding, which no valid entry may depend on."""
+    if n < 257:
+        cost = rng.random(size=(B, n, n), dtype=np.float32)
+    else:
+        cost = cost_from_grid(rng.integers(0, 1 << 12, size=(B, n, n)).astype(np.uint16))
+    u_target = rng.uniform(-4.0, 4.0, size=(B, n)).astype(np.float32)
+    u_pred = (u_target + 0.05 * rng.standard_normal((B, n))).astype(np.float32)
+    return pad(cost, u_pred, u_target, sizes)
+
+
+def integer_case(rng, B, n, sizes):
+    """Small-integer costs with integer u: ties in every column and every row."""
+    cost = rng.integers(0, 6, size=(B, n, n)).astype(np.float32)
+    u_target = rng.integers(-2, 3, size=(B, n)).astype(np.float32)
+    u_pred = (u_target + rng.integers(-1, 2, size=(B, n))).astype(np.float32)
+    return pad(cost, u_pred, u_target, sizes)
+
+
+def sparse_inf_case(rng, B, n, sizes):
+    """uniform_case on the grid with about 10 % of the entries +inf.  Every valid row and every valid column
+    keeps a finite entry, so v stays finite and no inf - inf arises; the padding stays finite."""
+    assert n >= 257
+    cost, u_pred, u_target = uniform_case(rng, B, n, sizes)
+    cost[rng.random(size=(B, n, n)) < 0.1] = np.inf
+    pad(cost, u_pred, u_target, sizes)
+    for b, nb in enumerate(sizes):
+        finite = np.isfinite(cost[b, :nb, :nb])
+        assert finite.any(axis=0).all() and finite.any(axis=1).all(), (b, "a row or column of +inf")
+        assert not finite.all()
+    return cost, u_pred, u_target
+
+
+def pad(cost, u_pred, u_target, sizes):
+    for b, nb in enumerate(sizes):
+        cost[b, nb:, :] = -7.0
+        cost[b, :, nb:] = -7.0
+        u_pred[b, nb:] = 3.0
+        u_target[b, nb:] = -3.0
+    return cost, u_pred, u_target
+
+
+RECIPES = dict(uniform=uniform_case, integer=integer_case, inf=sparse_inf_case)
+
+# label -> (recipe, seed, B, n, sizes): the cases above n = 257, regenerated where they are needed
+LARGE_SPECS = {
+    "uniform-n1025-B8": ("uniform", 2024110101, 8, 1025, [1025] * 8),
+    "uniform-n1028-mixed": ("uniform", 2024110102, 8, 1028, [1028, 1025, 1, 513, 1024, 64, 1027, 1000]),
+    "uniform-n4097-B1": ("uniform", 2024110103, 1, 4097, [4097]),
+    "uniform-n4100-mixed": ("uniform", 2024110104, 3, 4100, [4100, 4097, 2049]),
+    "integer-n1025-B2": ("integer", 2024110105, 2, 1025, [1025, 1024]),
+    "inf-n1028-B2": ("inf", 2024110106, 2, 1028, [1028, 1025]),
+    "uniform-n1028-B2": ("uniform", 2024110107, 2, 1028, [1028, 1025]),
+}
+LARGE_REF_LABELS = ("uniform-n1028-B2", "inf-n1028-B2")  # the cases train_loss_large_ref.npz covers
+
+
+def large_case(label):
+    """The inputs of LARGE_SPECS[label], drawn afresh from the case's own seed."""
+    kind, seed, B, n, sizes = LARGE_SPECS[label]
+    sizes = np.asarray(sizes, dtype=np.int32)
+    cost, u_pred, u_target = RECIPES[kind](np.random.default_rng(seed), B, n, sizes)
+    return dict(label=label, kind=kind, seed=seed, B=B, n=n, cost=cost, u_pred=u_pred, u_target=u_target,
+                sizes=sizes)
+
+
+def input_crc(m):
+    """CRC32 over the bytes of cost, u_pred, u_target and sizes: tells a different NumPy random stream from a
+    different result."""
+    crc = 0
+    for key in ("cost", "u_pred", "u_target", "sizes"):
+        crc = zlib.crc32(np.ascontiguousarray(m[key]).tobytes(), crc)
+    return crc
 
 
 def restate_instance(C, u, t, nb, batch, weights=WEIGHTS):
