@@ -18,6 +18,7 @@
 #include "onegnn_refine.hpp"
 #include "oracle_duals.hpp"
 #include "ragged_batch.hpp"
+#include "ragged_duals.hpp"
 #include "solve_plan.hpp"
 #include "train_loss.hpp"
 
@@ -733,6 +734,94 @@ int lapwarm_reduce_costs_batched(const double *C, int batch, int n, const double
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     HIP_TRY(launch_reduced_min(C, n, batch, u, v, sweep_layout(workspace, batch, n).rowpart, gmin, stream));
     HIP_TRY(launch_reduce_costs(C, n, batch, u, v, gmin, shift_nonneg, out, stream));
+    return 0;
+}
+
+// ---- dual utilities of a ragged batch (ragged_duals.hip) ----
+static RaggedDualsWs ragged_duals_layout(void *workspace, int batch, int N, size_t *bytes)
+{
+    Carver c{reinterpret_cast<unsigned char *>(workspace), 0};
+    RaggedDualsWs w;
+    w.part = c.take<double>((size_t)batch * N);
+    w.done = c.take<int>(batch);
+    w.running = c.take<int>(1);
+    *bytes = c.off;
+    return w;
+}
+
+size_t lapwarm_ragged_duals_workspace_bytes(int batch, int N)
+{
+    if (N <= 0 || batch <= 0 || batch > 65535 || N > 16384) return 0;
+    size_t bytes = 0;
+    ragged_duals_layout(nullptr, batch, N, &bytes);
+    return bytes;
+}
+
+static int check_ragged_duals_ws(const void *workspace, size_t workspace_bytes, int batch, int N)
+{
+    if (!workspace) return -2;
+    const size_t need = lapwarm_ragged_duals_workspace_bytes(batch, N);
+    if (workspace_bytes < need) {
+        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, need);
+        return -1;
+    }
+    return 0;
+}
+
+int lapwarm_rowmin_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                          const double *v, double *out, int *ret, void *workspace, size_t workspace_bytes,
+                          void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!out) return -2;
+    if (int rc = check_ragged_duals_ws(workspace, workspace_bytes, batch, N)) return rc;
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    HIP_TRY(launch_rowmin_ragged(g, v, out, ret, reinterpret_cast<hipStream_t>(stream_)));
+    return 0;
+}
+
+// The rounds are launched in chunks (1, then 2, 4, ... 32 at a time) up to max(1, max_rounds), with one host
+// synchronisation after each chunk but the last to learn whether any instance still runs: almost every call on
+// finite costs ends with the first.  Not graph-capturable.
+int lapwarm_project_feasible_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch,
+                                    int N, double *u, double *v, int max_rounds, double tol, double *gmin,
+                                    int *rounds, int *ret, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!u || !v || !gmin || !rounds || !ret) return -2;
+    if (int rc = check_ragged_duals_ws(workspace, workspace_bytes, batch, N)) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    size_t bytes = 0;
+    const RaggedDualsWs w = ragged_duals_layout(workspace, batch, N, &bytes);
+    HIP_TRY(launch_project_init_ragged(g, w, u, v, gmin, rounds, ret, stream));
+    const int total = (max_rounds < 1) ? 1 : max_rounds;  // max(1, int(max_rounds)), advanced_dual.py:28
+    int r = 0, chunk = 1;
+    for (;;) {
+        const int k = (chunk < total - r) ? chunk : total - r;
+        for (int t = 0; t < k; ++t, ++r) HIP_TRY(launch_project_round_ragged(g, w, u, v, tol, gmin, rounds, stream));
+        if (r >= total) break;
+        int host_running = 0;
+        HIP_TRY(hipMemcpyAsync(&host_running, w.running, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (host_running == 0) break;
+        if (chunk < 32) chunk *= 2;
+    }
+    return 0;
+}
+
+int lapwarm_reduce_costs_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                const double *u, const double *v, int shift_nonneg, double *out, double *gmin,
+                                int *ret, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!u || !v || !gmin) return -2;
+    if (int rc = check_ragged_duals_ws(workspace, workspace_bytes, batch, N)) return rc;
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    size_t bytes = 0;
+    const RaggedDualsWs w = ragged_duals_layout(workspace, batch, N, &bytes);
+    HIP_TRY(launch_reduce_costs_ragged(g, w, u, v, shift_nonneg, out, gmin, ret,
+                                       reinterpret_cast<hipStream_t>(stream_)));
     return 0;
 }
 

@@ -8,7 +8,7 @@ importable names that raise NotImplementedError when USED, so that the harness' 
 succeeds and its OneGNN branch runs; a DualGNN checkpoint is reported, not silently mishandled."""
 from .collate import DeviceBatch, collate_device
 from .features import (compute_row_features, compute_row_features_torch, positional_encodings, ragged_pack,
-                       RaggedPack, ROW_FEATURE_DIM)
+                       RaggedPack, ROW_FEATURE_DIM, row_min_ragged)
 from .one_gnn import OneGNN, ResidualBlock
 from .pipeline import GNNPredictor, WarmStartPipeline, load_checkpoint
 
@@ -27,4 +27,5 @@ def compute_features(*args, **kwargs):
 
 __all__ = ["OneGNN", "ResidualBlock", "DualGNN", "compute_features", "compute_row_features",
            "compute_row_features_torch", "positional_encodings", "ROW_FEATURE_DIM", "GNNPredictor",
-           "WarmStartPipeline", "load_checkpoint", "collate_device", "DeviceBatch", "ragged_pack", "RaggedPack"]
+           "WarmStartPipeline", "load_checkpoint", "collate_device", "DeviceBatch", "ragged_pack", "RaggedPack",
+           "row_min_ragged"]

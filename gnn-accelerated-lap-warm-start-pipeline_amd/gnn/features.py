@@ -281,6 +281,49 @@ def min_trick_ragged(pack: RaggedPack, u=None):
     return v
 
 
+def _check_pack_vector(pack, name, t, optional=False):
+    """Argument errors of a (B, N) fp64 device vector of a packed batch: type and dtype, then shape, then device."""
+    import torch
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"Argument '{name}' must be a torch.Tensor, not {type(t).__name__}")
+    if t.dtype != torch.float64:
+        raise TypeError(f"{name} must be torch.float64, not {t.dtype}")
+    B, N = len(pack.host_sizes), pack.N
+    if tuple(t.shape) != (B, N) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous ({B}, {N}) tensor, not {tuple(t.shape)}")
+    if t.device != pack.C.device:
+        raise ValueError(f"{name} must be on {pack.C.device} like the packed costs, not {t.device}")
+
+
+def ragged_duals_workspace(pack):
+    """The workspace of one call of the ragged dual utilities (lapwarm_ragged_duals_workspace_bytes)."""
+    import torch
+    nbytes = int(_hip.load().lapwarm_ragged_duals_workspace_bytes(len(pack.host_sizes), pack.N))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=pack.C.device), nbytes
+
+
+def row_min_ragged(pack: RaggedPack, v=None):
+    """out (B, N) f64 with out[b][i] = min_{j < n_b} (C_b[i][j] - v[b][j]) and 0 beyond n_b; v (B, N) f64 on the
+    device, or None for the plain row minima.  One kernel on the current torch stream."""
+    import torch
+    if not isinstance(pack, RaggedPack):
+        raise TypeError(f"Argument 'pack' must be a RaggedPack, not {type(pack).__name__}")
+    _check_pack_vector(pack, "v", v, optional=True)
+    lib = _hip.require_device()
+    B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
+    out = torch.empty((B, N), dtype=torch.float64, device=dev)
+    ws, ws_bytes = ragged_duals_workspace(pack)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.lapwarm_rowmin_ragged(pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), pack.ld, B, N,
+                                   v.data_ptr() if v is not None else None, out.data_ptr(), None, ws.data_ptr(),
+                                   ws_bytes, ct.c_void_p(stream))
+    if _hip.check(rc, "row_min_ragged") != 0:
+        raise RuntimeError(f"row_min_ragged failed (code {rc})")
+    return out
+
+
 def compute_row_features_torch(cost):
     """Device-resident variant: CUDA tensor (n, n) of any float dtype -> (n, 21) float32 on the
     same device.  float32 inputs are widened exactly to float64 before the sweep."""

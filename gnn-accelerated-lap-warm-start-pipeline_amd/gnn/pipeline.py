@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from lap import _hip
-from .features import (ROW_FEATURE_DIM, RaggedPack, min_trick_device, min_trick_ragged, ragged_pack,
-                       row_features_device, row_features_packed)
+from .features import (ROW_FEATURE_DIM, RaggedPack, _check_pack_vector, min_trick_device, min_trick_ragged,
+                       ragged_pack, row_features_device, row_features_packed, row_min_ragged)
 from .one_gnn import OneGNN
 
 STATS_FIELDS = ("branch", "tight_edges", "free_rows", "arr_fired", "paths", "finds", "scan_steps",
@@ -57,6 +57,32 @@ def load_checkpoint(path, device="cpu") -> Tuple[OneGNN, dict]:
     model.load_state_dict(state)
     model.to(device).eval()
     return model, info
+
+
+def _check_rounds(value, name):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"Argument '{name}' must be an int, not {type(value).__name__}")
+    if not -2**31 <= value < 2**31:
+        raise ValueError(f"{name} must fit an int32, not {value}")
+    return int(value)
+
+
+def _check_real(value, name):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise TypeError(f"Argument '{name}' must be a float, not {type(value).__name__}")
+    return float(value)
+
+
+def _check_noise_args(std, prob, generator, names):
+    """(std, prob) as floats: types first, then values; `generator` a torch.Generator or None."""
+    std, prob = _check_real(std, names[0]), _check_real(prob, names[1])
+    if generator is not None and not isinstance(generator, torch.Generator):
+        raise TypeError(f"Argument 'generator' must be a torch.Generator, not {type(generator).__name__}")
+    if not std >= 0.0:
+        raise ValueError(f"{names[0]} must be >= 0, not {std}")
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"{names[1]} must be in [0, 1], not {prob}")
+    return std, prob
 
 
 class RaggedDuals(Sequence):
@@ -332,14 +358,20 @@ class WarmStartPipeline:
         u, v, ret, sweeps = self.oracle_duals_ragged(pack, xd)
         return RaggedDuals(xd, u, v, ret, sweeps, host_sizes)
 
-    def training_batch(self, costs):
+    def training_batch(self, costs, dual_noise_std: float = 0.0, dual_noise_prob: float = 0.0, generator=None):
         """costs of different sizes -> a labelled DeviceBatch (gnn/collate.py) with no per-instance host work
         (where seeded_ragged takes every size; other sizes are solved per size, as in solve_many):
         one ragged_pack (the only upload of the costs), one ragged feature call (features, top-16, float32
         costs, mask), the matching of the seeded solve from this pipeline's model, and the ragged oracle duals
         of that matching as the float32 targets u, v (0 on padded rows).  Raises RuntimeError naming the first
-        instance whose oracle duals fail, with its code."""
+        instance whose oracle duals fail, with its code.
+        dual_noise_prob > 0 with dual_noise_std > 0 is the noisy-label recipe of the reference's data generator
+        (data/generators.py:131-135) on the device: with that probability an instance's fp64 duals get N(0,
+        dual_noise_std) noise and are projected back to feasibility in 75 rounds at most (noisy_duals_ragged, with
+        `generator`); only u and v of the batch differ.  With the defaults nothing is added to the clean path."""
         from .collate import DeviceBatch
+        dual_noise_std, dual_noise_prob = _check_noise_args(dual_noise_std, dual_noise_prob, generator,
+                                                            ("dual_noise_std", "dual_noise_prob"))
         pack = ragged_pack(costs, self.device)
         r = row_features_packed(pack, return_topk=True, want_cost32=True)
         x = self._matching_packed(pack, r)
@@ -348,8 +380,124 @@ class WarmStartPipeline:
         if bad:
             raise RuntimeError(f"training_batch: oracle duals of instance {bad[0]} (n = {pack.host_sizes[bad[0]]}) "
                                f"failed with code {int(ret[bad[0]])}")
+        if dual_noise_prob > 0.0 and dual_noise_std > 0.0:
+            u, v, _ = self.noisy_duals_ragged(pack, u, v, dual_noise_std, generator=generator, prob=dual_noise_prob)
         return DeviceBatch(cost=r.cost32, u=u.to(torch.float32), v=v.to(torch.float32), row_feat=r.feat,
                            topk=r.topk, mask=r.mask, sizes=r.sizes)
+
+    # ---- dual utilities of a ragged batch (csrc/ragged_duals.hip): solvers/advanced_dual.py:14-63 and the
+    # classical seeds of solvers/seed_baselines.py for every instance of a pack in one call each
+    def _check_duals_args(self, pack, u, v):
+        """Argument errors, raised before any device work: types and dtypes, then shapes, then devices."""
+        if not isinstance(pack, RaggedPack):
+            raise TypeError(f"Argument 'pack' must be a RaggedPack, not {type(pack).__name__}")
+        if pack.C.dtype != torch.float64:
+            raise TypeError(f"the packed costs must be torch.float64, not {pack.C.dtype}")
+        _check_pack_vector(pack, "u", u)
+        _check_pack_vector(pack, "v", v)
+        return len(pack.host_sizes), pack.N, pack.C.device
+
+    def _duals_workspace(self, B, N):
+        return self._cached_workspace(("ragged_duals", B, N),
+                                      lambda: self.lib.lapwarm_ragged_duals_workspace_bytes(B, N))
+
+    def _project_ragged(self, pack, sizes, u, v, max_rounds, tol):
+        """lapwarm_project_feasible_ragged on u, v in place; `sizes` (B,) int32 on the device is pack.sizes, or a
+        copy with 0 for the instances to leave out."""
+        B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
+        gmin = torch.empty((B,), dtype=torch.float64, device=dev)
+        rounds = torch.empty((B,), dtype=torch.int32, device=dev)
+        ret = torch.empty((B,), dtype=torch.int32, device=dev)
+        ws, nbytes = self._duals_workspace(B, N)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lapwarm_project_feasible_ragged(
+            pack.C.data_ptr(), pack.offsets.data_ptr(), sizes.data_ptr(), pack.ld, B, N, u.data_ptr(), v.data_ptr(),
+            int(max_rounds), float(tol), gmin.data_ptr(), rounds.data_ptr(), ret.data_ptr(), ws.data_ptr(), nbytes,
+            ct.c_void_p(stream))
+        if _hip.check(rc, "project_feasible_ragged") != 0:
+            raise RuntimeError(f"lapwarm_project_feasible_ragged failed (code {rc}): {_hip.last_error()}")
+        return u, v, gmin, rounds, ret
+
+    def project_feasible_ragged(self, pack: RaggedPack, u: torch.Tensor, v: torch.Tensor, max_rounds: int = 50,
+                                tol: float = 1e-12):
+        """project_feasible (solvers/advanced_dual.py:14-36) of every instance of a ragged batch in one call.
+        u, v (B, N) fp64 on the device of the pack, read on each prefix and left as they are.  Returns new u, v
+        (B, N) fp64 (0 beyond n_b), gmin (B,) fp64 the last min((C - u) - v), rounds (B,) int32 the rounds each
+        instance ran (it stops on its own, on the device) and ret (B,) int32 (0; 2 for a size the device treats
+        as empty).  Row b is, bit for bit, what solvers.project_feasible gives instance b alone.  Synchronises
+        the stream once per chunk of rounds after the first round (not graph-capturable when max_rounds > 1)."""
+        self._check_duals_args(pack, u, v)
+        max_rounds, tol = _check_rounds(max_rounds, "max_rounds"), _check_real(tol, "tol")
+        return self._project_ragged(pack, pack.sizes, u.clone(), v.clone(), max_rounds, tol)
+
+    def reduce_costs_ragged(self, pack: RaggedPack, u: torch.Tensor, v: torch.Tensor, shift_nonneg: bool = True,
+                            want_matrix: bool = True):
+        """reduce_costs (solvers/advanced_dual.py:39-53) of every instance of a ragged batch: returns (out, gmin,
+        ret).  out, a tensor like pack.C (the same offsets and row stride; 0 in the padding of a padded layout),
+        holds (C - u) - v of every instance, minus its minimum where shift_nonneg and that is negative; None
+        without want_matrix.  gmin (B,) fp64 is the unshifted minimum, ret (B,) int32 0 or 2.  Bit for bit
+        solvers.reduce_costs per instance.  Kernels on the current stream only."""
+        B, N, dev = self._check_duals_args(pack, u, v)
+        out = None
+        if want_matrix:
+            out = torch.empty_like(pack.C) if pack.ld == 0 else torch.zeros_like(pack.C)
+        gmin = torch.empty((B,), dtype=torch.float64, device=dev)
+        ret = torch.empty((B,), dtype=torch.int32, device=dev)
+        ws, nbytes = self._duals_workspace(B, N)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lapwarm_reduce_costs_ragged(
+            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), pack.ld, B, N, u.data_ptr(),
+            v.data_ptr(), int(bool(shift_nonneg)), out.data_ptr() if want_matrix else None, gmin.data_ptr(),
+            ret.data_ptr(), ws.data_ptr(), nbytes, ct.c_void_p(stream))
+        if _hip.check(rc, "reduce_costs_ragged") != 0:
+            raise RuntimeError(f"lapwarm_reduce_costs_ragged failed (code {rc}): {_hip.last_error()}")
+        return out, gmin, ret
+
+    def dual_feasible_ragged(self, pack: RaggedPack, u: torch.Tensor, v: torch.Tensor, tol: float = 1e-8):
+        """check_dual_feasible (solvers/advanced_dual.py:56-63) of every instance: a (B,) bool tensor on the
+        device, False where the reference raises (min((C - u) - v) < -tol; NaN passes, as it does there).  It
+        does not raise and nothing is read back."""
+        self._check_duals_args(pack, u, v)
+        tol = _check_real(tol, "tol")
+        _, gmin, _ = self.reduce_costs_ragged(pack, u, v, shift_nonneg=False, want_matrix=False)
+        return ~(gmin < -tol)
+
+    def seed_row_col_minima_ragged(self, pack: RaggedPack, project_rounds: int = 50):
+        """seed_row_col_minima (solvers/seed_baselines.py:18-37) of every instance: the row minima, the ragged
+        min-trick of them, then the ragged projection.  Returns what project_feasible_ragged returns."""
+        if not isinstance(pack, RaggedPack):
+            raise TypeError(f"Argument 'pack' must be a RaggedPack, not {type(pack).__name__}")
+        project_rounds = _check_rounds(project_rounds, "project_rounds")
+        u = row_min_ragged(pack)
+        v = min_trick_ragged(pack, u)
+        return self._project_ragged(pack, pack.sizes, u, v, project_rounds, 1e-12)
+
+    def noisy_duals_ragged(self, pack: RaggedPack, u: torch.Tensor, v: torch.Tensor, noise_std: float,
+                           project_rounds: int = 75, generator=None, prob: float = 1.0):
+        """Perturbed and re-projected duals of a ragged batch (solvers/seed_baselines.py:91-110; with `prob` the
+        recipe of data/generators.py:131-135), on the device.  One Bernoulli draw per instance with `prob`
+        decides whether it is perturbed; a perturbed instance gets u + N(0, noise_std), v + N(0, noise_std)
+        (fp64 torch.randn on the device, from `generator`, used on its prefix) and then the ragged projection,
+        in which the other instances take no part: they keep u, v bit for bit.  The draws are (B, N) normals
+        for u, (B, N) for v, then (B,) uniforms, in that order, whatever `prob` is.  Returns u, v (B, N) fp64
+        and the (B,) bool tensor of perturbed instances; the inputs are left as they are."""
+        B, N, dev = self._check_duals_args(pack, u, v)
+        noise_std, prob = _check_noise_args(noise_std, prob, generator, ("noise_std", "prob"))
+        project_rounds = _check_rounds(project_rounds, "project_rounds")
+        if generator is not None and generator.device.type != dev.type:
+            raise ValueError(f"generator must be on {dev} like the packed costs, not {generator.device}")
+        nu = torch.randn((B, N), dtype=torch.float64, device=dev, generator=generator)
+        nv = torch.randn((B, N), dtype=torch.float64, device=dev, generator=generator)
+        hit = torch.rand((B,), dtype=torch.float64, device=dev, generator=generator) < prob
+        prefix = torch.arange(N, device=dev).unsqueeze(0) < pack.sizes.unsqueeze(1)
+        take = prefix & hit.unsqueeze(1)
+        un = torch.where(take, u + noise_std * nu, u).contiguous()
+        vn = torch.where(take, v + noise_std * nv, v).contiguous()
+        # an instance that is not perturbed is given size 0: the projection treats it as empty and gives it no work
+        sizes = torch.where(hit, pack.sizes, torch.zeros_like(pack.sizes)).contiguous()
+        self._project_ragged(pack, sizes, un, vn, project_rounds, 1e-12)
+        keep = ~hit.unsqueeze(1)
+        return torch.where(keep, u, un), torch.where(keep, v, vn), hit
 
     @torch.inference_mode()
     def solve_batch(self, C: torch.Tensor, eps: float = 1e-12, want_stats: bool = True) -> dict:
@@ -518,6 +666,18 @@ class WarmStartPipeline:
         s_pred.synchronize()
         s_solve.synchronize()
         self._pending = None
+
+
+_shared = {}
+
+
+def shared_pipeline(device="cuda:0") -> WarmStartPipeline:
+    """One WarmStartPipeline per process and device for callers that need its entries and workspaces but not a
+    trained model (the NumPy-facing helpers of `solvers`): built on first use, with an untrained OneGNN."""
+    key = str(torch.device(device))
+    if key not in _shared:
+        _shared[key] = WarmStartPipeline(OneGNN(ROW_FEATURE_DIM), device)
+    return _shared[key]
 
 
 class GNNPredictor:

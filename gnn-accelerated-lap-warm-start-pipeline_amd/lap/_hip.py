@@ -70,6 +70,14 @@ SIGNATURES = {
     "lapwarm_oracle_duals_ragged_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
     "lapwarm_oracle_duals_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_ip, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp,
                                                c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_ragged_duals_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_rowmin_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
+                                         ct.c_size_t, c_vp]),
+    "lapwarm_project_feasible_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp,
+                                                   ct.c_int, ct.c_double, c_vp, c_vp, c_vp, c_vp, ct.c_size_t,
+                                                   c_vp]),
+    "lapwarm_reduce_costs_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, ct.c_int,
+                                               c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
     "lapwarm_train_loss_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
     "lapwarm_train_loss_forward": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                               c_vp, c_vp, ct.c_size_t, c_vp]),

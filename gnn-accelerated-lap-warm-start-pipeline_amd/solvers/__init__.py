@@ -15,10 +15,12 @@ from .lap_solver import LAPSolver, SeededLAPSolver
 from .warmstart_solver import WarmStartLAPSolver
 from .timing import time_solver_rigorous
 from .advanced_dual import (project_feasible, reduce_costs, check_dual_feasible, check_dual_and_match,
-                            make_feasible_duals)
+                            make_feasible_duals, project_feasible_many, reduce_costs_many,
+                            check_dual_feasible_many)
 from .dual_computation import compute_oracle_duals, dual_from_matching_diff_constraints
 from .verification import verify_solver_correctness
-from .seed_baselines import seed_row_col_minima, seed_noisy_optimal
+from .seed_baselines import (seed_row_col_minima, seed_noisy_optimal, seed_row_col_minima_many,
+                             seed_noisy_optimal_many)
 from .generators import (
     generate_uniform_costs,
     generate_near_diagonal_costs,
@@ -36,6 +38,8 @@ __all__ = [
     "project_feasible", "reduce_costs", "check_dual_feasible", "check_dual_and_match", "make_feasible_duals",
     "compute_oracle_duals", "dual_from_matching_diff_constraints", "verify_solver_correctness",
     "seed_row_col_minima", "seed_noisy_optimal",
+    "project_feasible_many", "reduce_costs_many", "check_dual_feasible_many",
+    "seed_row_col_minima_many", "seed_noisy_optimal_many",
     "generate_uniform_costs", "generate_near_diagonal_costs", "generate_sparse_costs",
     "generate_metric_costs", "generate_clustered_costs", "generate_noisy_linear_costs",
     "generate_worst_case_costs", "generate_identity_like_costs", "generate_hard_random_costs",

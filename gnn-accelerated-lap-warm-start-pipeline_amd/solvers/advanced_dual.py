@@ -64,6 +64,101 @@ def check_dual_feasible(C: np.ndarray, u: np.ndarray, v: np.ndarray, tol: float 
     return True
 
 
+# ---- many instances of different sizes per call: one pack (one upload of the costs), one call of the ragged entry
+def _square_costs(costs):
+    mats = [_mat(c) for c in costs]
+    if len(mats) < 1:
+        raise ValueError("at least one cost matrix expected")
+    for c in mats:
+        if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] < 1:
+            raise ValueError(f"square, non-empty cost matrices expected, not {tuple(c.shape)}")
+    return mats
+
+
+def _many_args(costs, us, vs):
+    """Argument errors of the *_many functions, raised before any device work: the costs, then u, then v."""
+    mats = _square_costs(costs)
+    sizes = [c.shape[0] for c in mats]
+    duals = []
+    for name, seq in (("us", us), ("vs", vs)):
+        seq = [np.asarray(x, dtype=np.float64) for x in seq]
+        if len(seq) != len(mats):
+            raise ValueError(f"{len(mats)} instances but {len(seq)} vectors in {name}")
+        for b, (x, n) in enumerate(zip(seq, sizes)):
+            if tuple(x.shape) != (n,):
+                raise ValueError(f"{name}[{b}] has shape {tuple(x.shape)} for an instance of size {n}")
+        duals.append(seq)
+    return mats, sizes, duals[0], duals[1]
+
+
+def _pad_upload(vectors, sizes, N, device):
+    import torch
+    host = np.zeros((len(sizes), N), dtype=np.float64)
+    for b, (x, n) in enumerate(zip(vectors, sizes)):
+        host[b, :n] = x
+    return torch.from_numpy(host).to(device)
+
+
+def _upload_pack(mats, device):
+    """One RaggedPack of host matrices.  Each matrix is uploaded from where it lies and the batch is packed on the
+    device: packing 32 matrices of 512 x 512 on the host first costs more than the projection itself."""
+    import torch
+    from gnn.features import ragged_pack
+    return ragged_pack([torch.from_numpy(c).to(device) for c in mats], device)
+
+
+def _split(padded, sizes):
+    host = padded.cpu().numpy()
+    return [host[b, :n].copy() for b, n in enumerate(sizes)]
+
+
+def _packed(costs, us, vs, pipeline):
+    from gnn.pipeline import shared_pipeline
+    mats, sizes, us, vs = _many_args(costs, us, vs)
+    pipe = pipeline if pipeline is not None else shared_pipeline()
+    pack = _upload_pack(mats, pipe.device)
+    u = _pad_upload(us, sizes, pack.N, pipe.device)
+    v = _pad_upload(vs, sizes, pack.N, pipe.device)
+    return pipe, pack, sizes, u, v
+
+
+def project_feasible_many(costs, us, vs, max_rounds: int = 50, tol: float = 1e-12, pipeline=None):
+    """project_feasible of B instances of different sizes in one device call (WarmStartPipeline.
+    project_feasible_ragged): costs, us, vs are sequences of B matrices and vectors.  Returns a list of (u, v),
+    each bit for bit what project_feasible gives the instance alone.  `pipeline`: a WarmStartPipeline, or None
+    for the one this process shares."""
+    pipe, pack, sizes, u, v = _packed(costs, us, vs, pipeline)
+    u, v, _, _, _ = pipe.project_feasible_ragged(pack, u, v, max_rounds, tol)
+    return list(zip(_split(u, sizes), _split(v, sizes)))
+
+
+def _reduce_many(costs, us, vs, shift_nonneg, want_matrix, pipeline):
+    pipe, pack, sizes, u, v = _packed(costs, us, vs, pipeline)
+    out, gmin, _ = pipe.reduce_costs_ragged(pack, u, v, shift_nonneg, want_matrix)
+    mats = None
+    if want_matrix:
+        flat, off, mats = out.cpu().numpy(), 0, []
+        for n in sizes:
+            mats.append(flat[off:off + n * n].reshape(n, n).copy())
+            off += n * n
+    return mats, gmin.cpu().numpy()
+
+
+def reduce_costs_many(costs, us, vs, shift_nonneg: bool = True, pipeline=None):
+    """reduce_costs of B instances of different sizes in one device call: a list of B matrices."""
+    return _reduce_many(costs, us, vs, shift_nonneg, True, pipeline)[0]
+
+
+def check_dual_feasible_many(costs, us, vs, tol: float = 1e-8, pipeline=None) -> bool:
+    """check_dual_feasible of B instances in one device call.  Raises the reference's AssertionError for the
+    first instance whose minimum reduced cost is below -tol, and names it."""
+    _, mins = _reduce_many(costs, us, vs, False, False, pipeline)
+    for b, mn in enumerate(mins.tolist()):
+        if mn < -tol:
+            raise AssertionError(f"Dual infeasible: min reduced cost {mn:.3e} < -tol (instance {b})")
+    return True
+
+
 def check_dual_and_match(C: np.ndarray, u: np.ndarray, v: np.ndarray,
                          rows: np.ndarray, cols: np.ndarray, tol: float = 1e-8) -> bool:
     """Dual feasibility ((C - u) - v >= -tol everywhere) and |reduced cost| <= 1e-6 on the matching."""
@@ -100,3 +195,7 @@ def make_feasible_duals(C: np.ndarray, iters: int = 2, noise_std: float = 0.0,
     rounds = max(int(project_rounds), int(iters or 0))
     u, v = project_feasible(C, u, v, max_rounds=max(10, rounds), tol=1e-12)
     return u, v
+
+
+__all__ = ["project_feasible", "reduce_costs", "check_dual_feasible", "check_dual_and_match", "make_feasible_duals",
+           "project_feasible_many", "reduce_costs_many", "check_dual_feasible_many"]

@@ -278,6 +278,50 @@ int lapwarm_oracle_duals_ragged(const double *C, const long long *offsets, const
                                 int ld, int batch, int N, const int *rows, const int *cols, double *u, double *v,
                                 int *ret, int *sweeps, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The dual utilities of solvers/advanced_dual.py:14-63 and the row minima of solvers/seed_baselines.py:29 for a
+ * ragged batch (C, offsets, sizes, ld, batch, N as above; packed and padded layouts; the 16-byte load path is
+ * chosen per instance as in lapwarm_colmin_ragged).  Every [batch][N] output is 0 beyond the prefix n_b.  An
+ * instance that is treated as empty (size outside 1..N, or wider than ld > 0) gets no work: its outputs are 0
+ * and ret[b] = 2; ret [batch] is 0 otherwise.  NaN as NumPy (np.min, np.minimum), like the uniform sweeps.  All
+ * three entries return 0, -2 (N <= 0, batch outside 1..65535, ld < 0, a NULL pointer that may not be NULL), -5
+ * (N > 16384), -1 (workspace below lapwarm_ragged_duals_workspace_bytes), <= -1000 HIP error.  Kernels on the
+ * caller's stream only (each one grid over all instances, never a launch per instance or per size); every
+ * word of every output, and every workspace word that is read, is written inside the call. */
+size_t lapwarm_ragged_duals_workspace_bytes(int batch, int N);
+
+/* out [batch][N]: out[b][i] = min_{j < n_b} (C_b[i][j] - v[b][j]) for i < n_b; v [batch][N] fp64 or NULL;
+ * ret [batch] or NULL.  Row b is, bit for bit, what lapwarm_rowmin_batched gives instance b alone.  One kernel,
+ * no host synchronisation: graph-capturable.  The workspace is not used; its size is checked all the same. */
+int lapwarm_rowmin_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                          const double *v, double *out, int *ret, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
+/* project_feasible (advanced_dual.py:14-36) of every instance: u, v [batch][N] fp64 in and out (read on the
+ * prefix, 0 beyond it afterwards), gmin [batch] the last min((C - u) - v) of the instance, rounds [batch] int32
+ * the rounds it ran, ret [batch].  An instance runs max(1, max_rounds) rounds at most and stops after the first
+ * round with gmin >= -tol (a comparison NaN fails: an instance with NaN runs every round); the stop is per
+ * instance and decided on the device, and the workgroups of a stopped instance return at once in later
+ * rounds.  u, v and gmin of instance b are what lapwarm_project_feasible gives it alone, bit for bit.
+ * A round is three kernels and two reads of C: rows (u), columns (v and the column's share of gmin, which is
+ * cap_j - v_j with cap_j = min_i (C_ij - u_i): subtraction of v_j is monotone), and one workgroup per instance
+ * that reduces gmin and sets the stop flag.  Rounds are launched in chunks of 1, 2, 4, ... 32 with one host
+ * synchronisation after each chunk but the last, to learn whether any instance still runs: a call with
+ * max_rounds <= 1 never synchronises, any other is NOT graph-capturable. */
+int lapwarm_project_feasible_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch,
+                                    int N, double *u, double *v, int max_rounds, double tol, double *gmin,
+                                    int *rounds, int *ret, void *workspace, size_t workspace_bytes, void *stream);
+
+/* reduce_costs (advanced_dual.py:39-53) of every instance: gmin [batch] receives the unshifted minima
+ * min((C - u) - v); out, in the layout of C (same offsets and ld) or NULL, receives (C - u) - v on the prefix of
+ * every instance, minus gmin[b] where shift_nonneg and gmin[b] < 0.  Elements of `out` outside the prefixes (the
+ * padding of a padded layout, and all of an instance treated as empty, whose extent is unknown) are not
+ * touched.  ret [batch] or NULL.  Bit for bit lapwarm_reduce_costs_batched per instance.  With out == NULL it
+ * is the feasibility check (advanced_dual.py:56-63) and makes two kernels, else three; no host
+ * synchronisation: graph-capturable. */
+int lapwarm_reduce_costs_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                const double *u, const double *v, int shift_nonneg, double *out, double *gmin,
+                                int *ret, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The OneGNN training loss, gnn/train_one_gnn.py:180-226 `compute_loss` with its host greedy
  * `greedy_primal_upper` (:137-177), float32 terms and fp64 sums.  C [batch][n][n] float32, padded to the batch
  * maximum n; sizes [batch] int32 = n_b, the valid rows and columns of instance b are the prefix 0..n_b-1
