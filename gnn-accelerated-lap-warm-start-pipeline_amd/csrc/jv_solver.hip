@@ -2474,10 +2474,13 @@ hipError_t launch_one_ragged(const SolverParams &p, int threads, size_t lds_byte
 
 }  // namespace
 
-// The 4 ragged instantiations: the (CH, TB) that plan_solve gives a seeded solve at LDS level 2.
+// The 4 ragged instantiations: the (CH, TB) that plan_solve gives a seeded solve at LDS level 2.  A cold
+// launch (lapwarm_lapjv_ragged) runs the same instantiations with mode = kModeCold: cold_prepare<false>, the
+// fallback of a seeded instance, from the start; it reads none of the seeded inputs and writes x_out, y_out.
 hipError_t launch_phase_ragged(const PhaseConfig &k, const SolverParams &p, hipStream_t stream)
 {
-    if (k.ldsl != 2 || k.lists || p.mode != kModeSeeded || p.phase != 0 || p.helper != 0) return hipErrorInvalidValue;
+    if (k.ldsl != 2 || k.lists || (p.mode != kModeSeeded && p.mode != kModeCold) || p.phase != 0 || p.helper != 0)
+        return hipErrorInvalidValue;
     if (!p.rg_offsets || !p.rg_sizes || p.rg_ld < 0 || p.rg_n_lo < 1 || p.rg_n_hi > p.rg_N ||
         (p.rg_ld > 0 && p.rg_n_hi > p.rg_ld))
         return hipErrorInvalidValue;

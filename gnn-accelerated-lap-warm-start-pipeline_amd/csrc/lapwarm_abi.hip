@@ -10,10 +10,12 @@
 #include <stdio.h>
 #include <string.h>
 #include <tuple>
+#include <vector>
 
 #include "../../include/lapwarm_hip.h"
 #include "dense_sweeps.hpp"
 #include "extend_costs.hpp"
+#include "extend_ragged.hpp"
 #include "jv_solver.hpp"
 #include "onegnn_refine.hpp"
 #include "oracle_duals.hpp"
@@ -709,6 +711,168 @@ int lapwarm_seeded_ragged(const double *C, const long long *offsets, const int *
         HIP_TRY(launch_phase_ragged(groups[k].k, sp, stream));
     }
     HIP_TRY(profile_end(stream));
+    return 0;
+}
+
+// ---- cold lapjv of a ragged batch (extend_ragged.hip around the ragged launches of jv_instance_kernel) ----
+size_t lapwarm_lapjv_ragged_workspace_bytes(int batch, int N)
+{
+    if (N <= 0 || batch <= 0 || batch > 65535 || N > 16384) return 0;
+    return align_up(1);  // every eligible instance keeps its solver state in LDS: the workspace is not used
+}
+
+int lapwarm_lapjv_ragged_groups(const int *sizes, int batch, int *group_of)
+{
+    if (!sizes || !group_of || batch <= 0) return -2;
+    RaggedGroup groups[kMaxRaggedGroups];
+    return plan_ragged_groups_cold(sizes, batch, group_of, groups);
+}
+
+// The solver launches of a ragged cold solve: one per group, every workgroup picks its own.
+static int lapjv_ragged_launches(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                 long long *x, long long *y, int *ret, long long *stats, const RaggedGroup *groups,
+                                 int n_groups, hipStream_t stream)
+{
+    SolverParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.C = C;
+    sp.n = N;
+    sp.batch = batch;
+    sp.mode = kModeCold;
+    sp.x_out = x;
+    sp.y_out = y;
+    sp.ret = ret;
+    sp.stats = stats;
+    sp.rg_offsets = offsets;
+    sp.rg_sizes = sizes;
+    sp.rg_ld = ld;
+    sp.rg_N = N;
+    HIP_TRY(profile_begin(stream));
+    for (int k = 0; k < n_groups; ++k) {
+        sp.rg_n_lo = groups[k].n_lo;
+        sp.rg_n_hi = groups[k].n_hi;
+        HIP_TRY(launch_phase_ragged(groups[k].k, sp, stream));
+    }
+    HIP_TRY(profile_end(stream));
+    return 0;
+}
+
+int lapwarm_lapjv_ragged(const double *C, const long long *offsets, const int *sizes, const int *host_sizes, int ld,
+                         int batch, int N, long long *x, long long *y, int *ret, long long *stats, void *workspace,
+                         size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!host_sizes || !x || !y || !ret || !workspace) return -2;
+    for (int b = 0; b < batch; ++b) {
+        if (host_sizes[b] < 1 || host_sizes[b] > N || (ld > 0 && host_sizes[b] > ld)) return -2;
+    }
+    RaggedGroup groups[kMaxRaggedGroups];
+    const int n_groups = plan_ragged_groups_cold(host_sizes, batch, nullptr, groups);
+    if (n_groups < 0) {
+        snprintf(g_err, sizeof(g_err), "lapwarm_lapjv_ragged: an instance is outside the one-launch, all-LDS, no-lists class");
+        return -6;
+    }
+    const size_t need = lapwarm_lapjv_ragged_workspace_bytes(batch, N);
+    if (workspace_bytes < need) {
+        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, need);
+        return -1;
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    HIP_TRY(launch_lapjv_ragged_init(x, y, ret, stats, batch, N, stream));
+    return lapjv_ragged_launches(C, offsets, sizes, ld, batch, N, x, y, ret, stats, groups, n_groups, stream);
+}
+
+// Rectangular / cost-limited lapjv of a ragged batch: the shapes block (E offsets and extended sizes), the
+// solver's x, y [batch][N] int64, the matched costs [batch][R], then the packed E_b: sum of n_b^2 elements.
+struct ExtendedRaggedWs {
+    long long *e_off, *xs, *ys;
+    int *e_n;
+    double *gath, *E;
+    size_t bytes;
+};
+
+static ExtendedRaggedWs extended_ragged_layout(void *ws, int batch, int N, int R, long long e_total)
+{
+    ExtendedRaggedWs w;
+    Carver c{reinterpret_cast<unsigned char *>(ws), 0};
+    w.e_off = c.take<long long>((size_t)batch);
+    w.e_n = c.take<int>((size_t)batch);
+    w.xs = c.take<long long>((size_t)batch * N);
+    w.ys = c.take<long long>((size_t)batch * N);
+    w.gath = c.take<double>((size_t)batch * R);
+    w.E = c.take<double>((size_t)e_total);
+    w.bytes = c.off;
+    return w;
+}
+
+// The host's plan of a ragged extended call: sizes [batch] = n_b, their largest, the sum of their squares and the
+// largest n_rows.  Returns 0 or the argument code (-2, -4, -5) of the first instance that has one.
+static int extended_ragged_sizes(const int *host_rows, const int *host_cols, const double *host_limits,
+                                 int extend_cost, int batch, std::vector<int> *sizes, int *N, int *R, int *Q,
+                                 long long *e_total)
+{
+    if (batch <= 0 || batch > 65535 || !host_rows || !host_cols || !host_limits) return -2;
+    sizes->resize((size_t)batch);
+    *N = *R = *Q = 0;
+    *e_total = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int n = lapwarm_lapjv_extended_n(host_rows[b], host_cols[b], extend_cost, host_limits[b]);
+        if (n < 0) return n;
+        (*sizes)[b] = n;
+        if (n > *N) *N = n;
+        if (host_rows[b] > *R) *R = host_rows[b];
+        if (host_cols[b] > *Q) *Q = host_cols[b];
+        *e_total += (long long)n * n;
+    }
+    return 0;
+}
+
+size_t lapwarm_lapjv_extended_ragged_workspace_bytes(const int *host_rows, const int *host_cols,
+                                                     const double *host_limits, int extend_cost, int batch)
+{
+    std::vector<int> sizes;
+    int N, R, Q;
+    long long e_total;
+    if (extended_ragged_sizes(host_rows, host_cols, host_limits, extend_cost, batch, &sizes, &N, &R, &Q, &e_total))
+        return 0;
+    return extended_ragged_layout(nullptr, batch, N, R, e_total).bytes;
+}
+
+int lapwarm_lapjv_extended_ragged(const double *C, const long long *offsets, const int *n_rows, const int *n_cols,
+                                  const double *cost_limit, const int *host_rows, const int *host_cols,
+                                  const double *host_limits, int ld, int extend_cost, int batch, int R, int Q, int *x,
+                                  int *y, double *opt, int *matched, int *ret, long long *stats, void *workspace,
+                                  size_t workspace_bytes, void *stream_)
+{
+    std::vector<int> sizes;
+    int N, Rmax, Qmax;
+    long long e_total;
+    if (int rc = extended_ragged_sizes(host_rows, host_cols, host_limits, extend_cost, batch, &sizes, &N, &Rmax, &Qmax,
+                                       &e_total))
+        return rc;
+    if (ld < 0 || R < Rmax || Q < Qmax || (ld > 0 && Qmax > ld)) return -2;
+    if (!C || !offsets || !n_rows || !n_cols || !cost_limit || !x || !y || !ret || !workspace) return -2;
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return -2;  // E is written with 16-byte stores
+    RaggedGroup groups[kMaxRaggedGroups];
+    const int n_groups = plan_ragged_groups_cold(sizes.data(), batch, nullptr, groups);
+    if (n_groups < 0) {
+        snprintf(g_err, sizeof(g_err),
+                 "lapwarm_lapjv_extended_ragged: an instance is outside the one-launch, all-LDS, no-lists class");
+        return -6;
+    }
+    const ExtendedRaggedWs w = extended_ragged_layout(workspace, batch, N, R, e_total);
+    if (workspace_bytes < w.bytes) {
+        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
+        return -1;
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const ExtRagged g{C, offsets, n_rows, n_cols, cost_limit, ld, extend_cost ? 1 : 0, batch, R, Q, N, e_total,
+                      w.e_off, w.e_n, w.E};
+    HIP_TRY(launch_extend_shapes(g, stream));
+    HIP_TRY(launch_extend_costs_ragged(g, ret, stats, stream));
+    if (int rc = lapjv_ragged_launches(w.E, w.e_off, w.e_n, 0, batch, N, w.xs, w.ys, ret, stats, groups, n_groups, stream))
+        return rc;
+    HIP_TRY(launch_extended_finish_ragged(g, w.xs, w.ys, ret, x, y, opt, matched, w.gath, stream));
     return 0;
 }
 

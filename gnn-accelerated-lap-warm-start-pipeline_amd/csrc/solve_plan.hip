@@ -254,14 +254,25 @@ bool ragged_solve_eligible(int n)
     return solve_shape(n, false) == SolveShape::kOneLaunch && !solver_uses_helpers(n) && !solver_needs_global_state(n);
 }
 
-int plan_ragged_groups(const int *sizes, int batch, int *group_of, RaggedGroup *groups)
+// A cold instance of a ragged launch: one launch, all state in LDS, no candidate lists (the RAGGED
+// instantiations are compiled without them), and a (CH, TB) that launch_phase_ragged has.
+bool ragged_cold_eligible(int n)
+{
+    if (n < 1 || n > 16384 || arr_lists_enabled(n)) return false;
+    const SolvePlan plan = plan_solve(kModeCold, 1, n, 0, false, 0);
+    const PhaseConfig &k = plan.prep;
+    if (plan.shape != SolveShape::kOneLaunch || k.ldsl != 2 || plan.helper != 0) return false;
+    return k.tb == 1024 ? (k.ch == 1 || k.ch == 2 || k.ch == 4) : (k.tb == 256 && k.ch == 1);
+}
+
+static int plan_groups(int mode, const int *sizes, int batch, int *group_of, RaggedGroup *groups)
 {
     int count = 0;
     for (int b = 0; b < batch; ++b) {
         const int n = sizes[b];
-        if (!ragged_solve_eligible(n)) return -1;
+        if (!(mode == kModeCold ? ragged_cold_eligible(n) : ragged_solve_eligible(n))) return -1;
         // (batch and the CU count only decide about helpers, which an eligible size does not have)
-        const PhaseConfig k = plan_solve(kModeSeeded, batch, n, 0, false, 0).prep;
+        const PhaseConfig k = plan_solve(mode, batch, n, 0, false, 0).prep;
         int g = 0;
         for (; g < count; ++g) {
             const PhaseConfig &q = groups[g].k;
@@ -284,6 +295,16 @@ int plan_ragged_groups(const int *sizes, int batch, int *group_of, RaggedGroup *
         }
     }
     return count;
+}
+
+int plan_ragged_groups(const int *sizes, int batch, int *group_of, RaggedGroup *groups)
+{
+    return plan_groups(kModeSeeded, sizes, batch, group_of, groups);
+}
+
+int plan_ragged_groups_cold(const int *sizes, int batch, int *group_of, RaggedGroup *groups)
+{
+    return plan_groups(kModeCold, sizes, batch, group_of, groups);
 }
 
 bool solver_needs_global_state(int n)

@@ -59,6 +59,14 @@ constexpr int kMaxRaggedGroups = 16;
 // kMaxRaggedGroups configurations, or two intervals overlap: neither happens with the rules above).
 int plan_ragged_groups(const int *sizes, int batch, int *group_of, RaggedGroup *groups);
 
+// ---- cold solves of a ragged batch (lapwarm_lapjv_ragged, lapwarm_lapjv_extended_ragged) ----
+// Eligible: the instance's own cold plan (plan_solve(kModeCold, ..), no threads hint) is one launch at LDS
+// level 2 without helper workgroups, and arr_lists_enabled(n) is false: every n <= 511 with the default
+// settings; LAPWARM_ARR_LISTS=0 widens the class to where the state leaves LDS.  Groups as above, by the
+// PhaseConfig of the cold plan (so 1024 < n <= 2048 gets the 512-thread geometry it gets alone).
+bool ragged_cold_eligible(int n);
+int plan_ragged_groups_cold(const int *sizes, int batch, int *group_of, RaggedGroup *groups);
+
 int solver_lds_level(int n, int ch);
 bool solver_needs_global_state(int n);
 // candidate lists for the augmenting row reduction: from the size where a row is a few times its list

@@ -104,6 +104,77 @@ class RaggedDuals(Sequence):
         return self.x[b, :n], self.u[b, :n], self.v[b, :n], self.ret[b], self.sweeps[b]
 
 
+NONSQUARE = "Square cost array expected. If cost is intentionally non-square, pass extend_cost=True."
+
+
+class ExtendedPack:
+    """A batch of cost matrices of different shapes on the device, as lapwarm_lapjv_extended_ragged takes it:
+    C fp64 (flat), offsets (B,) int64, limits (B,) fp64, rows and cols (B,) int32 (views of one uploaded block),
+    ld (0: packed), and the shapes and limits on the host."""
+    __slots__ = ("C", "offsets", "limits", "rows", "cols", "ld", "host_rows", "host_cols", "host_limits")
+
+    def __init__(self, C, offsets, limits, rows, cols, ld, host_rows, host_cols, host_limits):
+        self.C, self.offsets, self.limits, self.rows, self.cols, self.ld = C, offsets, limits, rows, cols, ld
+        self.host_rows, self.host_cols, self.host_limits = host_rows, host_cols, host_limits
+
+
+def _extended_meta(offsets, host_rows, host_cols, host_limits, device):
+    """offsets, limits, rows, cols on the device from one host block and one copy."""
+    B = len(host_rows)
+    block = np.empty((24 * B,), dtype=np.uint8)
+    block[:8 * B].view(np.int64)[:] = offsets
+    block[8 * B:16 * B].view(np.float64)[:] = host_limits
+    block[16 * B:20 * B].view(np.int32)[:] = host_rows
+    block[20 * B:].view(np.int32)[:] = host_cols
+    d = torch.from_numpy(block).to(device)
+    return (d[:8 * B].view(torch.int64), d[8 * B:16 * B].view(torch.float64), d[16 * B:20 * B].view(torch.int32),
+            d[20 * B:].view(torch.int32))
+
+
+def _limits_of(cost_limit, count):
+    """One fp64 limit per instance from a scalar or a sequence of `count` values."""
+    if np.ndim(cost_limit) == 0:
+        return [float(cost_limit)] * count
+    limits = [float(t) for t in cost_limit]
+    if len(limits) != count:
+        raise ValueError(f"{count} cost matrices but {len(limits)} cost limits")
+    return limits
+
+
+def extended_pack(costs, cost_limit=float("inf"), device="cuda:0") -> ExtendedPack:
+    """Host-side half of a ragged lapjv_extended call: `costs` is a sequence of non-empty 2-D fp64 matrices
+    (NumPy: packed on the host, one H2D copy; CUDA tensors: packed on the device), `cost_limit` a scalar or one
+    value per instance.  Raises before any device work."""
+    mats = list(costs)
+    if not mats:
+        raise ValueError("at least one cost matrix expected")
+    on_device = all(isinstance(c, torch.Tensor) and c.is_cuda for c in mats)
+    if not on_device:
+        mats = [np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c) for c in mats]
+    for c in mats:
+        if c.ndim != 2:
+            raise ValueError("2-dimensional array expected")
+        if on_device and c.dtype != torch.float64:
+            raise ValueError("CUDA cost matrices must be float64")
+        if c.shape[0] < 1 or c.shape[1] < 1:
+            raise ValueError("non-empty cost matrices expected")
+    host_limits = _limits_of(cost_limit, len(mats))
+    host_rows, host_cols = [int(c.shape[0]) for c in mats], [int(c.shape[1]) for c in mats]
+    counts = np.asarray(host_rows, dtype=np.int64) * np.asarray(host_cols, dtype=np.int64)
+    offsets = np.concatenate(([0], np.cumsum(counts)[:-1])).astype(np.int64)
+    _hip.require_device()
+    if on_device:
+        device = mats[0].device
+        C = torch.cat([c.reshape(-1) for c in mats])
+    else:
+        buf = np.empty(int(counts.sum()), dtype=np.float64)
+        for c, o in zip(mats, offsets.tolist()):
+            buf[o:o + c.size] = np.asarray(c, dtype=np.float64).reshape(-1)
+        C = torch.from_numpy(buf).to(torch.device(device))
+    offs_d, lim_d, rows_d, cols_d = _extended_meta(offsets, host_rows, host_cols, host_limits, C.device)
+    return ExtendedPack(C, offs_d, lim_d, rows_d, cols_d, 0, host_rows, host_cols, host_limits)
+
+
 class WarmStartPipeline:
     """Batched, device-resident warm-start solve."""
 
@@ -116,6 +187,7 @@ class WarmStartPipeline:
         self.threads_hint = int(threads_hint)
         self._ws = {}
         self._ragged_ok = {}  # size -> does seeded_ragged take it
+        self._cold_ragged_ok = {}  # size -> does lapjv_ragged take it
 
     def _workspace(self, B, n, cold=False):
         # (cold solves carry the candidate lists of the row reduction: a larger block, cached separately)
@@ -221,6 +293,138 @@ class WarmStartPipeline:
         if _hip.check(rc, "lapjv_extended_batch") != 0:
             raise RuntimeError(f"lapwarm_lapjv_extended_batched failed (code {rc}): {_hip.last_error()}")
         return {"x": x, "y": y, "opt": opt, "matched": matched, "ret": ret, "stats": stats}
+
+    def lapjv_ragged_eligible(self, n: int) -> bool:
+        """Does lapjv_ragged take an instance of this size?  Those whose own cold plan is one launch with all
+        solver state in LDS and no candidate lists: every n <= 511 with the default settings (the library
+        decides, from the plan)."""
+        known = self._cold_ragged_ok
+        if n not in known:
+            one = (ct.c_int * 1)(int(n))
+            known[n] = self.lib.lapwarm_lapjv_ragged_groups(one, 1, (ct.c_int * 1)()) == 1
+        return known[n]
+
+    def lapjv_ragged(self, pack: RaggedPack, want_stats: bool = True):
+        """Cold lapjv of every instance of a ragged batch in one call (lapwarm_lapjv_ragged): one solver launch
+        per kernel configuration, `pack.C` read where it is.  Returns x, y (B, N) int64 with -1 beyond n_b, ret
+        (B,) int32, stats (B, 32) int64 or None; row b is what lapjv_batch gives instance b alone with
+        threads_hint 0 (x, y as int64).  Every size must be in the class `lapjv_ragged_eligible` describes."""
+        if not isinstance(pack, RaggedPack):
+            raise TypeError(f"Argument 'pack' must be a RaggedPack, not {type(pack).__name__}")
+        B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
+        x = torch.empty((B, N), dtype=torch.int64, device=dev)
+        y = torch.empty((B, N), dtype=torch.int64, device=dev)
+        ret = torch.empty((B,), dtype=torch.int32, device=dev)
+        stats = torch.empty((B, 32), dtype=torch.int64, device=dev) if want_stats else None
+        ws, nbytes = self._cached_workspace(("lapjv_ragged", B, N),
+                                            lambda: self.lib.lapwarm_lapjv_ragged_workspace_bytes(B, N))
+        host_sizes = (ct.c_int * B)(*pack.host_sizes)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lapwarm_lapjv_ragged(
+            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), host_sizes, pack.ld, B, N,
+            x.data_ptr(), y.data_ptr(), ret.data_ptr(), stats.data_ptr() if want_stats else None, ws.data_ptr(),
+            nbytes, ct.c_void_p(stream))
+        if _hip.check(rc, "lapjv_ragged") != 0:
+            raise RuntimeError(f"lapwarm_lapjv_ragged failed (code {rc}): {_hip.last_error()}")
+        return x, y, ret, stats
+
+    def lapjv_extended_ragged(self, pack: ExtendedPack, extend_cost: bool = True, want_stats: bool = True) -> dict:
+        """lapjv_extended_batch for instances of different shapes and limits in one call
+        (lapwarm_lapjv_extended_ragged): `pack` is an extended_pack result.  Returns the same dict, padded: x
+        (B, R), y (B, Q) int32 with -1 for unmatched and beyond the instance's shape (R, Q the largest n_rows,
+        n_cols), opt (B,) fp64, matched, ret (B,) int32 and stats (B, 32) int64 or None; row b is what
+        lapjv_extended_batch gives instance b alone.  Every extended size must be in the class
+        `lapjv_ragged_eligible` describes."""
+        if not isinstance(pack, ExtendedPack):
+            raise TypeError(f"Argument 'pack' must be an ExtendedPack, not {type(pack).__name__}")
+        B, dev, extend_cost = len(pack.host_rows), pack.C.device, int(bool(extend_cost))
+        rows, cols = (ct.c_int * B)(*pack.host_rows), (ct.c_int * B)(*pack.host_cols)
+        limits = (ct.c_double * B)(*pack.host_limits)
+        R, Q = max(pack.host_rows), max(pack.host_cols)
+        nbytes = int(self.lib.lapwarm_lapjv_extended_ragged_workspace_bytes(rows, cols, limits, extend_cost, B))
+        if nbytes == 0:
+            for r, c, t in zip(pack.host_rows, pack.host_cols, pack.host_limits):
+                n = self.lib.lapwarm_lapjv_extended_n(r, c, extend_cost, t)
+                if n == -4:
+                    raise ValueError(NONSQUARE)
+                _hip.check(n, "lapjv_extended_ragged")
+            raise ValueError("lapjv_extended_ragged: empty batch or empty cost matrices")
+        x = torch.empty((B, R), dtype=torch.int32, device=dev)
+        y = torch.empty((B, Q), dtype=torch.int32, device=dev)
+        opt = torch.empty((B,), dtype=torch.float64, device=dev)
+        matched = torch.empty((B,), dtype=torch.int32, device=dev)
+        ret = torch.empty((B,), dtype=torch.int32, device=dev)
+        stats = torch.empty((B, 32), dtype=torch.int64, device=dev) if want_stats else None
+        # (one block per power of two of the size: the shapes of a tracker change with every call)
+        bucket = max(1 << 16, 1 << (nbytes - 1).bit_length())
+        ws, cap = self._cached_workspace(("extended_ragged", bucket), lambda: bucket)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lapwarm_lapjv_extended_ragged(
+            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.rows.data_ptr(), pack.cols.data_ptr(),
+            pack.limits.data_ptr(), rows, cols, limits, pack.ld, extend_cost, B, R, Q, x.data_ptr(), y.data_ptr(),
+            opt.data_ptr(), matched.data_ptr(), ret.data_ptr(), stats.data_ptr() if want_stats else None,
+            ws.data_ptr(), cap, ct.c_void_p(stream))
+        if _hip.check(rc, "lapjv_extended_ragged") != 0:
+            raise RuntimeError(f"lapwarm_lapjv_extended_ragged failed (code {rc}): {_hip.last_error()}")
+        return {"x": x, "y": y, "opt": opt, "matched": matched, "ret": ret, "stats": stats}
+
+    def _extended_many_parts(self, costs, extend_cost=True, cost_limit=float("inf"), want_stats=True):
+        """lapjv_extended_many before the results are cut up: a list of (indices, rows, cols, padded dict), one
+        entry for the ragged call and one per lapjv_extended_batch call.  Argument errors come first."""
+        mats = list(costs)
+        limits = _limits_of(cost_limit, len(mats))
+        extend_cost = int(bool(extend_cost))
+        shapes = []
+        for c in mats:
+            if not isinstance(c, torch.Tensor):
+                c = np.asarray(c)
+            if c.ndim != 2:
+                raise ValueError("2-dimensional array expected")
+            shapes.append((int(c.shape[0]), int(c.shape[1])))
+        sizes = []
+        for (r, c), t in zip(shapes, limits):
+            n = self.lib.lapwarm_lapjv_extended_n(r, c, extend_cost, t)
+            if n == -4:
+                raise ValueError(NONSQUARE)
+            if n == -2:
+                raise ValueError("lapjv_extended_many: non-empty cost matrices expected")
+            sizes.append(_hip.check(n, "lapjv_extended_many"))
+        # (a threads_hint picks another geometry than the plan the ragged launches are grouped by)
+        ragged = [b for b, n in enumerate(sizes) if self.threads_hint == 0 and self.lapjv_ragged_eligible(n)]
+        parts = []
+        if ragged:
+            pack = extended_pack([mats[b] for b in ragged], [limits[b] for b in ragged], self.device)
+            parts.append((ragged, pack.host_rows, pack.host_cols,
+                          self.lapjv_extended_ragged(pack, extend_cost, want_stats)))
+        groups = {}
+        taken = set(ragged)
+        for b, (shape, t) in enumerate(zip(shapes, limits)):
+            if b not in taken:
+                groups.setdefault((shape, t), []).append(b)
+        for ((r, c), t), members in groups.items():
+            C = torch.stack([mats[b] if isinstance(mats[b], torch.Tensor)
+                             else torch.from_numpy(np.ascontiguousarray(mats[b], dtype=np.float64))
+                             for b in members]).to(self.device)
+            parts.append((members, [r] * len(members), [c] * len(members),
+                          self.lapjv_extended_batch(C, extend_cost, t, want_stats)))
+        return len(mats), parts
+
+    def lapjv_extended_many(self, costs, extend_cost: bool = True, cost_limit=float("inf"), want_stats: bool = True):
+        """The reference's `lapjv(cost, extend_cost, cost_limit)` for instances of different shapes: `costs` is
+        a sequence of 2-D fp64 arrays or CUDA tensors, `cost_limit` a scalar or one value per instance.  The
+        instances lapjv_extended_ragged takes go through one call of it; the rest (extended size above the class
+        of `lapjv_ragged_eligible`; every instance when this pipeline has a threads_hint) through
+        lapjv_extended_batch, once per distinct shape and limit.  Returns one dict per instance, in input order:
+        x (n_rows,), y (n_cols,) int32, opt, matched, ret, stats -- the rows of what lapjv_extended_batch returns
+        for the instance alone."""
+        count, parts = self._extended_many_parts(costs, extend_cost, cost_limit, want_stats)
+        out = [None] * count
+        for members, rows, cols, o in parts:
+            for k, b in enumerate(members):
+                out[b] = {"x": o["x"][k, :rows[k]], "y": o["y"][k, :cols[k]], "opt": o["opt"][k],
+                          "matched": o["matched"][k], "ret": o["ret"][k],
+                          "stats": o["stats"][k] if want_stats else None}
+        return out
 
     def optimal_duals_batch(self, C: torch.Tensor):
         """Cold JV + the optimal duals it ends with: x (B,n) int32, u, v (B,n) fp64, ret.

@@ -7,6 +7,7 @@ warm-start hot path:
     lapjv_seeded(C, u, v, eps=1e-12)                                  -> (x, y, cost)  int64
 
     lapjv_extended(cost, extend_cost=False, cost_limit=inf, return_cost=True)  -> (opt, x, y)   int32
+    lapjv_many(costs, extend_cost=False, cost_limit=inf, return_cost=True)     -> [(opt, x, y), ...]
 
 All run on the GPU through liblapwarm_hip.so (hand-written HIP, gfx950); there is no CPU
 implementation in this package.  `lapmod` (sparse LAPMOD) is outside the hot path and raises.
@@ -19,8 +20,12 @@ tests/test_gpu_reference_suite.py and tests/test_host_logic.py assert both.  Onc
 assertions are retired, routing is three lines in lap/_lapjv.py: replace the NotImplementedError
 branch of `lapjv` by `return lapjv_extended(cost, extend_cost, cost_limit, return_cost)` and add the
 name to `__all__`.
+
+`lapjv_many` is `lapjv_extended` for a sequence of matrices of any shapes, each with its own cost limit: the
+small ones (extended size up to 511) are solved by one ragged device call instead of one call each.  Like
+`lapjv_extended` it is importable without being listed in `__all__`.
 """
-from ._lapjv import lapjv, lapjv_extended, LARGE_ as LARGE, FP_1_ as FP_1, FP_2_ as FP_2, FP_DYNAMIC_ as FP_DYNAMIC
+from ._lapjv import lapjv, lapjv_extended, lapjv_many, LARGE_ as LARGE, FP_1_ as FP_1, FP_2_ as FP_2, FP_DYNAMIC_ as FP_DYNAMIC
 from ._seeded_jv import lapjv_seeded
 
 __version__ = "0.5.12+mi355x"

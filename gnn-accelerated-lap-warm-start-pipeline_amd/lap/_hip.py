@@ -60,6 +60,14 @@ SIGNATURES = {
     "lapwarm_seeded_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_ip, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp,
                                          ct.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
     "lapwarm_seeded_ragged_groups": (ct.c_int, [c_ip, ct.c_int, c_ip]),
+    "lapwarm_lapjv_ragged_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_lapjv_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_ip, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
+                                        c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_lapjv_ragged_groups": (ct.c_int, [c_ip, ct.c_int, c_ip]),
+    "lapwarm_lapjv_extended_ragged_workspace_bytes": (ct.c_size_t, [c_ip, c_ip, c_dp, ct.c_int, ct.c_int]),
+    "lapwarm_lapjv_extended_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_ip, c_ip, c_dp, ct.c_int, ct.c_int,
+                                                 ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                 c_vp, ct.c_size_t, c_vp]),
     "lapwarm_project_round_batched":(ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
                                                  ct.c_size_t, c_vp]),
     "lapwarm_reduce_costs_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, ct.c_int, c_vp, c_vp,

@@ -85,3 +85,59 @@ def lapjv_extended(cost, extend_cost=False, cost_limit=np.inf, return_cost=True)
     if return_cost:
         return opt, x, y
     return x, y
+
+
+def lapjv_many(costs, extend_cost=False, cost_limit=np.inf, return_cost=True):
+    """``lapjv_extended`` of every matrix of ``costs`` (a sequence of 2-D arrays of any shapes) with far fewer
+    launches: returns a list of ``(opt, x, y)``, or of ``(x, y)``, with exactly the dtypes and values
+    ``lapjv_extended(cost, extend_cost, cost_limit_b, return_cost)`` returns for each.  ``cost_limit`` is a scalar
+    or one value per matrix.  The matrices whose extended size is in the ragged class (n_rows + n_cols, or
+    max(n_rows, n_cols) without a limit, up to 511) are packed, copied to the device once and solved by one
+    ragged call (gnn.WarmStartPipeline.lapjv_extended_many); larger ones go through the batched entry, once per
+    distinct shape.  Every argument error of ``lapjv_extended`` is raised before any device work."""
+    if costs is None:
+        raise TypeError("Argument 'costs' must not be None")
+    mats = []
+    for cost in costs:
+        if cost is None:
+            raise TypeError("Argument 'cost' must not be None")
+        cost = np.asarray(cost)
+        if cost.ndim != 2:
+            raise ValueError("2-dimensional array expected")
+        mats.append(np.ascontiguousarray(cost, dtype=np.double))
+    if np.ndim(cost_limit) == 0:
+        limits = [cost_limit] * len(mats)
+    else:
+        limits = list(cost_limit)
+        if len(limits) != len(mats):
+            raise ValueError("%d cost matrices but %d cost limits" % (len(mats), len(limits)))
+    for k, t in enumerate(limits):
+        try:
+            limits[k] = float(t)
+        except ValueError:
+            raise TypeError("must be real number, not %s" % type(t).__name__) from None
+    for c in mats:
+        if c.shape[0] != c.shape[1] and not extend_cost:
+            raise ValueError("Square cost array expected. If cost is intentionally "
+                             "non-square, pass extend_cost=True.")
+    out = [None] * len(mats)
+    work = []
+    for b, c in enumerate(mats):
+        if c.shape[0] == 0 or c.shape[1] == 0:  # nothing to match: lapjv_extended answers without a device
+            out[b] = lapjv_extended(c, extend_cost, limits[b], return_cost)
+        else:
+            work.append(b)
+    if work:
+        _hip.require_device()
+        from gnn.pipeline import shared_pipeline  # (torch is needed from here on only)
+        _, parts = shared_pipeline()._extended_many_parts([mats[b] for b in work], extend_cost,
+                                                          [limits[b] for b in work], want_stats=False)
+        for members, rows, cols, o in parts:
+            ret, opt = o["ret"].cpu().numpy(), o["opt"].cpu().numpy()
+            x, y = o["x"].cpu().numpy(), o["y"].cpu().numpy()
+            for k, m in enumerate(members):
+                if ret[k] != 0:
+                    raise RuntimeError("Unknown error (lapjv_internal returned %d)." % ret[k])
+                xb, yb = x[k, :rows[k]].copy(), y[k, :cols[k]].copy()
+                out[work[m]] = (np.float64(opt[k]), xb, yb) if return_cost else (xb, yb)
+    return out

@@ -231,6 +231,55 @@ int lapwarm_seeded_ragged(const double *C, const long long *offsets, const int *
  * outside the class above, -2 for batch <= 0 or a NULL pointer. */
 int lapwarm_seeded_ragged_groups(const int *sizes, int batch, int *group_of);
 
+/* Cold lapjv of every instance of a ragged batch (C, offsets, sizes, host_sizes, ld, batch, N as for
+ * lapwarm_seeded_ragged) in one call: x, y [batch][N] int64 with -1 beyond n_b; ret [batch]; stats [batch][32] or
+ * NULL.  x, y, ret and the counters of instance b are what lapwarm_lapjv_batched gives it alone: the instance
+ * runs under the kernel instantiation of its own cold plan, and instances whose cold plans have the same kernel
+ * configuration share ONE launch (one init launch, then one solver launch per configuration).  Every instance
+ * must be in the class whose cold plan is one launch with all solver state in LDS and no candidate lists: with
+ * the default settings every n_b <= 511 (candidate lists start at 512; LAPWARM_ARR_LISTS=0 widens the class to
+ * the sizes whose state fits LDS).  An instance whose size on the device lies in no launch of the call keeps
+ * x, y -1, ret 2, stats 0.  Final duals are not returned: lapwarm_oracle_duals_ragged gives duals from a matching.
+ * The workspace is not used; its size is checked all the same.  Kernels only, no host synchronisation: the
+ * call can be captured into a graph.  Returns 0, -2 (N <= 0, batch outside 1..65535, ld < 0, a NULL pointer other
+ * than stats, a host size outside 1..N or above ld > 0), -5 (N > 16384), -6 (an instance outside the class: solve
+ * it with lapwarm_lapjv_batched), -1 (workspace too small), <= -1000 HIP error; only the last follows device work. */
+size_t lapwarm_lapjv_ragged_workspace_bytes(int batch, int N);
+int lapwarm_lapjv_ragged(const double *C, const long long *offsets, const int *sizes, const int *host_sizes, int ld,
+                         int batch, int N, long long *x, long long *y, int *ret, long long *stats, void *workspace,
+                         size_t workspace_bytes, void *stream);
+/* Host only: as lapwarm_seeded_ragged_groups, for the cold plans and the class of lapwarm_lapjv_ragged. */
+int lapwarm_lapjv_ragged_groups(const int *sizes, int batch, int *group_of);
+
+/* lapwarm_lapjv_extended_batched for instances of different shapes and limits in one call.  Instance b is the
+ * n_rows[b] x n_cols[b] fp64 matrix at C + offsets[b] (elements; 8-byte alignment is enough), rows ld elements
+ * apart, or n_cols[b] when ld == 0 (packed), with its own cost_limit[b] (+inf: none); extend_cost is one flag
+ * per call.  offsets, n_rows, n_cols, cost_limit are DEVICE arrays [batch]; host_rows, host_cols, host_limits
+ * are HOST copies from which the call is planned (the stream is never synchronised and nothing is copied).
+ * The extended size n_b is lapwarm_lapjv_extended_n's.  x [batch][R], y [batch][Q] int32 with -1 for unmatched
+ * and beyond the instance's shape, R >= every n_rows, Q >= every n_cols; opt, matched [batch] or NULL; ret
+ * [batch]; stats [batch][32] or NULL.  Everything of instance b is what lapwarm_lapjv_extended_batched gives it
+ * alone (bit for bit; the time slots of stats apart).  Instances with ret != 0: x, y -1, opt NaN, matched 0.
+ * Launches: one workgroup turns the device shapes into n_b and the offsets of the E_b; one launch (grid:
+ * largest n x batch) writes every E_b [n_b][n_b], packed one behind the other in the workspace (sum of n_b^2
+ * elements; a square instance without a limit is copied as well: one extra pass over a small matrix, where the
+ * uniform entry solves it in place); one ragged cold solver launch per kernel configuration
+ * (lapwarm_lapjv_ragged, every n_b must be in its class); one finish launch.  An instance whose shape on the
+ * device is not what the host copies say is solved only if it still fits what was planned (R, Q, ld, the
+ * largest n_b, the E area); otherwise it is treated as empty: x, y -1, opt NaN, matched 0, ret 2.
+ * Every workspace word that is read is written inside the call.  Returns 0, -2 (batch outside 1..65535, a shape
+ * with n_rows or n_cols <= 0, R or Q too small, ld < 0 or below an n_cols, a NULL pointer other than opt, matched
+ * and stats, a workspace that is not 16-byte aligned), -4 (a non-square instance without extend_cost), -5 (an
+ * n_b > 16384), -6 (an instance outside the class), -1 (workspace too small), <= -1000 HIP error; only the last
+ * follows device work.  The workspace query returns 0 where the call would return -2, -4 or -5. */
+size_t lapwarm_lapjv_extended_ragged_workspace_bytes(const int *host_rows, const int *host_cols,
+                                                     const double *host_limits, int extend_cost, int batch);
+int lapwarm_lapjv_extended_ragged(const double *C, const long long *offsets, const int *n_rows, const int *n_cols,
+                                  const double *cost_limit, const int *host_rows, const int *host_cols,
+                                  const double *host_limits, int ld, int extend_cost, int batch, int R, int Q, int *x,
+                                  int *y, double *opt, int *matched, int *ret, long long *stats, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+
 /* One round of project_feasible: u = min(u, rowmin(C-v)); v = min(v, colmin(C-u));
  * gmin[b] = min((C-u)-v).  The host loop decides when to stop. */
 int lapwarm_project_round_batched(const double *C, int batch, int n, double *u, double *v,
@@ -387,7 +436,8 @@ int lapwarm_refine_backward(const float *topk16, const float *u_pre, const float
                             float *grad_b1, int rows, int H, void *ws, size_t ws_bytes, void *stream);
 
 /* Profiling hook for bench.py: when enabled, lapwarm_seeded_batched / lapwarm_lapjv_batched /
- * lapwarm_seeded_ragged bracket their solver launches with HIP events on the caller's stream;
+ * lapwarm_seeded_ragged / lapwarm_lapjv_ragged / lapwarm_lapjv_extended_ragged bracket their solver launches
+ * with HIP events on the caller's stream;
  * lapwarm_profile_last_solver_ms() waits for the last bracket and returns its duration. */
 void lapwarm_profile_enable(int on);
 double lapwarm_profile_last_solver_ms(void);
