@@ -16,12 +16,13 @@ struct Knobs {
     int arr_lists;             // LAPWARM_ARR_LISTS=0: cold solves scan whole rows instead of candidate lists
     int helper;                // LAPWARM_HELPER=0: no helper workgroups beside seeded phase-0 launches
     int helper_max_n;          // LAPWARM_HELPER_MAX_N: largest n that gets helper workgroups
-    int helpers_per_instance;  // LAPWARM_HELPERS_PER_INSTANCE: helper workgroups per instance, 1..4
+    int helpers_per_instance;  // LAPWARM_HELPERS_PER_INSTANCE: helper workgroups per instance, 1..4 (tested: 2, 4)
     int coop;                  // LAPWARM_COOP=0: never plan the cooperative shortest-path kernel
-    int coop_min_n;            // LAPWARM_COOP_MIN_N: smallest n that takes the cooperative chain
-    int coop_ch;               // LAPWARM_COOP_CH: forced positions per lane {1,2,4,8,16} (0: by size)
-    int coop_xcd_stores;       // LAPWARM_COOP_XCD_STORES=0: mailbox stores stay agent-scope on one XCD
-    int coop_relaunches;       // LAPWARM_COOP_RELAUNCHES: (cooperative, phase 3) pairs per solve, 0..4096
+    int coop_min_n;            // LAPWARM_COOP_MIN_N: smallest n that takes the cooperative chain (tested: 1)
+    int coop_ch;               // LAPWARM_COOP_CH: forced positions per lane {1,2,4,8,16} (0: by size) (tested: all)
+    int coop_xcd_stores;       // LAPWARM_COOP_XCD_STORES=0: mailbox stores stay agent-scope on one XCD (tested)
+    int coop_relaunches;       // LAPWARM_COOP_RELAUNCHES: (cooperative, phase 3) pairs per solve, 0..4096 (tested: 0, 1)
+    // "tested": tests/test_gpu_coop_instantiations.py sweeps the setting against the oracle
 };
 
 int env_switch(const char *name)  // on unless the first character is '0'

@@ -5,6 +5,7 @@
 // fast iteration (no Python / torch start-up); tests/test_gpu_parity.py wraps it for pytest.
 //
 // usage: parity_driver [max_n] [reps] [verbose]
+// environment: PARITY_SIZES=n1,n2,... (replaces the size list), PARITY_ONLY=fam:kind:n (one case)
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -139,14 +140,33 @@ int main(int argc, char **argv)
     const char *only = getenv("PARITY_ONLY");
     const char *fams[] = {"uniform", "int9", "int100", "tie", "sparse", "metric", "clustered", "twozero", "sparse_neg", "uniform1e8"};
     const char *kinds[] = {"zeros", "rowmin", "rowmin32", "noisy", "randu", "huge", "arr"};
-    const int sizes[] = {1, 2, 3, 5, 8, 16, 33, 64, 100, 128, 200, 256, 400, 512, 777, 1024, 2048, 4096};
+    std::vector<int> sizes = {1, 2, 3, 5, 8, 16, 33, 64, 100, 128, 200, 256, 400, 512, 777, 1024, 2048, 4096};
+    // PARITY_SIZES=n1,n2,...: these sizes instead of the built-in list (max_n is then ignored)
+    const char *size_list = getenv("PARITY_SIZES");
+    if (size_list) {
+        sizes.clear();
+        for (const char *s = size_list; *s;) {
+            char *end;
+            const long n = strtol(s, &end, 10);
+            if (end == s || n < 1 || n > 16384 || (*end && *end != ',')) {
+                fprintf(stderr, "PARITY_SIZES: expected a comma-separated list of sizes 1..16384, got '%s'\n", size_list);
+                return 2;
+            }
+            sizes.push_back((int)n);
+            s = *end ? end + 1 : end;
+        }
+        if (sizes.empty()) {
+            fprintf(stderr, "PARITY_SIZES is set but empty\n");
+            return 2;
+        }
+    }
     int total = 0, bad = 0;
     long long branch_hist[5] = {0, 0, 0, 0, 0};
     int ret_hist_m3 = 0, proj_cases = 0, arr_cases = 0;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<double> C, u, v;
     for (int n : sizes) {
-        if (n > max_n) break;
+        if (!size_list && n > max_n) break;
         for (const char *fam : fams) {
             for (const char *kind : kinds) {
                 if (!strcmp(kind, "arr") && strcmp(fam, "uniform1e8")) continue;
@@ -220,7 +240,8 @@ int main(int argc, char **argv)
         }
         {
             const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            printf("[n<=%d] cases=%d bad=%d elapsed=%.1fs\n", n, total, bad, secs);
+            // coop_members > 0: the plan runs this size's shortest paths in the cooperative kernel
+            printf("[n<=%d] cases=%d bad=%d elapsed=%.1fs coop_members=%d\n", n, total, bad, secs, lapwarm_coop_members(n));
             fflush(stdout);
         }
     }

@@ -388,6 +388,45 @@ def test_forced_cooperative_geometry_without_an_instantiation_is_not_planned():
     assert r.stdout.split() == ["0", "10"], r.stdout
 
 
+def test_cooperative_configurations_are_what_the_planner_plans():
+    """tests/coop_configs_common.py: every row's (environment, n) gives the member count and the
+    coop_ssp_kernel<CH, NL> it names, the rows together reach all twelve instantiations of kCoopKernels, and
+    the switch sweeps reach the plan (agent-scope stores, relaunch pairs, helpers per instance) at every size.
+    One fresh interpreter per distinct environment: the library reads its settings once."""
+    import coop_configs_common as cc
+    assert {c.kernel for c in cc.CONFIGS} == {(1, 1), (1, 2), (2, 1), (2, 2), (4, 1), (4, 2), (4, 3), (8, 1), (8, 2),
+                                              (8, 3), (16, 1), (16, 2)} == cc.COOP_KERNELS
+    # kCoopKernels itself: {ch, nl, launch_cfg<ch, nl>} entries in csrc/coop_ssp.hip
+    src = (PKG / "csrc" / "coop_ssp.hip").read_text()
+    table = src[src.index("kCoopKernels[] = {"):]
+    shipped = re.findall(r"\{(\d+), (\d+), launch_cfg<(\d+), (\d+)>\}", table[:table.index("};")])
+    assert len(shipped) == 12 and all(e[:2] == e[2:] for e in shipped), shipped
+    assert {(int(ch), int(nl)) for ch, nl, _, _ in shipped} == cc.COOP_KERNELS
+    assert len({c.label for c in cc.CONFIGS}) == len(cc.CONFIGS)
+    envs = []
+    for c in cc.CONFIGS:
+        if c.env not in envs:
+            envs.append(c.env)
+    assert len(envs) == 6  # default, MIN_N alone, MIN_N + CH in {1, 2, 8, 16}
+    for env in envs:
+        rows = [c for c in cc.CONFIGS if c.env == env]
+        for c, (members, plan) in zip(rows, cc.planned(env, [c.n for c in rows])):
+            ch, nl = c.kernel
+            assert members == c.members > 0, (c.label, members)
+            assert (4 * members + 87) // 64 == nl, (c.label, members)
+            assert (members - 1) * 64 * ch < c.n <= members * 64 * ch, c.label  # with n, the member count pins CH
+            assert (plan["coop_ch"], plan["coop_nl"], plan["coop_members"]) == (ch, nl, members), (c.label, plan)
+            assert plan["shape"] == 2 and plan["helper"] == 0, (c.label, plan)  # the cooperative chain
+            assert plan["coop_pairs"] == 96 and plan["coop_xcd_stores"] == 1, (c.label, plan)
+    for s in cc.SWITCH_SWEEPS:
+        assert len(s.sizes) == len(s.members)
+        for n, want, (members, plan) in zip(s.sizes, s.members, cc.planned(s.env, s.sizes)):
+            assert members == want == plan["coop_members"], (s.label, n, members)
+            assert (plan["shape"] == 2) == (want > 0), (s.label, n, plan)
+            for field, value in s.plan.items():
+                assert plan[field] == value, (s.label, n, field, plan)
+
+
 # ---- the solve plan (csrc/solve_plan.hip) against tests/golden/solve_plans.json, recorded from the library
 # before the planner moved out of the kernel files: a wrong threads / ch / ldsl / tb / helper / cooperative
 # decision still solves correctly, so only a table catches it
