@@ -17,6 +17,7 @@
 #include "extend_costs.hpp"
 #include "extend_ragged.hpp"
 #include "jv_solver.hpp"
+#include "lapmod_sparse.hpp"
 #include "onegnn_refine.hpp"
 #include "oracle_duals.hpp"
 #include "ragged_batch.hpp"
@@ -873,6 +874,91 @@ int lapwarm_lapjv_extended_ragged(const double *C, const long long *offsets, con
     if (int rc = lapjv_ragged_launches(w.E, w.e_off, w.e_n, 0, batch, N, w.xs, w.ys, ret, stats, groups, n_groups, stream))
         return rc;
     HIP_TRY(launch_extended_finish_ragged(g, w.xs, w.ys, ret, x, y, opt, matched, w.gath, stream));
+    return 0;
+}
+
+// ---- sparse LAPMOD of a batch of CSR problems (lapmod_sparse.hip) ----
+// Workspace: the state offsets [batch], then the state of every instance above the LDS bound, one behind the other.
+struct LapmodWs {
+    long long *ws_off;
+    unsigned char *state;
+    size_t state_bytes, bytes;
+    int lds_n;  // the largest host size that keeps its state in LDS
+    bool any_global;
+};
+
+static int lapmod_layout(void *ws, const int *host_sizes, const long long *host_nnz, int batch, int N, LapmodWs *w)
+{
+    if (batch <= 0 || batch > 65535 || !host_sizes) return -2;
+    const int lds_max = lapmod_lds_max_n();
+    size_t state = 0;
+    w->lds_n = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int n = host_sizes[b];
+        if (n < 1 || (N > 0 && n > N)) return -2;
+        if (n > kLapmodMaxN) return -5;
+        if (host_nnz && (host_nnz[b] < 0 || host_nnz[b] > (long long)n * n)) return -2;
+        if (n <= lds_max) {
+            if (n > w->lds_n) w->lds_n = n;
+        } else {
+            state += lapmod_state_bytes(n);
+        }
+    }
+    Carver c{reinterpret_cast<unsigned char *>(ws), 0};
+    w->ws_off = c.take<long long>((size_t)batch);
+    w->state = c.take<unsigned char>(state);
+    w->state_bytes = state;
+    w->any_global = state > 0;
+    w->bytes = c.off;
+    return 0;
+}
+
+size_t lapwarm_lapmod_workspace_bytes(const int *sizes, const long long *nnz, int batch)
+{
+    LapmodWs w;
+    if (lapmod_layout(nullptr, sizes, nnz, batch, 0, &w)) return 0;
+    return w.bytes;
+}
+
+int lapwarm_lapmod_lds_max_n(void) { return lapmod_lds_max_n(); }
+
+int lapwarm_lapmod_ragged(const double *cc, const int *kk, const int *ii, const long long *nnz_offsets,
+                          const long long *row_offsets, const int *sizes, const int *host_sizes, int batch, int N,
+                          int fp_version, int *x, int *y, double *v, int *ret, long long *stats, void *workspace,
+                          size_t workspace_bytes, void *stream_)
+{
+    if (N <= 0 || fp_version < 1 || fp_version > 3) return -2;
+    if (N > kLapmodMaxN) return -5;
+    LapmodWs w;
+    if (int rc = lapmod_layout(workspace, host_sizes, nullptr, batch, N, &w)) return rc;
+    if (!cc || !kk || !ii || !nnz_offsets || !row_offsets || !sizes || !x || !y || !ret || !workspace) return -2;
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return -2;
+    if (workspace_bytes < w.bytes) {
+        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
+        return -1;
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    LapmodParams p;
+    p.cc = cc;
+    p.kk = kk;
+    p.ii = ii;
+    p.nnz_off = nnz_offsets;
+    p.row_off = row_offsets;
+    p.sizes = sizes;
+    p.batch = batch;
+    p.N = N;
+    p.fp_version = fp_version;
+    p.lds_n = w.lds_n;
+    p.x = x;
+    p.y = y;
+    p.v = v;
+    p.ret = ret;
+    p.stats = stats;
+    p.ws_off = w.any_global ? w.ws_off : nullptr;
+    p.ws_state = w.state;
+    p.ws_state_bytes = w.state_bytes;
+    if (w.any_global) HIP_TRY(launch_lapmod_plan(p, stream));
+    HIP_TRY(launch_lapmod(p, stream));
     return 0;
 }
 

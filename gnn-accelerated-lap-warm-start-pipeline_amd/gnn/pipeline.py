@@ -175,6 +175,54 @@ def extended_pack(costs, cost_limit=float("inf"), device="cuda:0") -> ExtendedPa
     return ExtendedPack(C, offs_d, lim_d, rows_d, cols_d, 0, host_rows, host_cols, host_limits)
 
 
+class SparsePack:
+    """A batch of CSR problems on the device, as lapwarm_lapmod_ragged takes it: cc fp64 and kk int32 (all entries,
+    one instance behind the other), ii int32 (n_b + 1 local row starts per instance), nnz_offsets, row_offsets (B,)
+    int64 and sizes (B,) int32, and the sizes and entry counts on the host."""
+    __slots__ = ("cc", "kk", "ii", "nnz_offsets", "row_offsets", "sizes", "host_sizes", "host_nnz")
+
+    def __init__(self, cc, kk, ii, nnz_offsets, row_offsets, sizes, host_sizes, host_nnz):
+        self.cc, self.kk, self.ii = cc, kk, ii
+        self.nnz_offsets, self.row_offsets, self.sizes = nnz_offsets, row_offsets, sizes
+        self.host_sizes, self.host_nnz = host_sizes, host_nnz
+
+
+def sparse_pack(problems, device="cuda:0") -> SparsePack:
+    """Host-side half of a lapmod_ragged call: `problems` is a sequence of (n, cc, ii, kk) (lap._lapmod checks
+    them); everything is packed into one host block and copied once."""
+    probs = [(int(n), np.ascontiguousarray(cc, dtype=np.float64), np.ascontiguousarray(ii, dtype=np.int32),
+              np.ascontiguousarray(kk, dtype=np.int32)) for n, cc, ii, kk in problems]
+    if not probs:
+        raise ValueError("at least one problem expected")
+    for n, cc, ii, kk in probs:
+        if n < 1 or ii.shape != (n + 1,) or cc.ndim != 1 or cc.shape != kk.shape or int(ii[-1]) != cc.size:
+            raise ValueError("sparse_pack: (n, cc, ii, kk) with len(ii) == n + 1 and ii[n] == len(cc) == len(kk)")
+        if cc.size >= 2 ** 31:
+            raise ValueError("sparse_pack: an instance must have fewer than 2**31 entries (ii is int32)")
+    B = len(probs)
+    host_sizes = [p[0] for p in probs]
+    host_nnz = [int(p[1].size) for p in probs]
+    nnz_off = np.concatenate(([0], np.cumsum(host_nnz)[:-1])).astype(np.int64)
+    row_off = np.concatenate(([0], np.cumsum([n + 1 for n in host_sizes])[:-1])).astype(np.int64)
+    total, rows = int(sum(host_nnz)), int(sum(host_sizes)) + B
+    o_kk = 8 * total
+    o_ii = o_kk + 4 * total
+    o_meta = (o_ii + 4 * rows + 7) & ~7
+    block = np.zeros((o_meta + 20 * B,), dtype=np.uint8)
+    block[:o_kk].view(np.float64)[:] = np.concatenate([p[1] for p in probs])
+    block[o_kk:o_ii].view(np.int32)[:] = np.concatenate([p[3] for p in probs])
+    block[o_ii:o_ii + 4 * rows].view(np.int32)[:] = np.concatenate([p[2] for p in probs])
+    block[o_meta:o_meta + 8 * B].view(np.int64)[:] = nnz_off
+    block[o_meta + 8 * B:o_meta + 16 * B].view(np.int64)[:] = row_off
+    block[o_meta + 16 * B:].view(np.int32)[:] = host_sizes
+    _hip.require_device()
+    d = torch.from_numpy(block).to(torch.device(device))
+    return SparsePack(d[:o_kk].view(torch.float64), d[o_kk:o_ii].view(torch.int32),
+                      d[o_ii:o_ii + 4 * rows].view(torch.int32), d[o_meta:o_meta + 8 * B].view(torch.int64),
+                      d[o_meta + 8 * B:o_meta + 16 * B].view(torch.int64), d[o_meta + 16 * B:].view(torch.int32),
+                      host_sizes, host_nnz)
+
+
 class WarmStartPipeline:
     """Batched, device-resident warm-start solve."""
 
@@ -367,6 +415,38 @@ class WarmStartPipeline:
         if _hip.check(rc, "lapjv_extended_ragged") != 0:
             raise RuntimeError(f"lapwarm_lapjv_extended_ragged failed (code {rc}): {_hip.last_error()}")
         return {"x": x, "y": y, "opt": opt, "matched": matched, "ret": ret, "stats": stats}
+
+    def lapmod_ragged(self, pack: SparsePack, fp_version: int = 3, want_stats: bool = True) -> dict:
+        """Sparse LAPMOD of every instance of a SparsePack in one call (lapwarm_lapmod_ragged), inputs read where
+        they are.  Returns x, y (B, N) int32 with -1 beyond n_b, v (B, N) fp64 (the final column duals, NaN beyond
+        n_b and where ret != 0), ret (B,) int32 (0 solved, 1 no perfect matching: x, y -1) and stats (B, 32) int64
+        or None.  Everything is enqueued on the current stream."""
+        if not isinstance(pack, SparsePack):
+            raise TypeError(f"Argument 'pack' must be a SparsePack, not {type(pack).__name__}")
+        if isinstance(fp_version, bool) or not isinstance(fp_version, (int, np.integer)) or not 1 <= fp_version <= 3:
+            raise ValueError(f"fp_version must be FP_1, FP_2 or FP_DYNAMIC (1, 2, 3), not {fp_version!r}")
+        B, N, dev = len(pack.host_sizes), max(pack.host_sizes), pack.cc.device
+        host_sizes = (ct.c_int * B)(*pack.host_sizes)
+        host_nnz = (ct.c_longlong * B)(*pack.host_nnz)
+        nbytes = int(self.lib.lapwarm_lapmod_workspace_bytes(host_sizes, host_nnz, B))
+        if nbytes == 0:
+            raise ValueError("lapmod_ragged: a batch of 1..65535 instances with 1 <= n <= 65535 expected")
+        x = torch.empty((B, N), dtype=torch.int32, device=dev)
+        y = torch.empty((B, N), dtype=torch.int32, device=dev)
+        v = torch.empty((B, N), dtype=torch.float64, device=dev)
+        ret = torch.empty((B,), dtype=torch.int32, device=dev)
+        stats = torch.empty((B, 32), dtype=torch.int64, device=dev) if want_stats else None
+        bucket = max(1 << 16, 1 << (nbytes - 1).bit_length())
+        ws, cap = self._cached_workspace(("lapmod_ragged", bucket), lambda: bucket)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lapwarm_lapmod_ragged(
+            pack.cc.data_ptr(), pack.kk.data_ptr(), pack.ii.data_ptr(), pack.nnz_offsets.data_ptr(),
+            pack.row_offsets.data_ptr(), pack.sizes.data_ptr(), host_sizes, B, N, int(fp_version), x.data_ptr(),
+            y.data_ptr(), v.data_ptr(), ret.data_ptr(), stats.data_ptr() if want_stats else None, ws.data_ptr(), cap,
+            ct.c_void_p(stream))
+        if _hip.check(rc, "lapmod_ragged") != 0:
+            raise RuntimeError(f"lapwarm_lapmod_ragged failed (code {rc}): {_hip.last_error()}")
+        return {"x": x, "y": y, "v": v, "ret": ret, "stats": stats}
 
     def _extended_many_parts(self, costs, extend_cost=True, cost_limit=float("inf"), want_stats=True):
         """lapjv_extended_many before the results are cut up: a list of (indices, rows, cols, padded dict), one

@@ -68,6 +68,10 @@ SIGNATURES = {
     "lapwarm_lapjv_extended_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_ip, c_ip, c_dp, ct.c_int, ct.c_int,
                                                  ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                  c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_lapmod_workspace_bytes": (ct.c_size_t, [c_ip, c_llp, ct.c_int]),
+    "lapwarm_lapmod_lds_max_n": (ct.c_int, []),
+    "lapwarm_lapmod_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ip, ct.c_int, ct.c_int, ct.c_int, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
     "lapwarm_project_round_batched":(ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
                                                  ct.c_size_t, c_vp]),
     "lapwarm_reduce_costs_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, ct.c_int, c_vp, c_vp,

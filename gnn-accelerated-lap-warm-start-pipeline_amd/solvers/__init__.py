@@ -7,11 +7,13 @@ Oracle duals (compute_oracle_duals, dual_from_matching_diff_constraints, make_fe
 run on the device too (csrc/oracle_duals.hip); their matching comes from lap.lapjv instead of
 SciPy (solvers/dual_computation.py).
 
-Not provided (outside the hot path): LAPMODSolver, logging helpers,
-seed_greedy_matching.
+LAPMODSolver wraps the sparse solver (lap.lapmod_sparse, csrc/lapmod_sparse.hip).
+
+Not provided (outside the hot path): logging helpers, seed_greedy_matching.
 """
 from .scipy_solver import SciPySolver
 from .lap_solver import LAPSolver, SeededLAPSolver
+from .lapmod_solver import LAPMODSolver
 from .warmstart_solver import WarmStartLAPSolver
 from .timing import time_solver_rigorous
 from .advanced_dual import (project_feasible, reduce_costs, check_dual_feasible, check_dual_and_match,
@@ -34,7 +36,7 @@ from .generators import (
 )
 
 __all__ = [
-    "SciPySolver", "LAPSolver", "SeededLAPSolver", "WarmStartLAPSolver", "time_solver_rigorous",
+    "SciPySolver", "LAPSolver", "SeededLAPSolver", "LAPMODSolver", "WarmStartLAPSolver", "time_solver_rigorous",
     "project_feasible", "reduce_costs", "check_dual_feasible", "check_dual_and_match", "make_feasible_duals",
     "compute_oracle_duals", "dual_from_matching_diff_constraints", "verify_solver_correctness",
     "seed_row_col_minima", "seed_noisy_optimal",

@@ -280,6 +280,35 @@ int lapwarm_lapjv_extended_ragged(const double *C, const long long *offsets, con
                                   int *y, double *opt, int *matched, int *ret, long long *stats, void *workspace,
                                   size_t workspace_bytes, void *stream);
 
+/* Sparse LAPMOD (LAP/_lapjv_cpp/lapmod.cpp, lapmod_internal) of a batch of CSR problems of different n and nnz in
+ * one call: one workgroup per instance.  cc (fp64) and kk (int32) hold the entries of all instances one behind the
+ * other, instance b from nnz_offsets[b]; ii (int32) holds n_b + 1 row starts per instance from row_offsets[b],
+ * counted from the instance's own first entry (ii[0] = 0).  nnz_offsets, row_offsets and sizes are DEVICE arrays
+ * [batch]; host_sizes is the HOST copy the call is planned from.  fp_version: 1 find_path_sparse_1, 2
+ * find_path_sparse_2, 3 chosen per matrix as the reference's FP_DYNAMIC does (nnz / n^2 > 0.25: 1).
+ * x, y [batch][N] int32, -1 beyond n_b; v [batch][N] fp64 or NULL: the final column duals (NaN beyond n_b and where
+ * ret != 0); ret [batch]; stats [batch][32] int64 or NULL: 0 free rows after column reduction and reduction transfer,
+ * 1 and 2 after the first and second ARR pass (-1: not run), 3 ARR iterations, 4 paths, 5 find calls, 6 scan steps,
+ * 7 the search that ran (0 none, 1, 2), 8 n, 9 nnz, 10 state in LDS (1) or in the workspace (0), 11 the search
+ * fp_version selects for the matrix.  x, y and v of an instance with ret 0 are the reference's bit for bit.
+ * ret: 0 solved; 1 no perfect matching (find_path_sparse_2 finds no candidate or scans a column that is absent from
+ * its row, or the smallest d of a find_path_sparse_1 search is >= LARGE; the reference reads outside its arrays
+ * there): x, y -1; 2 the instance is not what was planned or is malformed on the device (size outside 1..N, row
+ * starts not ascending from 0, a row longer than n, a column outside 0..n-1, a cost outside [0, LARGE) or NaN):
+ * x, y -1; < 0 a loop bound derived from n and nnz was exceeded.
+ * Solver state lives in LDS for n_b <= lapwarm_lapmod_lds_max_n() (the largest n whose 48 n + 8 ceil(n / 32) bytes
+ * fit 160 KB) and in the workspace above it.  lapwarm_lapmod_workspace_bytes: sizes and nnz are HOST arrays [batch]
+ * (nnz may be NULL); 0 where the call would return -2 or -5.  Kernels only, no host synchronisation: the call can
+ * be captured into a graph.  Returns 0, -2 (batch outside 1..65535, N <= 0, a host size outside 1..N, fp_version
+ * outside 1..3, a NULL pointer other than v and stats, a workspace that is not 16-byte aligned), -5 (N or a host size > 65535: the reference's 32-bit `current * n` and n * n wrap from 65536 on),
+ * -1 (workspace too small), <= -1000 HIP error; only the last follows device work. */
+size_t lapwarm_lapmod_workspace_bytes(const int *sizes, const long long *nnz, int batch);
+int lapwarm_lapmod_lds_max_n(void);
+int lapwarm_lapmod_ragged(const double *cc, const int *kk, const int *ii, const long long *nnz_offsets,
+                          const long long *row_offsets, const int *sizes, const int *host_sizes, int batch, int N,
+                          int fp_version, int *x, int *y, double *v, int *ret, long long *stats, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* One round of project_feasible: u = min(u, rowmin(C-v)); v = min(v, colmin(C-u));
  * gmin[b] = min((C-u)-v).  The host loop decides when to stop. */
 int lapwarm_project_round_batched(const double *C, int batch, int n, double *u, double *v,

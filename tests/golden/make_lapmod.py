@@ -1,0 +1,278 @@
+"""Writes tests/golden/lapmod_cases.npz: sparse LAPMOD inputs and what the reference's lapmod_internal returns for
+them with FP_1, FP_2 and FP_DYNAMIC.
+
+    python tests/golden/make_lapmod.py REFERENCE_ROOT [LDS_MAX_N]
+
+compiles REFERENCE_ROOT/LAP/_lapjv_cpp/lapmod.cpp into a temporary directory (nothing of it is kept), calls
+lapmod_internal through ctypes and stores data only.  Per case `c`: n, cc (divided by ccscale where it is stored as integers), ii, kk; solvable (a perfect matching
+exists), strict (unsolvable and certain to end with ret = 1 on the device: every row has an entry, and row 0 is
+not left holding an empty column by the column reduction), aug (the reference reaches the augmentation phase: an
+fp_version outside the enum makes it return -2 exactly then); per fp_version v in 1, 2, 3: ret_v, x_v, y_v, and
+for solvable cases and v in 1, 2 the final column duals v_v (the phases called with a caller-owned v)
+(unsolvable cases are run with FP_1 only and when it is FP_1 that FP_DYNAMIC selects: find_path_sparse_2 reads
+outside its arrays there).  LDS_MAX_N is lapwarm_lapmod_lds_max_n() of the built library (default 3395).
+"""
+import ctypes as ct
+import subprocess
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+
+HERE = Path(__file__).resolve().parent
+INF = np.inf
+
+
+def build(ref_root, tmp):
+    src = Path(ref_root) / "LAP" / "_lapjv_cpp"
+    so = Path(tmp) / "liblapmod_ref.so"
+    glue = Path(tmp) / "glue.cpp"  # (the C++ symbol behind an unmangled name)
+    # lapmod_c: the entry itself.  lapmod_v: the same three phases, called as lapmod_internal calls them, with v
+    # owned by the caller so that the final column duals can be stored.
+    glue.write_text(
+        '#include <vector>\n#include "lapjv.h"\n'
+        'int_t _ccrrt_sparse(const uint_t, cost_t *, uint_t *, uint_t *, int_t *, int_t *, int_t *, cost_t *);\n'
+        'int_t _carr_sparse(const uint_t, cost_t *, uint_t *, uint_t *, const uint_t, int_t *, int_t *, int_t *, '
+        'cost_t *);\n'
+        'int_t _ca_sparse(const uint_t, cost_t *, uint_t *, uint_t *, const uint_t, int_t *, int_t *, int_t *, '
+        'cost_t *, int);\n'
+        'extern "C" int lapmod_c(unsigned n, double *cc, unsigned *ii, unsigned *kk, int *x, int *y, int fp)\n'
+        '{ return lapmod_internal(n, cc, ii, kk, x, y, (fp_t)fp); }\n'
+        'extern "C" int lapmod_v(unsigned n, double *cc, unsigned *ii, unsigned *kk, int *x, int *y, double *v, '
+        'int fp)\n'
+        '{ std::vector<int_t> fr(n); int ret = _ccrrt_sparse(n, cc, ii, kk, fr.data(), x, y, v);\n'
+        '  for (int i = 0; ret > 0 && i < 2; ++i) ret = _carr_sparse(n, cc, ii, kk, ret, fr.data(), x, y, v);\n'
+        '  if (ret > 0) ret = _ca_sparse(n, cc, ii, kk, ret, fr.data(), x, y, v, fp);\n  return ret; }\n')
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", str(src), str(src / "lapmod.cpp"),
+                    str(glue), "-o", str(so)], check=True)
+    lib = ct.CDLL(str(so))
+    lib.lapmod_internal = lib.lapmod_c
+    lib.lapmod_internal.restype = ct.c_int
+    lib.lapmod_internal.argtypes = [ct.c_uint, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p,
+                                    ct.c_int]
+    lib.lapmod_v.restype = ct.c_int
+    lib.lapmod_v.argtypes = [ct.c_uint] + [ct.c_void_p] * 6 + [ct.c_int]
+    return lib
+
+
+def ref_solve(lib, n, cc, ii, kk, fp):
+    cc = np.ascontiguousarray(cc, dtype=np.float64)
+    ii = np.ascontiguousarray(ii, dtype=np.uint32)
+    kk = np.ascontiguousarray(kk, dtype=np.uint32)
+    x = np.full(n, -7, dtype=np.int32)
+    y = np.full(n, -7, dtype=np.int32)
+    t = time.perf_counter()
+    ret = lib.lapmod_internal(n, cc.ctypes.data, ii.ctypes.data, kk.ctypes.data, x.ctypes.data, y.ctypes.data, fp)
+    return ret, x, y, time.perf_counter() - t
+
+
+def ref_duals(lib, n, cc, ii, kk, fp):
+    """(ret, x, y, v) of the reference's phases with a caller-owned v."""
+    cc = np.ascontiguousarray(cc, dtype=np.float64)
+    ii = np.ascontiguousarray(ii, dtype=np.uint32)
+    kk = np.ascontiguousarray(kk, dtype=np.uint32)
+    x, y, v = np.full(n, -7, dtype=np.int32), np.full(n, -7, dtype=np.int32), np.full(n, np.nan)
+    ret = lib.lapmod_v(n, cc.ctypes.data, ii.ctypes.data, kk.ctypes.data, x.ctypes.data, y.ctypes.data,
+                       v.ctypes.data, fp)
+    return ret, x, y, v
+
+
+def from_masked(cost):
+    cost = np.asarray(cost, dtype=np.float64)
+    mask = np.isfinite(cost)
+    n = cost.shape[0]
+    ii = np.zeros(n + 1, dtype=np.int64)
+    ii[1:] = np.cumsum(mask.sum(axis=1))
+    kk = np.tile(np.arange(cost.shape[1]), n)[mask.ravel()]
+    return n, cost[mask], ii, kk
+
+
+def random_sparse(rng, n, k, draw, single_rows=0.0):
+    """k random columns per row plus a hidden permutation (so a perfect matching exists); `single_rows` of the
+    rows keep the permutation entry only."""
+    perm = rng.permutation(n)
+    cost = np.full((n, n), INF)
+    for i in range(n):
+        cols = [perm[i]]
+        if rng.random() >= single_rows:
+            cols = np.union1d(cols, rng.choice(n, size=min(k, n), replace=False))
+        cost[i, cols] = draw(len(cols))
+    return cost
+
+
+def has_perfect_matching(n, ii, kk):
+    match = [-1] * n
+
+    def aug(i, seen):
+        for j in kk[ii[i]:ii[i + 1]]:
+            if not seen[j]:
+                seen[j] = True
+                if match[j] < 0 or aug(match[j], seen):
+                    match[j] = i
+                    return True
+        return False
+    sys.setrecursionlimit(100000)
+    return all(aug(i, [False] * n) for i in range(n))
+
+
+def certain_ret1(n, cc, ii, kk):
+    """Every row has an entry, and the backward pass of the column reduction does not give row 0 an empty column."""
+    if np.any(np.diff(ii) == 0):
+        return False
+    v = np.full(n, 1e6)
+    y = np.zeros(n, dtype=np.int64)
+    for i in range(n):
+        for k in range(ii[i], ii[i + 1]):
+            if cc[k] < v[kk[k]]:
+                v[kk[k]], y[kk[k]] = cc[k], i
+    empty = np.ones(n, dtype=bool)
+    empty[kk] = False
+    claim0 = np.flatnonzero(y == 0)
+    return not empty[claim0.max()] if claim0.size else True
+
+
+def main():
+    lib_tmp = tempfile.TemporaryDirectory()
+    lib = build(sys.argv[1], lib_tmp.name)
+    lds_max = int(sys.argv[2]) if len(sys.argv) > 2 else 3395
+    rng = np.random.default_rng(20240611)
+    cases = []  # (label, n, cc, ii, kk, kind)
+
+    def add(label, cost, kind=""):
+        cases.append((label,) + from_masked(cost) + (kind,))
+
+    k8 = np.array([[1000, 2, 11, 10, 8, 7, 6, 5], [6, 1000, 1, 8, 8, 4, 6, 7], [5, 12, 1000, 11, 8, 12, 3, 11],
+                   [11, 9, 10, 1000, 1, 9, 8, 10], [11, 11, 9, 4, 1000, 2, 10, 9], [12, 8, 5, 2, 11, 1000, 11, 9],
+                   [10, 11, 12, 10, 9, 12, 1000, 3], [10, 10, 10, 10, 6, 3, 1, 1000]], dtype=np.float64)
+    add("known8_dense", k8)
+    add("known8_masked", np.where(k8 == 1000, INF, k8))
+    for t, m in enumerate([[[1000, 4, 1], [1, 1000, 3], [5, 1, 1000]], [[5, 1000, 3], [1000, 2, 2], [1, 5, 1000]],
+                           [[1000, 1001, 1000], [1000, 1000, 1001], [1, 2, 3]], [[10, 10, 13], [4, 8, 8], [8, 5, 8]],
+                           [[11, 10, 6], [10, 11, 11], [11, 12, 15]], [[12, 4, 9], [16, 15, 14], [19, 13, 17]],
+                           [[2, 5, 7], [7, 10, 12], [1, 5, 9]],
+                           [[10, 6, 14, 1], [17, 18, 17, 15], [14, 17, 15, 8], [11, 13, 11, 4]]]):
+        add(f"known_square{t}", np.array(m, dtype=np.float64))
+    add("known_sparse_square", [[11, 20, INF, INF, INF], [12, INF, 12, INF, INF], [INF, 11, 10, 15, 9],
+                                [15, INF, INF, 22, INF], [13, INF, INF, INF, 15]])
+    # test_arr_loop.py:63-78: a 7 x 3 COO problem extended to 10 x 10 with cost limit 1e3
+    acc = [2.593883482138951146e-01, 3.080381437461217620e-01, 1.976243020727339317e-01, 2.462740976049606068e-01,
+           4.203993396282833528e-01, 4.286184525458427985e-01, 1.706431415909629434e-01, 2.192929371231896185e-01,
+           2.117769622802734286e-01, 2.604267578125001315e-01]
+    ai, aj = [0, 0, 1, 1, 2, 2, 5, 5, 6, 6], [0, 1, 0, 1, 1, 2, 0, 1, 0, 1]
+    ext = np.full((10, 10), INF)
+    for c, i, j in zip(acc, ai, aj):
+        ext[i, j] = c
+        ext[7 + j, 3 + i] = 0.0
+    for i in range(7):
+        ext[i, 3 + i] = 1e3
+    for j in range(3):
+        ext[7 + j, j] = 1e3
+    add("arr_loop", ext)
+    z = 0.0
+    add("infs_unsolvable0", [[z, z, z, INF, INF], [INF, INF, INF, z, z], [INF, INF, INF, z, z],
+                             [INF, INF, INF, z, z], [z, z, z, INF, INF]], "unsolvable")
+    add("infs_unsolvable1", [[19, 22, 16, INF, INF], [INF, INF, INF, 4, 13], [INF, INF, INF, 3, 14],
+                             [INF, INF, INF, 10, 12], [11, 14, 13, INF, INF]], "unsolvable")
+    uniq = np.full((4, 4), INF)
+    uniq[:3, :3] = [[1000, 4, 1], [1, 1000, 3], [5, 1, 1000]]
+    uniq[3, 3] = 0
+    add("inf_unique", uniq)
+    add("inf_col", [[z, INF, z, z, INF], [INF, INF, z, z, z], [INF, INF, INF, z, INF], [INF, INF, INF, z, z],
+                    [z, INF, z, INF, INF]], "unsolvable")
+    add("inf_row", [[z, z, z, z, INF], [INF, INF, z, z, z], [INF, INF, INF, INF, INF], [INF, INF, INF, z, z],
+                    [z, z, z, INF, INF]], "unsolvable")
+
+    def ints(hi):
+        return lambda m: rng.integers(1, hi + 1, size=m).astype(np.float64)
+
+    def cont(m):
+        return rng.random(m) * 100.0
+
+    for n in (1, 2, 3):
+        add(f"n{n}_dense_int", rng.integers(1, 6, size=(n, n)).astype(np.float64))
+        add(f"n{n}_dense_cont", rng.random((n, n)) * 10.0)
+    for n in (63, 64, 65, 257):
+        add(f"n{n}_sparse_tie", random_sparse(rng, n, 4, ints(5)), "tie")
+        add(f"n{n}_dense_tie", random_sparse(rng, n, (2 * n) // 5, ints(5)), "tie")
+        add(f"n{n}_sparse_cont", random_sparse(rng, n, 6, cont))
+        add(f"n{n}_dense_cont", random_sparse(rng, n, (2 * n) // 5, cont))
+    add("n64_single_rows", random_sparse(rng, 64, 4, ints(5), single_rows=0.25), "tie")
+    # an empty column, with row 0 holding the strict minimum of a later column
+    ec = random_sparse(rng, 20, 4, ints(5))
+    ec[:, 3] = INF
+    ec[0, 19] = 0.0
+    ec[1, 0] = 1.0  # (the row whose permutation entry was in column 3 keeps an entry)
+    for i in range(20):
+        if not np.isfinite(ec[i]).any():
+            ec[i, (i + 5) % 20 if (i + 5) % 20 != 3 else 4] = 2.0
+    add("empty_column", ec, "unsolvable")
+    # a column whose only two entries tie
+    tc = random_sparse(rng, 32, 4, ints(5))
+    tc[:, 7] = INF
+    tc[5, 7] = tc[21, 7] = 3.0
+    add("tied_column", tc, "tie")
+    # the LDS / workspace boundary and a large instance: costs 1..40 keep the row reduction short
+    mostly_fine = ints(40)
+
+    add(f"n{lds_max}_lds_bound", random_sparse(rng, lds_max, 4, mostly_fine), "tie")
+    add(f"n{lds_max + 1}_above_lds", random_sparse(rng, lds_max + 1, 4, mostly_fine), "tie")
+    add("n4096_k16", random_sparse(rng, 4096, 16, mostly_fine), "tie")
+
+    out = {"labels": np.array([c[0] for c in cases]), "lds_max_n": np.int64(lds_max)}
+    tie_aug, disagree = {}, 0
+    for label, n, cc, ii, kk, kind in cases:
+        solvable = kind != "unsolvable"
+        if n <= 300:  # (the larger ones hold a permutation by construction)
+            assert has_perfect_matching(n, ii, kk) == solvable, label
+        dyn = 1 if ii[n] / float(n * n) > 0.25 else 2
+        aug = ref_solve(lib, n, cc, ii, kk, 99)[0] == -2
+        small = n < 32768
+        out[f"{label}__n"] = np.int64(n)
+        scale = next((q for q in (1, 64) if np.all(cc * q == np.floor(cc * q)) and cc.max() * q < 65536), 0)
+        if scale:
+            out[f"{label}__cc"] = (cc * scale).astype(np.uint16)  # cc = stored / ccscale, exactly
+        else:
+            out[f"{label}__cc"] = cc.astype(np.float32) if np.all(cc == cc.astype(np.float32)) else cc
+        out[f"{label}__ccscale"] = np.int64(max(scale, 1))
+        out[f"{label}__ii"] = ii.astype(np.int32)
+        out[f"{label}__kk"] = kk.astype(np.int16 if small else np.int32)
+        out[f"{label}__solvable"] = np.bool_(solvable)
+        out[f"{label}__strict"] = np.bool_(not solvable and certain_ret1(n, cc, ii, kk))
+        out[f"{label}__aug"] = np.bool_(aug)
+        out[f"{label}__dyn"] = np.int64(dyn)
+        xs = {}
+        for fp in (1, 2, 3):
+            if not solvable and (fp == 2 or (fp == 3 and dyn == 2)):
+                continue
+            ret, x, y, secs = ref_solve(lib, n, cc, ii, kk, fp)
+            if solvable:
+                assert ret == 0 and np.array_equal(np.sort(x), np.arange(n)), (label, fp, ret)
+                assert np.array_equal(x[y], np.arange(n)), (label, fp)
+            xs[fp] = x
+            if solvable and fp != 3:  # (FP_DYNAMIC is one of the two: v_3 would repeat v_dyn)
+                vret, vx, vy, v = ref_duals(lib, n, cc, ii, kk, fp)
+                assert vret == ret and np.array_equal(vx, x) and np.array_equal(vy, y), (label, fp)
+                assert np.all(np.isfinite(v)), (label, fp)
+                out[f"{label}__v_{fp}"] = v
+            out[f"{label}__ret_{fp}"] = np.int64(ret)
+            out[f"{label}__x_{fp}"] = x.astype(np.int16 if small else np.int32)
+            out[f"{label}__y_{fp}"] = y.astype(np.int16 if small else np.int32)
+            if n >= 257:
+                print(f"{label} fp={fp} aug={aug} reference {secs * 1e3:.2f} ms")
+        if 1 in xs and 2 in xs and not np.array_equal(xs[1], xs[2]):
+            disagree += 1
+        if kind == "tie" and n >= 63:
+            tie_aug.setdefault(n, []).append(aug)
+    for n, flags in tie_aug.items():
+        assert 2 * sum(flags) >= len(flags), (n, flags)
+    assert disagree >= 1
+    assert out["empty_column__strict"] and out["infs_unsolvable0__strict"] and out["inf_col__strict"]
+    path = HERE / "lapmod_cases.npz"
+    np.savez_compressed(path, **out)
+    print(f"{len(cases)} cases, {disagree} with FP_1 != FP_2, {path.stat().st_size} bytes")
+
+
+if __name__ == "__main__":
+    main()
