@@ -1,0 +1,37 @@
+// dual_gnn.hpp -- the two kernels of DualGNN's fused DualLayer attention (dual_gnn.hip).
+//
+// edge scores:  scores[b][dir][h][i][j] = g_{dir,h} . GELU(W2 GELU(W1 f(i,j) + b1) + b2), both directions in the
+//               natural [i][j] layout (nothing is stored transposed);
+// attention:    both directions in one launch.  The column direction reads scores[b][1] through LDS tiles whose
+//               global loads run along i's neighbour j, so its loads stay coalesced (16 queries x 64 keys per tile).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+namespace lapwarm {
+
+constexpr int kDualMaxHeads = 8;      // 2 * heads outputs fit the 16-wide MFMA tile
+constexpr int kDualMaxBatch = 32767;  // the attention grid is (tiles, heads, 2 * batch)
+constexpr int kDualEdgeHidden = 128;  // width of the edge MLP's two hidden layers (fixed by the model)
+constexpr int kDualEdgeIn = 10;
+
+struct DualAttnParams {
+    const float *scores;              // [batch][2][heads][n][n]
+    const float *a_row, *c_row;       // [batch][heads][n]: row direction, query i / key j
+    const float *a_col, *c_col;       // [batch][heads][n]: column direction, query j / key i
+    const float *kbias;               // [2][heads]
+    const unsigned char *mask;        // [batch][n] (0: padded node) or null
+    const float *row_val, *col_val;   // [batch][n][heads * head_dim]
+    float *row_msg, *col_msg;         // [batch][n][heads * head_dim]
+    int batch, n, heads, head_dim;
+};
+
+size_t dual_gnn_workspace_bytes(int batch, int n, int heads);  // the scores tensor; 0 for arguments out of range
+hipError_t launch_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                   const float *b2, const float *G, float *scores, int batch, int n, int heads,
+                                   hipStream_t stream);
+// heads <= 65535 here (the grid's y dimension): kDualMaxHeads limits the edge-scores kernel and the workspace only
+hipError_t launch_dual_attention(const DualAttnParams &p, hipStream_t stream);
+
+}  // namespace lapwarm

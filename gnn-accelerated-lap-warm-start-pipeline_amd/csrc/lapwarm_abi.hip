@@ -14,8 +14,10 @@
 
 #include "../../include/lapwarm_hip.h"
 #include "dense_sweeps.hpp"
+#include "dual_gnn.hpp"
 #include "extend_costs.hpp"
 #include "extend_ragged.hpp"
+#include "graph_features.hpp"
 #include "jv_solver.hpp"
 #include "lapmod_sparse.hpp"
 #include "onegnn_refine.hpp"
@@ -381,6 +383,50 @@ int lapwarm_refine_backward(const float *topk16, const float *u_pre, const float
     if (ws_bytes < refine_backward_workspace_bytes(rows, H)) return -2;
     HIP_TRY(launch_refine_backward(topk16, u_pre, w1, b1, grad_out, grad_wsum, grad_u, grad_w1, grad_b1, rows, H, ws,
                                    reinterpret_cast<hipStream_t>(stream_)));
+    return 0;
+}
+
+size_t lapwarm_graph_features_workspace_bytes(int batch, int n) { return graph_features_workspace_bytes(batch, n); }
+
+int lapwarm_graph_features_batched(const double *C, int batch, int n, const double *u, const float *posenc,
+                                   float *edge_out, float *row_out, float *col_out, void *ws, size_t ws_bytes,
+                                   void *stream_)
+{
+    if (batch < 1 || batch > kGraphMaxBatch || n < 1) return -2;
+    if (n > kGraphMaxN) return -5;
+    if (!C || !posenc || !edge_out || !row_out || !col_out || !ws) return -2;
+    if (ws_bytes < graph_features_workspace_bytes(batch, n)) return -1;
+    GraphFeatureParams p{C, u, posenc, batch, n, edge_out, row_out, col_out};
+    HIP_TRY(launch_graph_features(p, ws, reinterpret_cast<hipStream_t>(stream_)));
+    return 0;
+}
+
+size_t lapwarm_dual_gnn_workspace_bytes(int batch, int n, int heads) { return dual_gnn_workspace_bytes(batch, n, heads); }
+
+int lapwarm_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2, const float *b2,
+                             const float *G, float *scores, int batch, int n, int heads, void *stream_)
+{
+    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
+    if (n > 16384) return -5;
+    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !scores) return -2;
+    HIP_TRY(launch_dual_edge_scores(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads,
+                                    reinterpret_cast<hipStream_t>(stream_)));
+    return 0;
+}
+
+int lapwarm_dual_attention(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                           const float *c_col, const float *kbias, const unsigned char *mask, const float *row_val,
+                           const float *col_val, float *row_msg, float *col_msg, int batch, int n, int heads,
+                           int head_dim, void *stream_)
+{
+    // heads: the grid's y dimension, not kDualMaxHeads, which is the edge-scores kernel's tile limit
+    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > 65535 || head_dim < 1) return -2;
+    if (n > 16384) return -5;
+    if (!scores || !a_row || !c_row || !a_col || !c_col || !kbias || !row_val || !col_val || !row_msg || !col_msg)
+        return -2;
+    DualAttnParams p{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val, row_msg, col_msg,
+                     batch, n, heads, head_dim};
+    HIP_TRY(launch_dual_attention(p, reinterpret_cast<hipStream_t>(stream_)));
     return 0;
 }
 

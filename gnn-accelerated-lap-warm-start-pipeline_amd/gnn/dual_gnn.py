@@ -1,0 +1,222 @@
+"""DualGNN: graph attention over the O(n^2) edge features in both directions, predicting u and a v hint.
+
+Same constructor arguments, parameter names and shapes (reference state dicts load unchanged), call signature
+and output dict {"u", "v_hint"} as the reference module (gnn/dual_gnn.py:17-204).
+
+Two forwards:
+
+  * the FUSED path, taken when the module is in eval mode, the tensors are on CUDA, heads <= 8 and no gradient
+    is being recorded.  The reference materialises per layer a (B, N, N, hidden) edge embedding, two
+    (B, H, N, N, 3 head_dim) attention inputs and two attention matrices.  The edge embedding enters the layer
+    only through the attention scores, which are linear in it, so the last Linear(128, hidden) of the edge MLP
+    folds into the score weights (DualLayer.folded_parameters, DESIGN.md "DualGNN"):
+
+        score_row[h,i,j] = leaky_relu(a_h(i) + c_h(j) + g_h . h2(i,j) + k_h)
+
+    with h2 the 128-wide output of the edge MLP's second GELU.  Two HIP kernels do the rest (dual_gnn.hip):
+    lapwarm_dual_edge_scores (10 -> 128 -> 128 -> 2 heads per edge on the fp32 MFMA units) and
+    lapwarm_dual_attention (masked softmax and the weighted sum of the values, both directions).  The four
+    projections, the update MLPs and the LayerNorms stay with PyTorch-ROCm.  The path runs in float32 with
+    autocast DISABLED around it: a caller's `torch.autocast("cuda")` is ignored (exact f32 MFMA has no
+    reduced-precision variant to switch to, and the outputs seed an fp64 solver).
+
+  * the plain torch path otherwise (training mode, CPU tensors, a gradient being recorded, heads > 8), in the
+    reference's op order with its dropout placements: inside the edge MLP, on both attention-weight tensors and
+    in the two update MLPs.
+
+A backward for the fused path is out of scope: a gradient taken through the model runs the plain path.
+"""
+from __future__ import annotations
+
+import ctypes as ct
+from typing import Optional
+
+import torch
+from torch import nn
+
+from .features import EDGE_FEATURE_DIM, NODE_FEATURE_DIM
+
+FUSED_MAX_HEADS = 8
+EDGE_HIDDEN = 128
+
+
+def _records_grad(module, *tensors) -> bool:
+    if not torch.is_grad_enabled():
+        return False
+    return any(t.requires_grad for t in tensors) or any(p.requires_grad for p in module.parameters())
+
+
+class DualLayer(nn.Module):
+    def __init__(self, hidden_dim: int, heads: int = 4, dropout: float = 0.1) -> None:
+        super().__init__()
+        if hidden_dim % heads != 0:
+            raise ValueError("hidden_dim must be divisible by number of heads")
+        self.heads = heads
+        self.head_dim = hidden_dim // heads
+        self.edge_mlp = nn.Sequential(
+            nn.Linear(EDGE_FEATURE_DIM, EDGE_HIDDEN), nn.GELU(), nn.Dropout(dropout),
+            nn.Linear(EDGE_HIDDEN, EDGE_HIDDEN), nn.GELU(),
+            nn.Linear(EDGE_HIDDEN, hidden_dim))
+        self.row_proj = nn.Linear(hidden_dim, hidden_dim, bias=False)
+        self.col_proj = nn.Linear(hidden_dim, hidden_dim, bias=False)
+        self.row_val = nn.Linear(hidden_dim, hidden_dim, bias=False)
+        self.col_val = nn.Linear(hidden_dim, hidden_dim, bias=False)
+        self.attn_row_weight = nn.Parameter(torch.empty(heads, self.head_dim * 3))
+        self.attn_col_weight = nn.Parameter(torch.empty(heads, self.head_dim * 3))
+        self.attn_row_bias = nn.Parameter(torch.zeros(heads))
+        self.attn_col_bias = nn.Parameter(torch.zeros(heads))
+        self.dropout = nn.Dropout(dropout)
+        self.leaky_relu = nn.LeakyReLU(0.2)
+        self.row_update = nn.Sequential(nn.Linear(hidden_dim * 2, hidden_dim), nn.GELU(), nn.Dropout(dropout))
+        self.col_update = nn.Sequential(nn.Linear(hidden_dim * 2, hidden_dim), nn.GELU(), nn.Dropout(dropout))
+        self.row_norm = nn.LayerNorm(hidden_dim)
+        self.col_norm = nn.LayerNorm(hidden_dim)
+        nn.init.xavier_uniform_(self.attn_row_weight)
+        nn.init.xavier_uniform_(self.attn_col_weight)
+
+    # ---- the folding ---------------------------------------------------------------------------------------
+    def folded_parameters(self, row_proj: torch.Tensor, col_proj: torch.Tensor) -> dict:
+        """What the fused path passes to the kernels, from the projections (B, N, hidden) and the parameters:
+        a_row, c_row, a_col, c_col (B, H, N), G (2 H, 128) and kbias (2 H,), rows 0..H-1 the row direction.
+        attn_row_weight[h] = [w_r | w_c | w_e]; attn_col_weight[h] = [w_c | w_r | w_e]."""
+        H, D = self.heads, self.head_dim
+        B, N, _ = row_proj.shape
+        rp, cp = row_proj.reshape(B, N, H, D), col_proj.reshape(B, N, H, D)
+        W3 = self.edge_mlp[5].weight.reshape(H, D, EDGE_HIDDEN)
+        b3 = self.edge_mlp[5].bias.reshape(H, D)
+        wr, wc = self.attn_row_weight, self.attn_col_weight
+        g_row = torch.einsum("hd,hdk->hk", wr[:, 2 * D:], W3)
+        g_col = torch.einsum("hd,hdk->hk", wc[:, 2 * D:], W3)
+        k_row = (wr[:, 2 * D:] * b3).sum(-1) + self.attn_row_bias
+        k_col = (wc[:, 2 * D:] * b3).sum(-1) + self.attn_col_bias
+        return {
+            "a_row": torch.einsum("bnhd,hd->bhn", rp, wr[:, :D]).contiguous(),
+            "c_row": torch.einsum("bnhd,hd->bhn", cp, wr[:, D:2 * D]).contiguous(),
+            "a_col": torch.einsum("bnhd,hd->bhn", cp, wc[:, :D]).contiguous(),
+            "c_col": torch.einsum("bnhd,hd->bhn", rp, wc[:, D:2 * D]).contiguous(),
+            "G": torch.cat([g_row, g_col], 0).contiguous(),
+            "kbias": torch.cat([k_row, k_col], 0).contiguous(),
+        }
+
+    def _messages_fused(self, edge_feat, row_embed, col_embed, mask):
+        from lap import _hip
+        lib = _hip.require_device()
+        B, N = edge_feat.shape[:2]
+        H, D = self.heads, self.head_dim
+        dev = edge_feat.device
+        fold = self.folded_parameters(self.row_proj(row_embed), self.col_proj(col_embed))
+        row_val = self.row_val(row_embed).contiguous()
+        col_val = self.col_val(col_embed).contiguous()
+        nbytes = int(lib.lapwarm_dual_gnn_workspace_bytes(B, N, H))
+        if nbytes == 0:
+            raise ValueError(f"DualLayer: batch {B}, n {N} or heads {H} outside the fused kernels' range")
+        scores = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        stream = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        lin1, lin2 = self.edge_mlp[0], self.edge_mlp[3]
+        rc = lib.lapwarm_dual_edge_scores(edge_feat.data_ptr(), lin1.weight.data_ptr(), lin1.bias.data_ptr(),
+                                          lin2.weight.data_ptr(), lin2.bias.data_ptr(), fold["G"].data_ptr(),
+                                          scores.data_ptr(), B, N, H, stream)
+        if _hip.check(rc, "dual_edge_scores") != 0:
+            raise RuntimeError(f"lapwarm_dual_edge_scores failed (code {rc})")
+        row_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
+        col_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
+        mask8 = None if mask is None else mask.to(torch.uint8).contiguous()
+        rc = lib.lapwarm_dual_attention(scores.data_ptr(), fold["a_row"].data_ptr(), fold["c_row"].data_ptr(),
+                                        fold["a_col"].data_ptr(), fold["c_col"].data_ptr(), fold["kbias"].data_ptr(),
+                                        None if mask8 is None else mask8.data_ptr(), row_val.data_ptr(),
+                                        col_val.data_ptr(), row_msg.data_ptr(), col_msg.data_ptr(), B, N, H, D, stream)
+        if _hip.check(rc, "dual_attention") != 0:
+            raise RuntimeError(f"lapwarm_dual_attention failed (code {rc})")
+        return row_msg, col_msg
+
+    # ---- the plain path ------------------------------------------------------------------------------------
+    def _attend(self, first, second, edge, weight, bias, keep, values, transpose):
+        """One direction: scores from [first | second | edge] . weight + bias over (B, H, query, key)."""
+        x = torch.cat([first, second, edge], dim=-1)
+        x = x.permute(0, 3, 2, 1, 4) if transpose else x.permute(0, 3, 1, 2, 4)
+        s = torch.einsum("bhijm,hm->bhij", x, weight) + bias[None, :, None, None]
+        s = self.leaky_relu(s)
+        s = s.masked_fill(~keep[:, None, :, None], float("-inf"))
+        s = s.masked_fill(~keep[:, None, None, :], float("-inf"))
+        w = torch.softmax(s, dim=-1)
+        w = torch.where(torch.isfinite(w), w, torch.zeros_like(w))  # a fully masked query: zero message
+        w = self.dropout(w)
+        out = torch.einsum("bhij,bhjd->bhid", w, values.permute(0, 2, 1, 3))
+        B, _, N, _ = out.shape
+        return out.permute(0, 2, 1, 3).reshape(B, N, -1)
+
+    def _messages_plain(self, edge_feat, row_embed, col_embed, mask):
+        B, N = edge_feat.shape[:2]
+        H, D = self.heads, self.head_dim
+        keep = mask if mask is not None else edge_feat.new_ones((B, N), dtype=torch.bool)
+        rp = self.row_proj(row_embed).view(B, N, H, D)
+        cp = self.col_proj(col_embed).view(B, N, H, D)
+        rv = self.row_val(row_embed).view(B, N, H, D)
+        cv = self.col_val(col_embed).view(B, N, H, D)
+        edge = self.edge_mlp(edge_feat).view(B, N, N, H, D)
+        rows = rp.unsqueeze(2).expand(B, N, N, H, D)
+        cols = cp.unsqueeze(1).expand(B, N, N, H, D)
+        row_msg = self._attend(rows, cols, edge, self.attn_row_weight, self.attn_row_bias, keep, cv, False)
+        col_msg = self._attend(cols, rows, edge, self.attn_col_weight, self.attn_col_bias, keep, rv, True)
+        return row_msg, col_msg
+
+    def takes_fused_path(self, edge_feat, row_embed, col_embed) -> bool:
+        return (not self.training and edge_feat.is_cuda and self.heads <= FUSED_MAX_HEADS
+                and self.attn_row_weight.dtype == torch.float32  # (a .double() copy is a plain-path model)
+                and not _records_grad(self, edge_feat, row_embed, col_embed))
+
+    def forward(self, edge_feat: torch.Tensor, row_embed: torch.Tensor, col_embed: torch.Tensor,
+                mask: Optional[torch.Tensor]) -> tuple[torch.Tensor, torch.Tensor]:
+        if self.takes_fused_path(edge_feat, row_embed, col_embed):
+            with torch.autocast("cuda", enabled=False):
+                edge_feat = edge_feat.float().contiguous()
+                row_embed, col_embed = row_embed.float(), col_embed.float()
+                row_msg, col_msg = self._messages_fused(edge_feat, row_embed, col_embed, mask)
+                return self._update(row_embed, col_embed, row_msg, col_msg)
+        row_msg, col_msg = self._messages_plain(edge_feat, row_embed, col_embed, mask)
+        return self._update(row_embed, col_embed, row_msg, col_msg)
+
+    def _update(self, row_embed, col_embed, row_msg, col_msg):
+        row_new = self.row_update(torch.cat([row_embed, row_msg], dim=-1))
+        col_new = self.col_update(torch.cat([col_embed, col_msg], dim=-1))
+        return self.row_norm(row_embed + row_new), self.col_norm(col_embed + col_new)
+
+
+class DualGNN(nn.Module):
+    def __init__(self, hidden_dim: int = 128, layers: int = 4, heads: int = 4, dropout: float = 0.1) -> None:
+        super().__init__()
+        if layers <= 0:
+            raise ValueError("DualGNN must have at least one layer")
+        self.hidden_dim = hidden_dim
+        self.heads = heads
+        self.row_encoder = nn.Sequential(nn.Linear(NODE_FEATURE_DIM, hidden_dim), nn.GELU(), nn.LayerNorm(hidden_dim))
+        self.col_encoder = nn.Sequential(nn.Linear(NODE_FEATURE_DIM, hidden_dim), nn.GELU(), nn.LayerNorm(hidden_dim))
+        self.layers = nn.ModuleList([DualLayer(hidden_dim, heads=heads, dropout=dropout) for _ in range(layers)])
+        self.row_out = nn.Linear(hidden_dim, 1)
+        self.col_out = nn.Linear(hidden_dim, 1)
+
+    def _forward(self, edge_feat, row_feat, col_feat, mask):
+        nodes = (self.row_encoder(row_feat), self.col_encoder(col_feat))
+        for layer in self.layers:
+            nodes = layer(edge_feat, *nodes, mask)
+        u, v_hint = (head(x).squeeze(-1) for head, x in zip((self.row_out, self.col_out), nodes))
+        # the gauge: u is centred per instance (over all N slots, padded ones included, as the reference does) and
+        # v_hint takes the mean, so that u_i + v_j is unchanged
+        shift = u.mean(dim=-1, keepdim=True)
+        u, v_hint = u - shift, v_hint + shift
+        if mask is not None:
+            u, v_hint = (t.masked_fill(~mask, 0.0) for t in (u, v_hint))
+        return {"u": u, "v_hint": v_hint}
+
+    def forward(self, edge_feat: torch.Tensor, row_feat: torch.Tensor, col_feat: torch.Tensor,
+                mask: Optional[torch.Tensor] = None) -> dict[str, torch.Tensor]:
+        if edge_feat.ndim != 4:
+            raise ValueError("edge_feat must have shape (batch, n, n, F)")
+        if self.layers[0].takes_fused_path(edge_feat, row_feat, col_feat) and not _records_grad(self):
+            # float32 end to end, whatever autocast context the caller is in
+            with torch.autocast("cuda", enabled=False):
+                return self._forward(edge_feat.float(), row_feat.float(), col_feat.float(), mask)
+        return self._forward(edge_feat, row_feat, col_feat, mask)
+
+
+__all__ = ["DualGNN", "DualLayer", "EDGE_FEATURE_DIM", "NODE_FEATURE_DIM", "FUSED_MAX_HEADS"]

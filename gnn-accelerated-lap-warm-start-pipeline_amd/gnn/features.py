@@ -8,10 +8,16 @@ statistics cast to float32 followed by 8 positional encodings.
 (scripts/gnn_benchmark.py:233-240).  Unlike the reference's torch variant (gnn/features.py:246-351,
 float32 maths, ddof=1, argmin-only column counts) it returns exactly the same statistics as
 `compute_row_features`, because the same fp64 kernel produces both.
+
+`graph_features_device(C, u=None)` and `compute_features(C, ...)` are DualGNN's O(n^2) features (the reference's
+gnn/features.py:49-153): 10 edge channels and 14 row / column statistics, computed in fp64 by graph_features.hip.
+Ranks are stable (the lower index first among equal values), which is one of the rankings the reference's
+unstable argsort may return.  `gnn.compute_features` (the package-level name) still raises; see `gnn`.
 """
 from __future__ import annotations
 
 import ctypes as ct
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -20,6 +26,9 @@ from lap import _hip
 POS_FREQS = (1, 2, 4, 8)
 ROW_FEATURE_DIM = 13 + 2 * len(POS_FREQS)
 TOPK = 16
+EDGE_FEATURE_DIM = 10
+NODE_FEATURE_DIM = 6 + 2 * len(POS_FREQS)
+GRAPH_MAX_N = 4096  # a row, its sort keys and indices in LDS (graph_features.hpp)
 
 
 def positional_encodings(n: int) -> np.ndarray:
@@ -354,3 +363,64 @@ def min_trick_device(C, u):
     if _hip.check(rc, "min_trick_device") != 0:
         raise RuntimeError(f"min_trick_device failed (code {rc})")
     return v
+
+
+@dataclass
+class GraphFeatures:
+    row_feat: np.ndarray
+    col_feat: np.ndarray
+    edge_feat: np.ndarray
+
+
+def graph_features_device(C, u=None):
+    """C (B, n, n) or (n, n) CUDA float64, u (B, n) or (n,) CUDA or None -> edge (B, n, n, 10), row (B, n, 14),
+    col (B, n, 14), float32.  Channel 9 of edge is C - u - min_i(C - u) with u, 0 without.  Three kernels on the
+    current torch stream; no host synchronisation."""
+    import torch
+    if not C.is_cuda or C.dtype != torch.float64:
+        raise TypeError("graph_features_device expects a CUDA float64 tensor")
+    squeeze = C.ndim == 2
+    if squeeze:
+        C = C.unsqueeze(0)
+    C = C.contiguous()
+    B, n, m = C.shape
+    if n != m or n < 1:
+        raise ValueError("square, non-empty cost matrices expected")
+    if n > GRAPH_MAX_N:
+        raise ValueError(f"n exceeds the {GRAPH_MAX_N} limit of the graph features: {n}")
+    if u is not None:
+        u = u.to(device=C.device, dtype=torch.float64).reshape(B, n).contiguous()
+    lib = _hip.require_device()
+    edge = torch.empty((B, n, n, EDGE_FEATURE_DIM), dtype=torch.float32, device=C.device)
+    row = torch.empty((B, n, NODE_FEATURE_DIM), dtype=torch.float32, device=C.device)
+    col = torch.empty((B, n, NODE_FEATURE_DIM), dtype=torch.float32, device=C.device)
+    ws_bytes = int(lib.lapwarm_graph_features_workspace_bytes(B, n))
+    if ws_bytes == 0:
+        raise ValueError(f"graph_features_device: batch {B} or n {n} out of range")
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=C.device)
+    pos = _posenc_device(n, C.device)
+    stream = torch.cuda.current_stream(C.device).cuda_stream
+    rc = lib.lapwarm_graph_features_batched(C.data_ptr(), B, n, u.data_ptr() if u is not None else None,
+                                            pos.data_ptr(), edge.data_ptr(), row.data_ptr(), col.data_ptr(),
+                                            ws.data_ptr(), ws_bytes, ct.c_void_p(stream))
+    if _hip.check(rc, "graph_features_device") != 0:
+        raise RuntimeError(f"graph_features_device failed (code {rc})")
+    if squeeze:
+        edge, row, col = edge[0], row[0], col[0]
+    return edge, row, col
+
+
+def compute_features(C: np.ndarray, *, include_reduced_cost: bool = False, u=None) -> GraphFeatures:
+    """The reference's compute_features (gnn/features.py:49-153): float64 (n, n) NumPy in, GraphFeatures of
+    float32 NumPy out; the work happens on the GPU."""
+    import torch
+    C = np.ascontiguousarray(np.asarray(C, dtype=np.float64))
+    if C.ndim != 2 or C.shape[0] != C.shape[1] or C.shape[0] < 1:
+        raise ValueError("compute_features on the MI355X path expects a square, non-empty cost matrix")
+    _hip.require_device()
+    Cd = torch.from_numpy(C).to("cuda:0")
+    ud = None
+    if include_reduced_cost and u is not None:
+        ud = torch.from_numpy(np.ascontiguousarray(np.asarray(u, dtype=np.float64))).to("cuda:0")
+    edge, row, col = graph_features_device(Cd, ud)
+    return GraphFeatures(row_feat=row.cpu().numpy(), col_feat=col.cpu().numpy(), edge_feat=edge.cpu().numpy())

@@ -18,8 +18,9 @@ import numpy as np
 import torch
 
 from lap import _hip
-from .features import (ROW_FEATURE_DIM, RaggedPack, _check_pack_vector, min_trick_device, min_trick_ragged,
-                       ragged_pack, row_features_device, row_features_packed, row_min_ragged)
+from .dual_gnn import DualGNN
+from .features import (ROW_FEATURE_DIM, RaggedPack, _check_pack_vector, graph_features_device, min_trick_device,
+                       min_trick_ragged, ragged_pack, row_features_device, row_features_packed, row_min_ragged)
 from .one_gnn import OneGNN
 
 STATS_FIELDS = ("branch", "tight_edges", "free_rows", "arr_fired", "paths", "finds", "scan_steps",
@@ -54,6 +55,33 @@ def load_checkpoint(path, device="cpu") -> Tuple[OneGNN, dict]:
     if in_dim != ROW_FEATURE_DIM:
         raise ValueError(f"Checkpoint expects {in_dim} row features but the pipeline now uses {ROW_FEATURE_DIM}.")
     model = OneGNN(in_dim=in_dim, hidden=info["hidden_dim"], layers=info["layers"], dropout=info["dropout"])
+    model.load_state_dict(state)
+    model.to(device).eval()
+    return model, info
+
+
+def load_dual_checkpoint(path, device="cpu") -> Tuple[DualGNN, dict]:
+    """Build a DualGNN from a reference checkpoint, as scripts/gnn_benchmark.py:80-119 reads it.  A bare state
+    dict is a legacy DualGNN checkpoint: hidden 128, 4 layers, 4 heads, dropout 0.1.  The flat schema and the one
+    nested under 'config' are accepted with architecture == "dual_gnn" (the default of a file that names none),
+    `heads` included.  Files are read with weights_only=True."""
+    ckpt = torch.load(str(path), map_location=device, weights_only=True)
+    info = {"architecture": "dual_gnn", "hidden_dim": 128, "layers": 4, "heads": 4, "dropout": 0.1}
+    if isinstance(ckpt, dict) and "model_state_dict" in ckpt:
+        state = ckpt["model_state_dict"]
+        cfg = ckpt.get("config")
+        for k in info:
+            info[k] = ckpt.get(k, info[k])
+            if isinstance(cfg, dict):
+                info[k] = cfg.get(k, info[k])
+    elif isinstance(ckpt, dict):
+        state = ckpt
+    else:
+        raise ValueError(f"not a checkpoint: {type(ckpt).__name__}")
+    if info["architecture"] != "dual_gnn":
+        raise ValueError(f"architecture '{info['architecture']}' is not DualGNN; use load_checkpoint")
+    model = DualGNN(hidden_dim=info["hidden_dim"], layers=info["layers"], heads=info["heads"],
+                    dropout=info["dropout"])
     model.load_state_dict(state)
     model.to(device).eval()
     return model, info
@@ -952,6 +980,21 @@ class WarmStartPipeline:
         self._pending = None
 
 
+class DualWarmStartPipeline(WarmStartPipeline):
+    """The warm-start pipeline with DualGNN as its model: graph features -> DualGNN u -> v = min(C - u) ->
+    lapjv_seeded.  Only the prediction differs; solve_batch, the pipeline_* methods and every solver entry are
+    inherited.  The ragged predictions (predict_ragged, solve_many) are OneGNN's and are not available here."""
+
+    @torch.inference_mode()
+    def predict_batch(self, C: torch.Tensor):
+        """C (B,n,n) f64 CUDA -> u (B,n) f32, v (B,n) f64 by the fp64 min-trick, as the harness does
+        (scripts/gnn_benchmark.py:262); the model's v_hint is not used."""
+        edge, row, col = graph_features_device(C)
+        u = self.model(edge, row, col)["u"]
+        v = min_trick_device(C, u)
+        return u, v
+
+
 _shared = {}
 
 
@@ -985,6 +1028,34 @@ class GNNPredictor:
             model, self.model_info = load_checkpoint(Path(model_path), self.device)
         self.model = model.to(self.device).eval()
         self._pipe = WarmStartPipeline(self.model, self.device)
+
+    def predict(self, C: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        C = np.asarray(C, dtype=np.float64)
+        Cd = torch.from_numpy(np.ascontiguousarray(C)).to(self.device).unsqueeze(0)
+        u, v = self._pipe.predict_batch(Cd)
+        torch.cuda.synchronize()
+        return u[0].cpu().numpy().astype(np.float64), v[0].cpu().numpy().astype(np.float64)
+
+
+class DualGNNPredictor:
+    """`DualGNNPredictor(model_path).predict(C) -> (u, v)`, float64 NumPy, like GNNPredictor, for DualGNN
+    checkpoints (load_dual_checkpoint).  A ready DualGNN may be passed instead (`DualGNNPredictor(model=...)`)."""
+
+    def __init__(self, model_path: Optional[str] = None, device: Optional[str] = None,
+                 model: Optional[DualGNN] = None):
+        self.model_path = model_path
+        self.device = device or "cuda:0"
+        if "cuda" not in str(self.device):
+            raise RuntimeError("this DualGNNPredictor runs on the MI355X only")
+        self.use_cuda = True
+        self.row_only = False
+        self.model_info = {}
+        if model is None:
+            if model_path is None:
+                raise ValueError("model_path or model required")
+            model, self.model_info = load_dual_checkpoint(Path(model_path), self.device)
+        self.model = model.to(self.device).eval()
+        self._pipe = DualWarmStartPipeline(self.model, self.device)
 
     def predict(self, C: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         C = np.asarray(C, dtype=np.float64)

@@ -101,6 +101,14 @@ SIGNATURES = {
     "lapwarm_refine_backward_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
     "lapwarm_refine_backward": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int, ct.c_int,
                                            c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_graph_features_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_graph_features_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                  ct.c_size_t, c_vp]),
+    "lapwarm_dual_gnn_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int, ct.c_int]),
+    "lapwarm_dual_edge_scores": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int,
+                                            c_vp]),
+    "lapwarm_dual_attention": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int,
+                                          ct.c_int, ct.c_int, ct.c_int, c_vp]),
     "lapwarm_profile_enable": (None, [ct.c_int]),
     "lapwarm_profile_last_solver_ms": (ct.c_double, []),
     "lapwarm_solver_uses_helpers": (ct.c_int, [ct.c_int]),

@@ -464,6 +464,48 @@ int lapwarm_refine_backward(const float *topk16, const float *u_pre, const float
                             const float *grad_out, const float *grad_wsum, float *grad_u, float *grad_w1,
                             float *grad_b1, int rows, int H, void *ws, size_t ws_bytes, void *stream);
 
+/* DualGNN graph features (the reference's compute_features, gnn/features.py:49-153) of a resident batch.
+ *   edge_out [batch][n][n][10] f32: scaled cost, row rank, col rank, row gap, col gap, row tie, col tie, row entropy,
+ *                                   col entropy, reduced cost C - u - min_i(C - u) (0 when u is NULL)
+ *   row_out, col_out [batch][n][14] f32: min, max, mean, std, MAD, entropy, then posenc[i][0..8)
+ * All statistics in fp64, rounded once.  Median and MAD are exact selections (a MAD below 1e-9 becomes 1e-9), the
+ * entropy is the unstabilised exp(-C) form, the tie share counts gap <= 1e-3, ranks are STABLE (among equal values
+ * the lower index ranks first) over n - 1 (0 at n = 1).  Column statistics are the row kernel on a transposed copy.
+ * At every n a row's ranks come from a bitonic sort of (value, index) pairs in LDS, which also yields the median and
+ * the MAD (a choice; counting ranks at small n has not been timed against it): n <= 4096, batch <= 32767.
+ * Three kernels on the caller's stream, no allocation, no host synchronisation; every workspace word that is read
+ * is written inside the call.  Returns 0, -1 (workspace too small), -2 (arguments), -5 (n > 4096), <= -1000 HIP. */
+size_t lapwarm_graph_features_workspace_bytes(int batch, int n);
+int lapwarm_graph_features_batched(const double *C, int batch, int n, const double *u_or_null, const float *posenc,
+                                   float *edge_out, float *row_out, float *col_out, void *ws, size_t ws_bytes,
+                                   void *stream);
+
+/* DualGNN's DualLayer attention with the edge MLP's last Linear folded into the score weights (float32).
+ * lapwarm_dual_edge_scores:  scores[b][dir][h][i][j] = G[dir * heads + h] . h2(i, j),
+ *   h2 = GELU(W2 GELU(W1 f(i,j) + b1) + b2), f = edge_feat[b][i][j][0..10), erf GELU.
+ *   W1 [128][10], b1 [128], W2 [128][128], b2 [128], G [2 * heads][128], scores [batch][2][heads][n][n];
+ *   heads <= 8.  The three products run on the fp32 MFMA units (exact f32 fma chains).
+ * lapwarm_dual_attention, both directions in one launch:
+ *   row:  s_j = leaky_relu_0.2(a_row[b][h][i] + c_row[b][h][j] + scores[b][0][h][i][j] + kbias[0][h]), softmax over
+ *         the j with mask[b][j] != 0, row_msg[b][i][h][:] = sum_j w_j col_val[b][j][h][:];
+ *   col:  s_i = leaky_relu_0.2(a_col[b][h][j] + c_col[b][h][i] + scores[b][1][h][i][j] + kbias[1][h]), softmax over
+ *         the unmasked i, col_msg[b][j][h][:] = sum_i w_i row_val[b][i][h][:].
+ *   A masked query, or one without an unmasked key, gets a zero message.  mask [batch][n] bytes or NULL (all set);
+ *   a_*, c_* [batch][heads][n]; values and messages [batch][n][heads * head_dim].  fp32 with max-subtraction, sums in
+ *   a fixed order: equal inputs give equal bits.
+ * lapwarm_dual_gnn_workspace_bytes is the size of the scores tensor, rounded up to 256 (0: arguments out of range).
+ * Limits: batch <= 32767 and n <= 16384 for all three.  heads <= 8 for lapwarm_dual_edge_scores and the workspace
+ *   query (2 * heads outputs fit one 16-wide MFMA tile).  lapwarm_dual_attention itself takes heads <= 65535 (the
+ *   y dimension of its grid) and any head_dim >= 1, so it also serves scores that a caller produced elsewhere.
+ * Returns 0, -2 (arguments, a heads value above the entry's limit included), -5 (n > 16384), <= -1000 HIP error. */
+size_t lapwarm_dual_gnn_workspace_bytes(int batch, int n, int heads);
+int lapwarm_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2, const float *b2,
+                             const float *G, float *scores, int batch, int n, int heads, void *stream);
+int lapwarm_dual_attention(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                           const float *c_col, const float *kbias, const unsigned char *mask, const float *row_val,
+                           const float *col_val, float *row_msg, float *col_msg, int batch, int n, int heads,
+                           int head_dim, void *stream);
+
 /* Profiling hook for bench.py: when enabled, lapwarm_seeded_batched / lapwarm_lapjv_batched /
  * lapwarm_seeded_ragged / lapwarm_lapjv_ragged / lapwarm_lapjv_extended_ragged bracket their solver launches
  * with HIP events on the caller's stream;
