@@ -1,5 +1,6 @@
-"""Shared by test_dual_gnn_host.py and test_gpu_dual_gnn.py: the fixture reader, models built from the fixture's
-weights, the bound for outputs compared against fp64, and the folded formulation written with torch ops."""
+"""Shared by test_dual_gnn_host.py and the GPU tests of DualGNN: the fixture reader, models built from the fixture's
+weights, the bound for outputs compared against fp64, the folded formulation written with torch ops, and the graph
+features in NumPy fp64 with stable ranks."""
 import numpy as np
 import torch
 
@@ -116,3 +117,87 @@ def folded_forward(model, edge, row, col, mask):
         if mask is not None:
             u, v = u.masked_fill(~mask, 0.0), v.masked_fill(~mask, 0.0)
     return u, v
+
+
+# ---- the graph features in NumPy ------------------------------------------------------------------------------
+
+FEATURE_EPS = 1e-9   # added to both entropy terms; the floor of the MAD
+FEATURE_TAU = 1e-3   # a gap up to this counts as a tie with the minimum
+
+
+def _side_numpy(C, axis):
+    """The statistics of every line of C along `axis` (1: rows, 0: columns), each with that axis kept at length 1:
+    min, max, mean, population std, median, MAD floored at FEATURE_EPS, entropy, tie share, and the stable ranks
+    0..n-1 (the lower index first among equal values) as an (n, n) integer array."""
+    n = C.shape[axis]
+    s = {"min": C.min(axis=axis, keepdims=True), "max": C.max(axis=axis, keepdims=True),
+         "mean": C.mean(axis=axis, keepdims=True), "std": C.std(axis=axis, keepdims=True),
+         "med": np.median(C, axis=axis, keepdims=True)}
+    mad = np.median(np.abs(C - s["med"]), axis=axis, keepdims=True)
+    s["mad"] = np.where(mad < FEATURE_EPS, FEATURE_EPS, mad)
+    p = np.exp(-C)  # not stabilised: exp(-C) as it is
+    p = p / (p.sum(axis=axis, keepdims=True) + FEATURE_EPS)
+    s["ent"] = -(p * np.log(p + FEATURE_EPS)).sum(axis=axis, keepdims=True)
+    s["gap"] = C - s["min"]
+    s["tie"] = (s["gap"] <= FEATURE_TAU).sum(axis=axis, keepdims=True) / max(1, n)
+    order = np.argsort(C, axis=axis, kind="stable")
+    rank = np.empty_like(order)
+    np.put_along_axis(rank, order, np.arange(n).reshape((1, n) if axis == 1 else (n, 1)), axis=axis)
+    s["rank"] = rank
+    return s
+
+
+def _features_numpy_one(C, u):
+    from gnn.features import positional_encodings
+    n = C.shape[0]
+    r, c = _side_numpy(C, 1), _side_numpy(C, 0)
+    full = lambda a: np.broadcast_to(a, (n, n))  # noqa: E731
+    d = max(1, n - 1)
+    if u is None:
+        reduced = np.zeros((n, n))
+    else:
+        lifted = C - u[:, None]
+        reduced = lifted - lifted.min(axis=0, keepdims=True)
+    edge = np.stack([(C - r["med"]) / r["mad"], r["rank"] / d, c["rank"] / d, r["gap"], c["gap"], full(r["tie"]),
+                     full(c["tie"]), full(r["ent"]), full(c["ent"]), reduced], axis=-1).astype(np.float32)
+    pos = positional_encodings(n)
+    node = lambda s: np.concatenate(  # noqa: E731
+        [s[k].reshape(n, 1) for k in ("min", "max", "mean", "std", "mad", "ent")] + [pos], axis=1).astype(np.float32)
+    return edge, node(r), node(c)
+
+
+def features_numpy(C, u=None):
+    """The graph features of graph_features_device in NumPy fp64, rounded once to float32: C (n, n) or (B, n, n),
+    u (n,), (B, n) or None -> edge (.., n, n, 10), row (.., n, 14), col (.., n, 14).  Edge channels: the cost scaled
+    by the row's median and MAD, row rank, column rank (stable, over max(1, n - 1)), gap to the row minimum, gap to
+    the column minimum, tie share of the row, of the column, entropy of the row, of the column, and
+    C - u - min_i(C - u) (0 without u).  Node channels: min, max, mean, std, MAD, entropy, 8 positional encodings."""
+    C = np.asarray(C, dtype=np.float64)
+    if C.ndim == 2:
+        return _features_numpy_one(C, None if u is None else np.asarray(u, dtype=np.float64).reshape(-1))
+    us = [None] * C.shape[0] if u is None else np.asarray(u, dtype=np.float64).reshape(C.shape[0], -1)
+    parts = [_features_numpy_one(Cb, ub) for Cb, ub in zip(C, us)]
+    return tuple(np.stack(p) for p in zip(*parts))
+
+
+def assert_valid_stable_ranks(values, ranks):
+    """each row of `ranks` is a permutation of 0..n-1, non-decreasing in the value, increasing in the index among
+    equal values"""
+    n = values.shape[1]
+    for i in range(values.shape[0]):
+        r = ranks[i]
+        assert sorted(r.tolist()) == list(range(n)), i
+        order = np.argsort(r)
+        v = values[i][order]
+        assert np.all(np.diff(v) >= 0), i
+        same = np.diff(v) == 0
+        assert np.all(np.diff(order)[same] > 0), i
+
+
+def integer_ranks(channel, n):
+    """The ranks 0..n-1 behind a float32 rank channel, after checking that every entry is exactly k / max(1, n - 1)
+    rounded to float32."""
+    d = max(1, n - 1)
+    k = np.rint(channel.astype(np.float64) * d).astype(np.int64)
+    assert np.array_equal((k / d).astype(np.float32), channel)
+    return k

@@ -61,6 +61,43 @@ def test_folded_formulation_equals_the_plain_path_in_fp64(label):
     assert np.abs(plain["v_hint"].numpy() - z[f"out/{label}/v64"]).max() <= 1e-12
 
 
+@pytest.mark.parametrize("label", dg.feat_labels())
+def test_features_numpy_equals_the_reference_recorded_features_bit_for_bit(label):
+    """What lets the GPU tests use features_numpy as their reference at sizes the fixture does not hold.  The tied
+    case's rank channels are excluded: the recorded ranking comes from an unstable argsort and is one valid
+    ranking among several; features_numpy's must be the stable one."""
+    z = dg.cases()
+    C = z[f"feat/{label}/C"]
+    key = f"feat/{label}/u"
+    edge, row, col = dg.features_numpy(C, z[key] if key in z.files else None)
+    want = {k: z[f"feat/{label}/{k}"] for k in ("edge", "row", "col")}
+    assert edge.dtype == np.float32 and row.dtype == np.float32 and col.dtype == np.float32
+    assert np.array_equal(row, want["row"]) and np.array_equal(col, want["col"])
+    tied = label.startswith("ties")
+    assert edge.shape == want["edge"].shape
+    for ch in range(10):
+        if tied and ch in (1, 2):
+            continue
+        assert np.array_equal(edge[..., ch], want["edge"][..., ch]), (label, ch)
+    n = C.shape[0]
+    dg.assert_valid_stable_ranks(C, dg.integer_ranks(edge[..., 1], n))
+    dg.assert_valid_stable_ranks(C.T, dg.integer_ranks(edge[..., 2], n).T)
+
+
+def test_features_numpy_batches_like_single_calls_and_ranks_signed_zeros_by_index():
+    rng = np.random.default_rng(3)
+    C = rng.random((2, 6, 6)) - 0.5
+    C[0, 0, :5] = [0.0, -0.0, 0.0, -0.0, 0.0]
+    u = rng.random((2, 6))
+    both = dg.features_numpy(C, u)
+    for b in range(2):
+        for got, one in zip(both, dg.features_numpy(C[b], u[b])):
+            assert np.array_equal(got[b], one)
+    ranks = dg.integer_ranks(both[0][0, 0, :, 1], 6)
+    zeros_first = int((C[0, 0] < 0).sum())
+    assert ranks[:5].tolist() == list(range(zeros_first, zeros_first + 5))
+
+
 def test_training_mode_and_gradients_take_the_plain_path():
     model = dg.build_model("h32_H4_L2")
     edge, row, col, mask = dg.model_inputs("h32_H4_L2@pad")

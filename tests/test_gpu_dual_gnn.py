@@ -40,20 +40,6 @@ def _device_features(label):
     return edge.cpu().numpy(), row.cpu().numpy(), col.cpu().numpy()
 
 
-def _assert_valid_stable_ranks(values, ranks):
-    """each row of `ranks` is a permutation of 0..n-1, non-decreasing in the value, increasing in the index among
-    equal values"""
-    n = values.shape[1]
-    for i in range(values.shape[0]):
-        r = ranks[i]
-        assert sorted(r.tolist()) == list(range(n)), i
-        order = np.argsort(r)
-        v = values[i][order]
-        assert np.all(np.diff(v) >= 0), i
-        same = np.diff(v) == 0
-        assert np.all(np.diff(order)[same] > 0), i
-
-
 @pytest.mark.parametrize("label", dg.feat_labels())
 def test_graph_features_against_the_reference(label):
     z = dg.cases()
@@ -77,8 +63,8 @@ def test_graph_features_against_the_reference(label):
     assert np.array_equal((rr / d).astype(np.float32), edge[..., 1] if n > 1 else np.zeros_like(edge[..., 1]))
     assert np.array_equal((cr / d).astype(np.float32), edge[..., 2] if n > 1 else np.zeros_like(edge[..., 2]))
     if tied:
-        _assert_valid_stable_ranks(C, rr)
-        _assert_valid_stable_ranks(C.T, cr.T)
+        dg.assert_valid_stable_ranks(C, rr)
+        dg.assert_valid_stable_ranks(C.T, cr.T)
     else:
         assert np.array_equal(rr, np.rint(want["edge"][..., 1].astype(np.float64) * d).astype(np.int64))
         assert np.array_equal(cr, np.rint(want["edge"][..., 2].astype(np.float64) * d).astype(np.int64))
@@ -103,18 +89,27 @@ def test_graph_features_batched_equal_single_and_compute_features_wraps_them():
 
 # ---- lapwarm_dual_edge_scores ---------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("heads", [1, 4, 8])
-@pytest.mark.parametrize("N", [1, 7, 16, 17, 65])
-def test_edge_scores_against_fp64_torch_and_nothing_outside_is_written(lib, N, heads):
+def _edge_score_case(B, N, heads):
     g = torch.Generator().manual_seed(1000 * N + heads)
-    B = 2
     edge = torch.rand((B, N, N, 10), generator=g) * 2.0 - 0.5
     W1 = (torch.rand((128, 10), generator=g) - 0.5) * 0.6
     b1 = (torch.rand((128,), generator=g) - 0.5) * 0.2
     W2 = (torch.rand((128, 128), generator=g) - 0.5) * 0.18
     b2 = (torch.rand((128,), generator=g) - 0.5) * 0.2
     G = (torch.rand((2 * heads, 128), generator=g) - 0.5) * 0.3
-    args = (edge, W1, b1, W2, b2, G)
+    return edge, W1, b1, W2, b2, G
+
+
+def _launch_edge_scores(lib, d, out_ptr, B, N, heads):
+    """d: the six arguments on the device, contiguous"""
+    rc = lib.lapwarm_dual_edge_scores(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
+                                      d[4].data_ptr(), d[5].data_ptr(), out_ptr, B, N, heads, _stream())
+    torch.cuda.synchronize()
+    assert rc == 0
+
+
+def _check_edge_scores(lib, B, N, heads):
+    args = _edge_score_case(B, N, heads)
     want = dg.edge_scores_torch(*(a.double() for a in args))
     dev32 = (dg.edge_scores_torch(*args).double() - want).abs().max().item()
     bound = dg.bound_from(dev32)
@@ -123,24 +118,54 @@ def test_edge_scores_against_fp64_torch_and_nothing_outside_is_written(lib, N, h
     poison = float.fromhex("0x1.5p+100")
     buf = torch.full((count + 2 * guard,), poison, dtype=torch.float32, device=DEV)
     d = [a.to(DEV).contiguous() for a in args]
-    rc = lib.lapwarm_dual_edge_scores(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
-                                      d[4].data_ptr(), d[5].data_ptr(), buf[guard:].data_ptr(), B, N, heads, _stream())
-    torch.cuda.synchronize()
-    assert rc == 0
+    _launch_edge_scores(lib, d, buf[guard:].data_ptr(), B, N, heads)
     out = buf.cpu()
     assert torch.all(out[:guard] == poison) and torch.all(out[guard + count:] == poison)
     got = out[guard:guard + count].reshape(B, 2, heads, N, N).double()
     err = (got - want).abs().max().item()
-    print(f"N={N} heads={heads}: device {err:.3e}, torch fp32 {dev32:.3e}, bound {bound:.3e}")
+    print(f"B={B} N={N} heads={heads}: device {err:.3e}, torch fp32 {dev32:.3e}, bound {bound:.3e}")
     assert err <= bound
+
+
+@pytest.mark.parametrize("heads", [1, 4, 8])
+@pytest.mark.parametrize("N", [1, 7, 16, 17, 65])
+def test_edge_scores_against_fp64_torch_and_nothing_outside_is_written(lib, N, heads):
+    _check_edge_scores(lib, 2, N, heads)
+
+
+# The launch caps the grid at 256 workgroups, each walking tiles of 128 edges with a stride of the grid: (1, 257, 8)
+# and (3, 151, 3) are 66 049 and 68 403 edges, 517 and 535 tiles, so every workgroup takes two or three, and the
+# second has its two instance boundaries inside tiles.  heads 3 and 5 end 2 * heads inside a lane group of four.
+@pytest.mark.parametrize("B,N,heads", [(1, 257, 8), (3, 151, 3), (2, 17, 3), (2, 17, 5)])
+def test_edge_scores_past_one_trip_of_the_tile_loop_and_with_odd_head_counts(lib, B, N, heads):
+    _check_edge_scores(lib, B, N, heads)
+
+
+def test_edge_scores_of_a_batch_equal_single_instance_launches_bit_for_bit(lib):
+    """An edge's scores depend on its own column of the MFMA tiles only, so neither its place in a tile nor the
+    tile's place in the grid may matter: instances 1 and 2 start inside a tile here (22 801 edges each)."""
+    B, N, heads = 3, 151, 3
+    d = [a.to(DEV).contiguous() for a in _edge_score_case(B, N, heads)]
+    count = 2 * heads * N * N
+    together = torch.full((B * count,), float("nan"), dtype=torch.float32, device=DEV)
+    _launch_edge_scores(lib, d, together.data_ptr(), B, N, heads)
+    assert torch.isfinite(together).all()
+    for b in range(B):
+        alone = torch.full((count,), float("nan"), dtype=torch.float32, device=DEV)
+        _launch_edge_scores(lib, [d[0][b:b + 1].contiguous()] + d[1:], alone.data_ptr(), 1, N, heads)
+        assert torch.equal(alone, together[b * count:(b + 1) * count]), b
 
 
 # ---- lapwarm_dual_attention -----------------------------------------------------------------------------------
 
-def _attention_case(B, N, H, D, mask, seed):
+SCORE_RANGE = 3.0  # the generator's scores are uniform in [-3, 3); a, c and the bias in [-1, 1)
+
+
+def _attention_case(B, N, H, D, mask, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     r = lambda *s: torch.rand(s, generator=g) * 2.0 - 1.0  # noqa: E731
-    return dict(scores=r(B, 2, H, N, N) * 3.0, a_row=r(B, H, N), c_row=r(B, H, N), a_col=r(B, H, N), c_col=r(B, H, N),
+    return dict(scores=r(B, 2, H, N, N) * (SCORE_RANGE * scale), a_row=r(B, H, N), c_row=r(B, H, N),
+                a_col=r(B, H, N), c_col=r(B, H, N),
                 kbias=r(2 * H), mask=mask, row_val=r(B, N, H * D), col_val=r(B, N, H * D))
 
 
@@ -171,12 +196,11 @@ def _masks(kind, B, N):
     return m
 
 
-@pytest.mark.parametrize("N,H,D,kind", [(70, 4, 8, "all"), (70, 4, 8, "ragged"), (33, 8, 8, "empty"),
-                                        (1, 2, 16, "none"), (17, 1, 136, "ragged"), (130, 2, 32, "ragged")])
-def test_attention_against_fp64_torch_and_twice_the_same_bits(lib, N, H, D, kind):
+def _check_attention(lib, N, H, D, kind, scale=1.0):
+    """-> the fp64 reference's largest |logit| (after the leaky ReLU, over the unmasked pairs)"""
     B = 3
     mask = _masks(kind, B, N)
-    case = _attention_case(B, N, H, D, mask, seed=N * 100 + H)
+    case = _attention_case(B, N, H, D, mask, seed=N * 100 + H, scale=scale)
     as64 = {k: (v.double() if v is not None and v.dtype != torch.bool else v) for k, v in case.items()}
     want = dg.attention_torch(**as64)
     ref32 = dg.attention_torch(**case)
@@ -192,6 +216,31 @@ def test_attention_against_fp64_torch_and_twice_the_same_bits(lib, N, H, D, kind
         assert err <= bound
     if mask is not None:
         assert not got[0][~mask].any() and not got[1][~mask].any()  # masked queries: zero messages
+    keep = mask if mask is not None else torch.ones((B, N), dtype=torch.bool)
+    pair = (keep[:, None, :, None] & keep[:, None, None, :])[:, None]  # (B, 1, 1, N, N) over both directions
+    s64, k64 = as64["scores"], as64["kbias"].reshape(1, 2, H, 1, 1)
+    pre = torch.stack([as64["a_row"][..., :, None] + as64["c_row"][..., None, :],
+                       as64["c_col"][..., :, None] + as64["a_col"][..., None, :]], dim=1) + s64 + k64
+    logits = torch.nn.functional.leaky_relu(pre, 0.2)
+    return logits.abs().masked_fill(~pair, 0.0).max().item()
+
+
+@pytest.mark.parametrize("N,H,D,kind", [(70, 4, 8, "all"), (70, 4, 8, "ragged"), (33, 8, 8, "empty"),
+                                        (1, 2, 16, "none"), (17, 1, 136, "ragged"), (130, 2, 32, "ragged")])
+def test_attention_against_fp64_torch_and_twice_the_same_bits(lib, N, H, D, kind):
+    assert _check_attention(lib, N, H, D, kind) < 10.0
+
+
+def test_attention_with_logits_beyond_100_needs_the_maximum_subtracted(lib):
+    """scores uniform in [-150, 150): expf overflows near 88, so a softmax without its maximum subtracted gives inf
+    or NaN here, while every other case of this file has logits of at most about 6."""
+    largest = _check_attention(lib, 70, 2, 8, "ragged", scale=150.0 / SCORE_RANGE)
+    print(f"largest |logit| of the fp64 reference: {largest:.1f}")
+    assert largest > 100.0
+
+
+def test_attention_with_a_head_dimension_below_the_16_slots_and_odd(lib):
+    _check_attention(lib, 20, 3, 5, "none")  # hidden = 15
 
 
 # ---- the whole model ------------------------------------------------------------------------------------------
@@ -240,6 +289,41 @@ def test_fused_forward_against_the_plain_path_on_the_device():
         bound = dg.bound_from(dev)
         print(f"h128 H4 L4 B=2 n=96 {k}: fused {err:.3e}, plain on the device {dev:.3e}, bound {bound:.3e}")
         assert err <= bound, k
+
+
+def test_fused_forward_with_a_mask_where_every_kernel_loop_repeats():
+    """B = 3, N = 150, sizes (150, 97, 1): 67 500 edges are 528 tiles for at most 256 workgroups, and attention needs
+    three key tiles; the masked model cases of the fixture stop at N = 40."""
+    from gnn.dual_gnn import DualGNN
+    sizes, N = (150, 97, 1), 150
+    rng = np.random.default_rng(150)
+    edge = np.zeros((len(sizes), N, N, 10), np.float32)
+    row = np.zeros((len(sizes), N, 14), np.float32)
+    col = np.zeros_like(row)
+    mask = torch.zeros((len(sizes), N), dtype=torch.bool)
+    for b, n in enumerate(sizes):  # every instance's features at its own size, zero-padded to N
+        edge[b, :n, :n], row[b, :n], col[b, :n] = dg.features_numpy(rng.random((n, n)) * 10.0)
+        mask[b, :n] = True
+    edge, row, col = torch.from_numpy(edge), torch.from_numpy(row), torch.from_numpy(col)
+    torch.manual_seed(12)
+    model = DualGNN(hidden_dim=64, layers=2, heads=8).eval()
+    with torch.no_grad():
+        ref64 = model.double()(edge.double(), row.double(), col.double(), mask)
+        model = model.float().to(DEV)
+        e, r, c, m = edge.to(DEV), row.to(DEV), col.to(DEV), mask.to(DEV)
+        assert model.layers[0].takes_fused_path(e, r, c)
+        fused = model(e, r, c, m)
+    plain = model(e, r, c, m)  # a gradient is recorded: the plain path
+    assert plain["u"].requires_grad and not fused["u"].requires_grad
+    torch.cuda.synchronize()
+    for k in ("u", "v_hint"):  # each output against 4 x the plain path's own deviation on that output
+        dev = (plain[k].detach().cpu().double() - ref64[k]).abs().max().item()
+        err = (fused[k].cpu().double() - ref64[k]).abs().max().item()
+        bound = dg.bound_from(dev)
+        print(f"h64 H8 L2 B=3 N=150 masked {k}: fused {err:.3e}, plain on the device {dev:.3e}, bound {bound:.3e}")
+        assert err <= bound, k
+        assert torch.isfinite(fused[k]).all()
+        assert not fused[k].cpu()[~mask].any() and not ref64[k][~mask].any()  # padded slots are exactly 0
 
 
 # ---- the pipeline ---------------------------------------------------------------------------------------------
