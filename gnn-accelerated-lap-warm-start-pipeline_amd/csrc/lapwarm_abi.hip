@@ -45,6 +45,16 @@ int fail(hipError_t e, const char *where)
         if (_e != hipSuccess) return fail(_e, #expr);   \
     } while (0)
 
+// The one workspace check of every entry point that takes one.
+int check_workspace(size_t have, size_t need)
+{
+    if (have >= need) return 0;
+    snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", have, need);
+    return -1;
+}
+
+hipStream_t as_stream(void *stream) { return reinterpret_cast<hipStream_t>(stream); }
+
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Carver {
@@ -61,17 +71,47 @@ struct Carver {
 
 // ---- workspace layouts: one function per kind; a null base measures the workspace ----------
 
+// The seeded prelude's buffers, [batch][stride] each but the flags [batch].  The tight-edge bitmap of instance b
+// is n_b rows of ceil(n_b / 32) words at b * stride * ceil(stride / 32).
+struct PreludeWs {
+    double *u_work, *v_work, *u_tight;
+    int *viol_cnt, *tight_cnt, *flags;
+    uint32_t *tight_bits;
+};
+
+PreludeWs prelude_layout(Carver &c, int batch, int stride)
+{
+    PreludeWs w;
+    const size_t bn = (size_t)batch * stride;
+    w.u_work = c.take<double>(bn);
+    w.v_work = c.take<double>(bn);
+    w.u_tight = c.take<double>(bn);
+    w.viol_cnt = c.take<int>(bn);
+    w.tight_cnt = c.take<int>(bn);
+    w.flags = c.take<int>((size_t)batch);
+    w.tight_bits = c.take<uint32_t>(bn * ((size_t)(stride + 31) / 32));
+    return w;
+}
+
 // The solver workspace of a seeded or a cold solve, laid out into the kernel argument block (the
 // caller adds C and its results).  Its size depends on neither the mode nor the threads hint: the
 // global solver state is carved whenever any geometry of this size needs it.
 struct SolverWs {
     SolverParams sp;
-    double *u_work, *v_work, *u_tight;  // the seeded prelude's buffers
-    int *viol_cnt, *tight_cnt, *flags;
-    uint32_t *tight_bits;
+    PreludeWs pre;
     bool lists;  // carries the candidate lists of the cold row reduction
     size_t bytes;
 };
+
+// what the prelude leaves for the solver (seeded_prelude adds tight_eps)
+void hand_prelude_to_solver(const PreludeWs &pre, SolverParams *sp)
+{
+    sp->u_tight = pre.u_tight;
+    sp->v_work = pre.v_work;
+    sp->tight_cnt = pre.tight_cnt;
+    sp->tight_bits = pre.tight_bits;
+    sp->inst_flags = pre.flags;
+}
 
 SolverWs solver_layout(void *ws, int batch, int n, int mode, bool with_lists)
 {
@@ -83,16 +123,9 @@ SolverWs solver_layout(void *ws, int batch, int n, int mode, bool with_lists)
     sp.mode = mode;
     Carver c{reinterpret_cast<unsigned char *>(ws), 0};
     const size_t bn = (size_t)batch * n;
-    const size_t W = (size_t)(n + 31) / 32;
     w.lists = with_lists && arr_lists_enabled(n);
     const SolveShape shape = solve_shape(n, w.lists);
-    w.u_work = c.take<double>(bn);
-    w.v_work = c.take<double>(bn);
-    w.u_tight = c.take<double>(bn);
-    w.viol_cnt = c.take<int>(bn);
-    w.tight_cnt = c.take<int>(bn);
-    w.flags = c.take<int>((size_t)batch);
-    w.tight_bits = c.take<uint32_t>(bn * W);
+    w.pre = prelude_layout(c, batch, n);
     sp.pf_ring = c.take<int>((size_t)batch * kRingInts);
     // a two-phase solve hands the state from phase 1 to the later launches through these
     if (shape != SolveShape::kOneLaunch) {
@@ -119,25 +152,17 @@ SolverWs solver_layout(void *ws, int batch, int n, int mode, bool with_lists)
         sp.arr_ltau = c.take<double>(bn);
     }
     w.bytes = c.off;
-    if (mode == kModeSeeded) {  // what the prelude leaves for the solver
-        sp.u_tight = w.u_tight;
-        sp.v_work = w.v_work;
-        sp.tight_cnt = w.tight_cnt;
-        sp.tight_bits = w.tight_bits;
-        sp.inst_flags = w.flags;
-    } else {
+    if (mode == kModeSeeded)
+        hand_prelude_to_solver(w.pre, &sp);
+    else
         sp.pf_ring = nullptr;  // a cold solve starts from C alone
-    }
     return w;
 }
 
-// The seeded solve of a ragged batch: the prelude's buffers with the padded stride N.  The tight-edge bitmap
-// of instance b is n_b rows of ceil(n_b / 32) words at b * N * ceil(N / 32).  Nothing else: an instance this
-// entry takes keeps its solver state in LDS and has no helper ring.
+// The seeded solve of a ragged batch: the prelude's buffers with the padded stride N.  Nothing else: an
+// instance this entry takes keeps its solver state in LDS and has no helper ring.
 struct RaggedSolverWs {
-    double *u_work, *v_work, *u_tight;
-    int *viol_cnt, *tight_cnt, *flags;
-    uint32_t *tight_bits;
+    PreludeWs pre;
     size_t bytes;
 };
 
@@ -145,14 +170,7 @@ RaggedSolverWs ragged_solver_layout(void *ws, int batch, int N)
 {
     RaggedSolverWs w;
     Carver c{reinterpret_cast<unsigned char *>(ws), 0};
-    const size_t bn = (size_t)batch * N;
-    w.u_work = c.take<double>(bn);
-    w.v_work = c.take<double>(bn);
-    w.u_tight = c.take<double>(bn);
-    w.viol_cnt = c.take<int>(bn);
-    w.tight_cnt = c.take<int>(bn);
-    w.flags = c.take<int>((size_t)batch);
-    w.tight_bits = c.take<uint32_t>(bn * ((size_t)(N + 31) / 32));
+    w.pre = prelude_layout(c, batch, N);
     w.bytes = c.off;
     return w;
 }
@@ -320,8 +338,105 @@ hipError_t profile_end(hipStream_t s)
 int check_dims(int batch, int n)
 {
     if (n <= 0 || batch <= 0) return -2;
-    if (n > 16384) return -5;
+    if (n > kMaxN) return -5;
     return 0;
+}
+
+// The prelude of a seeded solve on the prepared u_work, v_work: prelude, projection, prelude again.  `g`: the
+// ragged batch (stride n = g->N), or null for a uniform one.  *tight_eps is what the solver is to use.
+int seeded_prelude(const double *C, int batch, int n, const PreludeWs &w, double eps, const RaggedBatch *g,
+                   hipStream_t stream, double *tight_eps)
+{
+    PreludeParams pp;
+    pp.C = C;
+    pp.n = n;
+    pp.batch = batch;
+    pp.u = w.u_work;
+    pp.v = w.v_work;
+    pp.eps = eps;
+    pp.tight_eps = (eps < 1e-9) ? 1e-9 : eps;  // std::max(eps, 1e-9), lapjv_seeded.cpp:76
+    pp.u_tight = w.u_tight;
+    pp.viol_cnt = w.viol_cnt;
+    pp.tight_cnt = w.tight_cnt;
+    pp.tight_bits = w.tight_bits;
+    pp.inst_flags = w.flags;
+    const auto prelude = [&] { return g ? launch_prelude_ragged(pp, *g, stream) : launch_prelude(pp, stream); };
+    pp.rerun = 0;
+    HIP_TRY(prelude());
+    HIP_TRY(g ? launch_projection_ragged(*g, w.u_work, w.v_work, w.viol_cnt, w.flags, eps, stream)
+              : launch_projection(C, n, batch, w.u_work, w.v_work, w.viol_cnt, w.flags, eps, stream));
+    pp.rerun = 1;
+    HIP_TRY(prelude());
+    *tight_eps = pp.tight_eps;
+    return 0;
+}
+
+// The solves of a ragged batch take no instance the device would treat as empty (size outside 1..N, or wider
+// than its row stride).
+bool host_sizes_ok(const int *host_sizes, int batch, int N, int ld)
+{
+    for (int b = 0; b < batch; ++b) {
+        if (host_sizes[b] < 1 || host_sizes[b] > N || (ld > 0 && host_sizes[b] > ld)) return false;
+    }
+    return true;
+}
+
+// The kernel argument block of the solver launches of a ragged batch; `pre`: the prelude's buffers of a seeded
+// solve (the caller adds tight_eps), null for a cold one.
+SolverParams ragged_solver_params(int mode, const RaggedBatch &g, long long *x, long long *y, int *ret,
+                                  long long *stats, const PreludeWs *pre)
+{
+    SolverParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.C = g.C;
+    sp.n = g.N;
+    sp.batch = g.batch;
+    sp.mode = mode;
+    if (pre) hand_prelude_to_solver(*pre, &sp);
+    sp.x_out = x;
+    sp.y_out = y;
+    sp.ret = ret;
+    sp.stats = stats;
+    sp.rg_offsets = g.offsets;
+    sp.rg_sizes = g.sizes;
+    sp.rg_ld = g.ld;
+    sp.rg_N = g.N;
+    return sp;
+}
+
+// One launch per kernel configuration; the launches are independent and each workgroup picks its own.  The
+// bracket of lapwarm_profile_enable holds all solver launches of the call.
+int launch_ragged_groups(SolverParams sp, const RaggedGroup *groups, int n_groups, hipStream_t stream)
+{
+    HIP_TRY(profile_begin(stream));
+    for (int k = 0; k < n_groups; ++k) {
+        sp.rg_n_lo = groups[k].n_lo;
+        sp.rg_n_hi = groups[k].n_hi;
+        HIP_TRY(launch_phase_ragged(groups[k].k, sp, stream));
+    }
+    HIP_TRY(profile_end(stream));
+    return 0;
+}
+
+// ---- the copies of the host-pointer entry points (blocking, on the null stream) ----
+template <typename T>
+hipError_t upload(T *dst, const T *src, size_t count)
+{
+    return hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyHostToDevice);
+}
+
+template <typename T>
+hipError_t download(T *dst, const T *src, size_t count)
+{
+    return hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost);
+}
+
+// The per-instance code a batch of one left on the device (>= 0), or the code of the copy's failure.
+int device_ret(const int *dret)
+{
+    int ret = 0;
+    HIP_TRY(download(&ret, dret, 1));
+    return ret;
 }
 
 }  // namespace
@@ -357,8 +472,7 @@ int lapwarm_refine_aggregate_wsum(const float *topk16, const float *u_pre, const
                                   const float *b1, float *out, float *wsum, int rows, int H, void *stream_)
 {
     if (rows <= 0 || H <= 0) return -2;
-    HIP_TRY(launch_refine_aggregate(topk16, u_pre, w1, b1, out, wsum, rows, H,
-                                    reinterpret_cast<hipStream_t>(stream_)));
+    HIP_TRY(launch_refine_aggregate(topk16, u_pre, w1, b1, out, wsum, rows, H, as_stream(stream_)));
     return 0;
 }
 
@@ -380,9 +494,9 @@ int lapwarm_refine_backward(const float *topk16, const float *u_pre, const float
     if (rows < 0 || H < 1) return -2;
     if (rows == 0) return 0;
     if (!topk16 || !u_pre || !w1 || !b1 || !grad_out || !grad_u || !grad_w1 || !grad_b1 || !ws) return -2;
-    if (ws_bytes < refine_backward_workspace_bytes(rows, H)) return -2;
+    if (ws_bytes < refine_backward_workspace_bytes(rows, H)) return -2;  // (this entry's code: not check_workspace)
     HIP_TRY(launch_refine_backward(topk16, u_pre, w1, b1, grad_out, grad_wsum, grad_u, grad_w1, grad_b1, rows, H, ws,
-                                   reinterpret_cast<hipStream_t>(stream_)));
+                                   as_stream(stream_)));
     return 0;
 }
 
@@ -395,9 +509,9 @@ int lapwarm_graph_features_batched(const double *C, int batch, int n, const doub
     if (batch < 1 || batch > kGraphMaxBatch || n < 1) return -2;
     if (n > kGraphMaxN) return -5;
     if (!C || !posenc || !edge_out || !row_out || !col_out || !ws) return -2;
-    if (ws_bytes < graph_features_workspace_bytes(batch, n)) return -1;
+    if (int rc = check_workspace(ws_bytes, graph_features_workspace_bytes(batch, n))) return rc;
     GraphFeatureParams p{C, u, posenc, batch, n, edge_out, row_out, col_out};
-    HIP_TRY(launch_graph_features(p, ws, reinterpret_cast<hipStream_t>(stream_)));
+    HIP_TRY(launch_graph_features(p, ws, as_stream(stream_)));
     return 0;
 }
 
@@ -407,10 +521,9 @@ int lapwarm_dual_edge_scores(const float *edge_feat, const float *W1, const floa
                              const float *G, float *scores, int batch, int n, int heads, void *stream_)
 {
     if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
-    if (n > 16384) return -5;
+    if (n > kMaxN) return -5;
     if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !scores) return -2;
-    HIP_TRY(launch_dual_edge_scores(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads,
-                                    reinterpret_cast<hipStream_t>(stream_)));
+    HIP_TRY(launch_dual_edge_scores(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, as_stream(stream_)));
     return 0;
 }
 
@@ -420,13 +533,13 @@ int lapwarm_dual_attention(const float *scores, const float *a_row, const float 
                            int head_dim, void *stream_)
 {
     // heads: the grid's y dimension, not kDualMaxHeads, which is the edge-scores kernel's tile limit
-    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > 65535 || head_dim < 1) return -2;
-    if (n > 16384) return -5;
+    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kMaxGridY || head_dim < 1) return -2;
+    if (n > kMaxN) return -5;
     if (!scores || !a_row || !c_row || !a_col || !c_col || !kbias || !row_val || !col_val || !row_msg || !col_msg)
         return -2;
     DualAttnParams p{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val, row_msg, col_msg,
                      batch, n, heads, head_dim};
-    HIP_TRY(launch_dual_attention(p, reinterpret_cast<hipStream_t>(stream_)));
+    HIP_TRY(launch_dual_attention(p, as_stream(stream_)));
     return 0;
 }
 
@@ -463,37 +576,14 @@ int lapwarm_seeded_batched(const double *C, int batch, int n, const double *u_se
                            int threads_hint, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     SolverWs w = solver_layout(workspace, batch, n, kModeSeeded, false);
     SolverParams &sp = w.sp;
-    if (workspace_bytes < w.bytes) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-        return -1;
-    }
-    HIP_TRY(launch_seed_prepare(u_seed, v_seed, w.u_work, w.v_work, (size_t)batch * n, w.flags, batch, sp.pf_ring,
-                                batch * kRingInts, stream));
-
-    PreludeParams pp;
-    pp.C = C;
-    pp.n = n;
-    pp.batch = batch;
-    pp.u = w.u_work;
-    pp.v = w.v_work;
-    pp.eps = eps;
-    pp.tight_eps = (eps < 1e-9) ? 1e-9 : eps;  // std::max(eps, 1e-9), lapjv_seeded.cpp:76
-    pp.rerun = 0;
-    pp.u_tight = w.u_tight;
-    pp.viol_cnt = w.viol_cnt;
-    pp.tight_cnt = w.tight_cnt;
-    pp.tight_bits = w.tight_bits;
-    pp.inst_flags = w.flags;
-    HIP_TRY(launch_prelude(pp, stream));
-    HIP_TRY(launch_projection(C, n, batch, w.u_work, w.v_work, w.viol_cnt, w.flags, eps, stream));
-    pp.rerun = 1;
-    HIP_TRY(launch_prelude(pp, stream));
-
+    if (int rc = check_workspace(workspace_bytes, w.bytes)) return rc;
+    HIP_TRY(launch_seed_prepare(u_seed, v_seed, w.pre.u_work, w.pre.v_work, (size_t)batch * n, w.pre.flags, batch,
+                                sp.pf_ring, batch * kRingInts, stream));
+    if (int rc = seeded_prelude(C, batch, n, w.pre, eps, nullptr, stream, &sp.tight_eps)) return rc;
     sp.C = C;
-    sp.tight_eps = pp.tight_eps;
     sp.x_out = x;
     sp.y_out = y;
     sp.ret = ret;
@@ -509,15 +599,12 @@ static int lapjv_batched_impl(const double *C, int batch, int n, int *x, int *y,
                               int threads_hint, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     // a workspace of lapwarm_lapjv_workspace_bytes() carries the candidate lists of the row reduction;
     // the smaller lapwarm_seeded_workspace_bytes() is still accepted (plain row scans then)
     SolverWs w = solver_layout(workspace, batch, n, kModeCold, true);
     if (workspace_bytes < w.bytes) w = solver_layout(workspace, batch, n, kModeCold, false);
-    if (workspace_bytes < w.bytes) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-        return -1;
-    }
+    if (int rc = check_workspace(workspace_bytes, w.bytes)) return rc;
     SolverParams &sp = w.sp;
     sp.C = C;
     sp.x32_out = x;
@@ -554,7 +641,7 @@ int lapwarm_lapjv_extended_n(int n_rows, int n_cols, int extend_cost, double cos
     if (n_rows != n_cols && !extend_cost) return -4;  // _lapjv.pyx:80-83, whatever the limit
     const long long n = cost_limited(cost_limit) ? (long long)n_rows + n_cols
                                                  : (n_rows > n_cols ? n_rows : n_cols);
-    return n > 16384 ? -5 : (int)n;
+    return n > kMaxN ? -5 : (int)n;
 }
 
 size_t lapwarm_lapjv_extended_workspace_bytes(int batch, int n_rows, int n_cols, int extend_cost,
@@ -573,17 +660,14 @@ int lapwarm_lapjv_extended_batched(const double *C, int batch, int n_rows, int n
 {
     const int n = lapwarm_lapjv_extended_n(n_rows, n_cols, extend_cost, cost_limit);
     if (n < 0) return n;
-    if (batch <= 0 || batch > 65535) return -2;  // (the extension kernel's grid: rows x batch)
+    if (batch <= 0 || batch > kMaxGridY) return -2;  // (the extension kernel's grid: rows x batch)
     if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return -2;  // E is written with 16-byte stores
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     const bool limited = cost_limited(cost_limit);
     // a square matrix without a limit is solved where it is (_lapjv.pyx:91-95 copies it into zeros)
     const bool copy = limited || n_rows != n_cols;
     const ExtendedWs w = extended_layout(workspace, batch, n_rows, n_cols, n, copy);
-    if (workspace_bytes < w.bytes) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-        return -1;
-    }
+    if (int rc = check_workspace(workspace_bytes, w.bytes)) return rc;
     if (copy)
         HIP_TRY(launch_extend_costs(C, batch, n_rows, n_cols, n, limited ? cost_limit / 2. : 0.0, w.E, stream));
     if (int rc = lapjv_batched_impl(copy ? w.E : C, batch, n, w.xs, w.ys, nullptr, nullptr, ret, stats, w.solver,
@@ -598,16 +682,15 @@ int lapwarm_colmin_batched(const double *C, int batch, int n, const double *u, d
                            void *workspace, size_t workspace_bytes, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    if (workspace_bytes < lapwarm_sweep_workspace_bytes(batch, n)) return -1;
-    HIP_TRY(launch_colmin(C, n, batch, u, out, sweep_layout(workspace, batch, n).partial,
-                          reinterpret_cast<hipStream_t>(stream_)));
+    if (int rc = check_workspace(workspace_bytes, lapwarm_sweep_workspace_bytes(batch, n))) return rc;
+    HIP_TRY(launch_colmin(C, n, batch, u, out, sweep_layout(workspace, batch, n).partial, as_stream(stream_)));
     return 0;
 }
 
 int lapwarm_rowmin_batched(const double *C, int batch, int n, const double *v, double *out, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    HIP_TRY(launch_rowmin(C, n, batch, v, out, reinterpret_cast<hipStream_t>(stream_)));
+    HIP_TRY(launch_rowmin(C, n, batch, v, out, as_stream(stream_)));
     return 0;
 }
 
@@ -615,8 +698,8 @@ int lapwarm_row_features_batched(const double *C, int batch, int n, const float 
                                  float *topk16, void *workspace, size_t workspace_bytes, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    if (workspace_bytes < lapwarm_sweep_workspace_bytes(batch, n)) return -1;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (int rc = check_workspace(workspace_bytes, lapwarm_sweep_workspace_bytes(batch, n))) return rc;
+    hipStream_t stream = as_stream(stream_);
     const SweepWs w = sweep_layout(workspace, batch, n);
     HIP_TRY(launch_colmin(C, n, batch, nullptr, w.colmin, w.partial, stream));
     FeatureParams fp;
@@ -634,15 +717,16 @@ int lapwarm_row_features_batched(const double *C, int batch, int n, const float 
 // ---- ragged batches: B instances of different sizes behind one offset and one size per instance ----
 static int check_ragged(const void *C, const void *offsets, const void *sizes, int ld, int batch, int N)
 {
-    if (N <= 0 || batch <= 0 || batch > 65535 || ld < 0) return -2;  // the batch is one dimension of every grid
-    if (N > 16384) return -5;
+    const int rc = check_ragged_dims(batch, N);
+    if (rc == -2 || ld < 0) return -2;
+    if (rc) return rc;
     if (!C || !offsets || !sizes) return -2;
     return 0;
 }
 
 size_t lapwarm_ragged_workspace_bytes(int batch, int N)
 {
-    if (N <= 0 || batch <= 0 || batch > 65535 || N > 16384) return 0;
+    if (check_ragged_dims(batch, N)) return 0;
     return align_up(sizeof(double) * (size_t)batch * N);  // the column minima the feature kernel compares with
 }
 
@@ -651,9 +735,9 @@ int lapwarm_colmin_ragged(const double *C, const long long *offsets, const int *
 {
     if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
     if (!out || !workspace) return -2;
-    if (workspace_bytes < lapwarm_ragged_workspace_bytes(batch, N)) return -1;
+    if (int rc = check_workspace(workspace_bytes, lapwarm_ragged_workspace_bytes(batch, N))) return rc;
     const RaggedBatch g{C, offsets, sizes, ld, batch, N};
-    HIP_TRY(launch_colmin_ragged(g, u, out, reinterpret_cast<hipStream_t>(stream_)));
+    HIP_TRY(launch_colmin_ragged(g, u, out, as_stream(stream_)));
     return 0;
 }
 
@@ -663,8 +747,8 @@ int lapwarm_row_features_ragged(const double *C, const long long *offsets, const
 {
     if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
     if (!posenc || !pos_off || !feat || !ret || !workspace) return -2;
-    if (workspace_bytes < lapwarm_ragged_workspace_bytes(batch, N)) return -1;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (int rc = check_workspace(workspace_bytes, lapwarm_ragged_workspace_bytes(batch, N))) return rc;
+    hipStream_t stream = as_stream(stream_);
     const RaggedBatch g{C, offsets, sizes, ld, batch, N};
     double *colmin = reinterpret_cast<double *>(workspace);
     HIP_TRY(launch_colmin_ragged(g, nullptr, colmin, stream));
@@ -675,7 +759,7 @@ int lapwarm_row_features_ragged(const double *C, const long long *offsets, const
 
 size_t lapwarm_seeded_ragged_workspace_bytes(int batch, int N)
 {
-    if (N <= 0 || batch <= 0 || batch > 65535 || N > 16384) return 0;
+    if (check_ragged_dims(batch, N)) return 0;
     return ragged_solver_layout(nullptr, batch, N).bytes;
 }
 
@@ -693,9 +777,7 @@ int lapwarm_seeded_ragged(const double *C, const long long *offsets, const int *
 {
     if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
     if (!host_sizes || !u_seed || !v_seed || !x || !y || !ret || !workspace) return -2;
-    for (int b = 0; b < batch; ++b) {
-        if (host_sizes[b] < 1 || host_sizes[b] > N || (ld > 0 && host_sizes[b] > ld)) return -2;
-    }
+    if (!host_sizes_ok(host_sizes, batch, N, ld)) return -2;
     RaggedGroup groups[kMaxRaggedGroups];
     const int n_groups = plan_ragged_groups(host_sizes, batch, nullptr, groups);
     if (n_groups < 0) {
@@ -703,68 +785,21 @@ int lapwarm_seeded_ragged(const double *C, const long long *offsets, const int *
         return -6;
     }
     const RaggedSolverWs w = ragged_solver_layout(workspace, batch, N);
-    if (workspace_bytes < w.bytes) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-        return -1;
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (int rc = check_workspace(workspace_bytes, w.bytes)) return rc;
+    const PreludeWs &pre = w.pre;
+    hipStream_t stream = as_stream(stream_);
     const RaggedBatch g{C, offsets, sizes, ld, batch, N};
-    HIP_TRY(launch_seed_prepare_ragged(g, u_seed, v_seed, w.u_work, w.v_work, w.flags, x, y, ret, stats, stream));
-
-    PreludeParams pp;
-    pp.C = C;
-    pp.n = N;
-    pp.batch = batch;
-    pp.u = w.u_work;
-    pp.v = w.v_work;
-    pp.eps = eps;
-    pp.tight_eps = (eps < 1e-9) ? 1e-9 : eps;  // std::max(eps, 1e-9), lapjv_seeded.cpp:76
-    pp.rerun = 0;
-    pp.u_tight = w.u_tight;
-    pp.viol_cnt = w.viol_cnt;
-    pp.tight_cnt = w.tight_cnt;
-    pp.tight_bits = w.tight_bits;
-    pp.inst_flags = w.flags;
-    HIP_TRY(launch_prelude_ragged(pp, g, stream));
-    HIP_TRY(launch_projection_ragged(g, w.u_work, w.v_work, w.viol_cnt, w.flags, eps, stream));
-    pp.rerun = 1;
-    HIP_TRY(launch_prelude_ragged(pp, g, stream));
-
-    SolverParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.C = C;
-    sp.n = N;
-    sp.batch = batch;
-    sp.mode = kModeSeeded;
-    sp.u_tight = w.u_tight;
-    sp.v_work = w.v_work;
-    sp.tight_cnt = w.tight_cnt;
-    sp.tight_bits = w.tight_bits;
-    sp.inst_flags = w.flags;
-    sp.tight_eps = pp.tight_eps;
-    sp.x_out = x;
-    sp.y_out = y;
-    sp.ret = ret;
-    sp.stats = stats;
-    sp.rg_offsets = offsets;
-    sp.rg_sizes = sizes;
-    sp.rg_ld = ld;
-    sp.rg_N = N;
-    // one launch per kernel configuration; the launches are independent and each workgroup picks its own
-    HIP_TRY(profile_begin(stream));  // (the bracket of lapwarm_profile_enable: all solver launches of the call)
-    for (int k = 0; k < n_groups; ++k) {
-        sp.rg_n_lo = groups[k].n_lo;
-        sp.rg_n_hi = groups[k].n_hi;
-        HIP_TRY(launch_phase_ragged(groups[k].k, sp, stream));
-    }
-    HIP_TRY(profile_end(stream));
-    return 0;
+    HIP_TRY(launch_seed_prepare_ragged(g, u_seed, v_seed, pre.u_work, pre.v_work, pre.flags, x, y, ret, stats,
+                                       stream));
+    SolverParams sp = ragged_solver_params(kModeSeeded, g, x, y, ret, stats, &pre);
+    if (int rc = seeded_prelude(C, batch, N, pre, eps, &g, stream, &sp.tight_eps)) return rc;
+    return launch_ragged_groups(sp, groups, n_groups, stream);
 }
 
 // ---- cold lapjv of a ragged batch (extend_ragged.hip around the ragged launches of jv_instance_kernel) ----
 size_t lapwarm_lapjv_ragged_workspace_bytes(int batch, int N)
 {
-    if (N <= 0 || batch <= 0 || batch > 65535 || N > 16384) return 0;
+    if (check_ragged_dims(batch, N)) return 0;
     return align_up(1);  // every eligible instance keeps its solver state in LDS: the workspace is not used
 }
 
@@ -775,58 +810,25 @@ int lapwarm_lapjv_ragged_groups(const int *sizes, int batch, int *group_of)
     return plan_ragged_groups_cold(sizes, batch, group_of, groups);
 }
 
-// The solver launches of a ragged cold solve: one per group, every workgroup picks its own.
-static int lapjv_ragged_launches(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
-                                 long long *x, long long *y, int *ret, long long *stats, const RaggedGroup *groups,
-                                 int n_groups, hipStream_t stream)
-{
-    SolverParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.C = C;
-    sp.n = N;
-    sp.batch = batch;
-    sp.mode = kModeCold;
-    sp.x_out = x;
-    sp.y_out = y;
-    sp.ret = ret;
-    sp.stats = stats;
-    sp.rg_offsets = offsets;
-    sp.rg_sizes = sizes;
-    sp.rg_ld = ld;
-    sp.rg_N = N;
-    HIP_TRY(profile_begin(stream));
-    for (int k = 0; k < n_groups; ++k) {
-        sp.rg_n_lo = groups[k].n_lo;
-        sp.rg_n_hi = groups[k].n_hi;
-        HIP_TRY(launch_phase_ragged(groups[k].k, sp, stream));
-    }
-    HIP_TRY(profile_end(stream));
-    return 0;
-}
-
 int lapwarm_lapjv_ragged(const double *C, const long long *offsets, const int *sizes, const int *host_sizes, int ld,
                          int batch, int N, long long *x, long long *y, int *ret, long long *stats, void *workspace,
                          size_t workspace_bytes, void *stream_)
 {
     if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
     if (!host_sizes || !x || !y || !ret || !workspace) return -2;
-    for (int b = 0; b < batch; ++b) {
-        if (host_sizes[b] < 1 || host_sizes[b] > N || (ld > 0 && host_sizes[b] > ld)) return -2;
-    }
+    if (!host_sizes_ok(host_sizes, batch, N, ld)) return -2;
     RaggedGroup groups[kMaxRaggedGroups];
     const int n_groups = plan_ragged_groups_cold(host_sizes, batch, nullptr, groups);
     if (n_groups < 0) {
         snprintf(g_err, sizeof(g_err), "lapwarm_lapjv_ragged: an instance is outside the one-launch, all-LDS, no-lists class");
         return -6;
     }
-    const size_t need = lapwarm_lapjv_ragged_workspace_bytes(batch, N);
-    if (workspace_bytes < need) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, need);
-        return -1;
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (int rc = check_workspace(workspace_bytes, lapwarm_lapjv_ragged_workspace_bytes(batch, N))) return rc;
+    hipStream_t stream = as_stream(stream_);
     HIP_TRY(launch_lapjv_ragged_init(x, y, ret, stats, batch, N, stream));
-    return lapjv_ragged_launches(C, offsets, sizes, ld, batch, N, x, y, ret, stats, groups, n_groups, stream);
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    return launch_ragged_groups(ragged_solver_params(kModeCold, g, x, y, ret, stats, nullptr), groups, n_groups,
+                                stream);
 }
 
 // Rectangular / cost-limited lapjv of a ragged batch: the shapes block (E offsets and extended sizes), the
@@ -858,7 +860,7 @@ static int extended_ragged_sizes(const int *host_rows, const int *host_cols, con
                                  int extend_cost, int batch, std::vector<int> *sizes, int *N, int *R, int *Q,
                                  long long *e_total)
 {
-    if (batch <= 0 || batch > 65535 || !host_rows || !host_cols || !host_limits) return -2;
+    if (batch <= 0 || batch > kMaxGridY || !host_rows || !host_cols || !host_limits) return -2;
     sizes->resize((size_t)batch);
     *N = *R = *Q = 0;
     *e_total = 0;
@@ -908,16 +910,15 @@ int lapwarm_lapjv_extended_ragged(const double *C, const long long *offsets, con
         return -6;
     }
     const ExtendedRaggedWs w = extended_ragged_layout(workspace, batch, N, R, e_total);
-    if (workspace_bytes < w.bytes) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-        return -1;
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (int rc = check_workspace(workspace_bytes, w.bytes)) return rc;
+    hipStream_t stream = as_stream(stream_);
     const ExtRagged g{C, offsets, n_rows, n_cols, cost_limit, ld, extend_cost ? 1 : 0, batch, R, Q, N, e_total,
                       w.e_off, w.e_n, w.E};
     HIP_TRY(launch_extend_shapes(g, stream));
     HIP_TRY(launch_extend_costs_ragged(g, ret, stats, stream));
-    if (int rc = lapjv_ragged_launches(w.E, w.e_off, w.e_n, 0, batch, N, w.xs, w.ys, ret, stats, groups, n_groups, stream))
+    const RaggedBatch extended{w.E, w.e_off, w.e_n, 0, batch, N};
+    if (int rc = launch_ragged_groups(ragged_solver_params(kModeCold, extended, w.xs, w.ys, ret, stats, nullptr),
+                                      groups, n_groups, stream))
         return rc;
     HIP_TRY(launch_extended_finish_ragged(g, w.xs, w.ys, ret, x, y, opt, matched, w.gath, stream));
     return 0;
@@ -935,7 +936,7 @@ struct LapmodWs {
 
 static int lapmod_layout(void *ws, const int *host_sizes, const long long *host_nnz, int batch, int N, LapmodWs *w)
 {
-    if (batch <= 0 || batch > 65535 || !host_sizes) return -2;
+    if (batch <= 0 || batch > kMaxGridY || !host_sizes) return -2;
     const int lds_max = lapmod_lds_max_n();
     size_t state = 0;
     w->lds_n = 0;
@@ -979,11 +980,8 @@ int lapwarm_lapmod_ragged(const double *cc, const int *kk, const int *ii, const 
     if (int rc = lapmod_layout(workspace, host_sizes, nullptr, batch, N, &w)) return rc;
     if (!cc || !kk || !ii || !nnz_offsets || !row_offsets || !sizes || !x || !y || !ret || !workspace) return -2;
     if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return -2;
-    if (workspace_bytes < w.bytes) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-        return -1;
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (int rc = check_workspace(workspace_bytes, w.bytes)) return rc;
+    hipStream_t stream = as_stream(stream_);
     LapmodParams p;
     p.cc = cc;
     p.kk = kk;
@@ -1012,8 +1010,8 @@ int lapwarm_project_round_batched(const double *C, int batch, int n, double *u, 
                                   double *gmin, void *workspace, size_t workspace_bytes, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    if (workspace_bytes < lapwarm_sweep_workspace_bytes(batch, n)) return -1;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (int rc = check_workspace(workspace_bytes, lapwarm_sweep_workspace_bytes(batch, n))) return rc;
+    hipStream_t stream = as_stream(stream_);
     const SweepWs w = sweep_layout(workspace, batch, n);
     HIP_TRY(launch_cap_rows(C, n, batch, u, v, stream));
     HIP_TRY(launch_cap_cols(C, n, batch, u, v, w.partial, stream));
@@ -1026,42 +1024,35 @@ int lapwarm_reduce_costs_batched(const double *C, int batch, int n, const double
                                  size_t workspace_bytes, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    if (workspace_bytes < lapwarm_sweep_workspace_bytes(batch, n)) return -1;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (int rc = check_workspace(workspace_bytes, lapwarm_sweep_workspace_bytes(batch, n))) return rc;
+    hipStream_t stream = as_stream(stream_);
     HIP_TRY(launch_reduced_min(C, n, batch, u, v, sweep_layout(workspace, batch, n).rowpart, gmin, stream));
     HIP_TRY(launch_reduce_costs(C, n, batch, u, v, gmin, shift_nonneg, out, stream));
     return 0;
 }
 
 // ---- dual utilities of a ragged batch (ragged_duals.hip) ----
-static RaggedDualsWs ragged_duals_layout(void *workspace, int batch, int N, size_t *bytes)
+static RaggedDualsWs ragged_duals_layout(void *workspace, int batch, int N)
 {
     Carver c{reinterpret_cast<unsigned char *>(workspace), 0};
     RaggedDualsWs w;
     w.part = c.take<double>((size_t)batch * N);
     w.done = c.take<int>(batch);
     w.running = c.take<int>(1);
-    *bytes = c.off;
+    w.bytes = c.off;
     return w;
 }
 
 size_t lapwarm_ragged_duals_workspace_bytes(int batch, int N)
 {
-    if (N <= 0 || batch <= 0 || batch > 65535 || N > 16384) return 0;
-    size_t bytes = 0;
-    ragged_duals_layout(nullptr, batch, N, &bytes);
-    return bytes;
+    if (check_ragged_dims(batch, N)) return 0;
+    return ragged_duals_layout(nullptr, batch, N).bytes;
 }
 
 static int check_ragged_duals_ws(const void *workspace, size_t workspace_bytes, int batch, int N)
 {
     if (!workspace) return -2;
-    const size_t need = lapwarm_ragged_duals_workspace_bytes(batch, N);
-    if (workspace_bytes < need) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, need);
-        return -1;
-    }
-    return 0;
+    return check_workspace(workspace_bytes, lapwarm_ragged_duals_workspace_bytes(batch, N));
 }
 
 int lapwarm_rowmin_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
@@ -1072,7 +1063,7 @@ int lapwarm_rowmin_ragged(const double *C, const long long *offsets, const int *
     if (!out) return -2;
     if (int rc = check_ragged_duals_ws(workspace, workspace_bytes, batch, N)) return rc;
     const RaggedBatch g{C, offsets, sizes, ld, batch, N};
-    HIP_TRY(launch_rowmin_ragged(g, v, out, ret, reinterpret_cast<hipStream_t>(stream_)));
+    HIP_TRY(launch_rowmin_ragged(g, v, out, ret, as_stream(stream_)));
     return 0;
 }
 
@@ -1086,10 +1077,9 @@ int lapwarm_project_feasible_ragged(const double *C, const long long *offsets, c
     if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
     if (!u || !v || !gmin || !rounds || !ret) return -2;
     if (int rc = check_ragged_duals_ws(workspace, workspace_bytes, batch, N)) return rc;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     const RaggedBatch g{C, offsets, sizes, ld, batch, N};
-    size_t bytes = 0;
-    const RaggedDualsWs w = ragged_duals_layout(workspace, batch, N, &bytes);
+    const RaggedDualsWs w = ragged_duals_layout(workspace, batch, N);
     HIP_TRY(launch_project_init_ragged(g, w, u, v, gmin, rounds, ret, stream));
     const int total = (max_rounds < 1) ? 1 : max_rounds;  // max(1, int(max_rounds)), advanced_dual.py:28
     int r = 0, chunk = 1;
@@ -1114,10 +1104,8 @@ int lapwarm_reduce_costs_ragged(const double *C, const long long *offsets, const
     if (!u || !v || !gmin) return -2;
     if (int rc = check_ragged_duals_ws(workspace, workspace_bytes, batch, N)) return rc;
     const RaggedBatch g{C, offsets, sizes, ld, batch, N};
-    size_t bytes = 0;
-    const RaggedDualsWs w = ragged_duals_layout(workspace, batch, N, &bytes);
-    HIP_TRY(launch_reduce_costs_ragged(g, w, u, v, shift_nonneg, out, gmin, ret,
-                                       reinterpret_cast<hipStream_t>(stream_)));
+    const RaggedDualsWs w = ragged_duals_layout(workspace, batch, N);
+    HIP_TRY(launch_reduce_costs_ragged(g, w, u, v, shift_nonneg, out, gmin, ret, as_stream(stream_)));
     return 0;
 }
 
@@ -1159,7 +1147,7 @@ static int oracle_duals_impl(const double *C, int batch, int n, const int *rows,
                              double tol, hipStream_t stream)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    if (workspace_bytes < lapwarm_oracle_duals_workspace_bytes(batch, n)) return -1;
+    if (int rc = check_workspace(workspace_bytes, lapwarm_oracle_duals_workspace_bytes(batch, n))) return rc;
     OracleParams p;
     p.C = C;
     p.n = n;
@@ -1178,12 +1166,12 @@ int lapwarm_oracle_duals_batched(const double *C, int batch, int n, const int *r
                                  void *stream_)
 {
     return oracle_duals_impl(C, batch, n, rows, cols, u, v, ret, sweeps, workspace, workspace_bytes, 1e-12,
-                             reinterpret_cast<hipStream_t>(stream_));
+                             as_stream(stream_));
 }
 
 size_t lapwarm_oracle_duals_ragged_workspace_bytes(int batch, int N)
 {
-    if (N <= 0 || batch <= 0 || batch > 65535 || N > kOracleMaxN) return 0;
+    if (check_ragged_dims(batch, N) || N > kOracleMaxN) return 0;
     OracleParams p;
     return oracle_layout(nullptr, batch, N, &p).bytes;  // the uniform slots with the padded stride N
 }
@@ -1209,22 +1197,21 @@ int lapwarm_oracle_duals_ragged(const double *C, const long long *offsets, const
     p.rows = rows;
     p.cols = cols;
     const OracleWs w = oracle_layout(workspace, batch, N, &p);
-    if (workspace_bytes < w.bytes) {
-        snprintf(g_err, sizeof(g_err), "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-        return -1;
-    }
-    int max_s = 0;  // a host size the device would treat as empty asks for no sweeps
+    if (int rc = check_workspace(workspace_bytes, w.bytes)) return rc;
+    // (not host_sizes_ok: this entry skips a host size the device would treat as empty, which asks for no
+    // sweeps, where the solves reject the batch)
+    int max_s = 0;
     for (int b = 0; b < batch; ++b) {
         const int n = host_sizes[b];
         if (n >= 1 && n <= N && (ld == 0 || n <= ld) && n - 1 > max_s) max_s = n - 1;
     }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     return oracle_run(p, w, max_s, 1e-12, u, v, ret, sweeps, stream);
 }
 
 size_t lapwarm_train_loss_workspace_bytes(int batch, int n)
 {
-    if (check_dims(batch, n) || batch > 65535) return 0;
+    if (check_ragged_dims(batch, n)) return 0;  // (the batch is the y dimension of its grids too)
     TrainLossParams p{};
     p.n = n;
     p.batch = batch;
@@ -1237,8 +1224,8 @@ int lapwarm_train_loss_forward(const float *C, int batch, int n, const int *size
                                int *ret, void *workspace, size_t workspace_bytes, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    if (batch > 65535) return -2;  // the batch is one dimension of every grid
-    if (workspace_bytes < lapwarm_train_loss_workspace_bytes(batch, n)) return -1;
+    if (batch > kMaxGridY) return -2;  // the batch is one dimension of every grid
+    if (int rc = check_workspace(workspace_bytes, lapwarm_train_loss_workspace_bytes(batch, n))) return rc;
     TrainLossParams p{};
     p.C = C;
     p.n = n;
@@ -1253,7 +1240,7 @@ int lapwarm_train_loss_forward(const float *C, int batch, int n, const int *size
     p.ret = ret;
     train_loss_plan(&p);
     train_loss_layout(workspace, &p);
-    HIP_TRY(launch_train_loss_forward(p, reinterpret_cast<hipStream_t>(stream_)));
+    HIP_TRY(launch_train_loss_forward(p, as_stream(stream_)));
     return 0;
 }
 
@@ -1262,8 +1249,8 @@ int lapwarm_train_loss_backward(int batch, int n, const int *sizes, const float 
                                 size_t workspace_bytes, void *stream_)
 {
     if (int rc = check_dims(batch, n)) return rc;
-    if (batch > 65535) return -2;
-    if (workspace_bytes < lapwarm_train_loss_workspace_bytes(batch, n)) return -1;
+    if (batch > kMaxGridY) return -2;
+    if (int rc = check_workspace(workspace_bytes, lapwarm_train_loss_workspace_bytes(batch, n))) return rc;
     TrainLossParams p{};
     p.n = n;
     p.batch = batch;
@@ -1272,7 +1259,7 @@ int lapwarm_train_loss_backward(int batch, int n, const int *sizes, const float 
     p.ut = u_target;
     train_loss_plan(&p);
     train_loss_layout(const_cast<void *>(workspace), &p);  // the kernel only reads it
-    HIP_TRY(launch_train_loss_backward(p, weights, grad_scale, grad_u, reinterpret_cast<hipStream_t>(stream_)));
+    HIP_TRY(launch_train_loss_backward(p, weights, grad_scale, grad_u, as_stream(stream_)));
     return 0;
 }
 
@@ -1285,24 +1272,22 @@ int lapjv_seeded(const double *C, int n_rows, int n_cols, long long *x, long lon
     if (n_rows <= 0 || n_cols <= 0) return -2;  // lapjv_seeded.cpp:25
     if (n_rows != n_cols) return -4;            // lapjv_seeded.cpp:27
     const int n = n_rows;
-    if (n > 16384) return -5;
+    if (n > kMaxN) return -5;
     std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t ws_bytes = lapwarm_seeded_workspace_bytes(1, n);
+    const size_t ws_bytes = lapwarm_seeded_workspace_bytes(1, n), nn = (size_t)n * n;
     const auto [dC, du, dv, dx, dy, dret, ws] = g_arena.stage([&](Carver &c) {
-        return std::tuple{c.take<double>((size_t)n * n), c.take<double>(n), c.take<double>(n), c.take<long long>(n),
+        return std::tuple{c.take<double>(nn), c.take<double>(n), c.take<double>(n), c.take<long long>(n),
                           c.take<long long>(n), c.take<int>(1), c.take<unsigned char>(ws_bytes)};
     });
     if (!dC) return -1;
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(du, u_seed, sizeof(double) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dv, v_seed, sizeof(double) * n, hipMemcpyHostToDevice));
-    int rc = lapwarm_seeded_batched(dC, 1, n, du, dv, eps, dx, dy, dret, nullptr, ws, ws_bytes, 0, nullptr);
-    if (rc) return rc;
-    int ret = 0;
-    HIP_TRY(hipMemcpy(&ret, dret, sizeof(int), hipMemcpyDeviceToHost));
-    if (ret != 0) return ret;
-    HIP_TRY(hipMemcpy(x, dx, sizeof(long long) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(y, dy, sizeof(long long) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(upload(dC, C, nn));
+    HIP_TRY(upload(du, u_seed, n));
+    HIP_TRY(upload(dv, v_seed, n));
+    if (int rc = lapwarm_seeded_batched(dC, 1, n, du, dv, eps, dx, dy, dret, nullptr, ws, ws_bytes, 0, nullptr))
+        return rc;
+    if (int ret = device_ret(dret)) return ret;
+    HIP_TRY(download(x, dx, n));
+    HIP_TRY(download(y, dy, n));
     return 0;
 }
 
@@ -1310,20 +1295,17 @@ int lapwarm_lapjv_dense(const double *C, int n, int *x, int *y)
 {
     if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t ws_bytes = lapwarm_lapjv_workspace_bytes(1, n);
+    const size_t ws_bytes = lapwarm_lapjv_workspace_bytes(1, n), nn = (size_t)n * n;
     const auto [dC, dx, dy, dret, ws] = g_arena.stage([&](Carver &c) {
-        return std::tuple{c.take<double>((size_t)n * n), c.take<int>(n), c.take<int>(n), c.take<int>(1),
+        return std::tuple{c.take<double>(nn), c.take<int>(n), c.take<int>(n), c.take<int>(1),
                           c.take<unsigned char>(ws_bytes)};
     });
     if (!dC) return -1;
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    int rc = lapwarm_lapjv_batched(dC, 1, n, dx, dy, dret, nullptr, ws, ws_bytes, 0, nullptr);
-    if (rc) return rc;
-    int ret = 0;
-    HIP_TRY(hipMemcpy(&ret, dret, sizeof(int), hipMemcpyDeviceToHost));
-    if (ret != 0) return ret;
-    HIP_TRY(hipMemcpy(x, dx, sizeof(int) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(y, dy, sizeof(int) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(upload(dC, C, nn));
+    if (int rc = lapwarm_lapjv_batched(dC, 1, n, dx, dy, dret, nullptr, ws, ws_bytes, 0, nullptr)) return rc;
+    if (int ret = device_ret(dret)) return ret;
+    HIP_TRY(download(x, dx, n));
+    HIP_TRY(download(y, dy, n));
     return 0;
 }
 
@@ -1341,16 +1323,14 @@ int lapwarm_lapjv_extended(const double *C, int n_rows, int n_cols, int extend_c
                           c.take<int>(1), c.take<unsigned char>(ws_bytes)};
     });
     if (!dC) return -1;
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * nc, hipMemcpyHostToDevice));
-    int rc = lapwarm_lapjv_extended_batched(dC, 1, n_rows, n_cols, extend_cost, cost_limit, dx, dy, dopt, nullptr,
-                                            dret, nullptr, ws, ws_bytes, 0, nullptr);
-    if (rc) return rc;
-    int ret = 0;
-    HIP_TRY(hipMemcpy(&ret, dret, sizeof(int), hipMemcpyDeviceToHost));
-    if (ret != 0) return ret;
-    HIP_TRY(hipMemcpy(x, dx, sizeof(int) * n_rows, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(y, dy, sizeof(int) * n_cols, hipMemcpyDeviceToHost));
-    if (opt) HIP_TRY(hipMemcpy(opt, dopt, sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(upload(dC, C, nc));
+    if (int rc = lapwarm_lapjv_extended_batched(dC, 1, n_rows, n_cols, extend_cost, cost_limit, dx, dy, dopt, nullptr,
+                                                dret, nullptr, ws, ws_bytes, 0, nullptr))
+        return rc;
+    if (int ret = device_ret(dret)) return ret;
+    HIP_TRY(download(x, dx, n_rows));
+    HIP_TRY(download(y, dy, n_cols));
+    if (opt) HIP_TRY(download(opt, dopt, 1));
     return 0;
 }
 
@@ -1360,26 +1340,23 @@ int lapwarm_warmstart_lapjv(const double *C, int n, const double *u, const doubl
     if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t ws_sweep = lapwarm_sweep_workspace_bytes(1, n);
-    const size_t ws_solve = lapwarm_lapjv_workspace_bytes(1, n);
+    const size_t ws_solve = lapwarm_lapjv_workspace_bytes(1, n), nn = (size_t)n * n;
     // (dR, the reduced matrix, never leaves the device)
     const auto [dC, dR, du, dv, dg, dx, dy, dret, wsA, wsB] = g_arena.stage([&](Carver &c) {
-        return std::tuple{c.take<double>((size_t)n * n), c.take<double>((size_t)n * n), c.take<double>(n),
-                          c.take<double>(n), c.take<double>(1), c.take<int>(n), c.take<int>(n), c.take<int>(1),
+        return std::tuple{c.take<double>(nn), c.take<double>(nn), c.take<double>(n), c.take<double>(n),
+                          c.take<double>(1), c.take<int>(n), c.take<int>(n), c.take<int>(1),
                           c.take<unsigned char>(ws_sweep), c.take<unsigned char>(ws_solve)};
     });
     if (!dC) return -1;
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(du, u, sizeof(double) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
-    int rc = lapwarm_reduce_costs_batched(dC, 1, n, du, dv, shift_nonneg, dR, dg, wsA, ws_sweep, nullptr);
-    if (rc) return rc;
-    rc = lapwarm_lapjv_batched(dR, 1, n, dx, dy, dret, nullptr, wsB, ws_solve, 0, nullptr);
-    if (rc) return rc;
-    int ret = 0;
-    HIP_TRY(hipMemcpy(&ret, dret, sizeof(int), hipMemcpyDeviceToHost));
-    if (ret != 0) return ret;
-    HIP_TRY(hipMemcpy(x, dx, sizeof(int) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(y, dy, sizeof(int) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(upload(dC, C, nn));
+    HIP_TRY(upload(du, u, n));
+    HIP_TRY(upload(dv, v, n));
+    if (int rc = lapwarm_reduce_costs_batched(dC, 1, n, du, dv, shift_nonneg, dR, dg, wsA, ws_sweep, nullptr))
+        return rc;
+    if (int rc = lapwarm_lapjv_batched(dR, 1, n, dx, dy, dret, nullptr, wsB, ws_solve, 0, nullptr)) return rc;
+    if (int ret = device_ret(dret)) return ret;
+    HIP_TRY(download(x, dx, n));
+    HIP_TRY(download(y, dy, n));
     return 0;
 }
 
@@ -1401,22 +1378,19 @@ int lapwarm_row_features(const double *C, int n, float *feat, float *topk16)
 {
     if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n);
+    const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n), rows = (size_t)n;
     const auto [dC, dpos, dfeat, dtop, ws] = g_arena.stage([&](Carver &c) {
-        return std::tuple{c.take<double>((size_t)n * n), c.take<float>((size_t)n * 8), c.take<float>((size_t)n * 21),
-                          c.take<float>((size_t)n * 16), c.take<unsigned char>(ws_bytes)};
+        return std::tuple{c.take<double>(rows * n), c.take<float>(rows * 8), c.take<float>(rows * 21),
+                          c.take<float>(rows * 16), c.take<unsigned char>(ws_bytes)};
     });
     if (!dC) return -1;
-    float *pos = new float[(size_t)n * 8];
-    host_posenc(n, pos);
-    hipError_t e1 = hipMemcpy(dpos, pos, sizeof(float) * n * 8, hipMemcpyHostToDevice);
-    delete[] pos;
-    HIP_TRY(e1);
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    int rc = lapwarm_row_features_batched(dC, 1, n, dpos, dfeat, dtop, ws, ws_bytes, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(feat, dfeat, sizeof(float) * n * 21, hipMemcpyDeviceToHost));
-    if (topk16) HIP_TRY(hipMemcpy(topk16, dtop, sizeof(float) * n * 16, hipMemcpyDeviceToHost));
+    std::vector<float> pos(rows * 8);
+    host_posenc(n, pos.data());
+    HIP_TRY(upload(dpos, pos.data(), pos.size()));
+    HIP_TRY(upload(dC, C, rows * n));
+    if (int rc = lapwarm_row_features_batched(dC, 1, n, dpos, dfeat, dtop, ws, ws_bytes, nullptr)) return rc;
+    HIP_TRY(download(feat, dfeat, rows * 21));
+    if (topk16) HIP_TRY(download(topk16, dtop, rows * 16));
     return 0;
 }
 
@@ -1424,17 +1398,15 @@ int lapwarm_min_trick(const double *C, int n, const double *u, double *v)
 {
     if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n);
+    const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n), nn = (size_t)n * n;
     const auto [dC, du, dv, ws] = g_arena.stage([&](Carver &c) {
-        return std::tuple{c.take<double>((size_t)n * n), c.take<double>(n), c.take<double>(n),
-                          c.take<unsigned char>(ws_bytes)};
+        return std::tuple{c.take<double>(nn), c.take<double>(n), c.take<double>(n), c.take<unsigned char>(ws_bytes)};
     });
     if (!dC) return -1;
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    if (u) HIP_TRY(hipMemcpy(du, u, sizeof(double) * n, hipMemcpyHostToDevice));
-    int rc = lapwarm_colmin_batched(dC, 1, n, u ? du : nullptr, dv, ws, ws_bytes, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(v, dv, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(upload(dC, C, nn));
+    if (u) HIP_TRY(upload(du, u, n));
+    if (int rc = lapwarm_colmin_batched(dC, 1, n, u ? du : nullptr, dv, ws, ws_bytes, nullptr)) return rc;
+    HIP_TRY(download(v, dv, n));
     return 0;
 }
 
@@ -1442,15 +1414,15 @@ int lapwarm_row_min(const double *C, int n, const double *v, double *out)
 {
     if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
+    const size_t nn = (size_t)n * n;
     const auto [dC, dv, dout] = g_arena.stage([&](Carver &c) {
-        return std::tuple{c.take<double>((size_t)n * n), c.take<double>(n), c.take<double>(n)};
+        return std::tuple{c.take<double>(nn), c.take<double>(n), c.take<double>(n)};
     });
     if (!dC) return -1;
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    if (v) HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
-    int rc = lapwarm_rowmin_batched(dC, 1, n, v ? dv : nullptr, dout, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(upload(dC, C, nn));
+    if (v) HIP_TRY(upload(dv, v, n));
+    if (int rc = lapwarm_rowmin_batched(dC, 1, n, v ? dv : nullptr, dout, nullptr)) return rc;
+    HIP_TRY(download(out, dout, n));
     return 0;
 }
 
@@ -1458,25 +1430,24 @@ int lapwarm_project_feasible(const double *C, int n, double *u, double *v, int m
 {
     if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n);
+    const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n), nn = (size_t)n * n;
     const auto [dC, du, dv, dg, ws] = g_arena.stage([&](Carver &c) {
-        return std::tuple{c.take<double>((size_t)n * n), c.take<double>(n), c.take<double>(n), c.take<double>(1),
+        return std::tuple{c.take<double>(nn), c.take<double>(n), c.take<double>(n), c.take<double>(1),
                           c.take<unsigned char>(ws_bytes)};
     });
     if (!dC) return -1;
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(du, u, sizeof(double) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIP_TRY(upload(dC, C, nn));
+    HIP_TRY(upload(du, u, n));
+    HIP_TRY(upload(dv, v, n));
     const int rounds = (max_rounds < 1) ? 1 : max_rounds;  // max(1, int(max_rounds)), advanced_dual.py:28
     for (int r = 0; r < rounds; ++r) {
-        int rc = lapwarm_project_round_batched(dC, 1, n, du, dv, dg, ws, ws_bytes, nullptr);
-        if (rc) return rc;
+        if (int rc = lapwarm_project_round_batched(dC, 1, n, du, dv, dg, ws, ws_bytes, nullptr)) return rc;
         double g = 0.0;
-        HIP_TRY(hipMemcpy(&g, dg, sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(download(&g, dg, 1));
         if (g >= -tol) break;
     }
-    HIP_TRY(hipMemcpy(u, du, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(v, dv, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(download(u, du, n));
+    HIP_TRY(download(v, dv, n));
     return 0;
 }
 
@@ -1485,19 +1456,19 @@ int lapwarm_reduce_costs(const double *C, int n, const double *u, const double *
 {
     if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n);
+    const size_t ws_bytes = lapwarm_sweep_workspace_bytes(1, n), nn = (size_t)n * n;
     const auto [dC, dO, du, dv, dg, ws] = g_arena.stage([&](Carver &c) {
-        return std::tuple{c.take<double>((size_t)n * n), c.take<double>((size_t)n * n), c.take<double>(n),
-                          c.take<double>(n), c.take<double>(1), c.take<unsigned char>(ws_bytes)};
+        return std::tuple{c.take<double>(nn), c.take<double>(nn), c.take<double>(n), c.take<double>(n),
+                          c.take<double>(1), c.take<unsigned char>(ws_bytes)};
     });
     if (!dC) return -1;
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(du, u, sizeof(double) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dv, v, sizeof(double) * n, hipMemcpyHostToDevice));
-    int rc = lapwarm_reduce_costs_batched(dC, 1, n, du, dv, shift_nonneg, dO, dg, ws, ws_bytes, nullptr);
-    if (rc) return rc;
-    if (out) HIP_TRY(hipMemcpy(out, dO, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
-    if (min_out) HIP_TRY(hipMemcpy(min_out, dg, sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(upload(dC, C, nn));
+    HIP_TRY(upload(du, u, n));
+    HIP_TRY(upload(dv, v, n));
+    if (int rc = lapwarm_reduce_costs_batched(dC, 1, n, du, dv, shift_nonneg, dO, dg, ws, ws_bytes, nullptr))
+        return rc;
+    if (out) HIP_TRY(download(out, dO, nn));
+    if (min_out) HIP_TRY(download(min_out, dg, 1));
     return 0;
 }
 
@@ -1506,24 +1477,20 @@ int lapwarm_oracle_duals(const double *C, int n, const int *rows, const int *col
 {
     if (int rc = check_dims(1, n)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t ws_bytes = lapwarm_oracle_duals_workspace_bytes(1, n);
+    const size_t ws_bytes = lapwarm_oracle_duals_workspace_bytes(1, n), nn = (size_t)n * n;
     const auto [dC, dr, dc, du, dv, dret, ws] = g_arena.stage([&](Carver &c) {
-        return std::tuple{c.take<double>((size_t)n * n), c.take<int>(n), c.take<int>(n), c.take<double>(n),
-                          c.take<double>(n), c.take<int>(1), c.take<unsigned char>(ws_bytes)};
+        return std::tuple{c.take<double>(nn), c.take<int>(n), c.take<int>(n), c.take<double>(n), c.take<double>(n),
+                          c.take<int>(1), c.take<unsigned char>(ws_bytes)};
     });
     if (!dC) return -1;
-    HIP_TRY(hipMemcpy(dC, C, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dr, rows, sizeof(int) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dc, cols, sizeof(int) * n, hipMemcpyHostToDevice));
-    int rc = oracle_duals_impl(dC, 1, n, dr, dc, du, dv, dret, nullptr, ws, ws_bytes, tol, nullptr);
-    if (rc) return rc;
-    int r = 0;
-    HIP_TRY(hipMemcpy(&r, dret, sizeof(int), hipMemcpyDeviceToHost));
-    if (r == 0) {
-        HIP_TRY(hipMemcpy(u, du, sizeof(double) * n, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(v, dv, sizeof(double) * n, hipMemcpyDeviceToHost));
-    }
-    return r;
+    HIP_TRY(upload(dC, C, nn));
+    HIP_TRY(upload(dr, rows, n));
+    HIP_TRY(upload(dc, cols, n));
+    if (int rc = oracle_duals_impl(dC, 1, n, dr, dc, du, dv, dret, nullptr, ws, ws_bytes, tol, nullptr)) return rc;
+    if (int ret = device_ret(dret)) return ret;
+    HIP_TRY(download(u, du, n));
+    HIP_TRY(download(v, dv, n));
+    return 0;
 }
 
 }  // extern "C"

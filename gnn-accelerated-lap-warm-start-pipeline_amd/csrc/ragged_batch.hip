@@ -110,7 +110,7 @@ __global__ void __launch_bounds__(kRowThreads) vecmin_ragged_kernel(RaggedBatch 
 hipError_t launch_reduced_min_ragged(const RaggedBatch &g, const double *u, const double *v, double *rowpart,
                                      double *gmin, hipStream_t stream)
 {
-    if (g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(reduced_rowmin_ragged_kernel, dim3(g.N, g.batch), dim3(kRowThreads), 0, stream, g, u, v,
                        rowpart);
     hipLaunchKernelGGL(vecmin_ragged_kernel, dim3(g.batch), dim3(kRowThreads), 0, stream, g, rowpart, gmin);
@@ -119,7 +119,7 @@ hipError_t launch_reduced_min_ragged(const RaggedBatch &g, const double *u, cons
 
 hipError_t launch_colmin_ragged(const RaggedBatch &g, const double *u, double *out, hipStream_t stream)
 {
-    if (g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N)) return hipErrorInvalidValue;
     const dim3 grid((g.N + kTileCols - 1) / kTileCols, g.batch), block(kColminThreads);
     if (u)
         hipLaunchKernelGGL(colmin_ragged_kernel<true>, grid, block, 0, stream, g, u, out);

@@ -9,6 +9,19 @@
 
 namespace lapwarm {
 
+// The limits of every dense entry point: a row of n values is what the row kernels keep in LDS, and the batch
+// (or the heads) is the y dimension of a grid.
+constexpr int kMaxN = 16384;
+constexpr int kMaxGridY = 65535;
+
+// The (batch, N) of a ragged call: 0, or the C ABI's argument code (-2 empty or too many instances, -5 N too large).
+inline int check_ragged_dims(int batch, int N)
+{
+    if (N <= 0 || batch <= 0 || batch > kMaxGridY) return -2;
+    if (N > kMaxN) return -5;
+    return 0;
+}
+
 // Instance b is the n_b x n_b matrix at C + offsets[b] with row stride ld, or n_b when ld == 0 (packed).
 // offsets are multiples of 8 bytes only.  N is the padded width of every output.
 struct RaggedBatch {

@@ -220,13 +220,11 @@ reduce_costs_ragged_kernel(RaggedBatch g, const double *u, const double *v, cons
     }
 }
 
-bool bad_shape(const RaggedBatch &g) { return g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535; }
-
 }  // namespace
 
 hipError_t launch_rowmin_ragged(const RaggedBatch &g, const double *v, double *out, int *ret, hipStream_t stream)
 {
-    if (bad_shape(g)) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N)) return hipErrorInvalidValue;
     const RowArgs a{nullptr, v, out, ret, nullptr, nullptr};
     hipLaunchKernelGGL(row_pass_ragged_kernel<kRowMin>, dim3(g.N, g.batch), dim3(kRowThreads), 0, stream, g, a);
     return hipGetLastError();
@@ -235,7 +233,7 @@ hipError_t launch_rowmin_ragged(const RaggedBatch &g, const double *v, double *o
 hipError_t launch_project_init_ragged(const RaggedBatch &g, const RaggedDualsWs &w, double *u, double *v, double *gmin,
                                       int *rounds, int *ret, hipStream_t stream)
 {
-    if (bad_shape(g)) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(project_init_ragged_kernel, dim3((g.N + kRowThreads - 1) / kRowThreads, g.batch),
                        dim3(kRowThreads), 0, stream, g, u, v, gmin, rounds, ret, w.done);
     return hipGetLastError();
@@ -244,7 +242,7 @@ hipError_t launch_project_init_ragged(const RaggedBatch &g, const RaggedDualsWs 
 hipError_t launch_project_round_ragged(const RaggedBatch &g, const RaggedDualsWs &w, double *u, double *v, double tol,
                                        double *gmin, int *rounds, hipStream_t stream)
 {
-    if (bad_shape(g)) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N)) return hipErrorInvalidValue;
     const RowArgs a{nullptr, v, u, nullptr, w.done, w.running};
     hipLaunchKernelGGL(row_pass_ragged_kernel<kRowCap>, dim3(g.N, g.batch), dim3(kRowThreads), 0, stream, g, a);
     hipLaunchKernelGGL(col_cap_ragged_kernel, dim3((g.N + kTileCols - 1) / kTileCols, g.batch), dim3(kColThreads), 0,
@@ -257,7 +255,7 @@ hipError_t launch_project_round_ragged(const RaggedBatch &g, const RaggedDualsWs
 hipError_t launch_reduce_costs_ragged(const RaggedBatch &g, const RaggedDualsWs &w, const double *u, const double *v,
                                       int shift_nonneg, double *out, double *gmin, int *ret, hipStream_t stream)
 {
-    if (bad_shape(g)) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N)) return hipErrorInvalidValue;
     const RowArgs a{u, v, w.part, nullptr, nullptr, nullptr};
     hipLaunchKernelGGL(row_pass_ragged_kernel<kRowReduced>, dim3(g.N, g.batch), dim3(kRowThreads), 0, stream, g, a);
     hipLaunchKernelGGL(gmin_ragged_kernel<false>, dim3(g.batch), dim3(kRowThreads), 0, stream, g, w.part, gmin, 0.0,

@@ -12,6 +12,7 @@ struct RaggedDualsWs {
     double *part;  // [batch][N]
     int *done;     // [batch]
     int *running;  // [1]
+    size_t bytes;  // of the three, as the C ABI lays them out
 };
 
 // out[b][i] = min_{j < n_b} (C_b[i][j] - (v ? v[b][j] : 0)) for i < n_b and 0 for n_b <= i < N, NaN as np.min;

@@ -28,7 +28,6 @@ A backward for the fused path is out of scope: a gradient taken through the mode
 """
 from __future__ import annotations
 
-import ctypes as ct
 from typing import Optional
 
 import torch
@@ -100,6 +99,7 @@ class DualLayer(nn.Module):
 
     def _messages_fused(self, edge_feat, row_embed, col_embed, mask):
         from lap import _hip
+        from ._call import hip_call
         lib = _hip.require_device()
         B, N = edge_feat.shape[:2]
         H, D = self.heads, self.head_dim
@@ -111,22 +111,14 @@ class DualLayer(nn.Module):
         if nbytes == 0:
             raise ValueError(f"DualLayer: batch {B}, n {N} or heads {H} outside the fused kernels' range")
         scores = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-        stream = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         lin1, lin2 = self.edge_mlp[0], self.edge_mlp[3]
-        rc = lib.lapwarm_dual_edge_scores(edge_feat.data_ptr(), lin1.weight.data_ptr(), lin1.bias.data_ptr(),
-                                          lin2.weight.data_ptr(), lin2.bias.data_ptr(), fold["G"].data_ptr(),
-                                          scores.data_ptr(), B, N, H, stream)
-        if _hip.check(rc, "dual_edge_scores") != 0:
-            raise RuntimeError(f"lapwarm_dual_edge_scores failed (code {rc})")
+        hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", dev, edge_feat, lin1.weight, lin1.bias, lin2.weight,
+                 lin2.bias, fold["G"], scores, B, N, H)
         row_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
         col_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
         mask8 = None if mask is None else mask.to(torch.uint8).contiguous()
-        rc = lib.lapwarm_dual_attention(scores.data_ptr(), fold["a_row"].data_ptr(), fold["c_row"].data_ptr(),
-                                        fold["a_col"].data_ptr(), fold["c_col"].data_ptr(), fold["kbias"].data_ptr(),
-                                        None if mask8 is None else mask8.data_ptr(), row_val.data_ptr(),
-                                        col_val.data_ptr(), row_msg.data_ptr(), col_msg.data_ptr(), B, N, H, D, stream)
-        if _hip.check(rc, "dual_attention") != 0:
-            raise RuntimeError(f"lapwarm_dual_attention failed (code {rc})")
+        hip_call("lapwarm_dual_attention", "dual_attention", dev, scores, fold["a_row"], fold["c_row"], fold["a_col"],
+                 fold["c_col"], fold["kbias"], mask8, row_val, col_val, row_msg, col_msg, B, N, H, D)
         return row_msg, col_msg
 
     # ---- the plain path ------------------------------------------------------------------------------------

@@ -16,7 +16,6 @@ unstable argsort may return.  `gnn.compute_features` (the package-level name) st
 """
 from __future__ import annotations
 
-import ctypes as ct
 from dataclasses import dataclass
 
 import numpy as np
@@ -80,6 +79,7 @@ def row_features_device(C, return_topk: bool = True):
     """C: CUDA float64 tensor (B, n, n) or (n, n) -> feat (B, n, 21) f32 [, topk (B, n, 16) f32].
     Enqueued on the current torch stream; no host synchronisation."""
     import torch
+    from ._call import hip_call
     if not C.is_cuda or C.dtype != torch.float64:
         raise TypeError("row_features_device expects a CUDA float64 tensor")
     squeeze = C.ndim == 2
@@ -95,11 +95,7 @@ def row_features_device(C, return_topk: bool = True):
     ws_bytes = lib.lapwarm_sweep_workspace_bytes(B, n)
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=C.device)
     pos = _posenc_device(n, C.device)
-    stream = torch.cuda.current_stream(C.device).cuda_stream
-    rc = lib.lapwarm_row_features_batched(C.data_ptr(), B, n, pos.data_ptr(), feat.data_ptr(),
-                                          topk.data_ptr(), ws.data_ptr(), ws_bytes, ct.c_void_p(stream))
-    if _hip.check(rc, "row_features_device") != 0:
-        raise RuntimeError(f"row_features_device failed (code {rc})")
+    hip_call("lapwarm_row_features_batched", "row_features_device", C.device, C, B, n, pos, feat, topk, ws, ws_bytes)
     if squeeze:
         feat, topk = feat[0], topk[0]
     return (feat, topk) if return_topk else feat
@@ -250,6 +246,7 @@ def row_features_ragged(costs, return_topk: bool = True, want_cost32: bool = Fal
 def row_features_packed(pack: RaggedPack, return_topk: bool = True, want_cost32: bool = False):
     """row_features_ragged of a batch that is packed already."""
     import torch
+    from ._call import hip_call
     lib = _hip.require_device()
     dev, B, N = pack.C.device, len(pack.host_sizes), pack.N
     feat = torch.empty((B, N, ROW_FEATURE_DIM), dtype=torch.float32, device=dev)
@@ -259,14 +256,8 @@ def row_features_packed(pack: RaggedPack, return_topk: bool = True, want_cost32:
     ret = torch.empty((B,), dtype=torch.int32, device=dev)
     ws_bytes = lib.lapwarm_ragged_workspace_bytes(B, N)
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = lib.lapwarm_row_features_ragged(
-        pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), pack.ld, B, N, pack.posenc.data_ptr(),
-        pack.pos_off.data_ptr(), feat.data_ptr(), topk.data_ptr() if return_topk else None,
-        cost32.data_ptr() if want_cost32 else None, mask.data_ptr(), ret.data_ptr(), ws.data_ptr(), ws_bytes,
-        ct.c_void_p(stream))
-    if _hip.check(rc, "row_features_ragged") != 0:
-        raise RuntimeError(f"row_features_ragged failed (code {rc})")
+    hip_call("lapwarm_row_features_ragged", "row_features_ragged", dev, pack.C, pack.offsets, pack.sizes, pack.ld, B, N,
+             pack.posenc, pack.pos_off, feat, topk, cost32, mask, ret, ws, ws_bytes)
     return RaggedFeatures(feat, topk, cost32, mask.view(torch.bool), pack.sizes, ret)
 
 
@@ -274,6 +265,7 @@ def min_trick_ragged(pack: RaggedPack, u=None):
     """v (B, N) f64 with v[b][j] = min_{i < n_b} (C_b[i][j] - u[b][i]) and 0 beyond n_b; u (B, N) f64 on the
     device, or None for the plain column minima."""
     import torch
+    from ._call import hip_call
     lib = _hip.require_device()
     B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
     if u is not None and (u.dtype != torch.float64 or tuple(u.shape) != (B, N) or not u.is_contiguous()):
@@ -281,12 +273,8 @@ def min_trick_ragged(pack: RaggedPack, u=None):
     v = torch.empty((B, N), dtype=torch.float64, device=dev)
     ws_bytes = lib.lapwarm_ragged_workspace_bytes(B, N)
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = lib.lapwarm_colmin_ragged(pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), pack.ld, B, N,
-                                   u.data_ptr() if u is not None else None, v.data_ptr(), ws.data_ptr(), ws_bytes,
-                                   ct.c_void_p(stream))
-    if _hip.check(rc, "min_trick_ragged") != 0:
-        raise RuntimeError(f"min_trick_ragged failed (code {rc})")
+    hip_call("lapwarm_colmin_ragged", "min_trick_ragged", dev, pack.C, pack.offsets, pack.sizes, pack.ld, B, N, u, v,
+             ws, ws_bytes)
     return v
 
 
@@ -317,19 +305,16 @@ def row_min_ragged(pack: RaggedPack, v=None):
     """out (B, N) f64 with out[b][i] = min_{j < n_b} (C_b[i][j] - v[b][j]) and 0 beyond n_b; v (B, N) f64 on the
     device, or None for the plain row minima.  One kernel on the current torch stream."""
     import torch
+    from ._call import hip_call
     if not isinstance(pack, RaggedPack):
         raise TypeError(f"Argument 'pack' must be a RaggedPack, not {type(pack).__name__}")
     _check_pack_vector(pack, "v", v, optional=True)
-    lib = _hip.require_device()
+    _hip.require_device()
     B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
     out = torch.empty((B, N), dtype=torch.float64, device=dev)
     ws, ws_bytes = ragged_duals_workspace(pack)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = lib.lapwarm_rowmin_ragged(pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), pack.ld, B, N,
-                                   v.data_ptr() if v is not None else None, out.data_ptr(), None, ws.data_ptr(),
-                                   ws_bytes, ct.c_void_p(stream))
-    if _hip.check(rc, "row_min_ragged") != 0:
-        raise RuntimeError(f"row_min_ragged failed (code {rc})")
+    hip_call("lapwarm_rowmin_ragged", "row_min_ragged", dev, pack.C, pack.offsets, pack.sizes, pack.ld, B, N, v, out,
+             None, ws, ws_bytes)
     return out
 
 
@@ -350,6 +335,7 @@ def min_trick_device(C, u):
     """v[b][j] = min_i (C[b][i][j] - u[b][i]) in fp64 on the device (scripts/gnn_benchmark.py:262).
     C (B,n,n) f64 CUDA, u (B,n) any float dtype CUDA -> v (B,n) f64."""
     import torch
+    from ._call import hip_call
     C = C.contiguous()
     B, n, _ = C.shape
     u64 = u.to(torch.float64).contiguous()
@@ -357,11 +343,7 @@ def min_trick_device(C, u):
     v = torch.empty((B, n), dtype=torch.float64, device=C.device)
     ws_bytes = lib.lapwarm_sweep_workspace_bytes(B, n)
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=C.device)
-    stream = torch.cuda.current_stream(C.device).cuda_stream
-    rc = lib.lapwarm_colmin_batched(C.data_ptr(), B, n, u64.data_ptr(), v.data_ptr(), ws.data_ptr(),
-                                    ws_bytes, ct.c_void_p(stream))
-    if _hip.check(rc, "min_trick_device") != 0:
-        raise RuntimeError(f"min_trick_device failed (code {rc})")
+    hip_call("lapwarm_colmin_batched", "min_trick_device", C.device, C, B, n, u64, v, ws, ws_bytes)
     return v
 
 
@@ -377,6 +359,7 @@ def graph_features_device(C, u=None):
     col (B, n, 14), float32.  Channel 9 of edge is C - u - min_i(C - u) with u, 0 without.  Three kernels on the
     current torch stream; no host synchronisation."""
     import torch
+    from ._call import hip_call
     if not C.is_cuda or C.dtype != torch.float64:
         raise TypeError("graph_features_device expects a CUDA float64 tensor")
     squeeze = C.ndim == 2
@@ -399,12 +382,8 @@ def graph_features_device(C, u=None):
         raise ValueError(f"graph_features_device: batch {B} or n {n} out of range")
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=C.device)
     pos = _posenc_device(n, C.device)
-    stream = torch.cuda.current_stream(C.device).cuda_stream
-    rc = lib.lapwarm_graph_features_batched(C.data_ptr(), B, n, u.data_ptr() if u is not None else None,
-                                            pos.data_ptr(), edge.data_ptr(), row.data_ptr(), col.data_ptr(),
-                                            ws.data_ptr(), ws_bytes, ct.c_void_p(stream))
-    if _hip.check(rc, "graph_features_device") != 0:
-        raise RuntimeError(f"graph_features_device failed (code {rc})")
+    hip_call("lapwarm_graph_features_batched", "graph_features_device", C.device, C, B, n, u, pos, edge, row, col, ws,
+             ws_bytes)
     if squeeze:
         edge, row, col = edge[0], row[0], col[0]
     return edge, row, col

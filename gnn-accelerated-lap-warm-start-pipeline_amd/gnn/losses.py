@@ -24,12 +24,11 @@ matrix); only its row sums are used and the prefix property is not checked.
 """
 from __future__ import annotations
 
-import ctypes as ct
-
 import torch
 from torch.autograd.function import once_differentiable
 
 from lap import _hip
+from ._call import hip_call
 
 __all__ = ["warmstart_loss", "greedy_primal_upper_batch"]
 
@@ -98,12 +97,8 @@ def _forward(cost, u, u_target, sizes):
     ret = torch.empty((B,), dtype=torch.int32, device=dev)
     nbytes = int(lib.lapwarm_train_loss_workspace_bytes(B, n))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = lib.lapwarm_train_loss_forward(cost.data_ptr(), B, n, sizes.data_ptr(), u.data_ptr(), u_target.data_ptr(),
-                                        v_proj.data_ptr(), argmin_row.data_ptr(), assign.data_ptr(),
-                                        terms.data_ptr(), ret.data_ptr(), ws.data_ptr(), nbytes, ct.c_void_p(stream))
-    if _hip.check(rc, "train_loss_forward") != 0:
-        raise RuntimeError(f"lapwarm_train_loss_forward failed (code {rc}): {_hip.last_error()}")
+    hip_call("lapwarm_train_loss_forward", "train_loss_forward", dev, cost, B, n, sizes, u, u_target, v_proj,
+             argmin_row, assign, terms, ret, ws, nbytes)
     return v_proj, argmin_row, assign, terms, ret, ws
 
 
@@ -128,16 +123,12 @@ class _WarmstartLoss(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_loss, *unused):
         u, u_target, sizes, weights, ws = ctx.saved_tensors
-        lib = _hip.require_device()
+        _hip.require_device()
         B, n = u.shape
         w = (weights * grad_loss.to(torch.float32)).contiguous()
         grad_u = torch.empty_like(u)
-        stream = torch.cuda.current_stream(u.device).cuda_stream
-        rc = lib.lapwarm_train_loss_backward(B, n, sizes.data_ptr(), u.data_ptr(), u_target.data_ptr(), w.data_ptr(),
-                                             1.0 / B, grad_u.data_ptr(), ws.data_ptr(), ws.numel(),
-                                             ct.c_void_p(stream))
-        if _hip.check(rc, "train_loss_backward") != 0:
-            raise RuntimeError(f"lapwarm_train_loss_backward failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_train_loss_backward", "train_loss_backward", u.device, B, n, sizes, u, u_target, w, 1.0 / B,
+                 grad_u, ws, ws.numel())
         return grad_u.to(ctx.in_dtype), None, None, None, None
 
 

@@ -19,7 +19,6 @@ the MI355X:
 """
 from __future__ import annotations
 
-import ctypes as ct
 from typing import Optional
 
 import torch
@@ -41,18 +40,16 @@ class _RefineAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, base, u_pre, w1, b1):
         from lap import _hip
+        from ._call import hip_call
         rows, H = base.shape[0], b1.shape[0]
         up = u_pre.detach().to(torch.float32).contiguous().view(rows)
         w1f = w1.detach().to(torch.float32).contiguous().view(-1)
         b1f = b1.detach().to(torch.float32).contiguous()
         agg = torch.empty((rows, H), dtype=torch.float32, device=base.device)
         wsum = torch.empty((rows,), dtype=torch.float32, device=base.device)
-        lib = _hip.require_device()
-        stream = torch.cuda.current_stream(base.device).cuda_stream
-        rc = lib.lapwarm_refine_aggregate_wsum(base.data_ptr(), up.data_ptr(), w1f.data_ptr(), b1f.data_ptr(),
-                                               agg.data_ptr(), wsum.data_ptr(), rows, H, ct.c_void_p(stream))
-        if _hip.check(rc, "refine_aggregate") != 0:
-            raise RuntimeError(f"refine_aggregate failed (code {rc})")
+        _hip.require_device()
+        hip_call("lapwarm_refine_aggregate_wsum", "refine_aggregate", base.device, base, up, w1f, b1f, agg, wsum, rows,
+                 H)
         ctx.save_for_backward(base, up, w1f, b1f)
         ctx.meta = (u_pre.shape, u_pre.dtype, w1.shape, w1.dtype, b1.dtype)
         ctx.set_materialize_grads(False)
@@ -62,6 +59,7 @@ class _RefineAggregate(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_agg, grad_wsum):
         from lap import _hip
+        from ._call import hip_call
         base, up, w1f, b1f = ctx.saved_tensors
         u_shape, u_dtype, w1_shape, w1_dtype, b1_dtype = ctx.meta
         rows, H = base.shape[0], b1f.shape[0]
@@ -76,13 +74,8 @@ class _RefineAggregate(torch.autograd.Function):
         lib = _hip.require_device()
         nbytes = int(lib.lapwarm_refine_backward_workspace_bytes(rows, H))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=base.device)
-        stream = torch.cuda.current_stream(base.device).cuda_stream
-        rc = lib.lapwarm_refine_backward(base.data_ptr(), up.data_ptr(), w1f.data_ptr(), b1f.data_ptr(),
-                                         grad_agg.data_ptr(), None if grad_wsum is None else grad_wsum.data_ptr(),
-                                         grad_u.data_ptr(), grad_w1.data_ptr(), grad_b1.data_ptr(), rows, H,
-                                         ws.data_ptr(), nbytes, ct.c_void_p(stream))
-        if _hip.check(rc, "refine_backward") != 0:
-            raise RuntimeError(f"lapwarm_refine_backward failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_refine_backward", "refine_backward", base.device, base, up, w1f, b1f, grad_agg, grad_wsum,
+                 grad_u, grad_w1, grad_b1, rows, H, ws, nbytes)
         return (None, grad_u.view(u_shape).to(u_dtype), grad_w1.view(w1_shape).to(w1_dtype), grad_b1.to(b1_dtype))
 
 

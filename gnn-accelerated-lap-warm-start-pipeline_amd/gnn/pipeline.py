@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from lap import _hip
+from ._call import hip_call
 from .dual_gnn import DualGNN
 from .features import (ROW_FEATURE_DIM, RaggedPack, _check_pack_vector, graph_features_device, min_trick_device,
                        min_trick_ragged, ragged_pack, row_features_device, row_features_packed, row_min_ragged)
@@ -251,6 +252,16 @@ def sparse_pack(problems, device="cuda:0") -> SparsePack:
                       host_sizes, host_nnz)
 
 
+def _solve_outputs(B, width, index_dtype, device, want_stats, ragged=False):
+    """What a solve writes: x, y (B, width) of `index_dtype`, ret (B,) int32 and stats (B, 32) int64 or None.
+    The stats of a uniform batch start at zero; the first kernel of a ragged call initialises its own."""
+    x = torch.empty((B, width), dtype=index_dtype, device=device)
+    y = torch.empty((B, width), dtype=index_dtype, device=device)
+    ret = torch.empty((B,), dtype=torch.int32, device=device)
+    stats = (torch.empty if ragged else torch.zeros)((B, 32), dtype=torch.int64, device=device) if want_stats else None
+    return x, y, ret, stats
+
+
 class WarmStartPipeline:
     """Batched, device-resident warm-start solve."""
 
@@ -301,35 +312,20 @@ class WarmStartPipeline:
         B, n, _ = C.shape
         u = u.to(torch.float64).contiguous()
         v = v.to(torch.float64).contiguous()
-        x = torch.empty((B, n), dtype=torch.int64, device=C.device)
-        y = torch.empty((B, n), dtype=torch.int64, device=C.device)
-        ret = torch.empty((B,), dtype=torch.int32, device=C.device)
-        stats = torch.zeros((B, 32), dtype=torch.int64, device=C.device) if want_stats else None
+        x, y, ret, stats = _solve_outputs(B, n, torch.int64, C.device, want_stats)
         ws, nbytes = self._workspace(B, n)
-        stream = torch.cuda.current_stream(C.device).cuda_stream
-        rc = self.lib.lapwarm_seeded_batched(
-            C.data_ptr(), B, n, u.data_ptr(), v.data_ptr(), float(eps), x.data_ptr(), y.data_ptr(),
-            ret.data_ptr(), stats.data_ptr() if want_stats else None, ws.data_ptr(), nbytes,
-            self.threads_hint, ct.c_void_p(stream))
-        if _hip.check(rc, "seeded_batch") != 0:
-            raise RuntimeError(f"lapwarm_seeded_batched failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_seeded_batched", "seeded_batch", C.device, C, B, n, u, v, float(eps), x, y, ret, stats, ws,
+                 nbytes, self.threads_hint)
         return x, y, ret, stats
 
     def lapjv_batch(self, C: torch.Tensor, want_stats: bool = True):
         """Batched cold lapjv: x, y (B,n) int32, ret (B,), stats."""
         C = C.contiguous()
         B, n, _ = C.shape
-        x = torch.empty((B, n), dtype=torch.int32, device=C.device)
-        y = torch.empty((B, n), dtype=torch.int32, device=C.device)
-        ret = torch.empty((B,), dtype=torch.int32, device=C.device)
-        stats = torch.zeros((B, 32), dtype=torch.int64, device=C.device) if want_stats else None
+        x, y, ret, stats = _solve_outputs(B, n, torch.int32, C.device, want_stats)
         ws, nbytes = self._workspace(B, n, cold=True)
-        stream = torch.cuda.current_stream(C.device).cuda_stream
-        rc = self.lib.lapwarm_lapjv_batched(C.data_ptr(), B, n, x.data_ptr(), y.data_ptr(), ret.data_ptr(),
-                                            stats.data_ptr() if want_stats else None, ws.data_ptr(), nbytes,
-                                            self.threads_hint, ct.c_void_p(stream))
-        if _hip.check(rc, "lapjv_batch") != 0:
-            raise RuntimeError(f"lapwarm_lapjv_batched failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_lapjv_batched", "lapjv_batch", C.device, C, B, n, x, y, ret, stats, ws, nbytes,
+                 self.threads_hint)
         return x, y, ret, stats
 
     def lapjv_extended_batch(self, C: torch.Tensor, extend_cost: bool = True, cost_limit: float = float("inf"),
@@ -347,8 +343,7 @@ class WarmStartPipeline:
         extend_cost, cost_limit = int(bool(extend_cost)), float(cost_limit)
         n = self.lib.lapwarm_lapjv_extended_n(n_rows, n_cols, extend_cost, cost_limit)
         if n == -4:
-            raise ValueError("Square cost array expected. If cost is intentionally "
-                             "non-square, pass extend_cost=True.")
+            raise ValueError(NONSQUARE)
         if n == -2 or B < 1:
             raise ValueError("lapjv_extended_batch: empty batch or empty cost matrices")
         _hip.check(n, "lapjv_extended_batch")
@@ -361,13 +356,8 @@ class WarmStartPipeline:
         ws, nbytes = self._cached_workspace(
             ("extended", B, n_rows, n_cols, extend_cost, cost_limit < float("inf")),
             lambda: self.lib.lapwarm_lapjv_extended_workspace_bytes(B, n_rows, n_cols, extend_cost, cost_limit))
-        stream = torch.cuda.current_stream(C.device).cuda_stream
-        rc = self.lib.lapwarm_lapjv_extended_batched(
-            C.data_ptr(), B, n_rows, n_cols, extend_cost, cost_limit, x.data_ptr(), y.data_ptr(), opt.data_ptr(),
-            matched.data_ptr(), ret.data_ptr(), stats.data_ptr() if want_stats else None, ws.data_ptr(), nbytes,
-            self.threads_hint, ct.c_void_p(stream))
-        if _hip.check(rc, "lapjv_extended_batch") != 0:
-            raise RuntimeError(f"lapwarm_lapjv_extended_batched failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_lapjv_extended_batched", "lapjv_extended_batch", C.device, C, B, n_rows, n_cols, extend_cost,
+                 cost_limit, x, y, opt, matched, ret, stats, ws, nbytes, self.threads_hint)
         return {"x": x, "y": y, "opt": opt, "matched": matched, "ret": ret, "stats": stats}
 
     def lapjv_ragged_eligible(self, n: int) -> bool:
@@ -388,20 +378,12 @@ class WarmStartPipeline:
         if not isinstance(pack, RaggedPack):
             raise TypeError(f"Argument 'pack' must be a RaggedPack, not {type(pack).__name__}")
         B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
-        x = torch.empty((B, N), dtype=torch.int64, device=dev)
-        y = torch.empty((B, N), dtype=torch.int64, device=dev)
-        ret = torch.empty((B,), dtype=torch.int32, device=dev)
-        stats = torch.empty((B, 32), dtype=torch.int64, device=dev) if want_stats else None
+        x, y, ret, stats = _solve_outputs(B, N, torch.int64, dev, want_stats, ragged=True)
         ws, nbytes = self._cached_workspace(("lapjv_ragged", B, N),
                                             lambda: self.lib.lapwarm_lapjv_ragged_workspace_bytes(B, N))
         host_sizes = (ct.c_int * B)(*pack.host_sizes)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lapwarm_lapjv_ragged(
-            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), host_sizes, pack.ld, B, N,
-            x.data_ptr(), y.data_ptr(), ret.data_ptr(), stats.data_ptr() if want_stats else None, ws.data_ptr(),
-            nbytes, ct.c_void_p(stream))
-        if _hip.check(rc, "lapjv_ragged") != 0:
-            raise RuntimeError(f"lapwarm_lapjv_ragged failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_lapjv_ragged", "lapjv_ragged", dev, pack.C, pack.offsets, pack.sizes, host_sizes, pack.ld, B,
+                 N, x, y, ret, stats, ws, nbytes)
         return x, y, ret, stats
 
     def lapjv_extended_ragged(self, pack: ExtendedPack, extend_cost: bool = True, want_stats: bool = True) -> dict:
@@ -434,14 +416,9 @@ class WarmStartPipeline:
         # (one block per power of two of the size: the shapes of a tracker change with every call)
         bucket = max(1 << 16, 1 << (nbytes - 1).bit_length())
         ws, cap = self._cached_workspace(("extended_ragged", bucket), lambda: bucket)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lapwarm_lapjv_extended_ragged(
-            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.rows.data_ptr(), pack.cols.data_ptr(),
-            pack.limits.data_ptr(), rows, cols, limits, pack.ld, extend_cost, B, R, Q, x.data_ptr(), y.data_ptr(),
-            opt.data_ptr(), matched.data_ptr(), ret.data_ptr(), stats.data_ptr() if want_stats else None,
-            ws.data_ptr(), cap, ct.c_void_p(stream))
-        if _hip.check(rc, "lapjv_extended_ragged") != 0:
-            raise RuntimeError(f"lapwarm_lapjv_extended_ragged failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_lapjv_extended_ragged", "lapjv_extended_ragged", dev, pack.C, pack.offsets, pack.rows,
+                 pack.cols, pack.limits, rows, cols, limits, pack.ld, extend_cost, B, R, Q, x, y, opt, matched, ret,
+                 stats, ws, cap)
         return {"x": x, "y": y, "opt": opt, "matched": matched, "ret": ret, "stats": stats}
 
     def lapmod_ragged(self, pack: SparsePack, fp_version: int = 3, want_stats: bool = True) -> dict:
@@ -459,21 +436,12 @@ class WarmStartPipeline:
         nbytes = int(self.lib.lapwarm_lapmod_workspace_bytes(host_sizes, host_nnz, B))
         if nbytes == 0:
             raise ValueError("lapmod_ragged: a batch of 1..65535 instances with 1 <= n <= 65535 expected")
-        x = torch.empty((B, N), dtype=torch.int32, device=dev)
-        y = torch.empty((B, N), dtype=torch.int32, device=dev)
+        x, y, ret, stats = _solve_outputs(B, N, torch.int32, dev, want_stats, ragged=True)
         v = torch.empty((B, N), dtype=torch.float64, device=dev)
-        ret = torch.empty((B,), dtype=torch.int32, device=dev)
-        stats = torch.empty((B, 32), dtype=torch.int64, device=dev) if want_stats else None
         bucket = max(1 << 16, 1 << (nbytes - 1).bit_length())
         ws, cap = self._cached_workspace(("lapmod_ragged", bucket), lambda: bucket)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lapwarm_lapmod_ragged(
-            pack.cc.data_ptr(), pack.kk.data_ptr(), pack.ii.data_ptr(), pack.nnz_offsets.data_ptr(),
-            pack.row_offsets.data_ptr(), pack.sizes.data_ptr(), host_sizes, B, N, int(fp_version), x.data_ptr(),
-            y.data_ptr(), v.data_ptr(), ret.data_ptr(), stats.data_ptr() if want_stats else None, ws.data_ptr(), cap,
-            ct.c_void_p(stream))
-        if _hip.check(rc, "lapmod_ragged") != 0:
-            raise RuntimeError(f"lapwarm_lapmod_ragged failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_lapmod_ragged", "lapmod_ragged", dev, pack.cc, pack.kk, pack.ii, pack.nnz_offsets,
+                 pack.row_offsets, pack.sizes, host_sizes, B, N, int(fp_version), x, y, v, ret, stats, ws, cap)
         return {"x": x, "y": y, "v": v, "ret": ret, "stats": stats}
 
     def _extended_many_parts(self, costs, extend_cost=True, cost_limit=float("inf"), want_stats=True):
@@ -545,12 +513,8 @@ class WarmStartPipeline:
         v = torch.empty((B, n), dtype=torch.float64, device=C.device)
         ret = torch.empty((B,), dtype=torch.int32, device=C.device)
         ws, nbytes = self._workspace(B, n, cold=True)
-        stream = torch.cuda.current_stream(C.device).cuda_stream
-        rc = self.lib.lapwarm_lapjv_duals_batched(C.data_ptr(), B, n, x.data_ptr(), y.data_ptr(), u.data_ptr(),
-                                                  v.data_ptr(), ret.data_ptr(), None, ws.data_ptr(), nbytes,
-                                                  self.threads_hint, ct.c_void_p(stream))
-        if _hip.check(rc, "optimal_duals_batch") != 0:
-            raise RuntimeError(f"lapwarm_lapjv_duals_batched failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_lapjv_duals_batched", "optimal_duals_batch", C.device, C, B, n, x, y, u, v, ret, None, ws,
+                 nbytes, self.threads_hint)
         return x, u, v, ret
 
     def oracle_duals_batch(self, C: torch.Tensor, x: Optional[torch.Tensor] = None):
@@ -571,12 +535,8 @@ class WarmStartPipeline:
         sweeps = torch.empty((B, 4), dtype=torch.int32, device=C.device)
         nbytes = int(self.lib.lapwarm_oracle_duals_workspace_bytes(B, n))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=C.device)
-        stream = torch.cuda.current_stream(C.device).cuda_stream
-        rc = self.lib.lapwarm_oracle_duals_batched(C.data_ptr(), B, n, rows.data_ptr(), x.data_ptr(), u.data_ptr(),
-                                                   v.data_ptr(), ret.data_ptr(), sweeps.data_ptr(), ws.data_ptr(),
-                                                   nbytes, ct.c_void_p(stream))
-        if _hip.check(rc, "oracle_duals_batch") != 0:
-            raise RuntimeError(f"lapwarm_oracle_duals_batched failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_oracle_duals_batched", "oracle_duals_batch", C.device, C, B, n, rows, x, u, v, ret, sweeps,
+                 ws, nbytes)
         return x, u, v, ret, sweeps
 
     def oracle_duals_ragged(self, pack: RaggedPack, x: torch.Tensor):
@@ -606,13 +566,8 @@ class WarmStartPipeline:
         ws, nbytes = self._cached_workspace(("oracle_ragged", B, N),
                                             lambda: self.lib.lapwarm_oracle_duals_ragged_workspace_bytes(B, N))
         host_sizes = (ct.c_int * B)(*pack.host_sizes)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lapwarm_oracle_duals_ragged(
-            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), host_sizes, pack.ld, B, N,
-            rows.data_ptr(), cols.data_ptr(), u.data_ptr(), v.data_ptr(), ret.data_ptr(), sweeps.data_ptr(),
-            ws.data_ptr(), nbytes, ct.c_void_p(stream))
-        if _hip.check(rc, "oracle_duals_ragged") != 0:
-            raise RuntimeError(f"lapwarm_oracle_duals_ragged failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_oracle_duals_ragged", "oracle_duals_ragged", dev, pack.C, pack.offsets, pack.sizes,
+                 host_sizes, pack.ld, B, N, rows, cols, u, v, ret, sweeps, ws, nbytes)
         return u, v, ret, sweeps
 
     def _matching_packed(self, pack, r=None):
@@ -721,13 +676,8 @@ class WarmStartPipeline:
         rounds = torch.empty((B,), dtype=torch.int32, device=dev)
         ret = torch.empty((B,), dtype=torch.int32, device=dev)
         ws, nbytes = self._duals_workspace(B, N)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lapwarm_project_feasible_ragged(
-            pack.C.data_ptr(), pack.offsets.data_ptr(), sizes.data_ptr(), pack.ld, B, N, u.data_ptr(), v.data_ptr(),
-            int(max_rounds), float(tol), gmin.data_ptr(), rounds.data_ptr(), ret.data_ptr(), ws.data_ptr(), nbytes,
-            ct.c_void_p(stream))
-        if _hip.check(rc, "project_feasible_ragged") != 0:
-            raise RuntimeError(f"lapwarm_project_feasible_ragged failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_project_feasible_ragged", "project_feasible_ragged", dev, pack.C, pack.offsets, sizes,
+                 pack.ld, B, N, u, v, int(max_rounds), float(tol), gmin, rounds, ret, ws, nbytes)
         return u, v, gmin, rounds, ret
 
     def project_feasible_ragged(self, pack: RaggedPack, u: torch.Tensor, v: torch.Tensor, max_rounds: int = 50,
@@ -756,13 +706,8 @@ class WarmStartPipeline:
         gmin = torch.empty((B,), dtype=torch.float64, device=dev)
         ret = torch.empty((B,), dtype=torch.int32, device=dev)
         ws, nbytes = self._duals_workspace(B, N)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lapwarm_reduce_costs_ragged(
-            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), pack.ld, B, N, u.data_ptr(),
-            v.data_ptr(), int(bool(shift_nonneg)), out.data_ptr() if want_matrix else None, gmin.data_ptr(),
-            ret.data_ptr(), ws.data_ptr(), nbytes, ct.c_void_p(stream))
-        if _hip.check(rc, "reduce_costs_ragged") != 0:
-            raise RuntimeError(f"lapwarm_reduce_costs_ragged failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_reduce_costs_ragged", "reduce_costs_ragged", dev, pack.C, pack.offsets, pack.sizes, pack.ld,
+                 B, N, u, v, int(bool(shift_nonneg)), out, gmin, ret, ws, nbytes)
         return out, gmin, ret
 
     def dual_feasible_ragged(self, pack: RaggedPack, u: torch.Tensor, v: torch.Tensor, tol: float = 1e-8):
@@ -855,20 +800,12 @@ class WarmStartPipeline:
         for name, t in (("u", u), ("v", v)):
             if t.dtype != torch.float64 or tuple(t.shape) != (B, N) or not t.is_contiguous() or t.device != dev:
                 raise ValueError(f"{name} must be a contiguous float64 ({B}, {N}) tensor on {dev}")
-        x = torch.empty((B, N), dtype=torch.int64, device=dev)
-        y = torch.empty((B, N), dtype=torch.int64, device=dev)
-        ret = torch.empty((B,), dtype=torch.int32, device=dev)
-        stats = torch.empty((B, 32), dtype=torch.int64, device=dev) if want_stats else None
+        x, y, ret, stats = _solve_outputs(B, N, torch.int64, dev, want_stats, ragged=True)
         ws, nbytes = self._cached_workspace(("seeded_ragged", B, N),
                                             lambda: self.lib.lapwarm_seeded_ragged_workspace_bytes(B, N))
         host_sizes = (ct.c_int * B)(*pack.host_sizes)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lapwarm_seeded_ragged(
-            pack.C.data_ptr(), pack.offsets.data_ptr(), pack.sizes.data_ptr(), host_sizes, pack.ld, B, N,
-            u.data_ptr(), v.data_ptr(), float(eps), x.data_ptr(), y.data_ptr(), ret.data_ptr(),
-            stats.data_ptr() if want_stats else None, ws.data_ptr(), nbytes, ct.c_void_p(stream))
-        if _hip.check(rc, "seeded_ragged") != 0:
-            raise RuntimeError(f"lapwarm_seeded_ragged failed (code {rc}): {_hip.last_error()}")
+        hip_call("lapwarm_seeded_ragged", "seeded_ragged", dev, pack.C, pack.offsets, pack.sizes, host_sizes, pack.ld,
+                 B, N, u, v, float(eps), x, y, ret, stats, ws, nbytes)
         return x, y, ret, stats
 
     def ragged_solve_eligible(self, n: int) -> bool:

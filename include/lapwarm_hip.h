@@ -525,6 +525,9 @@ int lapwarm_solver_uses_helpers(int n);
 int lapwarm_coop_members(int n);
 
 /* Misc */
+/* The text of the calling thread's last failure that has one: every -1 of an entry point that takes a workspace
+ * ("workspace too small: <given> < <needed>", bytes), every -6 and every code <= -1000 (the HIP call and its
+ * error string).  Argument codes (-2, -4, -5) leave it as it was. */
 const char *lapwarm_last_error(void);
 int lapwarm_device_count(void);
 const char *lapwarm_build_info(void);

@@ -1,0 +1,230 @@
+"""The host-side contract of the C ABI (include/lapwarm_hip.h), recorded through ctypes without a GPU: what every
+lapwarm_*_workspace_bytes entry returns over a grid that straddles the branches of the layouts, and the return
+codes of calls that an entry point rejects before its first HIP call (argument checks, their order, the workspace
+check).  The command line prints the record of the environment it runs in as JSON; tests/golden/abi_contract.json
+holds "sizes" and "codes" of what it printed for the library of commit 8a46a51, before the ABI's repeated steps
+were gathered into helpers.  "short_text" (the error text after each too-small workspace) is asserted, not
+recorded: that commit left it unset at ten entry points."""
+import ctypes as ct
+import itertools
+import json
+import sys
+from pathlib import Path
+
+PKG = Path(__file__).resolve().parents[1] / "gnn-accelerated-lap-warm-start-pipeline_amd"
+
+GRID_N = (1, 31, 32, 33, 511, 512, 1024, 3631, 3635, 4428, 8192, 16384)
+GRID_BATCH = (1, 2, 129, 65535)
+OUT_N, OUT_BATCH = (0, 16385), (0, 65536)  # out of range: 0 bytes
+TWO_INT_SIZES = ("seeded", "lapjv", "sweep", "ragged", "seeded_ragged", "lapjv_ragged", "ragged_duals", "oracle_duals",
+                 "oracle_duals_ragged", "train_loss", "graph_features")
+INF = float("inf")
+P = 0x10000  # a pointer that is not null and never followed: every recorded call returns before the device sees it
+B, N = 2, 33  # the shape of the calls below
+
+
+def ints(*values):
+    return (ct.c_int * len(values))(*values)
+
+
+def sizes(lib):
+    out = {}
+    points = list(itertools.product(GRID_BATCH + OUT_BATCH, GRID_N + OUT_N))
+    for name in TWO_INT_SIZES:
+        f = getattr(lib, f"lapwarm_{name}_workspace_bytes")
+        out[name] = [f(b, n) for b, n in points]
+    out["refine_backward"] = [lib.lapwarm_refine_backward_workspace_bytes(r, h)
+                              for r, h in itertools.product((0, 1, 33, 1024), (0, 1, 64, 128))]
+    out["dual_gnn"] = [lib.lapwarm_dual_gnn_workspace_bytes(b, n, h)
+                       for b, n, h in itertools.product((0, 1, 2, 32768), (0, 1, 33, 512, 16385), (0, 1, 8, 9))]
+    out["lapjv_extended"] = [lib.lapwarm_lapjv_extended_workspace_bytes(b, r, c, e, t)
+                             for b, (r, c), e, t in itertools.product((0, 1, 2, 65535, 65536), ((3, 3), (3, 5), (5, 3)),
+                                                                      (0, 1), (INF, 10.0))]
+    lds = lib.lapwarm_lapmod_lds_max_n()
+    out["lapmod"] = [lib.lapwarm_lapmod_workspace_bytes(ints(*s), (ct.c_longlong * len(s))(*[n for n in s]), len(s))
+                     for s in ((1,), (3, 5, 4), (2, lds, lds + 1))]
+    out["lapjv_extended_ragged"] = [
+        lib.lapwarm_lapjv_extended_ragged_workspace_bytes(ints(*r), ints(*c), (ct.c_double * len(t))(*t), e, len(r))
+        for (r, c, t), e in itertools.product((((3,), (3,), (INF,)), ((3, 5, 4), (5, 3, 4), (INF, 10.0, INF)),
+                                               ((2, 512), (2, 512), (1.0, INF))), (0, 1))]
+    return out
+
+
+def _uniform(lib, symbol, query, args, ws_at, limits_batch=False, smaller=None):
+    """The cases of a uniform entry whose arguments start (C, batch, n) or (batch, n): `args(batch, n, ws, bytes)`."""
+    f = getattr(lib, symbol)
+    need = getattr(lib, f"lapwarm_{smaller or query}_workspace_bytes")(B, N) if query else 0
+    cases = {"n=0": f(*args(B, 0, P, need)), "batch=0": f(*args(0, N, P, need)),
+             "n=16385": f(*args(B, 16385, P, need))}
+    if limits_batch:
+        cases["batch=65536"] = f(*args(65536, N, P, need))
+        cases["batch=65536,n=16385"] = f(*args(65536, 16385, P, need))
+    if query:
+        cases["n=16385,ws=0"] = f(*args(B, 16385, P, 0))
+        cases["ws short"] = ws_at(lambda: f(*args(B, N, P, need - 1)))
+    return cases
+
+
+def codes(lib):
+    """symbol -> {case: return code}; `short` collects the error text after every too-small workspace."""
+    short = {}
+    one = ints(N, N)
+
+    def poison():  # leaves another text in the error buffer: the seeded solve of a size outside its class
+        rc = lib.lapwarm_seeded_ragged(P, P, P, ints(1024), 0, 1, 1024, P, P, 0.0, P, P, P, P, P, 1 << 40, None)
+        assert rc == -6, rc
+
+    def ws_at(symbol):
+        def run(call):
+            poison()
+            rc = call()
+            short[symbol] = lib.lapwarm_last_error().decode()
+            return rc
+        return run
+
+    out = {}
+    uniform = {  # symbol: (size query, arguments, batch limited, the query whose size the short workspace is short of)
+        "lapwarm_seeded_batched": ("seeded", lambda b, n, w, s: (P, b, n, P, P, 1e-12, P, P, P, P, w, s, 0, None)),
+        "lapwarm_lapjv_batched": ("lapjv", lambda b, n, w, s: (P, b, n, P, P, P, P, w, s, 0, None), False, "seeded"),
+        "lapwarm_lapjv_duals_batched": ("lapjv", lambda b, n, w, s: (P, b, n, P, P, P, P, P, P, w, s, 0, None), False,
+                                        "seeded"),
+        "lapwarm_colmin_batched": ("sweep", lambda b, n, w, s: (P, b, n, P, P, w, s, None)),
+        "lapwarm_rowmin_batched": (None, lambda b, n, w, s: (P, b, n, P, P, None)),
+        "lapwarm_row_features_batched": ("sweep", lambda b, n, w, s: (P, b, n, P, P, P, w, s, None)),
+        "lapwarm_project_round_batched": ("sweep", lambda b, n, w, s: (P, b, n, P, P, P, w, s, None)),
+        "lapwarm_reduce_costs_batched": ("sweep", lambda b, n, w, s: (P, b, n, P, P, 1, P, P, w, s, None)),
+        "lapwarm_oracle_duals_batched": ("oracle_duals", lambda b, n, w, s: (P, b, n, P, P, P, P, P, P, w, s, None)),
+        "lapwarm_train_loss_forward": ("train_loss", lambda b, n, w, s: (P, b, n, P, P, P, P, P, P, P, P, w, s, None),
+                                       True),
+        "lapwarm_train_loss_backward": ("train_loss", lambda b, n, w, s: (b, n, P, P, P, P, 1.0, P, w, s, None), True),
+    }
+    for symbol, (query, args, *rest) in uniform.items():
+        out[symbol] = _uniform(lib, symbol, query, args, ws_at(symbol), *rest)
+
+    f = lib.lapwarm_graph_features_batched
+    need = lib.lapwarm_graph_features_workspace_bytes(B, N)
+    g = lambda b=B, n=N, C=P, ws=P, s=need: f(C, b, n, None, P, P, P, P, ws, s, None)  # noqa: E731
+    out["lapwarm_graph_features_batched"] = {
+        "n=0": g(n=0), "batch=0": g(b=0), "batch=32768": g(b=32768), "n=4097": g(n=4097), "null C": g(C=None),
+        "null ws": g(ws=None), "n=4097,null C": g(n=4097, C=None), "null C,ws short": g(C=None, s=need - 1),
+        "ws short": ws_at("lapwarm_graph_features_batched")(lambda: g(s=need - 1))}
+    f = lib.lapwarm_dual_edge_scores
+    g = lambda b=B, n=N, h=4, e=P: f(e, P, P, P, P, P, P, b, n, h, None)  # noqa: E731
+    out["lapwarm_dual_edge_scores"] = {"n=0": g(n=0), "batch=0": g(b=0), "batch=32768": g(b=32768), "heads=9": g(h=9),
+                                       "n=16385": g(n=16385), "null": g(e=None), "n=16385,null": g(n=16385, e=None)}
+    f = lib.lapwarm_dual_attention
+    g = lambda b=B, n=N, h=4, s=P: f(s, P, P, P, P, P, None, P, P, P, P, b, n, h, 16, None)  # noqa: E731
+    out["lapwarm_dual_attention"] = {"n=0": g(n=0), "batch=0": g(b=0), "heads=65536": g(h=65536), "n=16385": g(n=16385),
+                                     "null": g(s=None), "n=16385,null": g(n=16385, s=None)}
+    f = lib.lapwarm_refine_backward
+    need = lib.lapwarm_refine_backward_workspace_bytes(N, 64)
+    g = lambda r=N, h=64, t=P, s=need: f(t, P, P, P, P, None, P, P, P, r, h, P, s, None)  # noqa: E731
+    out["lapwarm_refine_backward"] = {"rows=-1": g(r=-1), "rows=0": g(r=0), "H=0": g(h=0), "null": g(t=None),
+                                      "ws short": g(s=need - 1)}
+    out["lapwarm_refine_aggregate_wsum"] = {"rows=0": lib.lapwarm_refine_aggregate_wsum(P, P, P, P, P, P, 0, 64, None),
+                                            "H=0": lib.lapwarm_refine_aggregate_wsum(P, P, P, P, P, P, N, 0, None)}
+
+    f = lib.lapwarm_lapjv_extended_batched
+    for key, (r, c, e, t) in {"3x5": (3, 5, 1, INF), "5x3 limit": (5, 3, 1, 10.0), "3x3": (3, 3, 0, INF)}.items():
+        need = lib.lapwarm_lapjv_extended_workspace_bytes(B, r, c, e, t)
+        g = lambda b=B, r=r, c=c, e=e, t=t, ws=P, s=need: f(P, b, r, c, e, t, P, P, P, P, P, P, ws, s, 0, None)  # noqa: E731
+        out[f"lapwarm_lapjv_extended_batched {key}"] = {
+            "rows=0": g(r=0), "batch=0": g(b=0), "batch=65536": g(b=65536), "not square": g(r=3, c=5, e=0),
+            "n=16385": g(r=16385, c=16385), "rows+cols=16385": g(r=8192, c=8193, t=10.0),
+            "n=16385,batch=0": g(r=16385, c=16385, b=0), "not square,batch=0": g(r=3, c=5, e=0, b=0),
+            "n=16385,ws=0": g(r=16385, c=16385, s=0), "ws misaligned": g(ws=P + 8), "ws misaligned,short": g(ws=P + 8, s=0),
+            "ws short": ws_at(f"lapwarm_lapjv_extended_batched {key}")(lambda: g(s=need - 1))}
+
+    # ---- ragged entries: (C, offsets, sizes[, host_sizes], ld, batch, N, ...)
+    def ragged(symbol, query, tail, host=False, nulls=(), out_of_class=None):
+        f = getattr(lib, symbol)
+        need = getattr(lib, f"lapwarm_{query}_workspace_bytes")(B, N)
+
+        def g(b=B, n=N, C=P, ld=0, hs=one, ws=P, s=need, null=None):
+            t = list(tail(ws, s))
+            if null is not None:
+                t[null] = None
+            head = (C, P, P, hs, ld, b, n) if host else (C, P, P, ld, b, n)
+            return f(*head, *t)
+        cases = {"N=0": g(n=0), "batch=0": g(b=0), "batch=65536": g(b=65536), "N=16385": g(n=16385), "ld=-1": g(ld=-1),
+                 "null C": g(C=None), "N=16385,ld=-1": g(n=16385, ld=-1), "N=16385,null C": g(n=16385, C=None),
+                 "N=16385,ws=0": g(n=16385, s=0), "null C,ws short": g(C=None, s=need - 1),
+                 "ws short": ws_at(symbol)(lambda: g(s=need - 1))}
+        for k in nulls:
+            cases[f"null tail {k}"] = g(null=k)
+            cases[f"null tail {k},ws short"] = g(null=k, s=need - 1)
+        if host:
+            cases["null host sizes"] = g(hs=None)
+        if out_of_class is not None:
+            cases["host size 0"] = g(hs=ints(N, 0))
+            cases["host size above N"] = g(hs=ints(N, N + 1))
+            cases["host size above ld"] = g(hs=ints(N, N), ld=N - 1)
+            cases["out of class"] = g(n=out_of_class, hs=ints(N, out_of_class))
+            cases["out of class,ws=0"] = g(n=out_of_class, hs=ints(N, out_of_class), s=0)
+            cases["host size 0,out of class"] = g(n=out_of_class, hs=ints(0, out_of_class))
+        return cases
+
+    out["lapwarm_colmin_ragged"] = ragged("lapwarm_colmin_ragged", "ragged", lambda w, s: (P, P, w, s, None), nulls=(1, 2))
+    out["lapwarm_row_features_ragged"] = ragged("lapwarm_row_features_ragged", "ragged",
+                                                lambda w, s: (P, P, P, P, P, P, P, w, s, None), nulls=(0, 1, 2, 6, 7))
+    out["lapwarm_seeded_ragged"] = ragged("lapwarm_seeded_ragged", "seeded_ragged",
+                                          lambda w, s: (P, P, 1e-12, P, P, P, P, w, s, None), host=True,
+                                          nulls=(0, 1, 3, 4, 5, 7), out_of_class=1024)
+    out["lapwarm_lapjv_ragged"] = ragged("lapwarm_lapjv_ragged", "lapjv_ragged", lambda w, s: (P, P, P, P, w, s, None),
+                                         host=True, nulls=(0, 1, 2, 4), out_of_class=512)
+    out["lapwarm_rowmin_ragged"] = ragged("lapwarm_rowmin_ragged", "ragged_duals",
+                                          lambda w, s: (P, P, P, w, s, None), nulls=(1, 3))
+    out["lapwarm_project_feasible_ragged"] = ragged("lapwarm_project_feasible_ragged", "ragged_duals",
+                                                    lambda w, s: (P, P, 50, 1e-12, P, P, P, w, s, None),
+                                                    nulls=(0, 1, 4, 5, 6, 7))
+    out["lapwarm_reduce_costs_ragged"] = ragged("lapwarm_reduce_costs_ragged", "ragged_duals",
+                                                lambda w, s: (P, P, 1, P, P, P, w, s, None), nulls=(0, 1, 4, 6))
+    out["lapwarm_oracle_duals_ragged"] = ragged("lapwarm_oracle_duals_ragged", "oracle_duals_ragged",
+                                                lambda w, s: (P, P, P, P, P, P, w, s, None), host=True,
+                                                nulls=(0, 1, 2, 3, 4, 6))
+
+    f = lib.lapwarm_lapjv_extended_ragged
+    rows, cols, lims = (3, 5, 4), (5, 3, 4), (INF, 10.0, INF)
+
+    def ext(r=rows, c=cols, t=lims, e=1, b=3, ld=0, R=5, Q=5, C=P, ws=P, s=None, hr=True):
+        hr_, hc_, ht_ = ints(*r), ints(*c), (ct.c_double * len(t))(*t)
+        if s is None:
+            s = lib.lapwarm_lapjv_extended_ragged_workspace_bytes(hr_, hc_, ht_, e, len(r))
+        return f(C, P, P, P, P, hr_ if hr else None, hc_, ht_, ld, e, b, R, Q, P, P, P, P, P, P, ws, s, None)
+    need = lib.lapwarm_lapjv_extended_ragged_workspace_bytes(ints(*rows), ints(*cols), (ct.c_double * 3)(*lims), 1, 3)
+    out["lapwarm_lapjv_extended_ragged"] = {
+        "batch=0": ext(b=0), "batch=65536": ext(b=65536), "null host rows": ext(hr=False), "rows=0": ext(r=(3, 0, 4)),
+        "not square": ext(e=0), "n=16385": ext(r=(3, 16385, 4), c=(5, 16385, 4), R=16385, Q=16385),
+        "ld=-1": ext(ld=-1), "R small": ext(R=4), "Q small": ext(Q=4), "cols above ld": ext(ld=4), "null C": ext(C=None),
+        "null ws": ext(ws=None), "ws misaligned": ext(ws=P + 8), "not square,null C": ext(e=0, C=None),
+        "null C,ws short": ext(C=None, s=need - 1), "ws misaligned,short": ext(ws=P + 8, s=need - 1),
+        "out of class": ext(r=(3, 512), c=(3, 512), t=(INF, INF), b=2, R=512, Q=512),
+        "out of class,ws=0": ext(r=(3, 512), c=(3, 512), t=(INF, INF), b=2, R=512, Q=512, s=0),
+        "ws short": ws_at("lapwarm_lapjv_extended_ragged")(lambda: ext(s=need - 1))}
+
+    f = lib.lapwarm_lapmod_ragged
+    lds = lib.lapwarm_lapmod_lds_max_n()
+    hs = (3, lds + 1)
+    need = lib.lapwarm_lapmod_workspace_bytes(ints(*hs), None, 2)
+
+    def mod(h=hs, b=2, n=lds + 1, fp=3, cc=P, ws=P, s=need, host=True):
+        return f(cc, P, P, P, P, P, ints(*h) if host else None, b, n, fp, P, P, P, P, P, ws, s, None)
+    out["lapwarm_lapmod_ragged"] = {
+        "N=0": mod(n=0), "fp=0": mod(fp=0), "fp=4": mod(fp=4), "N=65536": mod(n=65536), "batch=0": mod(b=0),
+        "batch=65536": mod(b=65536), "null host sizes": mod(host=False), "host size 0": mod(h=(0, 3)),
+        "host size above N": mod(h=(3, lds + 2)), "null cc": mod(cc=None), "null ws": mod(ws=None),
+        "ws misaligned": mod(ws=P + 8), "N=65536,fp=0": mod(n=65536, fp=0), "N=65536,batch=0": mod(n=65536, b=0),
+        "null cc,ws short": mod(cc=None, s=need - 1), "ws misaligned,short": mod(ws=P + 8, s=need - 1),
+        "ws short": ws_at("lapwarm_lapmod_ragged")(lambda: mod(s=need - 1))}
+    return out, short
+
+
+def record(lib):
+    c, short = codes(lib)
+    return {"sizes": sizes(lib), "codes": c, "short_text": short}
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, str(PKG))
+    from lap import _hip
+    print(json.dumps(record(_hip.load())))

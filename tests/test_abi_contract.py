@@ -1,0 +1,51 @@
+"""The C ABI keeps its workspace sizes, its argument checks and their order (tests/abi_contract_common.py against
+tests/golden/abi_contract.json), and every too-small workspace is reported in lapwarm_last_error().  No GPU: every
+recorded call returns before its first HIP call."""
+import json
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+
+import abi_contract_common as acc
+
+GOLDEN = Path(__file__).resolve().parent / "golden" / "abi_contract.json"
+
+
+@pytest.fixture(scope="module")
+def contract():
+    """One record from a fresh interpreter with the library's tuning variables cleared: it reads them once."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("LAPWARM_")}
+    r = subprocess.run([sys.executable, acc.__file__], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads(r.stdout), json.loads(GOLDEN.read_text())
+
+
+def test_workspace_sizes_are_unchanged(contract):
+    got, want = contract
+    assert set(got["sizes"]) == set(want["sizes"])
+    for name, values in want["sizes"].items():
+        assert got["sizes"][name] == values, name
+    points = (len(acc.GRID_BATCH) + 2) * (len(acc.GRID_N) + 2)
+    assert all(len(want["sizes"][name]) == points for name in acc.TWO_INT_SIZES)
+    assert any(want["sizes"]["seeded"]) and 0 in want["sizes"]["seeded"]  # in range and out of range are both there
+
+
+def test_return_codes_and_check_order_are_unchanged(contract):
+    got, want = contract
+    assert set(got["codes"]) == set(want["codes"])
+    for symbol, cases in want["codes"].items():
+        assert got["codes"][symbol] == cases, symbol
+        assert all(code > -1000 for code in cases.values()), symbol  # nothing recorded reached the HIP runtime
+    seen = {code for cases in want["codes"].values() for code in cases.values()}
+    assert seen == {0, -1, -2, -4, -5, -6}
+
+
+def test_a_short_workspace_sets_the_error_text(contract):
+    got, want = contract
+    short = {symbol for symbol, cases in want["codes"].items() if cases.get("ws short") == -1}
+    assert set(got["short_text"]) == short and len(short) == 24
+    for symbol, text in got["short_text"].items():
+        assert text.startswith("workspace too small"), (symbol, text)
