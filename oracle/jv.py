@@ -32,7 +32,7 @@ class Stats(ct.Structure):
 
 
 def build(force: bool = False) -> Path:
-    """Compile the C restatement (and, where /root/reference exists, oracle/_ref)."""
+    """Compile the C restatement (oracle/_ref is oracle/ref.py's business)."""
     src = _HERE / "jv_oracle.c"
     stale = (not _LIB_PATH.exists()) or _LIB_PATH.stat().st_mtime < src.stat().st_mtime
     if force or stale:

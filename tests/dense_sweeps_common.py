@@ -109,7 +109,7 @@ def small_duals(batch, n, seed=0):
 
 
 # ------------------------------------------------------------------------------- references
-def quiet(fn):
+def quiet_errstate(fn):
     """inf - inf and NaN comparisons are part of what is tested; NumPy's warnings about them are not."""
     def wrapped(*a, **kw):
         with np.errstate(invalid="ignore", over="ignore"):
@@ -119,7 +119,7 @@ def quiet(fn):
     return wrapped
 
 
-@quiet
+@quiet_errstate
 def colmin(C, u=None):
     """(batch, n): min_i (C[b][i][j] - u[b][i]) through features_np.min_trick, one instance at a time."""
     if u is None:
@@ -127,12 +127,12 @@ def colmin(C, u=None):
     return np.stack([features_np.min_trick(C[b], u[b]) for b in range(C.shape[0])])
 
 
-@quiet
+@quiet_errstate
 def rowmin(C, v=None):
     return C.min(axis=-1) if v is None else (C - v[..., None, :]).min(axis=-1)
 
 
-@quiet
+@quiet_errstate
 def project_round(C, u, v):
     """One round of project_feasible, batched over the leading axis: (u', v', gmin)."""
     u1 = np.minimum(u, (C - v[..., None, :]).min(axis=-1))
@@ -141,7 +141,7 @@ def project_round(C, u, v):
     return u1, v1, gmin
 
 
-@quiet
+@quiet_errstate
 def reduce_costs(C, u, v, shift_nonneg):
     """(out, gmin) per instance: features_np.reduce_costs and the minimum of its unshifted matrix."""
     out = np.stack([features_np.reduce_costs(C[b], u[b], v[b], shift_nonneg) for b in range(C.shape[0])])
@@ -156,7 +156,7 @@ def same(a, b):
 
 
 # --------------------------------------------------------------------------- seeds for the dual sweeps
-@quiet
+@quiet_errstate
 def project_seeds(C, seed=0, feasible=()):
     """Seeds as tests/golden/make_golden.py: make_features draws them, u = C.min(1) + N(0, 0.05), v = N(0, 0.05);
     the instances listed in `feasible` get u = rowmin(C - v) - 1/64 instead, which no round changes."""
@@ -172,7 +172,7 @@ def project_seeds(C, seed=0, feasible=()):
 REDUCE_KINDS = ("negative", "zero", "positive")
 
 
-@quiet
+@quiet_errstate
 def reduce_seeds(C, shift=0, seed=0):
     """Instance b gets duals whose unshifted reduced minimum is negative, exactly 0 or positive, by
     (b + shift) % 3 (for finite C).  Returns (u, v, kinds)."""

@@ -6,8 +6,6 @@ import torch
 
 from conftest import GOLDEN
 
-ENTRIES = {"lapwarm_graph_features_workspace_bytes": 2, "lapwarm_graph_features_batched": 11,
-           "lapwarm_dual_gnn_workspace_bytes": 3, "lapwarm_dual_edge_scores": 11, "lapwarm_dual_attention": 16}
 ONEGNN_ABS = 1e-5  # what the project grants OneGNN against its CPU oracle: no bound here is looser
 
 _cases = None

@@ -10,7 +10,7 @@ from conftest import GOLDEN
 FIXTURE = GOLDEN / "dual_seeds_cases.npz"
 
 
-def quiet(fn):
+def quiet_warnings(fn):
     """inf - inf and NaN comparisons are part of the cases: no RuntimeWarning for them."""
     @functools.wraps(fn)
     def wrapped(*args, **kwargs):
@@ -56,7 +56,7 @@ def combos():
     return [(a, b, int(mr), float(tol)) for a, mr in enumerate(z["max_rounds"]) for b, tol in enumerate(z["tols"])]
 
 
-@quiet
+@quiet_warnings
 def np_project(C, u, v, max_rounds=50, tol=1e-12, two_read=False):
     """project_feasible as the formulas read: (u, v, gmin of the last round, rounds run).  two_read: gmin from
     the column pass, min_j (cap_j - v_j), instead of a third sweep over C."""
@@ -73,7 +73,7 @@ def np_project(C, u, v, max_rounds=50, tol=1e-12, two_read=False):
     return u, v, gmin, rounds
 
 
-@quiet
+@quiet_warnings
 def np_reduce(C, u, v, shift_nonneg=True):
     """reduce_costs: (matrix, unshifted minimum)."""
     red = (C - u[:, None]) - v[None, :]
@@ -83,7 +83,7 @@ def np_reduce(C, u, v, shift_nonneg=True):
     return red, m
 
 
-@quiet
+@quiet_warnings
 def np_seed_row_col_minima(C, project_rounds=50):
     u = C.min(axis=1)
     v = (C - u[:, None]).min(axis=0)

@@ -1,8 +1,10 @@
 """Writes tests/golden/dual_gnn_cases.npz: the reference's graph features and DualGNN outputs.
 
-Runs only where the reference repository exists (REF below).  It loads the reference's gnn/features.py and
-gnn/dual_gnn.py by file path (as a package named _ref_gnn, so that the model's relative import of the features
-resolves) and never copies them.
+Runs only where the reference repository exists (oracle/ref.py knows where).  It loads the reference's
+gnn/features.py and gnn/dual_gnn.py through oracle.ref.load_module (in a stand-in package named _ref_gnn, so that
+the model's relative import of the features resolves) and never copies them.
+
+Usage:  python tests/golden/make_dual_gnn.py          (from the repo root)
 
 Feature cases (`feat_labels`): cost C, the reference's edge_feat, row_feat, col_feat, and u where the case has one.
 Model configurations (`cfg_labels`): seeded random weights, stored as arrays `w/<cfg>/<parameter name>`.  The
@@ -13,34 +15,20 @@ eval-mode u and v_hint in float32 (u32, v32) and from a .double() copy of the sa
 and the reference's own float32 deviations du = max|u32 - u64| and dv = max|v32 - v64|, each on its own: the tests
 bound both outputs by 4 x du; dv is recorded for information.
 """
-import importlib.util
 import sys
-import types
 from pathlib import Path
 
 import numpy as np
 import torch
 
-REF = Path("/root/reference")
+sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
+from oracle.ref import load_module  # noqa: E402
+
 OUT = Path(__file__).resolve().parent / "dual_gnn_cases.npz"
 
 CONFIGS = {"h32_H4_L2": (32, 4, 2), "h128_H4_L1": (128, 4, 1), "h64_H8_L1": (64, 8, 1)}
 PARAM_COUNTS = {"h32_H4_L2": 62418, "h128_H4_L1": 171658}
 PAD_SIZES = (40, 33, 1)
-
-
-def load_reference():
-    pkg = types.ModuleType("_ref_gnn")
-    pkg.__path__ = [str(REF / "gnn")]
-    sys.modules["_ref_gnn"] = pkg
-    mods = {}
-    for name in ("features", "dual_gnn"):
-        spec = importlib.util.spec_from_file_location(f"_ref_gnn.{name}", str(REF / "gnn" / f"{name}.py"))
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[f"_ref_gnn.{name}"] = mod
-        spec.loader.exec_module(mod)
-        mods[name] = mod
-    return mods["features"], mods["dual_gnn"]
 
 
 def feature_cases(rf):
@@ -82,7 +70,8 @@ def run(model, edge, row, col, mask):
 
 
 def main():
-    rf, rm = load_reference()
+    rf = load_module("gnn/features.py", "features", package="_ref_gnn")
+    rm = load_module("gnn/dual_gnn.py", "dual_gnn", package="_ref_gnn")
     feats = feature_cases(rf)
     z = {"feat_labels": np.array(list(feats))}
     for label, f in feats.items():

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Generate tests/golden/dual_seeds_cases.npz FROM THE REFERENCE.
 
-Runs only where the reference repository exists (REF below).  It loads the reference's
-solvers/advanced_dual.py and solvers/seed_baselines.py by file path (imported, never copied) and stores
+Runs only where the reference repository exists (oracle/ref.py knows where).  It loads the reference's
+solvers/advanced_dual.py and solvers/seed_baselines.py through oracle.ref.load_module (imported, never copied) and
+stores
 inputs and outcomes as data:
 
   * cost matrices at n in SIZES: `uni` (uniform) and `int` (integers 0..4, many ties) directly; `inf` and
@@ -20,14 +21,14 @@ Usage:  python tests/golden/make_dual_seeds.py          (from the repo root)
 """
 from __future__ import annotations
 
-import importlib.util
 import sys
-import types
 from pathlib import Path
 
 import numpy as np
 
-REF = Path("/root/reference")
+sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
+from oracle.ref import load_module  # noqa: E402
+
 OUT = Path(__file__).resolve().parent / "dual_seeds_cases.npz"
 
 SIZES = (1, 2, 7, 33, 64, 65)
@@ -39,20 +40,10 @@ NOISY_SEED = 7
 NOISY_SIZES = (2, 7, 33, 64, 65)
 
 
-def load_by_path(name: str, path: Path):
-    spec = importlib.util.spec_from_file_location(name, str(path))
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules[name] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-_pkg = types.ModuleType("_ref_solvers")
-_pkg.__path__ = [str(REF / "solvers")]
-sys.modules["_ref_solvers"] = _pkg
-load_by_path("_ref_solvers.dual_computation", REF / "solvers" / "dual_computation.py")
-ref_ad = load_by_path("_ref_solvers.advanced_dual", REF / "solvers" / "advanced_dual.py")
-ref_sb = load_by_path("_ref_solvers.seed_baselines", REF / "solvers" / "seed_baselines.py")
+# seed_baselines imports `.advanced_dual` and `.dual_computation`: all three live in one stand-in package
+load_module("solvers/dual_computation.py", "dual_computation", package="_ref_solvers")
+ref_ad = load_module("solvers/advanced_dual.py", "advanced_dual", package="_ref_solvers")
+ref_sb = load_module("solvers/seed_baselines.py", "seed_baselines", package="_ref_solvers")
 
 
 def reduced_in_subset(n, kind, seed):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ FROM THE REFERENCE.
 
-Runs only where /root/reference exists (the build container).  It
-  * loads the reference's Python modules by file path (gnn/features.py,
+Runs only where the reference exists (oracle/ref.py knows where).  It
+  * loads the reference's Python modules through oracle.ref.load_module (gnn/features.py,
     gnn/one_gnn.py, solvers/advanced_dual.py) -- imported, never copied;
   * calls the reference's C++ solver through oracle/_ref/liblap_ref.so, which
     oracle/Makefile compiles from the reference's own sources where they lie;
@@ -14,7 +14,6 @@ Usage:  python tests/golden/make_golden.py          (from the repo root)
 from __future__ import annotations
 
 import hashlib
-import importlib.util
 import sys
 from pathlib import Path
 
@@ -22,27 +21,16 @@ import numpy as np
 import torch
 
 ROOT = Path(__file__).resolve().parents[2]
-REF = Path("/root/reference")
 OUT = Path(__file__).resolve().parent
-sys.path.insert(0, str(ROOT))
+sys.path[:0] = [str(ROOT), str(ROOT / "gnn-accelerated-lap-warm-start-pipeline_amd")]
 
 from oracle import jv as oracle_jv  # noqa: E402
 from oracle import ref as ref_lib  # noqa: E402
+from solvers import generators as gen  # noqa: E402
 
-
-def load_by_path(name: str, path: Path):
-    spec = importlib.util.spec_from_file_location(name, str(path))
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules[name] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-ref_features = load_by_path("_ref_features", REF / "gnn" / "features.py")
-ref_one_gnn = load_by_path("_ref_one_gnn", REF / "gnn" / "one_gnn.py")
-ref_dual = load_by_path("_ref_advanced_dual", REF / "solvers" / "advanced_dual.py")
-gen = load_by_path("_our_generators",
-                   ROOT / "gnn-accelerated-lap-warm-start-pipeline_amd" / "solvers" / "generators.py")
+ref_features = ref_lib.load_module("gnn/features.py", "_ref_features")
+ref_one_gnn = ref_lib.load_module("gnn/one_gnn.py", "_ref_one_gnn")
+ref_dual = ref_lib.load_module("solvers/advanced_dual.py", "_ref_advanced_dual")
 
 
 # --------------------------------------------------------------------------- inputs
@@ -370,12 +358,12 @@ def _ref_int_matrix(tu, n, hard, density, fill):
 
 def make_reference_suite():
     from gzip import GzipFile
-    tu = load_by_path("_ref_test_utils", REF / "LAP" / "lap" / "tests" / "test_utils.py")
+    tu = ref_lib.load_module("LAP/lap/tests/test_utils.py", "_ref_test_utils")
     out = {}
     mats = {}
     for k, (C, opt, x) in SUITE_INF.items():
         mats[k] = np.array(C, dtype=np.float64)
-    eps_C = np.genfromtxt(GzipFile(str(REF / "LAP" / "lap" / "tests" / "cost_eps.csv.gz")), delimiter=",")
+    eps_C = np.genfromtxt(GzipFile(str(ref_lib.REF_ROOT / "LAP" / "lap" / "tests" / "cost_eps.csv.gz")), delimiter=",")
     mats["eps"] = eps_C
     for k, (n, hard, dens, fill, opt) in SUITE_INT.items():
         C = _ref_int_matrix(tu, n, hard, dens, fill)
@@ -430,7 +418,7 @@ def make_reference_suite():
 
 
 if __name__ == "__main__":
-    assert REF.exists(), "needs /root/reference"
+    assert ref_lib.REF_ROOT.exists(), f"needs {ref_lib.REF_ROOT}"
     assert ref_lib.available(), "oracle/_ref/liblap_ref.so could not be built"
     make_seeded()
     make_cold()

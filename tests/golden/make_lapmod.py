@@ -1,10 +1,10 @@
 """Writes tests/golden/lapmod_cases.npz: sparse LAPMOD inputs and what the reference's lapmod_internal returns for
 them with FP_1, FP_2 and FP_DYNAMIC.
 
-    python tests/golden/make_lapmod.py REFERENCE_ROOT [LDS_MAX_N]
+    python tests/golden/make_lapmod.py [LDS_MAX_N]          (from the repo root)
 
-compiles REFERENCE_ROOT/LAP/_lapjv_cpp/lapmod.cpp into a temporary directory (nothing of it is kept), calls
-lapmod_internal through ctypes and stores data only.  Per case `c`: n, cc (divided by ccscale where it is stored as integers), ii, kk; solvable (a perfect matching
+calls lapmod_internal of oracle/_ref/liblapmod_ref.so (the reference's LAP/_lapjv_cpp/lapmod.cpp, compiled by
+oracle/Makefile where the reference exists; oracle.ref.lapmod_lib) and stores data only.  Per case `c`: n, cc (divided by ccscale where it is stored as integers), ii, kk; solvable (a perfect matching
 exists), strict (unsolvable and certain to end with ret = 1 on the device: every row has an entry, and row 0 is
 not left holding an empty column by the column reduction), aug (the reference reaches the augmentation phase: an
 fp_version outside the enum makes it return -2 exactly then); per fp_version v in 1, 2, 3: ret_v, x_v, y_v, and
@@ -12,10 +12,7 @@ for solvable cases and v in 1, 2 the final column duals v_v (the phases called w
 (unsolvable cases are run with FP_1 only and when it is FP_1 that FP_DYNAMIC selects: find_path_sparse_2 reads
 outside its arrays there).  LDS_MAX_N is lapwarm_lapmod_lds_max_n() of the built library (default 3395).
 """
-import ctypes as ct
-import subprocess
 import sys
-import tempfile
 import time
 from pathlib import Path
 
@@ -23,38 +20,8 @@ import numpy as np
 
 HERE = Path(__file__).resolve().parent
 INF = np.inf
-
-
-def build(ref_root, tmp):
-    src = Path(ref_root) / "LAP" / "_lapjv_cpp"
-    so = Path(tmp) / "liblapmod_ref.so"
-    glue = Path(tmp) / "glue.cpp"  # (the C++ symbol behind an unmangled name)
-    # lapmod_c: the entry itself.  lapmod_v: the same three phases, called as lapmod_internal calls them, with v
-    # owned by the caller so that the final column duals can be stored.
-    glue.write_text(
-        '#include <vector>\n#include "lapjv.h"\n'
-        'int_t _ccrrt_sparse(const uint_t, cost_t *, uint_t *, uint_t *, int_t *, int_t *, int_t *, cost_t *);\n'
-        'int_t _carr_sparse(const uint_t, cost_t *, uint_t *, uint_t *, const uint_t, int_t *, int_t *, int_t *, '
-        'cost_t *);\n'
-        'int_t _ca_sparse(const uint_t, cost_t *, uint_t *, uint_t *, const uint_t, int_t *, int_t *, int_t *, '
-        'cost_t *, int);\n'
-        'extern "C" int lapmod_c(unsigned n, double *cc, unsigned *ii, unsigned *kk, int *x, int *y, int fp)\n'
-        '{ return lapmod_internal(n, cc, ii, kk, x, y, (fp_t)fp); }\n'
-        'extern "C" int lapmod_v(unsigned n, double *cc, unsigned *ii, unsigned *kk, int *x, int *y, double *v, '
-        'int fp)\n'
-        '{ std::vector<int_t> fr(n); int ret = _ccrrt_sparse(n, cc, ii, kk, fr.data(), x, y, v);\n'
-        '  for (int i = 0; ret > 0 && i < 2; ++i) ret = _carr_sparse(n, cc, ii, kk, ret, fr.data(), x, y, v);\n'
-        '  if (ret > 0) ret = _ca_sparse(n, cc, ii, kk, ret, fr.data(), x, y, v, fp);\n  return ret; }\n')
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", str(src), str(src / "lapmod.cpp"),
-                    str(glue), "-o", str(so)], check=True)
-    lib = ct.CDLL(str(so))
-    lib.lapmod_internal = lib.lapmod_c
-    lib.lapmod_internal.restype = ct.c_int
-    lib.lapmod_internal.argtypes = [ct.c_uint, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p,
-                                    ct.c_int]
-    lib.lapmod_v.restype = ct.c_int
-    lib.lapmod_v.argtypes = [ct.c_uint] + [ct.c_void_p] * 6 + [ct.c_int]
-    return lib
+sys.path.insert(0, str(HERE.parents[1]))
+from oracle.ref import lapmod_lib  # noqa: E402
 
 
 def ref_solve(lib, n, cc, ii, kk, fp):
@@ -134,9 +101,8 @@ def certain_ret1(n, cc, ii, kk):
 
 
 def main():
-    lib_tmp = tempfile.TemporaryDirectory()
-    lib = build(sys.argv[1], lib_tmp.name)
-    lds_max = int(sys.argv[2]) if len(sys.argv) > 2 else 3395
+    lib = lapmod_lib()
+    lds_max = int(sys.argv[1]) if len(sys.argv) > 1 else 3395
     rng = np.random.default_rng(20240611)
     cases = []  # (label, n, cc, ii, kk, kind)
 

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generate tests/golden/oracle_duals_cases.npz FROM THE REFERENCE.
 
-Runs only where the reference repository exists (REF below).  It loads the reference's
-solvers/dual_computation.py and solvers/advanced_dual.py by file path (imported, never
+Runs only where the reference repository exists (oracle/ref.py knows where).  It loads the reference's
+solvers/dual_computation.py and solvers/advanced_dual.py through oracle.ref.load_module (imported, never
 copied), takes the matching from SciPy's linear_sum_assignment as the reference does, and
 stores inputs and outcomes as data:
 
@@ -18,38 +18,25 @@ from __future__ import annotations
 
 import contextlib
 import hashlib
-import importlib.util
 import io
 import json
 import sys
 import time
-import types
 from pathlib import Path
 
 import numpy as np
 import scipy.optimize
 
 ROOT = Path(__file__).resolve().parents[2]
-REF = Path("/root/reference")
 OUT = Path(__file__).resolve().parent / "oracle_duals_cases.npz"
+sys.path[:0] = [str(ROOT), str(ROOT / "gnn-accelerated-lap-warm-start-pipeline_amd")]
 
+from oracle.ref import load_module  # noqa: E402
+from solvers import generators as gen  # noqa: E402
 
-def load_by_path(name: str, path: Path):
-    spec = importlib.util.spec_from_file_location(name, str(path))
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules[name] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-# advanced_dual.make_feasible_duals imports `.dual_computation`: give both a package to live in
-_pkg = types.ModuleType("_ref_solvers")
-_pkg.__path__ = [str(REF / "solvers")]
-sys.modules["_ref_solvers"] = _pkg
-ref_dc = load_by_path("_ref_solvers.dual_computation", REF / "solvers" / "dual_computation.py")
-ref_ad = load_by_path("_ref_solvers.advanced_dual", REF / "solvers" / "advanced_dual.py")
-gen = load_by_path("_our_generators",
-                   ROOT / "gnn-accelerated-lap-warm-start-pipeline_amd" / "solvers" / "generators.py")
+# advanced_dual.make_feasible_duals imports `.dual_computation`: both live in one stand-in package
+ref_dc = load_module("solvers/dual_computation.py", "dual_computation", package="_ref_solvers")
+ref_ad = load_module("solvers/advanced_dual.py", "advanced_dual", package="_ref_solvers")
 
 
 def sha(a) -> str:

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Generate tests/golden/train_loss_cases.npz and tests/golden/train_loss_large_ref.npz FROM THE REFERENCE.
 
-Runs only where the reference repository exists (REF below).  It loads the reference's gnn/train_one_gnn.py by
-file path (imported, never copied; an empty stand-in module answers its `import h5py`, which only the dataset
-reader uses), calls its `compute_loss` on the CPU with `u_pred.requires_grad_()` and stores data only:
+Runs only where the reference repository exists (oracle/ref.py knows where).  It loads the reference's
+gnn/train_one_gnn.py through oracle.ref.load_module (imported, never copied; an empty stand-in module answers its
+`import h5py`, which only the dataset reader uses), calls its `compute_loss` on the CPU with
+`u_pred.requires_grad_()` and stores data only:
 
   * the inputs: cost (B, n, n), u_pred, u_target (B, n) float32, sizes (B,);
   * the reference's per-instance v_proj, dual_lower, feas, u_reg, primal_upper (the locals of `compute_loss`
@@ -29,29 +30,23 @@ Usage:  python tests/golden/make_train_loss.py          (from the repo root)
 """
 from __future__ import annotations
 
-import importlib.util
 import json
 import sys
-import types
 from pathlib import Path
 
 import numpy as np
 import torch
 
 ROOT = Path(__file__).resolve().parents[2]
-REF = Path("/root/reference")
 OUT = Path(__file__).resolve().parent / "train_loss_cases.npz"
 
-sys.path.insert(0, str(ROOT / "tests"))
+sys.path[:0] = [str(ROOT / "tests"), str(ROOT)]
 import train_loss_common as tl  # noqa: E402
+from oracle.ref import load_module  # noqa: E402
 
 OUT_LARGE = tl.LARGE_REF
 
-sys.modules.setdefault("h5py", types.ModuleType("h5py"))
-_spec = importlib.util.spec_from_file_location("_ref_train_one_gnn", str(REF / "gnn" / "train_one_gnn.py"))
-ref = importlib.util.module_from_spec(_spec)
-sys.modules["_ref_train_one_gnn"] = ref
-_spec.loader.exec_module(ref)
+ref = load_module("gnn/train_one_gnn.py", "_ref_train_one_gnn", stubs=("h5py",))
 
 CAPTURED = ("v_proj", "dual_lower", "feas", "u_reg", "primal_upper")
 

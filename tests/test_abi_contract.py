@@ -1,8 +1,11 @@
-"""The C ABI keeps its workspace sizes, its argument checks and their order (tests/abi_contract_common.py against
+"""Every entry of lap/_hip.py:SIGNATURES is declared in include/lapwarm_hip.h with that many parameters and exported
+by the library.  The C ABI keeps its workspace sizes, its argument checks and their order (abi_contract_common.py against
 tests/golden/abi_contract.json), and every too-small workspace is reported in lapwarm_last_error().  No GPU: every
 recorded call returns before its first HIP call."""
+import ctypes as ct
 import json
 import os
+import re
 import subprocess
 import sys
 from pathlib import Path
@@ -10,8 +13,35 @@ from pathlib import Path
 import pytest
 
 import abi_contract_common as acc
+from conftest import ROOT
+from host_common import lib  # noqa: F401
+from lap import _hip
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "abi_contract.json"
+HEADER = (ROOT / "include" / "lapwarm_hip.h").read_text()
+# entries whose bound types are asserted in full, not only counted
+_VP, _INT = _hip.c_vp, ct.c_int
+EXACT_SIGNATURES = {
+    "lapwarm_ragged_duals_workspace_bytes": (ct.c_size_t, [_INT, _INT]),
+    "lapwarm_oracle_duals_ragged_workspace_bytes": (ct.c_size_t, [_INT, _INT]),
+    # host_sizes (3) is a host array; ld, batch, N; ws_bytes (14); every other argument a device or stream pointer
+    "lapwarm_oracle_duals_ragged": (_INT, [_VP] * 3 + [_hip.c_ip] + [_INT] * 3 + [_VP] * 7 + [ct.c_size_t, _VP]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_hip.SIGNATURES))
+def test_header_declares_and_library_exports_the_entry_with_its_argument_count(lib, name):
+    """Every entry the binding lists: declared in the header with as many parameters as the binding has argument
+    types, and exported by the library."""
+    res, args = _hip.SIGNATURES[name]
+    m = re.search(r"\b%s\s*\(([^)]*)\)\s*;" % name, HEADER)
+    assert m, f"{name} is not declared in lapwarm_hip.h"
+    params = m.group(1).strip()
+    declared = 0 if params in ("", "void") else len(params.split(","))
+    assert declared == len(args), (name, m.group(1))
+    assert hasattr(lib, name), name
+    if name in EXACT_SIGNATURES:
+        assert (res, args) == EXACT_SIGNATURES[name], name
 
 
 @pytest.fixture(scope="module")

@@ -4,35 +4,13 @@ and the two-read form of gmin the device round uses), the stop cases the multi-r
 argument errors of every new Python entry, raised before any device work."""
 import ctypes as ct
 import inspect
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from dual_seeds_common import (case_key, case_names, cases, combos, matrix, np_project, np_reduce,
-                               np_seed_row_col_minima, quiet, same)
-
-ENTRIES = {"lapwarm_ragged_duals_workspace_bytes": 2, "lapwarm_rowmin_ragged": 12,
-           "lapwarm_project_feasible_ragged": 16, "lapwarm_reduce_costs_ragged": 15}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from lap import _hip
-    return _hip.load()
-
-
-def test_header_declares_and_library_exports_the_entries_with_their_argument_counts(lib):
-    from lap import _hip
-    header = (ROOT / "include" / "lapwarm_hip.h").read_text()
-    for name, n_args in ENTRIES.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)\s*;" % name, header)
-        assert m, f"{name} is not declared in lapwarm_hip.h"
-        assert len(m.group(1).split(",")) == n_args, (name, m.group(1))
-        assert hasattr(lib, name), name
-        assert len(_hip.SIGNATURES[name][1]) == n_args, name
-    assert _hip.SIGNATURES["lapwarm_ragged_duals_workspace_bytes"] == (ct.c_size_t, [ct.c_int, ct.c_int])
+                               np_seed_row_col_minima, quiet_warnings, same)
+from host_common import lib  # noqa: F401
 
 
 def test_workspace_query(lib):
@@ -99,7 +77,7 @@ def test_fixture_is_no_larger_than_the_largest_one_and_holds_every_case():
     assert (C == np.round(C)).all() and len(np.unique(C)) == 5  # ties everywhere
 
 
-@quiet
+@quiet_warnings
 def test_numpy_statements_reproduce_the_fixture_and_the_two_read_gmin_is_the_three_read_one():
     z = cases()
     for kind, n, seed in case_names():
@@ -127,7 +105,7 @@ def test_numpy_statements_reproduce_the_fixture_and_the_two_read_gmin_is_the_thr
             assert same(u, z[f"rcseed_u__{kind}_n{n}"]) and same(v, z[f"rcseed_v__{kind}_n{n}"])
 
 
-@quiet
+@quiet_warnings
 def test_two_read_gmin_on_random_tied_infinite_and_nan_rounds():
     """min_i fl(fl(C_ij - u_i) - v_j) = fl(cap_j - v_j) round by round, also where infinities meet."""
     rs = np.random.RandomState(5)

@@ -12,15 +12,10 @@ import pytest
 import torch
 
 import dual_gnn_common as dg
+from host_common import device_lib as lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from lap import _hip
-    return _hip.require_device()
 
 
 def _stream():

@@ -15,18 +15,11 @@ import pytest
 
 from conftest import PKG
 from dual_seeds_common import case_key, case_names, cases, combos, matrix, np_project, np_reduce, same
+from host_common import padded, shared_pipe as pipe  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 LAYOUTS = ("packed", "padded")
-
-
-def padded(mats, width):
-    """(B, width, width) with NaN outside every prefix: a kernel that read there would show it."""
-    C = np.full((len(mats), width, width), np.nan)
-    for b, m in enumerate(mats):
-        C[b, :m.shape[0], :m.shape[0]] = m
-    return C
 
 
 def pack(mats, layout):
@@ -137,12 +130,6 @@ def fixture_batch():
     return names, mats, us, vs
 
 
-@pytest.fixture(scope="module")
-def pipe():
-    from gnn.pipeline import shared_pipeline
-    return shared_pipeline()
-
-
 # ------------------------------------------------------------------------------------------- the fixture
 @pytest.mark.parametrize("layout", LAYOUTS)
 @pytest.mark.parametrize("a,b,max_rounds,tol", combos())
@@ -226,7 +213,7 @@ def shape_batch(family):
 
 
 @functools.lru_cache(maxsize=None)
-def uniform_reference(family):
+def uniform_duals_reference(family):
     """The uniform entries on every instance alone: computed once, shared, never modified."""
     import torch
 
@@ -263,7 +250,7 @@ def test_prefix_is_bit_equal_to_the_uniform_entries_where_the_sweeps_change_shap
     if layout == "packed":  # odd sizes: some bases are 8-byte aligned and no more
         bases = [p.C.data_ptr() + 8 * o for o in p.offsets.tolist()]
         assert any(a % 16 for a in bases) and all(a % 8 == 0 for a in bases)
-    want = uniform_reference(family)
+    want = uniform_duals_reference(family)
     rm, ret = raw_rowmin(p, vs)
     rm0, _ = raw_rowmin(p)
     u, v, gmin, rounds, _ = raw_project(p, us, vs, 3, -1e-3)

@@ -16,6 +16,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from host_common import pipe, torch_cuda  # noqa: F401
 from lapjv_extended_common import ExtendedCases, assert_case, bits, build_E, finish, solve_with
 
 pytestmark = pytest.mark.gpu
@@ -25,19 +26,6 @@ PKG = ROOT / "gnn-accelerated-lap-warm-start-pipeline_amd"
 CASES = ExtendedCases()
 COUNTERS = ((11, "arr_iters"), (4, "paths"), (6, "scan_steps"))
 INF = float("inf")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def pipe(torch_cuda):
-    from gnn import OneGNN, WarmStartPipeline
-    return WarmStartPipeline(OneGNN(21), "cuda:0")
 
 
 def _host(out):
@@ -206,7 +194,7 @@ def test_batch_of_eight_equals_eight_single_calls(torch_cuda, pipe):
         _check_against_oracle("batch8[5]", Cs[5], extend_cost, limit, o, b=5)
 
 
-def _raw_call(torch, lib, C, extend_cost, limit, want_opt=True, want_matched=True, fill=None, stream=None):
+def _raw_call_batched(torch, lib, C, extend_cost, limit, want_opt=True, want_matched=True, fill=None, stream=None):
     """lapwarm_lapjv_extended_batched with a workspace of this test's own."""
     B, n_rows, n_cols = C.shape
     nbytes = lib.lapwarm_lapjv_extended_workspace_bytes(B, n_rows, n_cols, int(extend_cost), limit)
@@ -244,8 +232,8 @@ def test_cost_matrix_on_an_odd_8_byte_offset(torch_cuda, pipe, shape, extend_cos
     C = buf[1:].view(Cs.shape)
     C.copy_(aligned)
     assert C.data_ptr() % 16 == 8 and aligned.data_ptr() % 16 == 0
-    base = _raw_call(torch, pipe.lib, aligned, extend_cost, limit)
-    o = _raw_call(torch, pipe.lib, C, extend_cost, limit, fill=0xFF)
+    base = _raw_call_batched(torch, pipe.lib, aligned, extend_cost, limit)
+    o = _raw_call_batched(torch, pipe.lib, C, extend_cost, limit, fill=0xFF)
     for key in ("x", "y", "matched", "ret"):
         assert np.array_equal(o[key], base[key]), key
     assert np.array_equal(bits(o["opt"]), bits(base["opt"]))
@@ -262,9 +250,9 @@ def test_cost_matrix_on_an_odd_8_byte_offset(torch_cuda, pipe, shape, extend_cos
 def test_null_opt_and_matched_are_accepted(torch_cuda, pipe):
     torch = torch_cuda
     C = torch.from_numpy(np.stack([_uniform(40, (70, 45)), _uniform(41, (70, 45))])).cuda()
-    full = _raw_call(torch, pipe.lib, C, True, 0.1)
+    full = _raw_call_batched(torch, pipe.lib, C, True, 0.1)
     for want_opt, want_matched in ((False, True), (True, False), (False, False)):
-        o = _raw_call(torch, pipe.lib, C, True, 0.1, want_opt, want_matched)
+        o = _raw_call_batched(torch, pipe.lib, C, True, 0.1, want_opt, want_matched)
         assert np.array_equal(o["x"], full["x"]) and np.array_equal(o["y"], full["y"]) and (o["ret"] == 0).all()
         assert np.array_equal(bits(o["opt"]), bits(full["opt"])) if want_opt else (o["opt"] == -7.0).all()
         assert np.array_equal(o["matched"], full["matched"]) if want_matched else (o["matched"] == -7).all()
@@ -291,9 +279,9 @@ def test_side_stream_and_poisoned_workspace(torch_cuda, pipe, shape, extend_cost
     torch = torch_cuda
     Cs = np.stack([_uniform(60 + b, shape) for b in range(2)])
     C = torch.from_numpy(Cs).cuda()
-    base = _raw_call(torch, pipe.lib, C, extend_cost, limit, fill=0)
+    base = _raw_call_batched(torch, pipe.lib, C, extend_cost, limit, fill=0)
     side = torch.cuda.Stream()
-    o = _raw_call(torch, pipe.lib, C, extend_cost, limit, fill=0xFF, stream=side)
+    o = _raw_call_batched(torch, pipe.lib, C, extend_cost, limit, fill=0xFF, stream=side)
     for key in ("x", "y", "matched", "ret"):
         assert np.array_equal(o[key], base[key]), key
     assert np.array_equal(bits(o["opt"]), bits(base["opt"]))

@@ -9,6 +9,7 @@ import ctypes as ct
 import numpy as np
 import pytest
 
+from host_common import pipe, torch_cuda  # noqa: F401
 from lapjv_extended_common import ExtendedCases, assert_case, bits, extended_n, solve_with
 
 pytestmark = pytest.mark.gpu
@@ -16,19 +17,6 @@ pytestmark = pytest.mark.gpu
 CASES = ExtendedCases()
 COUNTERS = ((11, "arr_iters"), (4, "paths"), (6, "scan_steps"))
 INF = float("inf")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def pipe(torch_cuda):
-    from gnn import OneGNN, WarmStartPipeline
-    return WarmStartPipeline(OneGNN(21), "cuda:0")
 
 
 def _host(o):
@@ -233,8 +221,8 @@ def test_inf_and_nan_instances_do_not_touch_their_neighbours(torch_cuda, pipe):
 
 
 # --------------------------------------------------------------------------- raw calls
-def _raw_call(torch, lib, mats, limits, extend_cost=True, fill=None, stream=None, want_opt=True, want_matched=True,
-              odd=False, descending=False, expect=0):
+def _raw_call_ragged(torch, lib, mats, limits, extend_cost=True, fill=None, stream=None, want_opt=True,
+                     want_matched=True, odd=False, descending=False, expect=0):
     """lapwarm_lapjv_extended_ragged with buffers of this test's own.  odd: C starts one double into a 16-byte
     aligned buffer; descending: the instances are stored in reverse order, so that the offsets fall."""
     B = len(mats)
@@ -291,11 +279,11 @@ def _assert_same(o, base):
 
 def test_odd_8_byte_offset_and_descending_offsets(torch_cuda, pipe):
     mats, limits = _raw_set()
-    base = _raw_call(torch_cuda, pipe.lib, mats, limits)
+    base = _raw_call_ragged(torch_cuda, pipe.lib, mats, limits)
     assert (base["ret"] == 0).all()
-    _assert_same(_raw_call(torch_cuda, pipe.lib, mats, limits, odd=True), base)
-    _assert_same(_raw_call(torch_cuda, pipe.lib, mats, limits, descending=True), base)
-    _assert_same(_raw_call(torch_cuda, pipe.lib, mats, limits, odd=True, descending=True), base)
+    _assert_same(_raw_call_ragged(torch_cuda, pipe.lib, mats, limits, odd=True), base)
+    _assert_same(_raw_call_ragged(torch_cuda, pipe.lib, mats, limits, descending=True), base)
+    _assert_same(_raw_call_ragged(torch_cuda, pipe.lib, mats, limits, odd=True, descending=True), base)
     from oracle import jv
     for b, (C, t) in enumerate(zip(mats, limits)):
         opt, x, y, _ = solve_with(jv.dense_raw, C, True, t)
@@ -308,11 +296,11 @@ def test_odd_8_byte_offset_and_descending_offsets(torch_cuda, pipe):
 def test_poisoned_workspace_on_a_side_stream_and_null_outputs(torch_cuda, pipe):
     torch = torch_cuda
     mats, limits = _raw_set()
-    base = _raw_call(torch, pipe.lib, mats, limits, fill=0)
-    o = _raw_call(torch, pipe.lib, mats, limits, fill=0xFF, stream=torch.cuda.Stream())
+    base = _raw_call_ragged(torch, pipe.lib, mats, limits, fill=0)
+    o = _raw_call_ragged(torch, pipe.lib, mats, limits, fill=0xFF, stream=torch.cuda.Stream())
     _assert_same(o, base)
     for want_opt, want_matched in ((False, True), (True, False), (False, False)):
-        o = _raw_call(torch, pipe.lib, mats, limits, fill=0xFF, want_opt=want_opt, want_matched=want_matched)
+        o = _raw_call_ragged(torch, pipe.lib, mats, limits, fill=0xFF, want_opt=want_opt, want_matched=want_matched)
         assert np.array_equal(o["x"], base["x"]) and np.array_equal(o["y"], base["y"]) and (o["ret"] == 0).all()
         assert np.array_equal(bits(o["opt"]), bits(base["opt"])) if want_opt else (o["opt"] == -7.0).all()
         assert np.array_equal(o["matched"], base["matched"]) if want_matched else (o["matched"] == -7).all()
@@ -329,7 +317,7 @@ def test_routing_of_an_instance_outside_the_class(torch_cuda, pipe, monkeypatch)
     assert calls == {"ragged": 1, "batch": 1}
     for b, o in enumerate(out):
         _assert_equals_alone(f"routing{b}", _host(o), alone[b])
-    _raw_call(torch_cuda, pipe.lib, mats, limits, expect=-6)
+    _raw_call_ragged(torch_cuda, pipe.lib, mats, limits, expect=-6)
 
 
 # --------------------------------------------------------------------------- 9. the drop-in

@@ -5,6 +5,7 @@ instance inside a batch, graph capture, and `solvers.LAPMODSolver`."""
 import numpy as np
 import pytest
 
+from host_common import shared_pipe as pipe  # noqa: F401
 from lapmod_common import FP_VERSIONS, densify, load_cases, problem
 
 pytestmark = pytest.mark.gpu
@@ -30,12 +31,6 @@ def expect(c, fp, opt, x, y, label):
         elif not unmatched and fp in c["ref"]:  # neither condition of `ret = 1` was met: the reference's result
             assert np.array_equal(x, c["ref"][fp][1]) and np.array_equal(y, c["ref"][fp][2]), (label, fp)
     assert x.dtype == np.int32 and y.dtype == np.int32 and x.shape == (n,) and y.shape == (n,)
-
-
-@pytest.fixture(scope="module")
-def pipe():
-    from gnn.pipeline import shared_pipeline
-    return shared_pipeline()
 
 
 @pytest.fixture(scope="module")

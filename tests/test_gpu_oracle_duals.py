@@ -9,6 +9,7 @@ import time
 import numpy as np
 import pytest
 
+from host_common import bits_equal, small_model_pipe as pipe  # noqa: F401
 from oracle_duals_common import OracleCases, jacobi, oracle_from_v, sha
 
 pytestmark = pytest.mark.gpu
@@ -17,21 +18,6 @@ CASES = OracleCases()
 DIFF = CASES.indices("diff")
 ORACLE = CASES.indices("oracle")
 FEASIBLE = CASES.indices("feasible")
-
-
-def bits_equal(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    b = np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-@pytest.fixture(scope="module")
-def pipe():
-    import torch
-
-    from gnn import OneGNN, WarmStartPipeline
-    torch.manual_seed(0)
-    return WarmStartPipeline(OneGNN(21, hidden=32, layers=1).eval(), torch.device("cuda:0"))
 
 
 @pytest.mark.parametrize("k", DIFF, ids=[CASES.meta[k]["label"] for k in DIFF])

@@ -7,6 +7,7 @@ import ctypes as ct
 import numpy as np
 import pytest
 
+from host_common import bits_equal, small_model_pipe as pipe  # noqa: F401
 from oracle_duals_common import OracleCases, jacobi, make_C, oracle_from_v
 from oracle_duals_ragged_common import EMPTY, chain_instance
 
@@ -16,21 +17,6 @@ CASES = OracleCases()
 DIFF = CASES.indices("diff")
 SIZES = (1, 2, 3, 7, 8, 33, 64, 129, 255, 256, 257, 511, 513, 640)
 FAMILIES = ("uniform", "sparse", "tie", "metric", "int100")
-
-
-def bits_equal(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    b = np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-@pytest.fixture(scope="module")
-def pipe():
-    import torch
-
-    from gnn import OneGNN, WarmStartPipeline
-    torch.manual_seed(0)
-    return WarmStartPipeline(OneGNN(21, hidden=32, layers=1).eval(), torch.device("cuda:0"))
 
 
 def alone(pipe, C, x):

@@ -10,16 +10,11 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from host_common import torch_cuda  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parents[1]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch
 
 
 def _seeded_ret(fn, C, u, v, eps):

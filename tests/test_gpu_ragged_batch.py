@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from dense_sweeps_common import same
+from host_common import padded
 
 pytestmark = pytest.mark.gpu
 
@@ -42,14 +43,6 @@ def instances(family):
     return tuple(out)
 
 
-def padded(mats, width=N):
-    """(B, width, width) with NaN outside every prefix: a kernel that read there would show it."""
-    C = np.full((len(mats), width, width), np.nan)
-    for b, m in enumerate(mats):
-        C[b, :m.shape[0], :m.shape[0]] = m
-    return C
-
-
 def pack(mats, layout):
     from gnn.features import ragged_pack
     if layout == "packed":
@@ -66,7 +59,7 @@ def pack(mats, layout):
 
 
 @functools.lru_cache(maxsize=None)
-def uniform_reference(family):
+def uniform_features_reference(family):
     """row_features_device of every instance alone: computed once, shared, never modified."""
     import torch
 
@@ -135,7 +128,7 @@ def test_prefix_is_bit_equal_to_the_uniform_kernel(family, layout):
     feat, topk = r.feat.cpu().numpy(), r.topk.cpu().numpy()
     assert (r.ret.cpu().numpy() == 0).all() and r.sizes.cpu().tolist() == SIZES
     assert r.mask.cpu().numpy().dtype == np.bool_ and r.mask.cpu().numpy().sum(1).tolist() == SIZES
-    for b, (n, (f1, t1)) in enumerate(zip(SIZES, uniform_reference(family))):
+    for b, (n, (f1, t1)) in enumerate(zip(SIZES, uniform_features_reference(family))):
         assert same(feat[b, :n], f1), (family, layout, n, np.argwhere(feat[b, :n] != f1)[:4])
         assert same(topk[b, :n], t1), (family, layout, n)
         assert (feat[b, n:] == 0).all() and np.isposinf(topk[b, n:]).all()
@@ -160,7 +153,7 @@ def test_every_word_of_every_output_is_written(layout):
     h = to_host(raw_call(pack(mats, layout)))
     assert (h["ret"] == 0).all()
     check_padding(h, SIZES, mats)
-    for b, (n, (f1, t1)) in enumerate(zip(SIZES, uniform_reference("uniform"))):
+    for b, (n, (f1, t1)) in enumerate(zip(SIZES, uniform_features_reference("uniform"))):
         assert same(h["feat"][b, :n], f1) and same(h["topk"][b, :n], t1)
 
 

@@ -8,6 +8,7 @@ or are deliberately unsupported."""
 import numpy as np
 import pytest
 
+from host_common import torch_cuda  # noqa: F401
 from lapjv_suite import INF4, INF5, INF_LABELS, Suite, assert_known_optimum
 
 pytestmark = pytest.mark.gpu
@@ -39,13 +40,6 @@ def _cases(labels):
 
 def _groups():
     return [pytest.param(g, marks=NAN_OPEN) if g.startswith("nan") else g for g in GROUPS]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch
 
 
 @pytest.fixture(scope="module")

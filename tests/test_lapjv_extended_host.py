@@ -9,6 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from host_common import lib_or_skip as lib  # noqa: F401
 from lapjv_extended_common import ExtendedCases, assert_case, build_E, extended_n, solve_with
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -16,15 +17,6 @@ SYMBOLS = ("lapwarm_lapjv_extended", "lapwarm_lapjv_extended_n", "lapwarm_lapjv_
            "lapwarm_lapjv_extended_batched")
 INF = float("inf")
 NONSQUARE = "Square cost array expected. If cost is intentionally non-square, pass extend_cost=True."
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from lap import _hip
-    try:
-        return _hip.load()
-    except ImportError:
-        pytest.skip("liblapwarm_hip.so is not built")
 
 
 def test_header_declares_the_four_symbols():

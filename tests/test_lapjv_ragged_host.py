@@ -3,34 +3,25 @@ lapwarm_lapjv_extended_ragged, the grouping of instances by the kernel configura
 (lapwarm_lapjv_ragged_groups, host only) against the planner's own per-size functions, the workspace queries,
 the argument errors, which return before any device work, and the exceptions of `lap.lapjv_many`."""
 import ctypes as ct
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_common import lib  # noqa: F401
 from solve_plan_common import plan_solve
 
-ENTRIES = {"lapwarm_lapjv_ragged_workspace_bytes": 2, "lapwarm_lapjv_ragged": 14, "lapwarm_lapjv_ragged_groups": 3,
-           "lapwarm_lapjv_extended_ragged_workspace_bytes": 5, "lapwarm_lapjv_extended_ragged": 22}
 ONE_LAUNCH, COLD = 0, 1  # SolveShape::kOneLaunch, kModeCold
 INF = float("inf")
 NONSQUARE = "Square cost array expected. If cost is intentionally non-square, pass extend_cost=True."
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from lap import _hip
-    return _hip.load()
-
-
-def groups_of(lib, sizes):
+def lapjv_groups_of(lib, sizes):
     arr = (ct.c_int * len(sizes))(*sizes)
     out = (ct.c_int * len(sizes))(*([-7] * len(sizes)))
     return lib.lapwarm_lapjv_ragged_groups(arr, len(sizes), out), list(out)
 
 
-def plan_queries(lib):
+def cold_plan_queries(lib):
     """-> eligible(n), config(n) from the planner's own per-size functions: plan_solve (cold, no hint, no
     lists) and arr_lists_enabled."""
     plan = plan_solve(lib)
@@ -46,24 +37,13 @@ def plan_queries(lib):
     return eligible, config, lists
 
 
-def test_header_declares_and_library_exports_the_entries_with_their_argument_counts(lib):
-    from lap import _hip
-    header = (ROOT / "include" / "lapwarm_hip.h").read_text()
-    for name, n_args in ENTRIES.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)\s*;" % name, header)
-        assert m, f"{name} is not declared in lapwarm_hip.h"
-        assert len(m.group(1).split(",")) == n_args, (name, m.group(1))
-        assert hasattr(lib, name), name
-        assert len(_hip.SIGNATURES[name][1]) == n_args, name
-
-
 def test_groups_are_the_classes_of_equal_cold_plan_configuration(lib):
-    eligible, config, lists = plan_queries(lib)
+    eligible, config, lists = cold_plan_queries(lib)
     first_lists = next(n for n in range(1, 16385) if lists(n))
     assert first_lists == 512  # (default settings: the suite runs without LAPWARM_* in the environment)
     sizes = list(range(1, first_lists))
     assert all(eligible(n) for n in sizes) and not eligible(first_lists)
-    count, group_of = groups_of(lib, sizes)
+    count, group_of = lapjv_groups_of(lib, sizes)
     by_config, by_group = {}, {}
     for n, g in zip(sizes, group_of):
         assert by_config.setdefault(config(n), g) == g, (n, "one configuration in two groups")
@@ -71,20 +51,20 @@ def test_groups_are_the_classes_of_equal_cold_plan_configuration(lib):
     assert count == len(by_config) == len(by_group) and count >= 4
     first = [group_of.index(g) for g in range(count)]
     assert sorted(by_group) == list(range(count)) and first == sorted(first)  # numbered by first appearance
-    count_r, group_r = groups_of(lib, sizes[::-1])
+    count_r, group_r = lapjv_groups_of(lib, sizes[::-1])
     assert count_r == count
     assert len({(a, b) for a, b in zip(group_of, group_r[::-1])}) == count
 
 
 def test_511_is_the_last_eligible_size_and_512_the_first_with_lists(lib):
-    eligible, _, lists = plan_queries(lib)
-    assert eligible(511) and not lists(511) and groups_of(lib, [511]) == (1, [0])
-    assert not eligible(512) and lists(512) and groups_of(lib, [512])[0] == -1
+    eligible, _, lists = cold_plan_queries(lib)
+    assert eligible(511) and not lists(511) and lapjv_groups_of(lib, [511]) == (1, [0])
+    assert not eligible(512) and lists(512) and lapjv_groups_of(lib, [512])[0] == -1
     for sizes in ([17, 512, 300], [17, 300, 511, 600], [5000]):
-        assert groups_of(lib, sizes)[0] == -1, sizes
-    assert groups_of(lib, [17, 100, 200, 300, 511]) == (4, [0, 1, 2, 3, 3])  # 64, 128, 256 and 512 threads
+        assert lapjv_groups_of(lib, sizes)[0] == -1, sizes
+    assert lapjv_groups_of(lib, [17, 100, 200, 300, 511]) == (4, [0, 1, 2, 3, 3])  # 64, 128, 256 and 512 threads
     for n in (0, -3, 16385):
-        assert groups_of(lib, [17, n])[0] == -1, n
+        assert lapjv_groups_of(lib, [17, n])[0] == -1, n
     one = (ct.c_int * 1)(5)
     assert lib.lapwarm_lapjv_ragged_groups(one, 0, one) == -2
     assert lib.lapwarm_lapjv_ragged_groups(None, 1, one) == -2 and lib.lapwarm_lapjv_ragged_groups(one, 1, None) == -2

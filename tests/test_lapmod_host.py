@@ -7,15 +7,10 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from host_common import lib  # noqa: F401
 from lapmod_common import densify, load_cases, problem
 
 ENTRIES = {"lapwarm_lapmod_workspace_bytes": 3, "lapwarm_lapmod_lds_max_n": 0, "lapwarm_lapmod_ragged": 18}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from lap import _hip
-    return _hip.load()
 
 
 def test_entries_are_declared_bound_and_exported(lib):

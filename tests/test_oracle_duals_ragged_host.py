@@ -2,41 +2,15 @@
 workspace query, and a NumPy model of its driver -- a chunk schedule shared by the batch, a sweep budget and a
 `last` check per instance -- which must leave every instance exactly where the uniform driver leaves it alone."""
 import ctypes as ct
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_common import lib  # noqa: F401
 from oracle_duals_common import jacobi, make_C, oracle_from_v
 from oracle_duals_ragged_common import chain_instance, hungarian, model_alone, model_ragged, run_driver, Instance
 
-ENTRIES = {"lapwarm_oracle_duals_ragged_workspace_bytes": 2, "lapwarm_oracle_duals_ragged": 16}
 SIZES = (2, 5, 7, 13, 37, 64)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from lap import _hip
-    return _hip.load()
-
-
-def test_header_declares_and_library_exports_the_entries_with_their_argument_counts(lib):
-    from lap import _hip
-    header = (ROOT / "include" / "lapwarm_hip.h").read_text()
-    for name, n_args in ENTRIES.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)\s*;" % name, header)
-        assert m, f"{name} is not declared in lapwarm_hip.h"
-        assert len(m.group(1).split(",")) == n_args, (name, m.group(1))
-        assert hasattr(lib, name), name
-        res, args = _hip.SIGNATURES[name]
-        assert len(args) == n_args, name
-    assert _hip.SIGNATURES["lapwarm_oracle_duals_ragged_workspace_bytes"] == (ct.c_size_t, [ct.c_int, ct.c_int])
-    res, args = _hip.SIGNATURES["lapwarm_oracle_duals_ragged"]
-    assert res is ct.c_int
-    assert args[3] is _hip.c_ip  # host_sizes: a host array
-    assert args[4:7] == [ct.c_int] * 3 and args[14] is ct.c_size_t
-    assert all(a is _hip.c_vp for k, a in enumerate(args) if k not in (3, 4, 5, 6, 14))
 
 
 def test_workspace_query(lib):

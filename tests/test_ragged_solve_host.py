@@ -2,30 +2,22 @@
 instances by kernel configuration (lapwarm_seeded_ragged_groups, host only) against the per-size plan queries
 the library exports, the workspace query, and the argument errors, which return before any device work."""
 import ctypes as ct
-import re
 
 import pytest
 
-from conftest import ROOT
+from host_common import lib  # noqa: F401
 from solve_plan_common import plan_solve
 
-ENTRIES = {"lapwarm_seeded_ragged_workspace_bytes": 2, "lapwarm_seeded_ragged": 17, "lapwarm_seeded_ragged_groups": 3}
 ONE_LAUNCH = 0  # SolveShape::kOneLaunch
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from lap import _hip
-    return _hip.load()
-
-
-def groups_of(lib, sizes):
+def seeded_groups_of(lib, sizes):
     arr = (ct.c_int * len(sizes))(*sizes)
     out = (ct.c_int * len(sizes))(*([-7] * len(sizes)))
     return lib.lapwarm_seeded_ragged_groups(arr, len(sizes), out), list(out)
 
 
-def plan_queries(lib):
+def seeded_plan_queries(lib):
     """-> eligible(n), config(n) from the planner's own per-size functions: plan_solve (seeded, no hint, no
     lists), solver_uses_helpers and solver_needs_global_state."""
     plan = plan_solve(lib)
@@ -41,23 +33,12 @@ def plan_queries(lib):
     return eligible, config
 
 
-def test_header_declares_and_library_exports_the_entries_with_their_argument_counts(lib):
-    from lap import _hip
-    header = (ROOT / "include" / "lapwarm_hip.h").read_text()
-    for name, n_args in ENTRIES.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)\s*;" % name, header)
-        assert m, f"{name} is not declared in lapwarm_hip.h"
-        assert len(m.group(1).split(",")) == n_args, (name, m.group(1))
-        assert hasattr(lib, name), name
-        assert len(_hip.SIGNATURES[name][1]) == n_args, name
-
-
 def test_groups_are_the_classes_of_equal_plan_configuration(lib):
-    eligible, config = plan_queries(lib)
+    eligible, config = seeded_plan_queries(lib)
     sizes = [n for n in range(1, 1101) if eligible(n)]
     # every size below the first helper size, and the odd ones above it
     assert [n for n in range(1, 1101) if n not in sizes] == list(range(1024, 1101, 2))
-    count, group_of = groups_of(lib, sizes)
+    count, group_of = seeded_groups_of(lib, sizes)
     by_config, by_group = {}, {}
     for n, g in zip(sizes, group_of):
         assert by_config.setdefault(config(n), g) == g, (n, "one configuration in two groups")
@@ -66,20 +47,20 @@ def test_groups_are_the_classes_of_equal_plan_configuration(lib):
     first = [group_of.index(g) for g in range(count)]
     assert sorted(by_group) == list(range(count)) and first == sorted(first)  # numbered by first appearance
     # the same classes whatever the order of the instances
-    count_r, group_r = groups_of(lib, sizes[::-1])
+    count_r, group_r = seeded_groups_of(lib, sizes[::-1])
     assert count_r == count
     assert len({(a, b) for a, b in zip(group_of, group_r[::-1])}) == count
 
 
 @pytest.mark.parametrize("bad", (1024, 5000))
 def test_one_ineligible_size_makes_the_whole_list_ineligible(lib, bad):
-    eligible, _ = plan_queries(lib)
+    eligible, _ = seeded_plan_queries(lib)
     assert not eligible(bad)
-    assert groups_of(lib, [17, 300, 1023])[0] == 3  # 64, 512 and 1024 threads
+    assert seeded_groups_of(lib, [17, 300, 1023])[0] == 3  # 64, 512 and 1024 threads
     for sizes in ([bad], [17, bad, 300], [17, 300, 1023, bad]):
-        assert groups_of(lib, sizes)[0] == -1, sizes
+        assert seeded_groups_of(lib, sizes)[0] == -1, sizes
     for n in (0, -3, 16385):
-        assert groups_of(lib, [17, n])[0] == -1, n
+        assert seeded_groups_of(lib, [17, n])[0] == -1, n
     one = (ct.c_int * 1)(5)
     assert lib.lapwarm_seeded_ragged_groups(one, 0, one) == -2
     assert lib.lapwarm_seeded_ragged_groups(None, 1, one) == -2 and lib.lapwarm_seeded_ragged_groups(one, 1, None) == -2

@@ -2,7 +2,7 @@
 features against NumPy on one core.
 
 The CPU side of the features comparison is the reference's own `compute_features` when `--reference DIR` names a
-checkout of the reference (its gnn/features.py is loaded by path; with `--cpu-only` nothing else runs and no GPU is
+checkout of the reference (its gnn/features.py is loaded by oracle.ref.load_module; with `--cpu-only` nothing else runs and no GPU is
 needed, so the CPU figure can come from a host that has the checkout).  Without it the tool times `numpy_features`
 below, a PARTIAL formulation (statistics and stable ranks of both sides; no edge-tensor assembly, no positional
 encodings, no reduced cost), and labels the figure so.
@@ -78,11 +78,8 @@ def cpu_features_ms(reference, n=512, runs=3):
     torch.set_num_threads(1)
     fn, what = numpy_features, "partial NumPy formulation (numpy_features)"
     if reference:
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("_ref_features", str(Path(reference) / "gnn" / "features.py"))
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules["_ref_features"] = mod
-        spec.loader.exec_module(mod)
+        from oracle.ref import load_module
+        mod = load_module("gnn/features.py", "_ref_features", root=reference)
         fn, what = mod.compute_features, "reference compute_features"
     C = np.random.default_rng(1).random((n, n)) * 10.0
     fn(C)
