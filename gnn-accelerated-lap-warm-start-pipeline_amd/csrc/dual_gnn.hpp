@@ -25,12 +25,23 @@ struct DualAttnParams {
     const float *row_val, *col_val;   // [batch][n][heads * head_dim]
     float *row_msg, *col_msg;         // [batch][n][heads * head_dim]
     int batch, n, heads, head_dim;
+    // [batch] on the device, or null.  With sizes the mask is the prefix [0, sizes[b]) (a size outside 1..n: empty)
+    // and `mask` is not read: a block of padded queries writes zeros and leaves, the key loops end with the last
+    // tile that holds a key of the prefix, and no score outside the prefix is loaded.  The messages are, bit for bit,
+    // those of the prefix mask: a masked key adds +0 to both sums.
+    const int *sizes = nullptr;
 };
 
 size_t dual_gnn_workspace_bytes(int batch, int n, int heads);  // the scores tensor; 0 for arguments out of range
 hipError_t launch_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2,
                                    const float *b2, const float *G, float *scores, int batch, int n, int heads,
                                    hipStream_t stream);
+// The same scores for a padded batch of instances of sizes[b] (device, [batch]; a size outside 1..n: no edge): only
+// the edges (i, j < sizes[b]) are computed, a row's tail rounded up to 16 edges, and written; scores outside the
+// prefixes are left as they are.  On the prefixes the bits are launch_dual_edge_scores's on the same input.
+hipError_t launch_dual_edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                          const float *b2, const float *G, float *scores, const int *sizes, int batch,
+                                          int n, int heads, hipStream_t stream);
 // heads <= 65535 here (the grid's y dimension): kDualMaxHeads limits the edge-scores kernel and the workspace only
 hipError_t launch_dual_attention(const DualAttnParams &p, hipStream_t stream);
 

@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "ragged_batch.hpp"
+
 namespace lapwarm {
 
 constexpr int kGraphMaxN = 4096;
@@ -36,5 +38,25 @@ struct GraphFeatureParams {
 // 0 for batch or n outside 1..kGraphMaxBatch / 1..kGraphMaxN
 size_t graph_features_workspace_bytes(int batch, int n);
 hipError_t launch_graph_features(const GraphFeatureParams &p, void *ws, hipStream_t stream);
+
+// The same features for a batch of instances of different sizes (ragged_batch.hpp), padded to N, in the same three
+// kernels: each is the uniform kernel's body per instance, so the prefix of instance b -- edge[b][:n_b][:n_b],
+// row_out[b][:n_b], col_out[b][:n_b] -- holds, bit for bit, what launch_graph_features gives instance b alone, and
+// everything outside it is 0, as the reference's collate pads.  Every element of every output is written.
+struct GraphFeatureRaggedOut {
+    const double *u;       // [batch][N], read on each prefix, or null: channel 9 is then 0
+    const float *posenc;   // [rows][8]: the per-n tables of the distinct sizes, one after the other
+    const int *pos_off;    // [batch]: first table row of instance b
+    float *edge;           // [batch][N][N][10]
+    float *row_out;        // [batch][N][14]
+    float *col_out;        // [batch][N][14]
+    unsigned char *mask;   // [batch][N] 1 on the prefix
+    int *ret;              // [batch] 0, or 2 for an instance treated as empty (all-zero outputs)
+};
+
+// the workspace with the padded stride N; 0 for batch or N outside 1..kGraphMaxBatch / 1..kGraphMaxN
+size_t graph_features_ragged_workspace_bytes(int batch, int N);
+hipError_t launch_graph_features_ragged(const RaggedBatch &g, const GraphFeatureRaggedOut &o, void *ws,
+                                        hipStream_t stream);
 
 }  // namespace lapwarm

@@ -543,6 +543,56 @@ int lapwarm_dual_attention(const float *scores, const float *a_row, const float 
     return 0;
 }
 
+// ---- DualGNN on a ragged batch: the features (graph_features.hip) and the size-aware attention (dual_gnn.hip) ----
+size_t lapwarm_graph_features_ragged_workspace_bytes(int batch, int N)
+{
+    return graph_features_ragged_workspace_bytes(batch, N);
+}
+
+int lapwarm_graph_features_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                  const double *u, const float *posenc, const int *pos_off, float *edge_out,
+                                  float *row_out, float *col_out, unsigned char *mask, int *ret, void *ws,
+                                  size_t ws_bytes, void *stream_)
+{
+    if (batch < 1 || batch > kGraphMaxBatch || N < 1 || ld < 0) return -2;
+    if (N > kGraphMaxN) return -5;
+    if (!C || !offsets || !sizes || !posenc || !pos_off || !edge_out || !row_out || !col_out || !mask || !ret || !ws)
+        return -2;
+    if (int rc = check_workspace(ws_bytes, graph_features_ragged_workspace_bytes(batch, N))) return rc;
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    const GraphFeatureRaggedOut o{u, posenc, pos_off, edge_out, row_out, col_out, mask, ret};
+    HIP_TRY(launch_graph_features_ragged(g, o, ws, as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_dual_edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                    const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
+                                    int heads, void *stream_)
+{
+    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
+    if (n > kMaxN) return -5;
+    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !scores || !sizes) return -2;
+    HIP_TRY(launch_dual_edge_scores_ragged(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads,
+                                           as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_dual_attention_ragged(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                                  const float *c_col, const float *kbias, const int *sizes, const float *row_val,
+                                  const float *col_val, float *row_msg, float *col_msg, int batch, int n, int heads,
+                                  int head_dim, void *stream_)
+{
+    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kMaxGridY || head_dim < 1) return -2;
+    if (n > kMaxN) return -5;
+    if (!scores || !a_row || !c_row || !a_col || !c_col || !kbias || !sizes || !row_val || !col_val || !row_msg ||
+        !col_msg)
+        return -2;
+    DualAttnParams p{scores, a_row, c_row, a_col, c_col, kbias, nullptr, row_val, col_val, row_msg, col_msg,
+                     batch, n, heads, head_dim, sizes};
+    HIP_TRY(launch_dual_attention(p, as_stream(stream_)));
+    return 0;
+}
+
 int lapwarm_solver_uses_helpers(int n)
 {
     return (solver_uses_helpers(n) && solve_shape(n, false) == SolveShape::kOneLaunch) ? 1 : 0;

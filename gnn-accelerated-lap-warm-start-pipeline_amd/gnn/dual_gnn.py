@@ -24,6 +24,12 @@ Two forwards:
     reference's op order with its dropout placements: inside the edge MLP, on both attention-weight tensors and
     in the two update MLPs.
 
+A padded batch of instances of different sizes passes `sizes` (B,) int32 on the device: `mask` is then the prefix
+mask of the sizes (built here when it is None).  The fused path hands the sizes to lapwarm_dual_edge_scores_ragged
+and lapwarm_dual_attention_ragged, which skip the padding: the edge MLP runs on the edges (i, j < n_b) only, and
+the attention neither loads a score nor walks a key tile outside a prefix.  The outputs are, bit for bit, those of
+the same call without `sizes`.  On the plain path `sizes` only supplies the mask.
+
 A backward for the fused path is out of scope: a gradient taken through the model runs the plain path.
 """
 from __future__ import annotations
@@ -43,6 +49,22 @@ def _records_grad(module, *tensors) -> bool:
     if not torch.is_grad_enabled():
         return False
     return any(t.requires_grad for t in tensors) or any(p.requires_grad for p in module.parameters())
+
+
+def _prefix_mask(sizes, mask, edge_feat) -> torch.Tensor:
+    """The (B, N) prefix mask of `sizes` after checking them, and `mask` against it when one is given."""
+    B, N = edge_feat.shape[:2]
+    if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int32:
+        raise TypeError("sizes must be a torch.int32 tensor")
+    if tuple(sizes.shape) != (B,) or not sizes.is_contiguous():
+        raise ValueError(f"sizes must be a contiguous ({B},) tensor, not {tuple(sizes.shape)}")
+    if sizes.device != edge_feat.device:
+        raise ValueError(f"sizes must be on {edge_feat.device} like the features, not {sizes.device}")
+    inside = (sizes >= 1) & (sizes <= N)
+    prefix = torch.arange(N, device=sizes.device).unsqueeze(0) < torch.where(inside, sizes, 0).unsqueeze(1)
+    if mask is not None and (tuple(mask.shape) != (B, N) or not torch.equal(mask.to(prefix.device, torch.bool), prefix)):
+        raise ValueError("mask is not the prefix mask of sizes")
+    return prefix
 
 
 class DualLayer(nn.Module):
@@ -97,7 +119,7 @@ class DualLayer(nn.Module):
             "kbias": torch.cat([k_row, k_col], 0).contiguous(),
         }
 
-    def _messages_fused(self, edge_feat, row_embed, col_embed, mask):
+    def _messages_fused(self, edge_feat, row_embed, col_embed, mask, sizes=None):
         from lap import _hip
         from ._call import hip_call
         lib = _hip.require_device()
@@ -112,10 +134,16 @@ class DualLayer(nn.Module):
             raise ValueError(f"DualLayer: batch {B}, n {N} or heads {H} outside the fused kernels' range")
         scores = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
         lin1, lin2 = self.edge_mlp[0], self.edge_mlp[3]
-        hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", dev, edge_feat, lin1.weight, lin1.bias, lin2.weight,
-                 lin2.bias, fold["G"], scores, B, N, H)
         row_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
         col_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
+        if sizes is not None:  # scores outside the prefixes are neither written nor read
+            hip_call("lapwarm_dual_edge_scores_ragged", "dual_edge_scores", dev, edge_feat, lin1.weight, lin1.bias,
+                     lin2.weight, lin2.bias, fold["G"], scores, sizes, B, N, H)
+            hip_call("lapwarm_dual_attention_ragged", "dual_attention", dev, scores, fold["a_row"], fold["c_row"],
+                     fold["a_col"], fold["c_col"], fold["kbias"], sizes, row_val, col_val, row_msg, col_msg, B, N, H, D)
+            return row_msg, col_msg
+        hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", dev, edge_feat, lin1.weight, lin1.bias, lin2.weight,
+                 lin2.bias, fold["G"], scores, B, N, H)
         mask8 = None if mask is None else mask.to(torch.uint8).contiguous()
         hip_call("lapwarm_dual_attention", "dual_attention", dev, scores, fold["a_row"], fold["c_row"], fold["a_col"],
                  fold["c_col"], fold["kbias"], mask8, row_val, col_val, row_msg, col_msg, B, N, H, D)
@@ -158,12 +186,14 @@ class DualLayer(nn.Module):
                 and not _records_grad(self, edge_feat, row_embed, col_embed))
 
     def forward(self, edge_feat: torch.Tensor, row_embed: torch.Tensor, col_embed: torch.Tensor,
-                mask: Optional[torch.Tensor]) -> tuple[torch.Tensor, torch.Tensor]:
+                mask: Optional[torch.Tensor], sizes: Optional[torch.Tensor] = None
+                ) -> tuple[torch.Tensor, torch.Tensor]:
+        """`sizes` (B,) int32 on the device of the tensors: `mask` is their prefix mask (DualGNN.forward checks it)."""
         if self.takes_fused_path(edge_feat, row_embed, col_embed):
             with torch.autocast("cuda", enabled=False):
                 edge_feat = edge_feat.float().contiguous()
                 row_embed, col_embed = row_embed.float(), col_embed.float()
-                row_msg, col_msg = self._messages_fused(edge_feat, row_embed, col_embed, mask)
+                row_msg, col_msg = self._messages_fused(edge_feat, row_embed, col_embed, mask, sizes)
                 return self._update(row_embed, col_embed, row_msg, col_msg)
         row_msg, col_msg = self._messages_plain(edge_feat, row_embed, col_embed, mask)
         return self._update(row_embed, col_embed, row_msg, col_msg)
@@ -187,10 +217,10 @@ class DualGNN(nn.Module):
         self.row_out = nn.Linear(hidden_dim, 1)
         self.col_out = nn.Linear(hidden_dim, 1)
 
-    def _forward(self, edge_feat, row_feat, col_feat, mask):
+    def _forward(self, edge_feat, row_feat, col_feat, mask, sizes=None):
         nodes = (self.row_encoder(row_feat), self.col_encoder(col_feat))
         for layer in self.layers:
-            nodes = layer(edge_feat, *nodes, mask)
+            nodes = layer(edge_feat, *nodes, mask, sizes)
         u, v_hint = (head(x).squeeze(-1) for head, x in zip((self.row_out, self.col_out), nodes))
         # the gauge: u is centred per instance (over all N slots, padded ones included, as the reference does) and
         # v_hint takes the mean, so that u_i + v_j is unchanged
@@ -201,14 +231,20 @@ class DualGNN(nn.Module):
         return {"u": u, "v_hint": v_hint}
 
     def forward(self, edge_feat: torch.Tensor, row_feat: torch.Tensor, col_feat: torch.Tensor,
-                mask: Optional[torch.Tensor] = None) -> dict[str, torch.Tensor]:
+                mask: Optional[torch.Tensor] = None, *, sizes: Optional[torch.Tensor] = None
+                ) -> dict[str, torch.Tensor]:
+        """`sizes`: (B,) int32 on the device of the features, the size of every instance of a padded batch (a size
+        outside 1..N is an empty instance).  `mask` must then be None or the prefix mask of the sizes; comparing a
+        given mask reads one flag back from the device."""
         if edge_feat.ndim != 4:
             raise ValueError("edge_feat must have shape (batch, n, n, F)")
+        if sizes is not None:
+            mask = _prefix_mask(sizes, mask, edge_feat)
         if self.layers[0].takes_fused_path(edge_feat, row_feat, col_feat) and not _records_grad(self):
             # float32 end to end, whatever autocast context the caller is in
             with torch.autocast("cuda", enabled=False):
-                return self._forward(edge_feat.float(), row_feat.float(), col_feat.float(), mask)
-        return self._forward(edge_feat, row_feat, col_feat, mask)
+                return self._forward(edge_feat.float(), row_feat.float(), col_feat.float(), mask, sizes)
+        return self._forward(edge_feat, row_feat, col_feat, mask, sizes)
 
 
 __all__ = ["DualGNN", "DualLayer", "EDGE_FEATURE_DIM", "NODE_FEATURE_DIM", "FUSED_MAX_HEADS"]

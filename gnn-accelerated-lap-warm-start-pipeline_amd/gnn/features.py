@@ -12,7 +12,8 @@ float32 maths, ddof=1, argmin-only column counts) it returns exactly the same st
 `graph_features_device(C, u=None)` and `compute_features(C, ...)` are DualGNN's O(n^2) features (the reference's
 gnn/features.py:49-153): 10 edge channels and 14 row / column statistics, computed in fp64 by graph_features.hip.
 Ranks are stable (the lower index first among equal values), which is one of the rankings the reference's
-unstable argsort may return.  `gnn.compute_features` (the package-level name) still raises; see `gnn`.
+unstable argsort may return.  `graph_features_ragged` / `graph_features_packed` compute them for instances of
+different sizes in one call, padded as the reference's collate pads them.  `gnn.compute_features` (the package-level name) still raises; see `gnn`.
 """
 from __future__ import annotations
 
@@ -387,6 +388,55 @@ def graph_features_device(C, u=None):
     if squeeze:
         edge, row, col = edge[0], row[0], col[0]
     return edge, row, col
+
+
+class RaggedGraphFeatures:
+    """What one ragged graph-feature call returns, padded to N = the largest size: edge (B, N, N, 10), row and col
+    (B, N, 14) f32, 0 outside every prefix, mask (B, N) bool, sizes (B,) int32 and ret (B,) int32 (0, or 2 for a
+    size outside 1..N), all on the device."""
+    __slots__ = ("edge", "row", "col", "mask", "sizes", "ret")
+
+    def __init__(self, edge, row, col, mask, sizes, ret):
+        self.edge, self.row, self.col, self.mask, self.sizes, self.ret = edge, row, col, mask, sizes, ret
+
+
+def graph_features_ragged(costs, u=None, device="cuda:0", sizes=None):
+    """DualGNN's graph features of B cost matrices of different sizes in one call (three kernels): a
+    RaggedGraphFeatures padded to the largest size.  edge[b, :n_b, :n_b], row[b, :n_b] and col[b, :n_b] are bit for
+    bit what graph_features_device gives instance b alone; everything else is 0, as the reference's collate
+    (gnn/train.py) pads.  `costs`, `device`, `sizes`: see ragged_pack; u: (B, N) float64 on the device, read on each
+    prefix, or None.  Enqueued on the current torch stream; nothing is read back."""
+    if sizes is None:
+        costs = list(costs)
+        width = max((int(np.shape(c)[0]) for c in costs if np.ndim(c) == 2), default=0)
+    else:
+        width = int(costs.shape[1]) if len(costs.shape) == 3 else 0
+    if width > GRAPH_MAX_N:
+        raise ValueError(f"n exceeds the {GRAPH_MAX_N} limit of the graph features: {width}")
+    return graph_features_packed(ragged_pack(costs, device, sizes), u)
+
+
+def graph_features_packed(pack: RaggedPack, u=None):
+    """graph_features_ragged of a batch that is packed already."""
+    import torch
+    from ._call import hip_call
+    B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
+    if N > GRAPH_MAX_N:
+        raise ValueError(f"n exceeds the {GRAPH_MAX_N} limit of the graph features: {N}")
+    _check_pack_vector(pack, "u", u, optional=True)
+    lib = _hip.require_device()
+    ws_bytes = int(lib.lapwarm_graph_features_ragged_workspace_bytes(B, N))
+    if ws_bytes == 0:
+        raise ValueError(f"graph_features_packed: batch {B} or N {N} out of range")
+    edge = torch.empty((B, N, N, EDGE_FEATURE_DIM), dtype=torch.float32, device=dev)
+    row = torch.empty((B, N, NODE_FEATURE_DIM), dtype=torch.float32, device=dev)
+    col = torch.empty((B, N, NODE_FEATURE_DIM), dtype=torch.float32, device=dev)
+    mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    ret = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    hip_call("lapwarm_graph_features_ragged", "graph_features_ragged", dev, pack.C, pack.offsets, pack.sizes, pack.ld,
+             B, N, u, pack.posenc, pack.pos_off, edge, row, col, mask, ret, ws, ws_bytes)
+    return RaggedGraphFeatures(edge, row, col, mask.view(torch.bool), pack.sizes, ret)
 
 
 def compute_features(C: np.ndarray, *, include_reduced_cost: bool = False, u=None) -> GraphFeatures:

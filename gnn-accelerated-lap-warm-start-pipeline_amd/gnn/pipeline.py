@@ -20,8 +20,8 @@ import torch
 from lap import _hip
 from ._call import hip_call
 from .dual_gnn import DualGNN
-from .features import (ROW_FEATURE_DIM, RaggedPack, _check_pack_vector, graph_features_device, min_trick_device,
-                       min_trick_ragged, ragged_pack, row_features_device, row_features_packed, row_min_ragged)
+from .features import (ROW_FEATURE_DIM, RaggedPack, _check_pack_vector, graph_features_device,
+                       graph_features_packed, min_trick_device, min_trick_ragged, ragged_pack, row_features_device, row_features_packed, row_min_ragged)
 from .one_gnn import OneGNN
 
 STATS_FIELDS = ("branch", "tight_edges", "free_rows", "arr_fired", "paths", "finds", "scan_steps",
@@ -768,14 +768,12 @@ class WarmStartPipeline:
 
     def _predict_packed(self, pack, r=None):
         """(pack, u_hat, v_hat) of a packed batch; `r`: its row features, where the caller has them already."""
+        if isinstance(self.model, DualGNN):
+            return _predict_packed_dual(self.model, pack)
         if r is None:
             r = row_features_packed(pack)
         u = self.model(r.feat, mask=r.mask, topk_values=r.topk)["u"].to(torch.float64)
-        # OneGNN centres u over the padded width (masked rows included, as the reference's forward does), which
-        # shifts every instance shorter than the batch maximum; centred over its own rows an instance gets
-        # what the model gives it alone
-        count = pack.sizes.to(torch.float64).unsqueeze(1)
-        u = ((u - u.sum(dim=1, keepdim=True) / count) * r.mask).contiguous()
+        u = _centre_per_instance(u, pack.sizes, r.mask)
         return pack, u, min_trick_ragged(pack, u)
 
     @torch.inference_mode()
@@ -783,7 +781,9 @@ class WarmStartPipeline:
         """costs: square fp64 matrices of different sizes (NumPy, or CUDA tensors) -> a list of (u_hat, v_hat),
         fp64 device tensors of length n_b, what predict_batch gives each instance alone: ragged features and
         top-16, one masked OneGNN forward over the padded batch, then the fp64 min-trick of u_hat per instance
-        (lapwarm_colmin_ragged)."""
+        (lapwarm_colmin_ragged).  With a DualGNN as the model: ragged graph features and one forward with the
+        sizes (_predict_packed_dual); u_hat then agrees with predict_batch within float32 rounding, not bit for
+        bit, because the torch GEMMs of the forward see another shape."""
         pack, u, v = self._predict_ragged(costs)
         return [(u[b, :n], v[b, :n]) for b, n in enumerate(pack.host_sizes)]
 
@@ -917,10 +917,30 @@ class WarmStartPipeline:
         self._pending = None
 
 
+def _centre_per_instance(u, sizes, mask):
+    """u (B, N) fp64, 0 on padded rows, centred over the padded width -> centred over each instance's own rows.
+    Both models centre u over all N slots (masked rows included, as the reference's forwards do), which shifts every
+    instance shorter than the batch maximum; centred over its own rows an instance gets what the model gives it
+    alone."""
+    count = sizes.to(torch.float64).unsqueeze(1)
+    return ((u - u.sum(dim=1, keepdim=True) / count) * mask).contiguous()
+
+
+def _predict_packed_dual(model, pack):
+    """WarmStartPipeline._predict_packed for a DualGNN: the ragged graph features, one forward over the padded batch
+    with the sizes (the fused kernels skip the padding), u centred per instance in fp64, then the ragged fp64
+    min-trick; the model's v_hint is not used."""
+    f = graph_features_packed(pack)
+    u = model(f.edge, f.row, f.col, sizes=f.sizes)["u"].to(torch.float64)
+    u = _centre_per_instance(u, pack.sizes, f.mask)
+    return pack, u, min_trick_ragged(pack, u)
+
+
 class DualWarmStartPipeline(WarmStartPipeline):
     """The warm-start pipeline with DualGNN as its model: graph features -> DualGNN u -> v = min(C - u) ->
     lapjv_seeded.  Only the prediction differs; solve_batch, the pipeline_* methods and every solver entry are
-    inherited.  The ragged predictions (predict_ragged, solve_many) are OneGNN's and are not available here."""
+    inherited.  So are predict_ragged and solve_many: their prediction (WarmStartPipeline._predict_packed) goes by
+    the model's type, and for a DualGNN it is the ragged graph features and one forward with `sizes`."""
 
     @torch.inference_mode()
     def predict_batch(self, C: torch.Tensor):

@@ -109,6 +109,13 @@ SIGNATURES = {
                                             c_vp]),
     "lapwarm_dual_attention": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int,
                                           ct.c_int, ct.c_int, ct.c_int, c_vp]),
+    "lapwarm_graph_features_ragged_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_graph_features_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, c_vp,
+                                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_dual_edge_scores_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int, ct.c_int,
+                                                   ct.c_int, c_vp]),
+    "lapwarm_dual_attention_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                 ct.c_int, ct.c_int, ct.c_int, ct.c_int, c_vp]),
     "lapwarm_profile_enable": (None, [ct.c_int]),
     "lapwarm_profile_last_solver_ms": (ct.c_double, []),
     "lapwarm_solver_uses_helpers": (ct.c_int, [ct.c_int]),

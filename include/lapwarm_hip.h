@@ -506,6 +506,35 @@ int lapwarm_dual_attention(const float *scores, const float *a_row, const float 
                            const float *col_val, float *row_msg, float *col_msg, int batch, int n, int heads,
                            int head_dim, void *stream);
 
+/* DualGNN on a batch of instances of different sizes (C, offsets, sizes, ld, batch, N as in lapwarm_colmin_ragged;
+ * N <= 4096 and batch <= 32767 for the features, the limits of the uniform entries for the other two).
+ * lapwarm_graph_features_ragged: lapwarm_graph_features_batched per instance, in the same three kernels, every
+ *   output padded to N and written in full: edge_out [batch][N][N][10], row_out, col_out [batch][N][14] f32, mask
+ *   [batch][N] bytes (1 on the prefix), ret [batch] (0; 2 for an instance treated as empty: all-zero outputs).  On the
+ *   prefix of instance b the outputs are, bit for bit, what lapwarm_graph_features_batched gives the instance alone;
+ *   outside it they are 0.  u [batch][N] fp64 is read on each prefix, or NULL (channel 9 is 0); posenc and pos_off
+ *   as in lapwarm_row_features_ragged.  The workspace has the layout of the uniform call with n = N.
+ * lapwarm_dual_edge_scores_ragged: lapwarm_dual_edge_scores with sizes [batch] on the device.  Only the edges
+ *   (i, j < sizes[b]) are computed (a row's tail rounded up to 16 edges) and written; scores outside the prefixes
+ *   are NOT written.  On the prefixes the bits are lapwarm_dual_edge_scores's on the same padded input.
+ * lapwarm_dual_attention_ragged: lapwarm_dual_attention with the prefix [0, sizes[b]) as the mask.  Blocks of padded
+ *   queries write zero messages and read nothing, the key loops stop at the prefix and no score outside a prefix is
+ *   loaded (it may hold anything).  The messages are, bit for bit, those of lapwarm_dual_attention with that mask.
+ * A size outside 1..N is an empty instance.  Returns 0, -1 (workspace too small), -2 (arguments), -5 (N above the
+ * entry's limit), <= -1000 HIP error; argument codes come before any HIP call. */
+size_t lapwarm_graph_features_ragged_workspace_bytes(int batch, int N);
+int lapwarm_graph_features_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                  const double *u_or_null, const float *posenc, const int *pos_off, float *edge_out,
+                                  float *row_out, float *col_out, unsigned char *mask, int *ret, void *ws,
+                                  size_t ws_bytes, void *stream);
+int lapwarm_dual_edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                    const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
+                                    int heads, void *stream);
+int lapwarm_dual_attention_ragged(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                                  const float *c_col, const float *kbias, const int *sizes, const float *row_val,
+                                  const float *col_val, float *row_msg, float *col_msg, int batch, int n, int heads,
+                                  int head_dim, void *stream);
+
 /* Profiling hook for bench.py: when enabled, lapwarm_seeded_batched / lapwarm_lapjv_batched /
  * lapwarm_seeded_ragged / lapwarm_lapjv_ragged / lapwarm_lapjv_extended_ragged bracket their solver launches
  * with HIP events on the caller's stream;
