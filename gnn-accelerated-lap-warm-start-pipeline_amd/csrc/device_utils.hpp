@@ -268,6 +268,18 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     return v;
 }
 
+// Inclusive prefix sum over the lanes of a wave: the six DPP steps of the prefix-min scan below.
+__device__ __forceinline__ int wave_incl_prefix_sum_i32(int v)
+{
+    v += dpp_move<kDppRowShr1, 0xf>(0, v);
+    v += dpp_move<kDppRowShr2, 0xf>(0, v);
+    v += dpp_move<kDppRowShr4, 0xf>(0, v);
+    v += dpp_move<kDppRowShr8, 0xf>(0, v);
+    v += dpp_move<kDppRowBcast15, 0xa>(0, v);
+    v += dpp_move<kDppRowBcast31, 0xc>(0, v);
+    return v;
+}
+
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ void scan_step_min_pair(double &v, int &i)
 {

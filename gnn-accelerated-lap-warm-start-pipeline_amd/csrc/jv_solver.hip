@@ -29,9 +29,9 @@
 //     compare), and a step with exactly one tie event -- the common case -- is resolved with a
 //     single barrier: the finder publishes (column, position, matched row, displaced column) in
 //     a double-buffered LDS slot, every thread advances the uniform state from it, and only the
-//     owner of the affected position touches order[].  Steps with 2-4 events are resolved the same
-//     way from arrival-slot records (round 2); more events, or events inside the swap window,
-//     fall back to the ordered replay by wave 0.
+//     owner of the affected position touches order[].  Steps with more events take a second barrier:
+//     the finders rank their events from the event bitmap and swap their own columns in between;
+//     events inside the swap window fall back to the ordered replay by wave 0.
 //   * round 2: one HELPER workgroup per instance (blocks beyond the batch, same XCD) pulls the rows
 //     the solver announces through a ring in global memory -- columns joining the SCAN list, the
 //     winner of a minima collection, the next path's start row -- into the L2 both share.  It writes
@@ -50,18 +50,19 @@ struct EventSlot {
     int j, p, i, a;  // event column, its position, its matched row (-1: free), column at order[hi]
 };
 
-constexpr int kRecEvents = 4;  // tie events of one relax step that are resolved without a second barrier
+// Only entry 0 of a parity's records is in use (the single-event step).  The entries stay four apart: every LDS
+// array sits behind Ctrl, and moving them has cost the seeded kernel 2 % before (ArrState, below).
+constexpr int kRecStride = 4;
 
 struct alignas(16) Ctrl {
     double level;
     int hi;
     int target;
-    // records of the first kRecEvents tie events of a step, per step parity, in ARRIVAL order
-    // (slot = returning atomicAdd on ev_total); entry 0 alone describes a single-event step
-    alignas(16) EventSlot rec[2][kRecEvents];
-    // columns at order[hi .. hi+3], published each step by the owners of those positions: what
-    // the events of the step will displace
-    alignas(16) int a_pub[2][kRecEvents];
+    // record of a tie event of the step, per step parity: entry 0, written by every finder and read only when the
+    // step had exactly one event (then it is that event's)
+    alignas(16) EventSlot rec[2][kRecStride];
+    // column at order[hi], published each step by the owner of that position: what a single event displaces
+    alignas(16) int a_pub[2][kRecStride];
     int tie_find;     // sequence number of the last minima collection that saw a tie
     int ev_total[2];  // monotonic tie-event counters, one per step parity (readers diff them;
                       // a reader of step t can never see an increment of step t+1)
@@ -79,7 +80,7 @@ struct ArrState {
     unsigned arr_current, arr_rr;
     int arr_new_free, arr_fwd, arr_iters, arr_fast, arr_err;
 };
-static_assert(sizeof(ArrState) <= sizeof(EventSlot) * 2 * kRecEvents, "ArrState is overlaid on Ctrl::rec");
+static_assert(sizeof(ArrState) <= sizeof(EventSlot) * 2 * kRecStride, "ArrState is overlaid on Ctrl::rec");
 
 constexpr int kSentinelIdx = 0x7ffffffe;  // the LARGE sentinel of the ARR scan (index -1 in the reference)
 constexpr int kEmptyIdx = 0x7fffffff;
@@ -107,6 +108,46 @@ __device__ __forceinline__ unsigned long long stamp_now()
 #define STAMPP(var) STAMP_G(4, var)
 #define STAMP_ADD(slot, t1, t0) stamps[slot] += (long long)((t1) - (t0))
 #define STAMP_INC(slot) stamps[slot] += 1
+#ifdef LAPWARM_STAMP_MULTI
+// Anatomy of the relax steps with two or more tie events (make stamps-multi, tools/diag_stamps.py): the slots the
+// minima collection and the path use otherwise (0, 8..15) and the slow-step counter (7) hold, per class of such a
+// step, the post cycles (low 40 bits) with the step count above them and the barrier wait that preceded the post
+// phase, and a histogram of the events per step.  Classes: 0 the finders swapped their own columns
+// (no event inside the window), 1 the path ended on a free column, 2 ordered replay of a step with more than four
+// events, 3 ordered replay of a step with two to four events.  (With up to four positions per thread only an event
+// inside [hi, hi + cnt) is replayed; with eight or more every multi-event step is.)
+static_assert((LAPWARM_STAMP_GROUPS) == 2, "the multi-event anatomy reuses the slots of stamp groups 1 and 4");
+#define STAMP_CLASS(cls)                                                           \
+    do {                                                                           \
+        const unsigned long long stamp_class_end = stamp_now();                    \
+        stamps[8 + 2 * (cls)] += (long long)(stamp_class_end - tr3) + (1ll << 40); \
+        stamps[9 + 2 * (cls)] += (long long)(tr3 - tr2);                           \
+    } while (0)
+// (constant slot numbers: a slot chosen at run time sends the whole stamps array to scratch memory)
+#define STAMP_CLASS_SWAPPED() STAMP_CLASS(0)
+#define STAMP_CLASS_FREE() STAMP_CLASS(1)
+#define STAMP_CLASS_REPLAYED(cnt) \
+    do {                          \
+        if ((cnt) > 4)            \
+            STAMP_CLASS(2);       \
+        else                      \
+            STAMP_CLASS(3);       \
+    } while (0)
+#define STAMP_EVENTS(cnt)                                                                             \
+    do {                                                                                              \
+        if ((cnt) <= 4)                                                                               \
+            stamps[0] += 1ll << (21 * ((cnt) - 2));                                                   \
+        else                                                                                          \
+            stamps[7] += ((cnt) <= 8) ? 1ll : (1ll << 32);                                            \
+    } while (0)
+#define STAMP_INC_UNLESS_MULTI(slot)
+#else
+#define STAMP_CLASS_SWAPPED()
+#define STAMP_CLASS_FREE()
+#define STAMP_CLASS_REPLAYED(cnt)
+#define STAMP_EVENTS(cnt)
+#define STAMP_INC_UNLESS_MULTI(slot) STAMP_INC(slot)
+#endif
 #else
 #define STAMP(var)
 #define STAMPR(var)
@@ -114,6 +155,11 @@ __device__ __forceinline__ unsigned long long stamp_now()
 #define STAMP_FI(bit, var)
 #define STAMP_ADD(slot, t1, t0)
 #define STAMP_INC(slot)
+#define STAMP_INC_UNLESS_MULTI(slot)
+#define STAMP_CLASS_SWAPPED()
+#define STAMP_CLASS_FREE()
+#define STAMP_CLASS_REPLAYED(cnt)
+#define STAMP_EVENTS(cnt)
 #endif
 
 // RAGGED: the instance is one of a ragged batch (jv_instance_kernel<.., true>): the rows of C are ldc apart, not n.
@@ -364,6 +410,9 @@ struct Solver {
     }
 
     // Several tie events in one relax step (lapjv.cpp:199-205): replay them in position order.
+    // KEEP_BITS: the other waves walk the same bitmap copy until the barrier that follows the replay, so the
+    // words stay as they are and the finders take their bits out behind that barrier.
+    template <bool KEEP_BITS = false>
     __device__ __forceinline__ void replay_scan(int hi, int par)
     {
         const int lane = bc.lane;
@@ -378,7 +427,9 @@ struct Solver {
             uint32_t ew = 0;
             if (idx < W) {
                 ew = evb[idx];
-                if (ew) evb[idx] = 0;
+                if constexpr (!KEEP_BITS) {
+                    if (ew) evb[idx] = 0;
+                }
             }
             unsigned long long mask = __ballot(ew != 0);
             while (mask && target < 0) {
@@ -461,13 +512,11 @@ struct Solver {
         STAMP_ADD(8, tp0, tpath);
         int seen0 = ctrl_seen0, seen1 = ctrl_seen1;
         int find_seq = ctrl_find_seq;
-        // columns appended to the SCAN list by the previous step's single-barrier paths (their
-        // owners may still be writing order[]): position app_pos and, after a multi-event step,
-        // app_pos + 1 -- the only two fresh entries the directly following step can look at
-        int app_pos = -1, app_j = 0, app_i = 0, app_j1 = 0, app_i1 = 0;
-        bool app_two = false;
-        // 2-4 tie events behind the single barrier: only with <= 4 positions per thread (with 8+
-        // the extra live values of that path spill: n = 16384 went from 25 s to 55 s with it)
+        // column appended to the SCAN list by the previous step's single-event path (its owner may
+        // still be writing order[]): position app_pos, the only fresh entry the directly following
+        // step can look at.  (A step with more events has a barrier behind its writes.)
+        int app_pos = -1, app_j = 0, app_i = 0;
+        // independent tie events swapped by their finders: only with <= 4 positions per thread
         constexpr bool kFastMulti = CH <= 4;
         bool pf_have = false;  // level 8: the current head's row sits in slot pf_slot
         int pf_slot = 0;
@@ -627,7 +676,7 @@ struct Solver {
                     head_i = uni(ctrl->head_i);
                     STAMP_FI(7, tfg);
                     STAMP_ADD(14, tfg, tfe);
-                    STAMP_INC(15);
+                    STAMP_INC_UNLESS_MULTI(15);
                     if (target >= 0) break;
                     ring_push_scan(lo, hi);
                     // the collection permuted order[]: rebind the registers of the positions we own
@@ -720,14 +769,9 @@ struct Solver {
             const bool queued = (lo + 1 < hi);
             int nq_j = 0, nq_i = 0;
             const int fwd_pos = app_pos;  // only meaningful for the pass that directly follows
-            const bool fwd_two = app_two;
             app_pos = -1;
-            app_two = false;
             if (queued) {
-                if (fwd_two && lo == fwd_pos) {
-                    nq_j = app_j1;
-                    nq_i = app_i1;
-                } else if (lo + 1 == fwd_pos) {
+                if (lo + 1 == fwd_pos) {
                     // appended by the previous step's single-event path: its owner may still be
                     // writing order[app_pos] (no barrier since), so take it from registers
                     nq_j = app_j;
@@ -761,21 +805,10 @@ struct Solver {
                     pf_issued = true;
                 }
             }
-            if constexpr (kFastMulti) {
-                // owners of positions hi .. hi+3 publish the columns sitting there
-                if (b0 <= hi + kRecEvents - 1 && b0 + CH - 1 >= hi) {  // our positions overlap the window
+            if (hi >= b0 && hi < b0 + CH && hi < n) {
 #pragma unroll
-                    for (int r = 0; r < CH; ++r) {
-                        const unsigned w = (unsigned)(b0 + r - hi);
-                        if (w < (unsigned)kRecEvents && b0 + r < n) ctrl->a_pub[par][w] = jr[r];
-                    }
-                }
-            } else {
-                if (hi >= b0 && hi < b0 + CH && hi < n) {
-#pragma unroll
-                    for (int r = 0; r < CH; ++r)
-                        if (b0 + r == hi) ctrl->a_pub[par][0] = jr[r];
-                }
+                for (int r = 0; r < CH; ++r)
+                    if (b0 + r == hi) ctrl->a_pub[par][0] = jr[r];
             }
             const double v_head = v[head_j];
             if constexpr (!ROWLDS) {
@@ -838,7 +871,7 @@ struct Solver {
                 }
             }
             const int seen = par ? seen1 : seen0;
-            if (my_events && !kFastMulti) {
+            if (my_events) {
                 // no returning atomic and no LDS read on this path: if this turns out to be the
                 // only event of the step the record is exactly right, otherwise nobody reads it
                 atomicAdd(&ctrl->ev_total[par], my_events);
@@ -858,28 +891,6 @@ struct Solver {
                 sl.p = b0 + ev_r;
                 sl.a = 0;
                 ctrl->rec[par][0] = sl;
-            }
-            if (my_events && kFastMulti) {
-                // arrival slot of our first event (the counter is cumulative: `seen` is what it
-                // held when the step began); the first kRecEvents events of a step leave a record
-                int slot_idx = atomicAdd(&ctrl->ev_total[par], my_events) - seen;
-#pragma unroll
-                for (int r = 0; r < CH; ++r) {
-                    if ((ev_mask >> r) & 1u) {
-                        if (slot_idx < kRecEvents) {
-                            EventSlot sl;
-                            sl.j = jr[r];
-                            if constexpr (CACHE_Y)
-                                sl.i = yr[r];
-                            else
-                                sl.i = y[jr[r]];
-                            sl.p = b0 + r;
-                            sl.a = 0;
-                            ctrl->rec[par][slot_idx] = sl;
-                        }
-                        ++slot_idx;
-                    }
-                }
             }
             STAMPR(tr2);
             STAMP_ADD(2, tr2, tr1);
@@ -961,143 +972,135 @@ struct Solver {
                     head_i = sl.i;
                 }
             } else {
-                STAMP_INC(7);
-                // ---- 2..kRecEvents events (24% of the steps of a uniform instance): still one
-                // barrier.  The serial rule (lapjv.cpp:199-205) takes the events in POSITION order;
-                // event s swaps the column at its position P_s with the one at hi+s.  When no
-                // event sits inside the window [hi, hi+cnt) the swaps are independent: the owner of
-                // P_s moves its column to hi+s and adopts the column published for hi+s.  A free
-                // column among the events ends the path at the first one in position order.
-                bool resolved = false;
-                // (with 8+ positions per thread the extra live values of this path spill: n = 16384
-                // went from 25 s to 55 s per instance with it -- those sizes keep the ordered replay)
-                if (kFastMulti && cnt <= kRecEvents) {
-                    // Every lane reads the same records, so the values below are wave-uniform but
-                    // deliberately kept in VECTOR registers: ranking them on the scalar unit is a
-                    // long dependent chain (and spills SGPRs); only the few results that steer
-                    // control flow are moved to scalars.
-                    const EventSlot e1 = ctrl->rec[par][1];
-                    const EventSlot e2 = ctrl->rec[par][2];
-                    const EventSlot e3 = ctrl->rec[par][3];
-                    const int4 aw = *reinterpret_cast<const int4 *>(ctrl->a_pub[par]);
-                    const int fp = ctrl->free_pos[par];
-                    const int kNone = 0x7fffffff;
-                    const int P0 = sl.p, P1 = e1.p, P2 = (cnt > 2) ? e2.p : kNone, P3 = (cnt > 3) ? e3.p : kNone;
-                    int pmin = (P0 < P1) ? P0 : P1;
-                    pmin = (P2 < pmin) ? P2 : pmin;
-                    pmin = (P3 < pmin) ? P3 : pmin;
-                    unsigned bad = ((unsigned)P0 >= (unsigned)n) | ((unsigned)sl.j >= (unsigned)n) | (sl.i >= n) |
-                                   ((unsigned)P1 >= (unsigned)n) | ((unsigned)e1.j >= (unsigned)n) | (e1.i >= n);
-                    if (cnt > 2) bad |= ((unsigned)P2 >= (unsigned)n) | ((unsigned)e2.j >= (unsigned)n) | (e2.i >= n);
-                    if (cnt > 3) bad |= ((unsigned)P3 >= (unsigned)n) | ((unsigned)e3.j >= (unsigned)n) | (e3.i >= n);
-                    bad |= (hi + cnt > n);
-                    if (uni((int)bad)) {
+                STAMP_INC_UNLESS_MULTI(7);
+                STAMP_EVENTS(cnt);
+                // ---- two or more events (24% of the steps of a uniform instance): two barriers.  The serial
+                // rule (lapjv.cpp:199-205) takes the events in POSITION order; event s swaps the column at its
+                // position P_s with the one at hi+s, and the first event whose column is free ends the path.
+                // The finders set their positions in evb[par] before the barrier, so behind it the bitmap holds
+                // the whole step: a free column ends the path before anything is written; when no event sits
+                // inside the window [hi, hi+cnt) the swaps are independent and every finder does its own, its
+                // rank being the number of event bits below its position; an event inside the window makes
+                // them a dependent chain, which wave 0 replays in order.  The second barrier comes after the
+                // swaps: the bitmap is cleared and order[] read again only behind it.
+                bool parallel = false;
+                if constexpr (kFastMulti) {
+                    // (with 8+ positions per thread the extra live values of this path spill: n = 16384
+                    // went from 25 s to 55 s per instance with it -- those sizes keep the ordered replay)
+                    const int fp = uni(ctrl->free_pos[par]);
+                    if (fp != 0x7fffffff) {
+                        // free_pos[par] is read by every thread in this phase: it is reset behind the barrier
+                        // at the path end, not here.  Nobody writes order[] in a step that ends the path, and
+                        // whatever the swaps of the earlier events would change is never read again.
+                        if ((unsigned)fp >= (unsigned)n) {
+                            err = 8;
+                            break;
+                        }
+                        const int tj = uni(order[fp]);
+                        // our event bits of this step's bitmap copy must not survive the path
+                        if (ev_mask) atomicAnd(&evb[par * Wpad + wordi], ~(ev_mask << shift));
+                        if ((unsigned)tj >= (unsigned)n) {
+                            err = 8;
+                            break;
+                        }
+                        target = tj;
+                        STAMP_CLASS_FREE();
+                        break;
+                    }
+                    // every wave walks the bitmap: lane l holds words l * kWordsPerLane ..., CH * TB <= 4096
+                    // positions are at most 128 words
+                    constexpr int kWordsPerLane = (CH * TB > 32 * kWave) ? 2 : 1;
+                    static_assert(CH * TB <= 32 * kWave * kWordsPerLane, "one wave holds the whole event bitmap");
+                    uint32_t wv[kWordsPerLane];
+                    int nbits = 0;
+#pragma unroll
+                    for (int q = 0; q < kWordsPerLane; ++q) {
+                        const int idx = bc.lane * kWordsPerLane + q;
+                        wv[q] = (idx < W) ? evb[par * Wpad + idx] : 0u;
+                        nbits += __popc(wv[q]);
+                    }
+                    const unsigned long long holders = __ballot(nbits != 0);
+                    // (the same in every wave: the bitmap copy of this step does not change between the
+                    // barrier behind us and the one that follows the swaps or the replay)
+                    if (holders == 0ull || hi + cnt > n) {
                         err = 8;
                         break;
                     }
-                    if (uni(fp) != kNone) {
-                        // the first free column in position order is the target (its finder recorded
-                        // the position); whatever the earlier swaps would change is never read again
-                        int tj = -1;
-                        tj = (P0 == fp) ? sl.j : tj;
-                        tj = (P1 == fp) ? e1.j : tj;
-                        tj = (P2 == fp) ? e2.j : tj;
-                        tj = (P3 == fp) ? e3.j : tj;
-                        tj = uni(tj);
-                        if (tj >= 0) {
-                            // (free_pos[par] is read by every thread in this phase: it is reset
-                            // behind the barrier at the path end, not here)
-                            // our event bits of this step's bitmap copy must not survive the path
-#pragma unroll
-                            for (int r = 0; r < CH; ++r)
-                                if ((ev_mask >> r) & 1u) atomicAnd(&evb[par * Wpad + ((b0 + r) >> 5)], ~(1u << ((b0 + r) & 31)));
-                            target = tj;
-                            break;
+                    const int first_lane = uni(__builtin_ctzll(holders));
+                    int first_pos;
+                    {
+                        const uint32_t f0 = (uint32_t)readlane((int)wv[0], first_lane);
+                        first_pos = first_lane * kWordsPerLane * 32 + __builtin_ctz(f0 | 0x80000000u);
+                        if constexpr (kWordsPerLane == 2) {
+                            const uint32_t f1 = (uint32_t)readlane((int)wv[1], first_lane);
+                            if (f0 == 0u) first_pos = (first_lane * 2 + 1) * 32 + __builtin_ctz(f1 | 0x80000000u);
                         }
-                    } else if (uni(pmin) >= hi + cnt) {
-                        // ranks = position order; entry q goes to SCAN slot hi + rank(q)
-                        const int r0 = (P1 < P0) + (P2 < P0) + (P3 < P0);
-                        const int r1 = (P0 < P1) + (P2 < P1) + (P3 < P1);
-                        const int r2 = (P0 < P2) + (P1 < P2) + (P3 < P2);
-                        const int r3 = (P0 < P3) + (P1 < P3) + (P2 < P3);
-                        int first_j = sl.j, first_i = sl.i, second_j = sl.j, second_i = sl.i;
-                        first_j = (r1 == 0) ? e1.j : first_j, first_i = (r1 == 0) ? e1.i : first_i;
-                        first_j = (r2 == 0) ? e2.j : first_j, first_i = (r2 == 0) ? e2.i : first_i;
-                        first_j = (r3 == 0) ? e3.j : first_j, first_i = (r3 == 0) ? e3.i : first_i;
-                        second_j = (r1 == 1) ? e1.j : second_j, second_i = (r1 == 1) ? e1.i : second_i;
-                        second_j = (r2 == 1) ? e2.j : second_j, second_i = (r2 == 1) ? e2.i : second_i;
-                        second_j = (r3 == 1) ? e3.j : second_j, second_i = (r3 == 1) ? e3.i : second_i;
+                    }
+                    parallel = first_pos >= hi + cnt;  // all events lie at or above hi: none inside the window
+                    if (parallel && __ballot(ev_mask != 0) != 0ull) {
+                        // a wave with a finder ranks its events: bits in the words below + bits below in the word
+                        const int below_lane = wave_incl_prefix_sum_i32(nbits) - nbits;
+                        const int src = wordi / kWordsPerLane;
+                        int below = __shfl(below_lane, src, kWave);
+                        uint32_t myw = (uint32_t)__shfl((int)wv[0], src, kWave);
+                        if constexpr (kWordsPerLane == 2) {
+                            const uint32_t w1 = (uint32_t)__shfl((int)wv[1], src, kWave);
+                            if (wordi & 1) {
+                                below += __popc(myw);
+                                myw = w1;
+                            }
+                        }
                         if (ev_mask) {
-                            // we found one (or more) of these events: our column goes to the SCAN
-                            // list, the column displaced from hi + rank comes to our position
+                            // our column goes to SCAN slot hi + rank, the column sitting there comes to our
+                            // position: slot and position are ours alone (no event inside the window)
 #pragma unroll
                             for (int r = 0; r < CH; ++r) {
                                 if ((ev_mask >> r) & 1u) {
                                     const int pk = b0 + r;
-                                    int rank = r0, jq = sl.j;
-                                    rank = (pk == P1) ? r1 : rank, jq = (pk == P1) ? e1.j : jq;
-                                    rank = (pk == P2) ? r2 : rank, jq = (pk == P2) ? e2.j : jq;
-                                    rank = (pk == P3) ? r3 : rank, jq = (pk == P3) ? e3.j : jq;
-                                    int a = aw.x;
-                                    a = (rank == 1) ? aw.y : a;
-                                    a = (rank == 2) ? aw.z : a;
-                                    a = (rank == 3) ? aw.w : a;
-                                    if ((unsigned)a >= (unsigned)n || (pk != P0 && pk != P1 && pk != P2 && pk != P3)) {
+                                    const int rank = below + __popc(myw & ((1u << (pk & 31)) - 1u));
+                                    if ((unsigned)rank >= (unsigned)cnt) {
                                         ctrl->err = 8;  // (read by all threads at the end of the kernel)
                                     } else {
-                                        jr[r] = a;
-                                        if constexpr (CACHE_V) {
-                                            vr[r] = v[a];
-                                            if constexpr (CACHE_Y) yr[r] = y[a];
+                                        const int a = order[hi + rank];
+                                        if ((unsigned)a >= (unsigned)n) {
+                                            ctrl->err = 8;
+                                        } else {
+                                            const int jq = jr[r];
+                                            jr[r] = a;
+                                            if constexpr (CACHE_V) {
+                                                vr[r] = v[a];
+                                                if constexpr (CACHE_Y) yr[r] = y[a];
+                                            }
+                                            dk[r] = dist[a];
+                                            order[pk] = a;
+                                            order[hi + rank] = jq;
                                         }
-                                        dk[r] = dist[a];
-                                        order[pk] = a;
-                                        order[hi + rank] = jq;
                                     }
-                                    atomicAnd(&evb[par * Wpad + (pk >> 5)], ~(1u << (pk & 31)));
                                 }
                             }
                         }
-                        app_pos = hi;
-                        app_j = uni(first_j);
-                        app_i = uni(first_i);
-                        app_j1 = uni(second_j);
-                        app_i1 = uni(second_i);
-                        app_two = true;
-                        ring_push(app_i);
-                        ring_push(app_i1);
-                        if (cnt > 2) {
-                            int third_i = sl.i, fourth_i = sl.i;
-                            third_i = (r1 == 2) ? e1.i : third_i, third_i = (r2 == 2) ? e2.i : third_i;
-                            third_i = (r3 == 2) ? e3.i : third_i;
-                            fourth_i = (r1 == 3) ? e1.i : fourth_i, fourth_i = (r2 == 3) ? e2.i : fourth_i;
-                            fourth_i = (r3 == 3) ? e3.i : fourth_i;
-                            ring_push(uni(third_i));
-                            if (cnt > 3) ring_push(uni(fourth_i));
-                        }
-                        hi += cnt;
-                        ++lo;
-                        if (queued) {
-                            head_j = uni(nq_j);
-                            head_i = uni(nq_i);
-                        } else {
-                            head_j = app_j;
-                            head_i = app_i;
-                        }
-                        resolved = true;
                     }
                 }
-                if (resolved) {
-                    STAMPR(tr4m);
-                    STAMP_ADD(4, tr4m, tr3);
-                    continue;
-                }
                 const int hi_before = hi;
-                if (bc.wave == 0) replay_scan(hi, par);
-                __syncthreads();
-                hi = uni(ctrl->hi);
-                target = uni(ctrl->target);
-                if (target >= 0) break;
+                if constexpr (kFastMulti) {
+                    if (!parallel && bc.wave == 0) replay_scan<true>(hi, par);
+                    __syncthreads();
+                    // every wave has walked the bitmap, which nobody changed between the two barriers (so
+                    // `parallel` and the early exits above are the same in every wave): the finders take their
+                    // bits out, on either branch
+                    if (ev_mask) atomicAnd(&evb[par * Wpad + wordi], ~(ev_mask << shift));
+                    // (no path ends here: a free column among the events left before the walk)
+                    hi = parallel ? hi + cnt : uni(ctrl->hi);
+                } else {
+                    if (bc.wave == 0) replay_scan(hi, par);
+                    __syncthreads();
+                    hi = uni(ctrl->hi);
+                    target = uni(ctrl->target);
+                    if (target >= 0) {
+                        STAMP_CLASS_FREE();
+                        break;
+                    }
+                }
                 ring_push_scan(hi_before - 1, hi);
                 ++lo;
                 if (queued) {
@@ -1111,8 +1114,9 @@ struct Solver {
                 // TODO positions whose column changed are this step's event positions -- and a
                 // thread knows its own (ev_mask).  Rebinding all CH positions here cost four
                 // gathers per position in 23% of the steps: harmless with the state in LDS,
-                // ruinous with the state in global memory (n > 4,427).
-                if (ev_mask) {
+                // ruinous with the state in global memory (n > 4,427).  (On the parallel path the
+                // finders rebound their positions when they swapped.)
+                if (!parallel && ev_mask) {
 #pragma unroll
                     for (int r = 0; r < CH; ++r) {
                         const int k = b0 + r;
@@ -1126,6 +1130,11 @@ struct Solver {
                             dk[r] = dist[j];
                         }
                     }
+                }
+                if (parallel) {
+                    STAMP_CLASS_SWAPPED();
+                } else {
+                    STAMP_CLASS_REPLAYED(cnt);
                 }
             }
             STAMPR(tr4);

@@ -24,6 +24,39 @@ for _ in range(2):
 torch.cuda.synchronize()
 st = st.cpu().numpy()
 print('ret nonzero:', int((ret != 0).sum()), 'err slots:', st[:,12].tolist()[:8])
+if os.environ.get("DIAG_MULTI"):
+    # `make stamps-multi` build: anatomy of the relax steps with two or more tie events (slot layout: jv_solver.hip)
+    classes = ["finders swapped their own columns", "path ended on a free column",
+               "ordered replay, more than 4 events", "ordered replay, 2-4 events"]
+    for f in ("uniform", "sparse", "clustered"):
+        idx = [b for b in range(B) if fams[b] == f]
+        if not idx:
+            continue
+        raw = st[idx].astype(np.int64)
+        s = raw.astype(np.float64).mean(0)
+        nb = len(idx)
+        relax = s[17] + s[18] + s[19] + s[20]
+        print(f"{f}: kernel {s[13] / 1e5:.1f} ms, paths {s[4]:.0f} finds {s[5]:.0f} steps {s[6]:.0f}; relax steps stamped "
+              f"{relax / 1e6:.1f} Mcycles (issue {s[17] / s[6]:.0f} + compute {s[18] / s[6]:.0f} + barrier {s[19] / s[6]:.0f} "
+              f"+ post {s[20] / s[6]:.0f} cycles each), n cnt0 {s[21]:.0f} n cnt1 {s[22]:.0f}")
+        kernel_cyc = s[13] * 1e-8 * 2.1e9  # 10 ns ticks at the 2.1 GHz-equivalent of the stamp clock
+        ac = 0.0
+        for c, nm in enumerate(classes):
+            packed = raw[:, 16 + 8 + 2 * c]
+            cnt = (packed >> 40).sum() / nb
+            post = (packed & ((1 << 40) - 1)).sum() / nb
+            bar = s[16 + 9 + 2 * c]
+            whole = post + bar + cnt * (s[17] + s[18]) / s[6]
+            if c != 1:
+                ac += whole
+            print(f"   {nm:42s} {cnt:8.0f} steps  post {post / max(cnt, 1):7.0f}  barrier wait {bar / max(cnt, 1):7.0f} cycles each; "
+                  f"post {100 * post / kernel_cyc:5.1f} %, whole steps {100 * whole / kernel_cyc:5.1f} % of the kernel")
+        print(f"   classes (a) + (c), whole steps: {100 * ac / kernel_cyc:5.1f} % of the kernel")
+        h0, h1 = raw[:, 16 + 0], raw[:, 16 + 7]
+        m21 = (1 << 21) - 1
+        hist = [(h0 & m21).sum(), ((h0 >> 21) & m21).sum(), ((h0 >> 42) & m21).sum(), (h1 & 0xffffffff).sum(), (h1 >> 32).sum()]
+        print("   events per step   " + "   ".join(f"{nm}: {v / nb:.0f}" for nm, v in zip(("2", "3", "4", "5-8", "9+"), hist)))
+    sys.exit(0)
 names = ["find", "relax:issue loads", "relax:wait+compute+publish", "relax:barrier", "relax:post", "n cnt0", "n cnt1", "n slow", "path end"]
 for f in ("uniform", "sparse", "clustered"):
     idx = [b for b in range(B) if fams[b] == f]
