@@ -15,7 +15,17 @@
 // 173 VGPRs, no scratch, 83 200 B of LDS: one workgroup per compute unit, two waves per SIMD.
 //
 // dual_attention_kernel: one workgroup per (16 queries, head, direction, instance), two passes over the keys
-// (maximum, then exp / sum / weighted values), fp32, sums in a fixed order: equal inputs give equal bits.
+// (maximum, then exp / sum / weighted values), fp32, sums in a fixed order: equal inputs give equal bits.  With the
+// two statistics pointers set it also leaves every query's maximum and sum for the backward.
+//
+// The backward ("DualGNN backward"), no atomics anywhere, no kernel with scratch:
+//   dual_attention_bwd_query_kernel  90 VGPRs, 49 664 B LDS, 3 waves/SIMD   dS, da, fp64 partials of dkb
+//   dual_attention_bwd_key_kernel    88 VGPRs, 41 088 B LDS, 3 waves/SIMD   dc, dval
+//   dual_attention_bwd_kbias_kernel  the partials in order, fp64
+//   dual_edge_backward_kernel        224 VGPRs, 83 200 B LDS (through es_raise_lds), 2 waves/SIMD: the recompute
+//                                    of a chunk of edges and the way back through it, rows into the workspace
+//   dual_edge_wgrad_kernel           62 VGPRs, no LDS, 8 waves/SIMD: the five sums over edges as TN MFMA products
+//   dual_edge_wgrad_reduce_kernel    workgroups and chunks in order, fp64, rounded once
 #include "dual_gnn.hpp"
 
 #include <atomic>
@@ -219,11 +229,14 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_kernel(DualAttnPara
     }
     const unsigned char *mask = (p.mask && !p.sizes) ? p.mask + (size_t)b * N : nullptr;
     const int cq = tid >> 4, slot = tid & 15;
+    float *stats = dir ? p.col_stats : p.row_stats;  // the training forward keeps every query's maximum and sum
+    if (stats) stats += ((size_t)b * p.heads + h) * N * 2;
     if (q0 >= nb) {  // a block of padded queries (workgroup-uniform): zero messages, no key is read
         for (int idx = tid; idx < kTQ * D; idx += kAtThreads) {
             const int q = q0 + idx / D;
             if (q < N) msg[(size_t)q * hidden + idx % D] = 0.0f;
         }
+        if (stats && tid < 2 * kTQ && q0 + (tid >> 1) < N) stats[(size_t)q0 * 2 + tid] = 0.0f;
         return;
     }
     const float kb = p.kbias[dir * p.heads + h];
@@ -291,7 +304,514 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_kernel(DualAttnPara
                 const int d = slot + 16 * r;
                 if (d < dlen) msg[(size_t)q * hidden + d0 + d] = sum > 0.0f ? acc[r] / sum : 0.0f;
             }
+            if (stats && d0 == 0 && slot == 0) {  // a masked query: (-inf, 0), which the backward never uses
+                stats[(size_t)q * 2] = s_max[cq];
+                stats[(size_t)q * 2 + 1] = sum;
+            }
         }
+    }
+}
+
+// ---- the backward of the attention -----------------------------------------------------------------------------
+// With z = ((a[q] + c[k]) + S) + kb, s = leaky_relu(z), w = exp(s - max_q) / sum_q from the forward's statistics:
+//   dz[q,k] = w (dw[q,k] - delta[q]) (z >= 0 ? 1 : 0.2), dw = dmsg[q] . val[k], delta = dmsg[q] . msg[q] formed as
+//   sum_k w dw (a first pass over the keys that also parks dw in dS); exactly 0 on a masked pair.
+// Every sum runs in a fixed order in fp32 (the parts of dkb in fp64); there is no atomic.
+
+struct AtBwdView {  // what both passes take from the parameters for their (b, dir, h)
+    const float *sc, *a, *c, *val, *msg, *dmsg, *stats;
+    const unsigned char *mask;
+    float kb;
+    int nb;
+};
+
+__device__ __forceinline__ AtBwdView at_bwd_view(const DualAttnBwdParams &p, int b, int dir, int h)
+{
+    const DualAttnParams &f = p.fwd;
+    const int N = f.n, D = f.head_dim, hidden = f.heads * D;
+    const size_t NN = (size_t)N * N, bh = (size_t)b * f.heads + h, node = (size_t)b * N * hidden + (size_t)h * D;
+    AtBwdView v;
+    v.sc = f.scores + (((size_t)b * 2 + dir) * f.heads + h) * NN;
+    v.a = (dir ? f.a_col : f.a_row) + bh * N;
+    v.c = (dir ? f.c_col : f.c_row) + bh * N;
+    v.val = (dir ? f.row_val : f.col_val) + node;
+    v.msg = (dir ? f.col_msg : f.row_msg) + node;
+    v.dmsg = (dir ? p.d_col_msg : p.d_row_msg) + node;
+    v.stats = (dir ? f.col_stats : f.row_stats) + bh * N * 2;
+    v.nb = N;
+    if (f.sizes) {
+        const int nb = f.sizes[b];
+        v.nb = (nb >= 1 && nb <= N) ? nb : 0;
+    }
+    v.mask = (f.mask && !f.sizes) ? f.mask + (size_t)b * N : nullptr;
+    v.kb = f.kbias[dir * f.heads + h];
+    return v;
+}
+
+constexpr int kBwVStride = kDChunk + 1;  // a thread reads the rows slot + 16 r of one column: odd stride, no conflict
+
+// Query-major: one workgroup per (16 queries, head, direction, instance) walks the key tiles; dS, da and the
+// workgroup's part of dkb.  The tile of z is loaded, and the tile of dz stored, along the contiguous index of the
+// scores as the forward's load_tile does; thread (cq, slot) owns the keys slot + 16 r of query cq in between.
+__global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_query_kernel(DualAttnBwdParams p)
+{
+    __shared__ float s_z[kTQ][kTK + 1];
+    __shared__ float s_v[kTK][kBwVStride];
+    __shared__ float s_dm[kTQ][kDChunk];
+    __shared__ float s_g[kTQ][kTK + 1];
+    __shared__ double s_dk[kTQ];
+    const int tid = threadIdx.x;
+    const int dir = blockIdx.z & 1, b = blockIdx.z >> 1, h = blockIdx.y;
+    const int q0 = blockIdx.x * kTQ;
+    const int N = p.fwd.n, D = p.fwd.head_dim, heads = p.fwd.heads, hidden = heads * D;
+    const AtBwdView v = at_bwd_view(p, b, dir, h);
+    const int nb = v.nb;
+    float *dS = p.dS + (((size_t)b * 2 + dir) * heads + h) * (size_t)N * N;
+    float *da = (dir ? p.da_col : p.da_row) + ((size_t)b * heads + h) * N;
+    double *part = p.partials + ((size_t)blockIdx.z * heads + h) * gridDim.x + blockIdx.x;
+    const int cq = tid >> 4, slot = tid & 15;
+    if (q0 >= nb) {  // padded queries: zero gradients, no score and no dS entry is touched
+        if (tid < kTQ && q0 + tid < N) da[q0 + tid] = 0.0f;
+        if (tid == 0) *part = 0.0;
+        return;
+    }
+    const int q = q0 + cq;
+    const bool live = q < nb && (!v.mask || v.mask[q]);
+    float mq = 0.0f, sq = 1.0f;
+    if (live) {
+        mq = v.stats[(size_t)q * 2];
+        sq = v.stats[(size_t)q * 2 + 1];
+    }
+    // the tile of z (and of what dS holds at the same places) in the load_tile mapping of the forward; a thread
+    // loads and stores the same places in both passes, so its own program order is all the passes need
+    auto load_z = [&](int k0, bool with_dw) {
+#pragma unroll
+        for (int r = 0; r < (kTQ * kTK) / kAtThreads; ++r) {
+            const int lq = dir ? (tid & 15) : ((tid >> 6) + 4 * r);
+            const int lk = dir ? ((tid >> 4) + 16 * r) : (tid & 63);
+            const int qq = q0 + lq, k = k0 + lk;
+            float z = at_neg_inf(), g = 0.0f;
+            if (qq < nb && k < nb && (!v.mask || (v.mask[qq] && v.mask[k]))) {
+                const size_t at = dir ? (size_t)k * N + qq : (size_t)qq * N + k;
+                z = ((v.a[qq] + v.c[k]) + v.sc[at]) + v.kb;
+                if (with_dw) g = dS[at];
+            }
+            s_z[lq][lk] = z;
+            if (with_dw) s_g[lq][lk] = g;
+        }
+    };
+    auto store_tile = [&](int k0) {  // s_z -> dS, inside the prefix (the whole matrix without sizes)
+#pragma unroll
+        for (int r = 0; r < (kTQ * kTK) / kAtThreads; ++r) {
+            const int lq = dir ? (tid & 15) : ((tid >> 6) + 4 * r);
+            const int lk = dir ? ((tid >> 4) + 16 * r) : (tid & 63);
+            const int qq = q0 + lq, k = k0 + lk;
+            if (qq < nb && k < nb) dS[dir ? (size_t)k * N + qq : (size_t)qq * N + k] = s_z[lq][lk];
+        }
+    };
+
+    // pass 1: dw[q,k] = dmsg[q] . val[k] into dS, and delta[q] = sum_k w dw.  That is dmsg[q] . msg[q], formed from
+    // the numbers dz subtracts it from: the rounding of delta then cancels in sum_k dz as it does in exact
+    // arithmetic, and one key gives exactly 0.
+    float delta = 0.0f;
+    for (int k0 = 0; k0 < nb; k0 += kTK) {
+        load_z(k0, false);
+        float dw[kTK / 16];
+#pragma unroll
+        for (int r = 0; r < kTK / 16; ++r) dw[r] = 0.0f;
+        for (int d0 = 0; d0 < D; d0 += kDChunk) {
+            const int dlen = (D - d0) < kDChunk ? (D - d0) : kDChunk;
+            for (int idx = tid; idx < kTK * dlen; idx += kAtThreads) {
+                const int k = idx / dlen, d = idx - k * dlen;
+                s_v[k][d] = (k0 + k < nb) ? v.val[(size_t)(k0 + k) * hidden + d0 + d] : 0.0f;
+            }
+            for (int idx = tid; idx < kTQ * dlen; idx += kAtThreads) {
+                const int lq = idx / dlen, d = idx - lq * dlen;
+                s_dm[lq][d] = (q0 + lq < nb) ? v.dmsg[(size_t)(q0 + lq) * hidden + d0 + d] : 0.0f;
+            }
+            __syncthreads();
+            for (int d = 0; d < dlen; ++d) {
+                const float x = s_dm[cq][d];
+#pragma unroll
+                for (int r = 0; r < kTK / 16; ++r) dw[r] += x * s_v[slot + 16 * r][d];
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int r = 0; r < kTK / 16; ++r) {
+            const int k = slot + 16 * r;
+            const float z = s_z[cq][k];
+            if (z != at_neg_inf()) {
+                const float s = z >= 0.0f ? z : 0.2f * z;
+                delta += (expf(s - mq) / sq) * dw[r];
+            }
+            s_z[cq][k] = dw[r];
+        }
+        __syncthreads();
+        store_tile(k0);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) delta += __shfl_xor(delta, off, 16);
+
+    // pass 2: dz from z, the statistics and the stored dw
+    float da_acc = 0.0f;
+    double dk_acc = 0.0;  // the workgroup's part of dkb: a sum that cancels, kept in fp64 from the first term
+    for (int k0 = 0; k0 < nb; k0 += kTK) {
+        load_z(k0, true);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < kTK / 16; ++r) {
+            const int k = slot + 16 * r;
+            const float z = s_z[cq][k];
+            float dz = 0.0f;
+            if (z != at_neg_inf()) {
+                const float s = z >= 0.0f ? z : 0.2f * z;
+                const float w = expf(s - mq) / sq;
+                dz = (w * (s_g[cq][k] - delta)) * (z >= 0.0f ? 1.0f : 0.2f);
+            }
+            s_z[cq][k] = dz;
+            da_acc += dz;
+            dk_acc += (double)dz;
+        }
+        __syncthreads();
+        store_tile(k0);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) {
+        da_acc += __shfl_xor(da_acc, off, 16);
+        dk_acc += __shfl_xor(dk_acc, off, 16);
+    }
+    if (slot == 0) {
+        if (q < N) da[q] = da_acc;
+        s_dk[cq] = dk_acc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (int i = 0; i < kTQ; ++i) t += s_dk[i];
+        *part = t;
+    }
+}
+
+// Key-major: one workgroup per (16 keys, head, direction, instance) walks the query tiles, the forward with the
+// roles swapped: dc[k] = sum_q dS[q,k] (read back) and dval[k] = sum_q w[q,k] dmsg[q] with w recomputed.
+__global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_key_kernel(DualAttnBwdParams p)
+{
+    __shared__ float s_w[kTQ][kTK + 1];   // [key][query]
+    __shared__ float s_g[kTQ][kTK + 1];
+    __shared__ float s_dm[kTK][kDChunk];
+    const int tid = threadIdx.x;
+    const int dir = blockIdx.z & 1, b = blockIdx.z >> 1, h = blockIdx.y;
+    const int kk0 = blockIdx.x * kTQ;
+    const int N = p.fwd.n, D = p.fwd.head_dim, heads = p.fwd.heads, hidden = heads * D;
+    const AtBwdView v = at_bwd_view(p, b, dir, h);
+    const int nb = v.nb;
+    const float *dS = p.dS + (((size_t)b * 2 + dir) * heads + h) * (size_t)N * N;
+    float *dc = (dir ? p.dc_col : p.dc_row) + ((size_t)b * heads + h) * N;
+    float *dval = (dir ? p.d_row_val : p.d_col_val) + (size_t)b * N * hidden + (size_t)h * D;
+    const int ck = tid >> 4, slot = tid & 15;
+    if (kk0 >= nb) {  // padded keys
+        for (int idx = tid; idx < kTQ * D; idx += kAtThreads) {
+            const int k = kk0 + idx / D;
+            if (k < N) dval[(size_t)k * hidden + idx % D] = 0.0f;
+        }
+        if (tid < kTQ && kk0 + tid < N) dc[kk0 + tid] = 0.0f;
+        return;
+    }
+    for (int d0 = 0; d0 < D; d0 += kDChunk) {
+        const int dlen = (D - d0) < kDChunk ? (D - d0) : kDChunk;
+        float acc[kDChunk / 16];
+#pragma unroll
+        for (int r = 0; r < kDChunk / 16; ++r) acc[r] = 0.0f;
+        float dcs = 0.0f;
+        for (int q0 = 0; q0 < nb; q0 += kTK) {
+#pragma unroll
+            for (int r = 0; r < (kTQ * kTK) / kAtThreads; ++r) {
+                const int lk = dir ? ((tid >> 6) + 4 * r) : (tid & 15);
+                const int lq = dir ? (tid & 63) : ((tid >> 4) + 16 * r);
+                const int q = q0 + lq, k = kk0 + lk;
+                float w = 0.0f, g = 0.0f;
+                if (q < nb && k < nb && (!v.mask || (v.mask[q] && v.mask[k]))) {
+                    const size_t at = dir ? (size_t)k * N + q : (size_t)q * N + k;
+                    const float z = ((v.a[q] + v.c[k]) + v.sc[at]) + v.kb;
+                    const float s = z >= 0.0f ? z : 0.2f * z;
+                    w = expf(s - v.stats[(size_t)q * 2]) / v.stats[(size_t)q * 2 + 1];
+                    g = dS[at];
+                }
+                s_w[lk][lq] = w;
+                s_g[lk][lq] = g;
+            }
+            for (int idx = tid; idx < kTK * dlen; idx += kAtThreads) {
+                const int lq = idx / dlen, d = idx - lq * dlen;
+                s_dm[lq][d] = (q0 + lq < nb) ? v.dmsg[(size_t)(q0 + lq) * hidden + d0 + d] : 0.0f;
+            }
+            __syncthreads();
+            for (int lq = 0; lq < kTK; ++lq) {
+                const float w = s_w[ck][lq];
+                dcs += s_g[ck][lq];
+#pragma unroll
+                for (int r = 0; r < kDChunk / 16; ++r) {
+                    const int d = slot + 16 * r;
+                    if (d < dlen) acc[r] += w * s_dm[lq][d];
+                }
+            }
+            __syncthreads();
+        }
+        const int k = kk0 + ck;
+        if (k < N) {
+#pragma unroll
+            for (int r = 0; r < kDChunk / 16; ++r) {
+                const int d = slot + 16 * r;
+                if (d < dlen) dval[(size_t)k * hidden + d0 + d] = acc[r];
+            }
+            if (d0 == 0 && slot == 0) dc[k] = dcs;
+        }
+    }
+}
+
+// dkb[dir][h]: the partials of the query-major workgroups, (instance, tile) in order, in fp64; one workgroup each
+__global__ void __launch_bounds__(kAtThreads)
+dual_attention_bwd_kbias_kernel(const double *partials, float *dkb, int batch, int heads, int tiles)
+{
+    __shared__ double s_sum[kAtThreads];
+    const int dir = blockIdx.x / heads, h = blockIdx.x - dir * heads;
+    const long long count = (long long)batch * tiles;
+    double t = 0.0;
+    for (long long i = threadIdx.x; i < count; i += kAtThreads) {
+        const long long b = i / tiles, x = i - b * tiles;
+        t += partials[((size_t)(2 * b + dir) * heads + h) * tiles + x];
+    }
+    s_sum[threadIdx.x] = t;
+    __syncthreads();
+    for (int half = kAtThreads / 2; half >= 1; half >>= 1) {
+        if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) dkb[blockIdx.x] = (float)s_sum[0];
+}
+
+// ---- the backward of the edge scores ---------------------------------------------------------------------------
+// Stage 1 (dual_edge_backward_kernel) recomputes a wave tile of 16 edges in the forward's transposed layout and
+// goes back through it: dh2 = G^T dS and dh1 = W2^T dh2pre are MFMA products whose A operand reads the staged G
+// and W2 column-wise (Gs[(4 s + g) * stride + 16 m + col], W2s[(16 m + 4 g + r) * stride + 16 t + col]; the lane
+// groups fall on disjoint banks) and whose B operand is already in registers.  The loop over m is the k loop of
+// dh1, so it stays rolled with the eight accumulators of dh1 live.  Each edge leaves one row of kRowFloats floats in
+// the workspace: h1, h2, dh2pre, dh1pre (128 each), dS (16, zero past 2 * heads) and the features (16: ten
+// channels, a one in column 10, zeros); a lane without an edge leaves zeros where a product's A operand reads.
+// Stage 2 (dual_edge_wgrad_kernel): out[o][k] = sum_e X[e][o] Y[e][k] on the same instruction, both fragments read
+// along the contiguous unit index of the rows.  A workgroup owns a slice of the chunk's rows, wave w the tiles:
+// dW2 row block w (8 tiles), dG column block w, dW1 row block w, and dh2pre^T F row block w, whose column 10 is
+// db2 as column 10 of dW1's tile is db1.  Stage 3 sums the workgroups' partials in fp64 in order, adds the chunk
+// to the running fp64 sums and, after the last chunk, rounds once.
+// VGPRs / LDS / scratch: see the header of this file.
+
+constexpr int kRowFloats = 4 * kHid + 2 * kOutPad;
+constexpr int kRowH1 = 0, kRowH2 = kHid, kRowDh2 = 2 * kHid, kRowDh1 = 3 * kHid, kRowDs = 4 * kHid;
+constexpr int kRowF = 4 * kHid + kOutPad;
+constexpr int kOnesCol = kDualEdgeIn;          // the column of ones in the padded features
+constexpr int kWgTiles = 88;                   // 64 of dW2, 8 of dG, 8 of dW1 | db1, 8 of db2
+constexpr int kWgOut = kWgTiles * 256;
+constexpr int kWgMaxBlocks = 128;
+constexpr int kWgMinRows = 64;
+
+__device__ __forceinline__ float gelu_grad(float x)
+{
+    const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
+    const float pdf = expf(-0.5f * x * x) * 0.39894228040143267794f;
+    return cdf + x * pdf;
+}
+
+// One wave tile.  f: the features of the lane's edge or null; ds: dS of the lane's edge for the outputs 4 s + g
+// (zeros for a lane without an edge and past 2 * heads); row: the lane's workspace row.
+__device__ __forceinline__ void eb_wave_tile(const EsWeights &w, const float *f, const float (&ds)[4], float *row,
+                                             int col, int g)
+{
+    float fb[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int k = 4 * s + g;
+        fb[s] = (f && k < kDualEdgeIn) ? f[k] : 0.0f;
+    }
+    f32x4 h1[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * m + 4 * g]);
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.W1s[(16 * m + col) * kKPad + 4 * s + g], fb[s], acc, 0, 0, 0);
+        h1[m] = gelu4(acc);
+        *reinterpret_cast<f32x4 *>(&row[kRowH1 + 16 * m + 4 * g]) = h1[m];
+    }
+    f32x4 dh1[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) dh1[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+    for (int m = 0; m < 8; ++m) {
+        f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b2s[16 * m + 4 * g]);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(&w.W2s[(16 * m + col) * kWStride + 16 * t + 4 * g]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], h1[t][r], acc, 0, 0, 0);
+        }
+        *reinterpret_cast<f32x4 *>(&row[kRowH2 + 16 * m + 4 * g]) = gelu4(acc);
+        f32x4 d = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(w.Gs[(4 * s + g) * kWStride + 16 * m + col], ds[s], d, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d[r] = d[r] * gelu_grad(acc[r]);
+        *reinterpret_cast<f32x4 *>(&row[kRowDh2 + 16 * m + 4 * g]) = d;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float *wr = &w.W2s[(16 * m + 4 * g + r) * kWStride + col];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) dh1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[16 * t], d[r], dh1[t], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {  // the first layer's pre-activation once more: three products, no register kept
+        f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * t + 4 * g]);
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.W1s[(16 * t + col) * kKPad + 4 * s + g], fb[s], acc, 0, 0, 0);
+        f32x4 d;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d[r] = dh1[t][r] * gelu_grad(acc[r]);
+        *reinterpret_cast<f32x4 *>(&row[kRowDh1 + 16 * t + 4 * g]) = d;
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int k = 4 * s + g;
+        row[kRowDs + k] = ds[s];
+        row[kRowF + k] = s < 3 ? (k == kOnesCol ? (f ? 1.0f : 0.0f) : fb[s]) : 0.0f;
+    }
+}
+
+// The wave tiles [t0, t1) of the batch: numbered 16 edges at a time in the linear edge order (sizes null) or as
+// dual_edge_scores_ragged_kernel numbers them.  Wave tile t writes the rows 16 (t - t0) .. + 15.
+__global__ void __launch_bounds__(kEsThreads)
+dual_edge_backward_kernel(const float *F, const float *W1, const float *b1, const float *W2, const float *b2,
+                          const float *G, const float *dS, const int *sizes, int batch, int N, int heads,
+                          long long t0, long long t1, float *rows)
+{
+    const int outs = 2 * heads;
+    const EsWeights w = es_stage_weights(W1, b1, W2, b2, G, outs);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15, g = lane >> 4;
+    const long long stride = (long long)gridDim.x * kEsWaves;
+    const size_t NN = (size_t)N * N;
+    long long next = t0 + (long long)blockIdx.x * kEsWaves + wave;
+    // at: the edge's offset inside its instance's [n][n] plane, or -1
+    auto tile = [&](long long t, int b, long long at) {
+        float ds[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int o = 4 * s + g;
+            ds[s] = (at >= 0 && o < outs) ? dS[((size_t)b * outs + o) * NN + (size_t)at] : 0.0f;
+        }
+        float *row = rows + ((size_t)(t - t0) * kEsEdgesPerWave + col) * kRowFloats;
+        eb_wave_tile(w, at >= 0 ? F + ((size_t)b * NN + (size_t)at) * kDualEdgeIn : nullptr, ds, row, col, g);
+    };
+    if (!sizes) {
+        const long long E = (long long)NN * batch;
+        for (; next < t1; next += stride) {
+            const long long e = next * kEsEdgesPerWave + col;
+            const long long b = e / (long long)NN;
+            tile(next, (int)b, e < E ? e - b * (long long)NN : -1);
+        }
+        return;
+    }
+    long long first = 0;
+    for (int b = 0; b < batch && first < t1; ++b) {
+        int n = sizes[b];
+        n = (n >= 1 && n <= N) ? n : 0;
+        const int groups = (n + kEsEdgesPerWave - 1) / kEsEdgesPerWave;
+        const long long count = (long long)n * groups;
+        const long long end = first + count < t1 ? first + count : t1;
+        for (; next < end; next += stride) {
+            const int t = (int)(next - first);
+            const int i = t / groups, j = (t - i * groups) * kEsEdgesPerWave + col;
+            tile(next, b, j < n ? (long long)i * N + j : -1);
+        }
+        first += count;
+    }
+}
+
+// rows of the chunk [t0, t1) that stage 1 wrote: all of them, or up to the last wave tile the sizes give
+__device__ __forceinline__ long long eb_chunk_rows(const int *sizes, int batch, int N, long long t0, long long t1)
+{
+    if (sizes) {
+        long long total = 0;
+        for (int b = 0; b < batch; ++b) {
+            int n = sizes[b];
+            n = (n >= 1 && n <= N) ? n : 0;
+            total += (long long)n * ((n + kEsEdgesPerWave - 1) / kEsEdgesPerWave);
+        }
+        t1 = total < t1 ? total : t1;
+    }
+    return t1 > t0 ? (t1 - t0) * kEsEdgesPerWave : 0;
+}
+
+__global__ void __launch_bounds__(kEsThreads)
+dual_edge_wgrad_kernel(const float *rows, const int *sizes, int batch, int N, long long t0, long long t1, int per,
+                       float *partials)
+{
+    const long long nrows = eb_chunk_rows(sizes, batch, N, t0, t1);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15, g = lane >> 4;
+    const long long begin = (long long)blockIdx.x * per;
+    const long long end = begin + per < nrows ? begin + per : nrows;  // per and nrows are multiples of 16
+    f32x4 acc[11];
+#pragma unroll
+    for (int j = 0; j < 11; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (long long e = begin; e < end; e += 4) {
+        const float *row = rows + (size_t)(e + g) * kRowFloats;
+        const float a2 = row[kRowDh2 + 16 * wave + col], a1 = row[kRowDh1 + 16 * wave + col];
+        const float as = row[kRowDs + col], bf = row[kRowF + col], bh = row[kRowH2 + 16 * wave + col];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, row[kRowH1 + 16 * j + col], acc[j], 0, 0, 0);
+        acc[8] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bh, acc[8], 0, 0, 0);
+        acc[9] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bf, acc[9], 0, 0, 0);
+        acc[10] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, bf, acc[10], 0, 0, 0);
+    }
+    float *out = partials + (size_t)blockIdx.x * kWgOut;
+#pragma unroll
+    for (int j = 0; j < 11; ++j) {
+        const int tile = j < 8 ? 8 * wave + j : 64 + 8 * (j - 8) + wave;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[tile * 256 + (4 * g + r) * 16 + col] = acc[j][r];
+    }
+}
+
+// output idx of the partials = tile * 256 + row * 16 + column of the tile
+__global__ void __launch_bounds__(256)
+dual_edge_wgrad_reduce_kernel(const float *partials, int blocks, double *sums, int first, int last, float *dW1,
+                              float *db1, float *dW2, float *db2, float *dG, int outs)
+{
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    double t = 0.0;
+    for (int k = 0; k < blocks; ++k) t += (double)partials[(size_t)k * kWgOut + idx];
+    if (!first) t += sums[idx];
+    sums[idx] = t;
+    if (!last) return;
+    const float v = (float)t;
+    const int tile = idx >> 8, r = (idx >> 4) & 15, c = idx & 15;
+    if (tile < 64) {
+        dW2[(16 * (tile >> 3) + r) * kHid + 16 * (tile & 7) + c] = v;
+    } else if (tile < 72) {
+        if (r < outs) dG[r * kHid + 16 * (tile - 64) + c] = v;
+    } else if (tile < 80) {
+        const int o = 16 * (tile - 72) + r;
+        if (c < kDualEdgeIn) dW1[o * kDualEdgeIn + c] = v;
+        if (c == kOnesCol) db1[o] = v;
+    } else if (c == kOnesCol) {
+        db2[16 * (tile - 80) + r] = v;
     }
 }
 
@@ -352,6 +872,90 @@ hipError_t launch_dual_attention(const DualAttnParams &p, hipStream_t stream)
     const dim3 grid((p.n + kTQ - 1) / kTQ, p.heads, 2 * p.batch);
     hipLaunchKernelGGL(dual_attention_kernel, grid, dim3(kAtThreads), 0, stream, p);
     return hipGetLastError();
+}
+
+namespace {
+
+// The edge backward's workspace: the chunk's rows, the workgroups' partials, the running fp64 sums.  It depends on
+// (batch, n) only through the padded batch's wave tiles, so the uniform and the ragged call share it.
+struct EdgeBwdLayout {
+    long long tiles;   // wave tiles of the padded batch in the ragged numbering (not fewer than the uniform one's)
+    long long rows;    // rows of the largest chunk
+    int per, blocks;   // rows per workgroup of stage 2 and its grid for a full chunk
+    size_t partials_at, sums_at, bytes;
+};
+
+EdgeBwdLayout edge_bwd_layout(int batch, int n)
+{
+    EdgeBwdLayout l;
+    l.tiles = (long long)batch * n * ((n + kEsEdgesPerWave - 1) / kEsEdgesPerWave);
+    const long long all = l.tiles * kEsEdgesPerWave;
+    l.rows = all < kDualBwdChunk ? all : kDualBwdChunk;
+    long long per = (l.rows + kWgMaxBlocks - 1) / kWgMaxBlocks;
+    per = (per + 15) / 16 * 16;
+    l.per = (int)(per < kWgMinRows ? kWgMinRows : per);
+    l.blocks = (int)((l.rows + l.per - 1) / l.per);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    l.partials_at = up((size_t)l.rows * kRowFloats * sizeof(float));
+    l.sums_at = l.partials_at + up((size_t)l.blocks * kWgOut * sizeof(float));
+    l.bytes = l.sums_at + up((size_t)kWgOut * sizeof(double));
+    return l;
+}
+
+}  // namespace
+
+size_t dual_backward_workspace_bytes(int batch, int n, int heads)
+{
+    if (dual_gnn_workspace_bytes(batch, n, heads) == 0) return 0;
+    const size_t attn = ((size_t)2 * batch * heads * ((n + kTQ - 1) / kTQ) * sizeof(double) + 255) & ~(size_t)255;
+    const size_t edge = edge_bwd_layout(batch, n).bytes;
+    return attn > edge ? attn : edge;
+}
+
+hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_t stream)
+{
+    const DualAttnParams &f = p.fwd;
+    const int tiles = (f.n + kTQ - 1) / kTQ;
+    const dim3 grid(tiles, f.heads, 2 * f.batch);
+    hipLaunchKernelGGL(dual_attention_bwd_query_kernel, grid, dim3(kAtThreads), 0, stream, p);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(dual_attention_bwd_key_kernel, grid, dim3(kAtThreads), 0, stream, p);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(dual_attention_bwd_kbias_kernel, dim3(2 * f.heads), dim3(kAtThreads), 0, stream, p.partials,
+                       p.dkb, f.batch, f.heads, tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                            const float *b2, const float *G, const float *dS, const int *sizes,
+                                            float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch,
+                                            int n, int heads, void *workspace, hipStream_t stream)
+{
+    const EdgeBwdLayout l = edge_bwd_layout(batch, n);
+    const long long E = (long long)batch * n * n;
+    const long long tiles = sizes ? l.tiles : (E + kEsEdgesPerWave - 1) / kEsEdgesPerWave;
+    const long long chunk = kDualBwdChunk / kEsEdgesPerWave;
+    float *rows = static_cast<float *>(workspace);
+    float *partials = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + l.partials_at);
+    double *sums = reinterpret_cast<double *>(static_cast<unsigned char *>(workspace) + l.sums_at);
+    static std::atomic<bool> raised{false};
+    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(dual_edge_backward_kernel), raised)) return e;
+    for (long long t0 = 0; t0 < tiles; t0 += chunk) {
+        const long long t1 = t0 + chunk < tiles ? t0 + chunk : tiles;
+        const long long wgs = (t1 - t0 + kEsWaves - 1) / kEsWaves;
+        const int blocks = (int)(wgs < kEsMaxBlocks ? wgs : kEsMaxBlocks);
+        hipLaunchKernelGGL(dual_edge_backward_kernel, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream, edge_feat,
+                           W1, b1, W2, b2, G, dS, sizes, batch, n, heads, t0, t1, rows);
+        if (hipError_t e = hipGetLastError()) return e;
+        const int wg = (int)(((t1 - t0) * kEsEdgesPerWave + l.per - 1) / l.per);
+        hipLaunchKernelGGL(dual_edge_wgrad_kernel, dim3(wg), dim3(kEsThreads), 0, stream, rows, sizes, batch, n, t0, t1,
+                           l.per, partials);
+        if (hipError_t e = hipGetLastError()) return e;
+        hipLaunchKernelGGL(dual_edge_wgrad_reduce_kernel, dim3(kWgOut / 256), dim3(256), 0, stream, partials, wg, sums,
+                           t0 == 0 ? 1 : 0, t1 == tiles ? 1 : 0, dW1, db1, dW2, db2, dG, 2 * heads);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace lapwarm

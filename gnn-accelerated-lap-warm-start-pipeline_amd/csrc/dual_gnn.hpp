@@ -30,7 +30,26 @@ struct DualAttnParams {
     // tile that holds a key of the prefix, and no score outside the prefix is loaded.  The messages are, bit for bit,
     // those of the prefix mask: a masked key adds +0 to both sums.
     const int *sizes = nullptr;
+    // [batch][heads][n][2] or null: the maximum and the sum of exp(s - max) of every query's softmax, for the
+    // backward.  Null pointers leave the kernel's arithmetic and every message bit as they are.
+    float *row_stats = nullptr, *col_stats = nullptr;
 };
+
+// The backward of the attention (dual_gnn.hip): fwd holds the forward's inputs, its messages and its statistics
+// (all read); partials is workspace of 2 * batch * heads * ceil(n / 16) doubles.
+struct DualAttnBwdParams {
+    DualAttnParams fwd;
+    const float *d_row_msg, *d_col_msg;          // [batch][n][heads * head_dim]
+    float *dS;                                   // [batch][2][heads][n][n], the scores' layout
+    float *da_row, *dc_row, *da_col, *dc_col;    // [batch][heads][n]
+    float *dkb;                                  // [2][heads]
+    float *d_row_val, *d_col_val;                // [batch][n][heads * head_dim]
+    double *partials;
+};
+
+// Edges per chunk of the edge-score backward: a chunk's workspace rows (544 floats per edge: h1, h2, dh2pre, dh1pre
+// of 128 each, dS and the features padded to 16) take 30720 * 2176 B = 63.75 MiB.
+constexpr int kDualBwdChunk = 30720;
 
 size_t dual_gnn_workspace_bytes(int batch, int n, int heads);  // the scores tensor; 0 for arguments out of range
 hipError_t launch_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2,
@@ -44,5 +63,16 @@ hipError_t launch_dual_edge_scores_ragged(const float *edge_feat, const float *W
                                           int n, int heads, hipStream_t stream);
 // heads <= 65535 here (the grid's y dimension): kDualMaxHeads limits the edge-scores kernel and the workspace only
 hipError_t launch_dual_attention(const DualAttnParams &p, hipStream_t stream);
+
+// The workspace of either backward launch below (the larger of the two); 0 for arguments out of range.
+size_t dual_backward_workspace_bytes(int batch, int n, int heads);
+// Three kernels: query-major (dS, da, per-workgroup partials of dkb), key-major (dc, dval), the reduce of dkb.
+hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_t stream);
+// Per chunk of kDualBwdChunk edges three kernels: the recompute (rows into the workspace), the TN products per
+// workgroup slice, the fp64 reduce over workgroups and chunks.  sizes null: the uniform batch.
+hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                            const float *b2, const float *G, const float *dS, const int *sizes,
+                                            float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch,
+                                            int n, int heads, void *workspace, hipStream_t stream);
 
 }  // namespace lapwarm

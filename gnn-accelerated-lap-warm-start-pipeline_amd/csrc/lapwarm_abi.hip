@@ -593,6 +593,99 @@ int lapwarm_dual_attention_ragged(const float *scores, const float *a_row, const
     return 0;
 }
 
+// ---- DualGNN training: the forward with its softmax statistics, and the two backwards (dual_gnn.hip) ----
+static int dual_attention_stats(const DualAttnParams &p, void *stream_)
+{
+    if (p.batch < 1 || p.batch > kDualMaxBatch || p.n < 1 || p.heads < 1 || p.heads > kMaxGridY || p.head_dim < 1)
+        return -2;
+    if (p.n > kMaxN) return -5;
+    if (!p.scores || !p.a_row || !p.c_row || !p.a_col || !p.c_col || !p.kbias || !p.row_val || !p.col_val ||
+        !p.row_msg || !p.col_msg || !p.row_stats || !p.col_stats)
+        return -2;
+    HIP_TRY(launch_dual_attention(p, as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_dual_attention_stats(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                                 const float *c_col, const float *kbias, const unsigned char *mask,
+                                 const float *row_val, const float *col_val, float *row_msg, float *col_msg,
+                                 float *row_stats, float *col_stats, int batch, int n, int heads, int head_dim,
+                                 void *stream_)
+{
+    DualAttnParams p{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val, row_msg, col_msg,
+                     batch, n, heads, head_dim, nullptr, row_stats, col_stats};
+    return dual_attention_stats(p, stream_);
+}
+
+int lapwarm_dual_attention_stats_ragged(const float *scores, const float *a_row, const float *c_row,
+                                        const float *a_col, const float *c_col, const float *kbias, const int *sizes,
+                                        const float *row_val, const float *col_val, float *row_msg, float *col_msg,
+                                        float *row_stats, float *col_stats, int batch, int n, int heads, int head_dim,
+                                        void *stream_)
+{
+    if (!sizes) return -2;
+    DualAttnParams p{scores, a_row, c_row, a_col, c_col, kbias, nullptr, row_val, col_val, row_msg, col_msg,
+                     batch, n, heads, head_dim, sizes, row_stats, col_stats};
+    return dual_attention_stats(p, stream_);
+}
+
+size_t lapwarm_dual_backward_workspace_bytes(int batch, int n, int heads)
+{
+    return dual_backward_workspace_bytes(batch, n, heads);
+}
+
+int lapwarm_dual_backward_chunk(void) { return kDualBwdChunk; }
+
+int lapwarm_dual_attention_backward(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                                    const float *c_col, const float *kbias, const unsigned char *mask,
+                                    const int *sizes, const float *row_val, const float *col_val,
+                                    const float *row_msg, const float *col_msg, const float *row_stats,
+                                    const float *col_stats, const float *d_row_msg, const float *d_col_msg, float *dS,
+                                    float *da_row, float *dc_row, float *da_col, float *dc_col, float *dkb,
+                                    float *d_row_val, float *d_col_val, int batch, int n, int heads, int head_dim,
+                                    void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads || head_dim < 1) return -2;
+    if (n > kMaxN) return -5;
+    if (!scores || !a_row || !c_row || !a_col || !c_col || !kbias || !row_val || !col_val || !row_msg || !col_msg ||
+        !row_stats || !col_stats || !d_row_msg || !d_col_msg || !dS || !da_row || !dc_row || !da_col || !dc_col ||
+        !dkb || !d_row_val || !d_col_val || !workspace)
+        return -2;
+    if (int rc = check_workspace(workspace_bytes, dual_backward_workspace_bytes(batch, n, heads))) return rc;
+    DualAttnBwdParams p{};
+    p.fwd = DualAttnParams{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val,
+                           const_cast<float *>(row_msg), const_cast<float *>(col_msg), batch, n, heads, head_dim,
+                           sizes, const_cast<float *>(row_stats), const_cast<float *>(col_stats)};
+    p.d_row_msg = d_row_msg;
+    p.d_col_msg = d_col_msg;
+    p.dS = dS;
+    p.da_row = da_row;
+    p.dc_row = dc_row;
+    p.da_col = da_col;
+    p.dc_col = dc_col;
+    p.dkb = dkb;
+    p.d_row_val = d_row_val;
+    p.d_col_val = d_col_val;
+    p.partials = static_cast<double *>(workspace);
+    HIP_TRY(launch_dual_attention_backward(p, as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                      const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
+                                      float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
+                                      void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
+    if (n > kMaxN) return -5;
+    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !dS || !dW1 || !db1 || !dW2 || !db2 || !dG || !workspace)
+        return -2;
+    if (int rc = check_workspace(workspace_bytes, dual_backward_workspace_bytes(batch, n, heads))) return rc;
+    HIP_TRY(launch_dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n,
+                                             heads, workspace, as_stream(stream_)));
+    return 0;
+}
+
 int lapwarm_solver_uses_helpers(int n)
 {
     return (solver_uses_helpers(n) && solve_shape(n, false) == SolveShape::kOneLaunch) ? 1 : 0;

@@ -24,13 +24,25 @@ Two forwards:
     reference's op order with its dropout placements: inside the edge MLP, on both attention-weight tensors and
     in the two update MLPs.
 
+  * with `fused_attention_training = True` (on a DualGNN: all its layers; on a DualLayer used alone: that layer)
+    the fused path is also taken in training mode and while a gradient is recorded, as long as `edge_feat` itself
+    needs no gradient.  Two autograd functions carry it: _EdgeScores (lapwarm_dual_edge_scores_backward: the edge
+    MLP is recomputed per chunk of edges on the MFMA units, gradients for its first two Linears and the folded G)
+    and _EdgeAttention (lapwarm_dual_attention_backward from the saved scores, messages and per-query softmax
+    statistics: dS, da, dc, dkb, dval).  folded_parameters is differentiable torch, so autograd carries dG, da, dc
+    and dkb on to attn_*_weight, attn_*_bias, edge_mlp[5], row_proj and col_proj.  No (B, N, N, hidden) tensor is
+    saved: per layer the scores, two messages and 4 B H N statistics.  DROPOUT on this path: the dropouts of the
+    two update MLPs are applied as always; the two inside the fused region (in the edge MLP, on the attention
+    weights) are NOT applied, in training mode too (there is no device RNG in the kernels).  The default, False,
+    routes exactly as before.
+
 A padded batch of instances of different sizes passes `sizes` (B,) int32 on the device: `mask` is then the prefix
 mask of the sizes (built here when it is None).  The fused path hands the sizes to lapwarm_dual_edge_scores_ragged
 and lapwarm_dual_attention_ragged, which skip the padding: the edge MLP runs on the edges (i, j < n_b) only, and
 the attention neither loads a score nor walks a key tile outside a prefix.  The outputs are, bit for bit, those of
 the same call without `sizes`.  On the plain path `sizes` only supplies the mask.
 
-A backward for the fused path is out of scope: a gradient taken through the model runs the plain path.
+The backward kernels are deterministic (fixed-order sums, no atomics): equal inputs give equal gradients.
 """
 from __future__ import annotations
 
@@ -67,7 +79,105 @@ def _prefix_mask(sizes, mask, edge_feat) -> torch.Tensor:
     return prefix
 
 
+def _backward_workspace(lib, B, N, H, dev) -> torch.Tensor:
+    nbytes = int(lib.lapwarm_dual_backward_workspace_bytes(B, N, H))
+    if nbytes == 0:
+        raise ValueError(f"DualLayer: batch {B}, n {N} or heads {H} outside the fused kernels' range")
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+
+
+class _EdgeScores(torch.autograd.Function):
+    """scores (B, 2, H, N, N) of lapwarm_dual_edge_scores[_ragged]; saves only its inputs.  The backward is
+    lapwarm_dual_edge_scores_backward: gradients for W1, b1, W2, b2 and G, none for edge_feat.  With `sizes` the
+    scores outside the prefixes are never written and their gradient is never read."""
+
+    @staticmethod
+    def forward(ctx, edge_feat, W1, b1, W2, b2, G, sizes):
+        from lap import _hip
+        from ._call import hip_call
+        _hip.require_device()
+        B, N = edge_feat.shape[:2]
+        H = G.shape[0] // 2
+        args = [t.detach().contiguous() for t in (edge_feat, W1, b1, W2, b2, G)]
+        scores = torch.empty((B, 2, H, N, N), dtype=torch.float32, device=edge_feat.device)
+        if sizes is not None:
+            hip_call("lapwarm_dual_edge_scores_ragged", "dual_edge_scores", scores.device, *args, scores, sizes, B, N, H)
+        else:
+            hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", scores.device, *args, scores, B, N, H)
+        ctx.save_for_backward(*args)
+        ctx.sizes = sizes
+        return scores
+
+    @staticmethod
+    def backward(ctx, d_scores):
+        from lap import _hip
+        from ._call import hip_call
+        edge_feat, W1, b1, W2, b2, G = ctx.saved_tensors
+        B, N = edge_feat.shape[:2]
+        H = G.shape[0] // 2
+        dev = edge_feat.device
+        ws = _backward_workspace(_hip.load(), B, N, H, dev)
+        grads = [torch.empty_like(t) for t in (W1, b1, W2, b2, G)]
+        hip_call("lapwarm_dual_edge_scores_backward", "dual_edge_scores_backward", dev, edge_feat, W1, b1, W2, b2, G,
+                 d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel())
+        return (None, *grads, None)
+
+
+class _EdgeAttention(torch.autograd.Function):
+    """(row_msg, col_msg) of lapwarm_dual_attention_stats[_ragged]; saves the scores, the per-query softmax
+    statistics and the messages.  The backward is lapwarm_dual_attention_backward."""
+
+    @staticmethod
+    def forward(ctx, scores, a_row, c_row, a_col, c_col, kbias, row_val, col_val, mask8, sizes):
+        from lap import _hip
+        from ._call import hip_call
+        _hip.require_device()
+        B, _, H, N, _ = scores.shape
+        D = row_val.shape[-1] // H
+        dev = scores.device
+        args = [t.detach().contiguous() for t in (scores, a_row, c_row, a_col, c_col, kbias)]
+        vals = [t.detach().contiguous() for t in (row_val, col_val)]
+        row_msg, col_msg = (torch.empty((B, N, H * D), dtype=torch.float32, device=dev) for _ in range(2))
+        row_stats, col_stats = (torch.empty((B, H, N, 2), dtype=torch.float32, device=dev) for _ in range(2))
+        if sizes is not None:
+            hip_call("lapwarm_dual_attention_stats_ragged", "dual_attention", dev, *args, sizes, *vals, row_msg, col_msg,
+                     row_stats, col_stats, B, N, H, D)
+        else:
+            hip_call("lapwarm_dual_attention_stats", "dual_attention", dev, *args, mask8, *vals, row_msg, col_msg,
+                     row_stats, col_stats, B, N, H, D)
+        ctx.save_for_backward(*args, *vals, row_msg, col_msg, row_stats, col_stats)
+        ctx.mask8, ctx.sizes = mask8, sizes
+        return row_msg, col_msg
+
+    @staticmethod
+    def backward(ctx, d_row_msg, d_col_msg):
+        from lap import _hip
+        from ._call import hip_call
+        (scores, a_row, c_row, a_col, c_col, kbias, row_val, col_val, row_msg, col_msg, row_stats,
+         col_stats) = ctx.saved_tensors
+        B, _, H, N, _ = scores.shape
+        D = row_val.shape[-1] // H
+        dev = scores.device
+        ws = _backward_workspace(_hip.load(), B, N, H, dev)
+        # with sizes the kernel leaves dS outside the prefixes alone: zeros there, so the tensor is a clean gradient
+        dS = (torch.zeros_like if ctx.sizes is not None else torch.empty_like)(scores)
+        da_row, dc_row, da_col, dc_col = (torch.empty_like(a_row) for _ in range(4))
+        dkb = torch.empty_like(kbias)
+        d_row_val, d_col_val = torch.empty_like(row_val), torch.empty_like(col_val)
+        hip_call("lapwarm_dual_attention_backward", "dual_attention_backward", dev, scores, a_row, c_row, a_col, c_col,
+                 kbias, ctx.mask8, ctx.sizes, row_val, col_val, row_msg, col_msg, row_stats, col_stats,
+                 d_row_msg.contiguous(), d_col_msg.contiguous(), dS, da_row, dc_row, da_col, dc_col, dkb, d_row_val,
+                 d_col_val, B, N, H, D, ws, ws.numel())
+        return dS, da_row, dc_row, da_col, dc_col, dkb, d_row_val, d_col_val, None, None
+
+
 class DualLayer(nn.Module):
+    # With True, CUDA float32 tensors with heads <= 8 and an edge_feat that needs no gradient take the fused path
+    # also in training mode and while a gradient is recorded (HIP forward and backward).  The two dropouts inside
+    # the fused region (in the edge MLP, on the attention weights) are then not applied; those of the update MLPs
+    # are.  DualGNN.fused_attention_training sets it on every layer of a model.
+    fused_attention_training = False
+
     def __init__(self, hidden_dim: int, heads: int = 4, dropout: float = 0.1) -> None:
         super().__init__()
         if hidden_dim % heads != 0:
@@ -132,10 +242,15 @@ class DualLayer(nn.Module):
         nbytes = int(lib.lapwarm_dual_gnn_workspace_bytes(B, N, H))
         if nbytes == 0:
             raise ValueError(f"DualLayer: batch {B}, n {N} or heads {H} outside the fused kernels' range")
-        scores = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
         lin1, lin2 = self.edge_mlp[0], self.edge_mlp[3]
+        if _records_grad(self, row_embed, col_embed):  # the trainable route: HIP forward and backward
+            scores = _EdgeScores.apply(edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], sizes)
+            mask8 = None if mask is None or sizes is not None else mask.to(torch.uint8).contiguous()
+            return _EdgeAttention.apply(scores, fold["a_row"], fold["c_row"], fold["a_col"], fold["c_col"],
+                                        fold["kbias"], row_val, col_val, mask8, sizes)
         row_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
         col_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
+        scores = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
         if sizes is not None:  # scores outside the prefixes are neither written nor read
             hip_call("lapwarm_dual_edge_scores_ragged", "dual_edge_scores", dev, edge_feat, lin1.weight, lin1.bias,
                      lin2.weight, lin2.bias, fold["G"], scores, sizes, B, N, H)
@@ -181,9 +296,11 @@ class DualLayer(nn.Module):
         return row_msg, col_msg
 
     def takes_fused_path(self, edge_feat, row_embed, col_embed) -> bool:
-        return (not self.training and edge_feat.is_cuda and self.heads <= FUSED_MAX_HEADS
-                and self.attn_row_weight.dtype == torch.float32  # (a .double() copy is a plain-path model)
-                and not _records_grad(self, edge_feat, row_embed, col_embed))
+        fits = (edge_feat.is_cuda and self.heads <= FUSED_MAX_HEADS
+                and self.attn_row_weight.dtype == torch.float32)  # (a .double() copy is a plain-path model)
+        if self.fused_attention_training:  # training mode and recorded gradients too; none for edge_feat
+            return fits and not (torch.is_grad_enabled() and edge_feat.requires_grad)
+        return fits and not self.training and not _records_grad(self, edge_feat, row_embed, col_embed)
 
     def forward(self, edge_feat: torch.Tensor, row_embed: torch.Tensor, col_embed: torch.Tensor,
                 mask: Optional[torch.Tensor], sizes: Optional[torch.Tensor] = None
@@ -217,6 +334,16 @@ class DualGNN(nn.Module):
         self.row_out = nn.Linear(hidden_dim, 1)
         self.col_out = nn.Linear(hidden_dim, 1)
 
+    @property
+    def fused_attention_training(self) -> bool:
+        """The switch of every layer (DualLayer.fused_attention_training); False unless set."""
+        return all(layer.fused_attention_training for layer in self.layers)
+
+    @fused_attention_training.setter
+    def fused_attention_training(self, on: bool) -> None:
+        for layer in self.layers:
+            layer.fused_attention_training = bool(on)
+
     def _forward(self, edge_feat, row_feat, col_feat, mask, sizes=None):
         nodes = (self.row_encoder(row_feat), self.col_encoder(col_feat))
         for layer in self.layers:
@@ -240,7 +367,8 @@ class DualGNN(nn.Module):
             raise ValueError("edge_feat must have shape (batch, n, n, F)")
         if sizes is not None:
             mask = _prefix_mask(sizes, mask, edge_feat)
-        if self.layers[0].takes_fused_path(edge_feat, row_feat, col_feat) and not _records_grad(self):
+        if self.layers[0].takes_fused_path(edge_feat, row_feat, col_feat) and (
+                self.fused_attention_training or not _records_grad(self)):
             # float32 end to end, whatever autocast context the caller is in
             with torch.autocast("cuda", enabled=False):
                 return self._forward(edge_feat.float(), row_feat.float(), col_feat.float(), mask, sizes)

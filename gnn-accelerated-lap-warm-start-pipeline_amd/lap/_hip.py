@@ -116,6 +116,12 @@ SIGNATURES = {
                                                    ct.c_int, c_vp]),
     "lapwarm_dual_attention_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                  ct.c_int, ct.c_int, ct.c_int, ct.c_int, c_vp]),
+    "lapwarm_dual_attention_stats": (ct.c_int, [c_vp] * 13 + [ct.c_int] * 4 + [c_vp]),
+    "lapwarm_dual_attention_stats_ragged": (ct.c_int, [c_vp] * 13 + [ct.c_int] * 4 + [c_vp]),
+    "lapwarm_dual_backward_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int, ct.c_int]),
+    "lapwarm_dual_backward_chunk": (ct.c_int, []),
+    "lapwarm_dual_attention_backward": (ct.c_int, [c_vp] * 24 + [ct.c_int] * 4 + [c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_dual_edge_scores_backward": (ct.c_int, [c_vp] * 13 + [ct.c_int] * 3 + [c_vp, ct.c_size_t, c_vp]),
     "lapwarm_profile_enable": (None, [ct.c_int]),
     "lapwarm_profile_last_solver_ms": (ct.c_double, []),
     "lapwarm_solver_uses_helpers": (ct.c_int, [ct.c_int]),

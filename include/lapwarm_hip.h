@@ -535,6 +535,64 @@ int lapwarm_dual_attention_ragged(const float *scores, const float *a_row, const
                                   const float *col_val, float *row_msg, float *col_msg, int batch, int n, int heads,
                                   int head_dim, void *stream);
 
+/* DualGNN training: the backward of the two kernels above (float32, heads <= 8, batch and n as the forward).
+ * lapwarm_dual_attention_stats / _stats_ragged: lapwarm_dual_attention / _ragged that also write, per query, the
+ *   maximum of its leaky_relu scores and the sum of exp(s - max): row_stats, col_stats [batch][heads][n][2].  The
+ *   messages are bit for bit those of the entries without statistics.
+ * lapwarm_dual_attention_backward, per (b, direction, h), q the query and k the key, from dmsg = dL/dmsg:
+ *     z[q,k] = ((a[q] + c[k]) + S[q,k]) + kb,  s = leaky_relu_0.2(z),  w[q,k] = exp(s - max_q) / sum_q
+ *     delta[q] = dmsg[q] . msg[q],   dw[q,k] = dmsg[q] . val[k]
+ *     dz[q,k]  = w[q,k] (dw[q,k] - delta[q]) (z >= 0 ? 1 : 0.2), exactly 0 where q or k is masked
+ *     dS = dz (in the layout of the scores: [i][j] for both directions),  da[q] = sum_k dz,  dc[k] = sum_q dz,
+ *     dkb[direction][h] = sum_{b,q,k} dz,   dval[k] = sum_q w[q,k] dmsg[q]
+ *   The kernel forms delta[q] as sum_k w[q,k] dw[q,k], which is dmsg[q] . msg[q]: built from the numbers it is
+ *   subtracted from, its rounding cancels in sum_k dz as in exact arithmetic (a query with one key gets exactly 0).
+ *   (val is col_val for the row direction and row_val for the column direction, so d_col_val comes from the row
+ *   direction.)  mask and sizes as in the forward, both nullable, sizes taking precedence.  With sizes no score and
+ *   no dS entry outside a prefix is read or written; padded or masked queries and keys get exactly 0 in da, dc and
+ *   dval.  Three kernels: a query-major pass over 16 queries (dS, da, one partial of dkb per workgroup), a key-major
+ *   pass over 16 keys (dc from dS read back, dval with w recomputed), and the reduce of the partials in fp64.
+ *   fp32 sums in a fixed order, no atomics: equal inputs give equal bits.
+ * lapwarm_dual_edge_scores_backward, from dS [batch][2 * heads][n][n] and the forward's inputs, with
+ *   x1 = W1 f + b1, h1 = GELU(x1), x2 = W2 h1 + b2, h2 = GELU(x2), GELU'(x) = Phi(x) + x phi(x), per edge e:
+ *     dh2 = G^T dS_e,  dx2 = dh2 * GELU'(x2),  dh1 = W2^T dx2,  dx1 = dh1 * GELU'(x1)
+ *     dG = sum_e dS_e h2^T,  dW2 = sum_e dx2 h1^T,  db2 = sum_e dx2,  dW1 = sum_e dx1 f^T,  db1 = sum_e dx1
+ *   dW1 [128][10], db1 [128], dW2 [128][128], db2 [128], dG [2 * heads][128]; edge_feat has no gradient.  Nothing
+ *   of width 128 per edge is kept from the forward: per chunk of lapwarm_dual_backward_chunk edges one kernel
+ *   recomputes the edge MLP on the MFMA units and leaves h1, h2, dx2, dx1, dS and f as rows in the workspace, a
+ *   second forms the five sums over a fixed slice of rows per workgroup on the same units, a third adds the
+ *   workgroups and the chunks in fp64 in order and rounds once after the last chunk.  With sizes (nullable) only
+ *   the edges (i, j < sizes[b]) are walked and dS outside the prefixes is never read.  Equal inputs give equal bits.
+ * lapwarm_dual_backward_workspace_bytes: the workspace of either backward (the larger), at most 64 MiB of rows plus
+ *   the partials; 0 for arguments out of range (the limits of lapwarm_dual_gnn_workspace_bytes).  Every workspace
+ *   word that is read is written inside the call.
+ * Returns 0, -1 (workspace too small), -2 (arguments), -5 (n > 16384), <= -1000 HIP error; argument codes come
+ * before any HIP call. */
+int lapwarm_dual_attention_stats(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                                 const float *c_col, const float *kbias, const unsigned char *mask,
+                                 const float *row_val, const float *col_val, float *row_msg, float *col_msg,
+                                 float *row_stats, float *col_stats, int batch, int n, int heads, int head_dim,
+                                 void *stream);
+int lapwarm_dual_attention_stats_ragged(const float *scores, const float *a_row, const float *c_row,
+                                        const float *a_col, const float *c_col, const float *kbias, const int *sizes,
+                                        const float *row_val, const float *col_val, float *row_msg, float *col_msg,
+                                        float *row_stats, float *col_stats, int batch, int n, int heads, int head_dim,
+                                        void *stream);
+size_t lapwarm_dual_backward_workspace_bytes(int batch, int n, int heads);
+int lapwarm_dual_backward_chunk(void);
+int lapwarm_dual_attention_backward(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                                    const float *c_col, const float *kbias, const unsigned char *mask,
+                                    const int *sizes, const float *row_val, const float *col_val,
+                                    const float *row_msg, const float *col_msg, const float *row_stats,
+                                    const float *col_stats, const float *d_row_msg, const float *d_col_msg, float *dS,
+                                    float *da_row, float *dc_row, float *da_col, float *dc_col, float *dkb,
+                                    float *d_row_val, float *d_col_val, int batch, int n, int heads, int head_dim,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+int lapwarm_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                      const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
+                                      float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* Profiling hook for bench.py: when enabled, lapwarm_seeded_batched / lapwarm_lapjv_batched /
  * lapwarm_seeded_ragged / lapwarm_lapjv_ragged / lapwarm_lapjv_extended_ragged bracket their solver launches
  * with HIP events on the caller's stream;
