@@ -18,9 +18,10 @@ EDGE_NAMES = ("dW1", "db1", "dW2", "db2", "dG")
 
 # ---- inputs ----------------------------------------------------------------------------------------------------
 
-def attention_case(B, N, H, D, mask_kind="none", scale=1.0, seed=0):
+def attention_case(B, N, H, D, mask_kind="none", scale=1.0, seed=0, sizes=None):
     """float32 CPU tensors: the nine forward arguments of dg.attention_torch (mask: bool (B, N) or None) and the two
-    message gradients.  mask_kind: none | prefix | scattered | one_empty (instance 0 fully masked)."""
+    message gradients.  mask_kind: none | prefix | scattered | one_empty (instance 0 fully masked).  `sizes`: the
+    sizes of the prefix mask in place of prefix_sizes(B, N); one outside 1..N is an empty instance."""
     g = torch.Generator().manual_seed(100003 * seed + 1009 * N + 31 * H + D)
     r = lambda *s: torch.randn(s, generator=g)  # noqa: E731
     scores = r(B, 2, H, N, N) * scale
@@ -30,8 +31,7 @@ def attention_case(B, N, H, D, mask_kind="none", scale=1.0, seed=0):
     if mask_kind == "none":
         mask = None
     elif mask_kind == "prefix":
-        sizes = prefix_sizes(B, N)
-        mask = torch.arange(N)[None, :] < sizes[:, None]
+        mask = prefix_mask(prefix_sizes(B, N) if sizes is None else sizes, N)
     elif mask_kind == "scattered":
         mask = torch.rand((B, N), generator=g) < 0.6
         mask[:, N // 2] = True
@@ -47,6 +47,70 @@ def attention_case(B, N, H, D, mask_kind="none", scale=1.0, seed=0):
 def prefix_sizes(B, N):
     """sizes (B,) int64 in 1..N, the first N itself when B > 1, the others spread below it."""
     return torch.tensor([N if (b == 0 and B > 1) else max(1, (N * (b + 2)) // (B + 2)) for b in range(B)])
+
+
+def prefix_mask(sizes, N):
+    """bool (B, N): node i of instance b is real when i < sizes[b]; a size outside 1..N is an empty instance."""
+    sizes = torch.as_tensor(sizes, dtype=torch.int64)
+    inside = (sizes >= 1) & (sizes <= N)
+    return torch.arange(N)[None, :] < torch.where(inside, sizes, torch.zeros_like(sizes))[:, None]
+
+
+# ---- the wave tiles of the edge backward -------------------------------------------------------------------------
+# With sizes lapwarm_dual_edge_scores_backward walks the edges (i, j < sizes[b]) only, a wave tile of 16 at a time as
+# lapwarm_dual_edge_scores_ragged numbers them: instance after instance, row after row, 16 columns at a time, so
+# n * ceil(n / 16) tiles for a size in 1..N and none for any other ("an empty instance", include/lapwarm_hip.h).
+# Without sizes a tile is 16 edges of the linear order.  A chunk is lapwarm_dual_backward_chunk() / 16 tiles.
+
+WAVE_EDGES = 16
+
+
+def ragged_wave_tiles(sizes, N):
+    """The number of wave tiles of every instance in the ragged numbering."""
+    return [n * -(-n // WAVE_EDGES) if 1 <= n <= N else 0 for n in (int(s) for s in sizes)]
+
+
+def chunk_crossings(sizes, N, chunk):
+    """[(t0, b, offset)] for every chunk start t0 > 0 (in wave tiles, `chunk` in edges) below the total of the
+    ragged numbering: the instance whose tiles contain t0 and the tile's number inside it.  offset 0: the chunk
+    starts with the instance."""
+    per = chunk // WAVE_EDGES
+    counts = ragged_wave_tiles(sizes, N)
+    out = []
+    for t0 in range(per, sum(counts), per):
+        first = 0
+        for b, count in enumerate(counts):
+            if first <= t0 < first + count:
+                out.append((t0, b, t0 - first))
+                break
+            first += count
+    return out
+
+
+def ragged_tile_edges(sizes, N, t):
+    """[(b, i, j)]: the edges of wave tile t of the ragged numbering, the columns past the size left out."""
+    first = 0
+    for b, count in enumerate(ragged_wave_tiles(sizes, N)):
+        if first <= t < first + count:
+            n = int(sizes[b])
+            groups = -(-n // WAVE_EDGES)
+            i, g = divmod(t - first, groups)
+            return [(b, i, j) for j in range(g * WAVE_EDGES, min(n, (g + 1) * WAVE_EDGES))]
+        first += count
+    raise ValueError(f"tile {t} is past the {first} tiles of the sizes")
+
+
+def uniform_tile_edges(B, N, t):
+    """[(b, i, j)]: the edges of wave tile t of the uniform numbering, 16 at a time in the linear edge order."""
+    return [(e // (N * N), e // N % N, e % N) for e in range(t * WAVE_EDGES, min(B * N * N, (t + 1) * WAVE_EDGES))]
+
+
+def probe_gradient(dS, edges):
+    """dS with zeros everywhere but on `edges` [(b, i, j)], every output channel of those kept."""
+    out = torch.zeros_like(dS)
+    for b, i, j in edges:
+        out[b, :, :, i, j] = dS[b, :, :, i, j]
+    return out
 
 
 def edge_case(B, N, heads, seed=0):

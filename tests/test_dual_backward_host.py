@@ -51,6 +51,54 @@ def test_edge_scores_closed_form_is_autograd_of_the_forward(N, heads):
         assert err <= 1e-12 * max(1.0, float(np.abs(ref).max())), name
 
 
+CHUNK = 30720  # the hand-worked values below are for this chunk; the GPU tests ask the library
+
+
+def test_ragged_wave_tiles_and_chunk_crossings_against_hand_worked_values(lib):
+    assert lib.lapwarm_dual_backward_chunk() == CHUNK  # otherwise work the values below out again
+    sizes = (130, 97, 130, 130)
+    # 130 * ceil(130 / 16) = 130 * 9, 97 * 7
+    assert dbc.ragged_wave_tiles(sizes, 130) == [1170, 679, 1170, 1170]
+    # 1920 - (1170 + 679) = 71 = 7 * 9 + 8: row 7, its ninth group, the columns 128 and 129
+    # 3840 - (1170 + 679 + 1170) = 821
+    assert dbc.chunk_crossings(sizes, 130, CHUNK) == [(1920, 2, 71), (3840, 3, 821)]
+    assert dbc.ragged_tile_edges(sizes, 130, 1920) == [(2, 7, 128), (2, 7, 129)]
+    assert dbc.ragged_tile_edges(sizes, 130, 1919) == [(2, 7, j) for j in range(112, 128)]
+    # sizes outside 1..N have no tile and contain no crossing
+    padded = (130, 0, 97, 130, 131, 130)
+    assert dbc.ragged_wave_tiles(padded, 130) == [1170, 0, 679, 1170, 0, 1170]
+    assert dbc.chunk_crossings(padded, 130, CHUNK) == [(1920, 3, 71), (3840, 5, 821)]
+    assert dbc.ragged_tile_edges(padded, 130, 1170) == [(2, 0, j) for j in range(16)]
+    with pytest.raises(ValueError):
+        dbc.ragged_tile_edges(padded, 130, 4189)
+    # the sizes of the padded model case: 679 + 1170 = 1849, 71 tiles into the third instance
+    assert dbc.chunk_crossings((97, 130, 130), 130, CHUNK) == [(1920, 2, 71)]
+    # a chunk that starts with an instance: offset 0; one that starts with the end of the tiles: no crossing
+    assert dbc.chunk_crossings((16, 16), 16, 256) == [(16, 1, 0)]
+    assert dbc.chunk_crossings((16,), 16, 256) == []
+    # the sizes every case had before: one chunk
+    assert dbc.prefix_sizes(2, 130).tolist() == [130, 97]
+    assert sum(dbc.ragged_wave_tiles(dbc.prefix_sizes(2, 130), 130)) == 1849 < CHUNK // 16
+    assert dbc.chunk_crossings(dbc.prefix_sizes(2, 130), 130, CHUNK) == []
+
+
+def test_uniform_tiles_probe_gradient_and_prefix_mask():
+    assert dbc.uniform_tile_edges(2, 3, 0) == [(0, i, j) for i in range(3) for j in range(3)] + \
+        [(1, i, j) for i in range(3) for j in range(3)][:7]
+    assert dbc.uniform_tile_edges(2, 3, 1) == [(1, 2, 1), (1, 2, 2)]
+    assert dbc.uniform_tile_edges(1, 248, 1920) == [(0, 123, 216 + k) for k in range(16)]  # 30720 = 123 * 248 + 216
+    mask = dbc.prefix_mask((3, 0, 4, 2), 3)
+    assert mask.tolist() == [[True] * 3, [False] * 3, [False] * 3, [True, True, False]]
+    assert torch.equal(dbc.prefix_mask(dbc.prefix_sizes(2, 130), 130)[1], torch.arange(130) < 97)
+    dS = torch.arange(2 * 2 * 2 * 3 * 3, dtype=torch.float32).reshape(2, 2, 2, 3, 3) + 1.0
+    probe = dbc.probe_gradient(dS, [(1, 2, 0)])
+    assert torch.equal(probe[1, :, :, 2, 0], dS[1, :, :, 2, 0]) and probe.count_nonzero() == 4
+    # an explicit size list gives attention_case the prefix mask of those sizes and the numbers of the default case
+    a, _ = dbc.attention_case(4, 3, 1, 2, "prefix", sizes=(3, 0, 4, 2))
+    b, _ = dbc.attention_case(4, 3, 1, 2, "prefix")
+    assert torch.equal(a[6], mask) and torch.equal(a[0], b[0]) and torch.equal(a[8], b[8])
+
+
 def test_the_switch_is_off_by_default_and_routing_is_unchanged_then():
     from gnn.dual_gnn import DualLayer
     model = dg.build_model("h32_H4_L2")
