@@ -176,6 +176,12 @@ struct Solver {
     static constexpr bool PF = ROWLDS;  // ... and the next queued head's row requested one step ahead
     static constexpr int kCacheLimit = (TB <= 256) ? 16 : ((TB <= 512) ? 32 : 4);  // positions per thread whose duals fit in registers
     static constexpr int kCacheLimitY = (TB <= 256) ? 16 : 2;
+    // the duals of the owned columns are cached in registers while the budget allows
+    // (1024-thread workgroups cap a thread at 128 VGPRs)
+    static constexpr bool CACHE_V = CH <= kCacheLimit;
+    static constexpr bool CACHE_Y = CH <= kCacheLimitY;  // ... and their matched rows (y is constant during a path)
+    // independent tie events swapped by their finders: only with <= 4 positions per thread
+    static constexpr bool kFastMulti = CH <= 4;
     // problem
     const double *C;
     int n, W;
@@ -461,6 +467,22 @@ struct Solver {
         }
     }
 
+    // Request a head row into an LDS row slot (level 8) by coalesced LDS-DMA: CH / 2 pieces of 16 bytes per lane.
+    // slot_lds is the LDS byte address of the slot.  The caller drains before the barrier that publishes the row.
+    __device__ __forceinline__ void request_row(const double *row, unsigned slot_lds)
+    {
+        const unsigned sbase = slot_lds + (unsigned)bc.wave * 1024u;
+        const int nt = (int)blockDim.x;
+#pragma unroll
+        for (int q = 0; q < CH / 2; ++q) {
+            // lane's 16 bytes: columns q*2*nt + 2*tid, +1 (clamped into the row; the
+            // padding beyond n is never read)
+            int col = q * 2 * nt + 2 * bc.tid;
+            col = (col < n - 2) ? col : n - 2;
+            dma_request16(row + col, sbase + (unsigned)q * (unsigned)nt * 16u);
+        }
+    }
+
     // ------------------------------------------------------------------ one shortest path
     // lapjv.cpp:221-282.  Returns the free column reached; updates v for the READY columns.
     __device__ __forceinline__ int find_path(int start)
@@ -468,12 +490,8 @@ struct Solver {
         const int b0 = base();
         const int wordi = b0 >> 5, shift = b0 & 31;
         STAMPP(tpath);
-        // the duals of the owned columns are cached in registers while the budget allows
-        // (1024-thread workgroups cap a thread at 128 VGPRs)
-        constexpr bool CACHE_V = CH <= kCacheLimit;
         double dk[CH], vr[CACHE_V ? CH : 1];
-        constexpr bool CACHE_Y = CH <= kCacheLimitY;
-        int jr[CH], yr[CACHE_Y ? CH : 1];  // yr: matched row of the owned column (y is constant during a path)
+        int jr[CH], yr[CACHE_Y ? CH : 1];  // yr: matched row of the owned column
         {
             // every load is issued before the first use: indices are clamped instead of
             // branching, so the CH gathers of a thread are all in flight together
@@ -516,8 +534,6 @@ struct Solver {
         // still be writing order[]): position app_pos, the only fresh entry the directly following
         // step can look at.  (A step with more events has a barrier behind its writes.)
         int app_pos = -1, app_j = 0, app_i = 0;
-        // independent tie events swapped by their finders: only with <= 4 positions per thread
-        constexpr bool kFastMulti = CH <= 4;
         bool pf_have = false;  // level 8: the current head's row sits in slot pf_slot
         int pf_slot = 0;
         double level = 0.0;
@@ -716,14 +732,7 @@ struct Solver {
                 if (!from_slot) {
                     // not requested ahead: request it now, wait, and let one barrier publish it
                     pf_slot = 0;
-                    const unsigned sbase = lds_address(slots) + (unsigned)bc.wave * 1024u;
-                    const int nt = (int)blockDim.x;
-#pragma unroll
-                    for (int q = 0; q < CH / 2; ++q) {
-                        int col = q * 2 * nt + 2 * bc.tid;
-                        col = (col < n - 2) ? col : n - 2;
-                        dma_request16(row + col, sbase + (unsigned)q * (unsigned)nt * 16u);
-                    }
+                    request_row(row, lds_address(slots));
                     drain();
                     __syncthreads();
                     from_slot = true;
@@ -791,17 +800,7 @@ struct Solver {
                 if (queued && (unsigned)ri < (unsigned)n && nslots > 1) {
                     pf_next_slot = from_slot ? (pf_slot ^ 1) : 0;
                     const double *nrow = C + (size_t)ri * (RAGGED ? ldc : n);
-                    const unsigned sbase = lds_address(slots) + (unsigned)pf_next_slot * (unsigned)slot_bytes +
-                                           (unsigned)bc.wave * 1024u;
-                    const int nt = (int)blockDim.x;
-#pragma unroll
-                    for (int q = 0; q < CH / 2; ++q) {
-                        // lane's 16 bytes: columns q*2*nt + 2*tid, +1 (clamped into the row; the
-                        // padding beyond n is never read)
-                        int col = q * 2 * nt + 2 * bc.tid;
-                        col = (col < n - 2) ? col : n - 2;
-                        dma_request16(nrow + col, sbase + (unsigned)q * (unsigned)nt * 16u);
-                    }
+                    request_row(nrow, lds_address(slots) + (unsigned)pf_next_slot * (unsigned)slot_bytes);
                     pf_issued = true;
                 }
             }
