@@ -242,6 +242,16 @@ size_t train_loss_layout(void *ws, TrainLossParams *p)
     return c.off;
 }
 
+// DualGNN loss: the training-loss layout, then d_j and the per-row sums S_i behind it.
+size_t dual_loss_layout(void *ws, TrainLossParams *p)
+{
+    Carver c{reinterpret_cast<unsigned char *>(ws), train_loss_layout(ws, p)};
+    const size_t bn = (size_t)p->batch * p->n;
+    p->dj = c.take<float>(bn);
+    p->vsum = c.take<double>(bn);
+    return c.off;
+}
+
 // Rectangular / cost-limited lapjv: the extended matrices (none when the solver reads the caller's C),
 // the solver's x, y of the n x n problem, the matched costs of the finish step, the cold workspace.
 struct ExtendedWs {
@@ -1403,6 +1413,60 @@ int lapwarm_train_loss_backward(int batch, int n, const int *sizes, const float 
     train_loss_plan(&p);
     train_loss_layout(const_cast<void *>(workspace), &p);  // the kernel only reads it
     HIP_TRY(launch_train_loss_backward(p, weights, grad_scale, grad_u, as_stream(stream_)));
+    return 0;
+}
+
+size_t lapwarm_dual_loss_workspace_bytes(int batch, int n)
+{
+    if (check_ragged_dims(batch, n)) return 0;
+    TrainLossParams p{};
+    p.n = n;
+    p.batch = batch;
+    train_loss_plan(&p);
+    return dual_loss_layout(nullptr, &p);
+}
+
+int lapwarm_dual_loss_forward(const float *C, int batch, int n, const int *sizes, const float *u_pred,
+                              const float *v_hint, float *v_proj, int *argmin_row, int *assign, float *terms,
+                              int *ret, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_dims(batch, n)) return rc;
+    if (batch > kMaxGridY) return -2;
+    if (int rc = check_workspace(workspace_bytes, lapwarm_dual_loss_workspace_bytes(batch, n))) return rc;
+    TrainLossParams p{};
+    p.C = C;
+    p.n = n;
+    p.batch = batch;
+    p.sizes = sizes;
+    p.u = u_pred;
+    p.vh = v_hint;
+    p.v = v_proj;
+    p.arow = argmin_row;
+    p.assign = assign;
+    p.terms = terms;
+    p.ret = ret;
+    train_loss_plan(&p);
+    dual_loss_layout(workspace, &p);
+    HIP_TRY(launch_train_loss_forward(p, as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_dual_loss_backward(int batch, int n, const int *sizes, const float *u_pred, const float *v_hint,
+                               const float *weights, float grad_scale, float *grad_u, float *grad_v_hint,
+                               const void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_dims(batch, n)) return rc;
+    if (batch > kMaxGridY) return -2;
+    if (int rc = check_workspace(workspace_bytes, lapwarm_dual_loss_workspace_bytes(batch, n))) return rc;
+    TrainLossParams p{};
+    p.n = n;
+    p.batch = batch;
+    p.sizes = sizes;
+    p.u = u_pred;
+    p.vh = v_hint;
+    train_loss_plan(&p);
+    dual_loss_layout(const_cast<void *>(workspace), &p);  // the kernel only reads it
+    HIP_TRY(launch_dual_loss_backward(p, weights, grad_scale, grad_u, grad_v_hint, as_stream(stream_)));
     return 0;
 }
 

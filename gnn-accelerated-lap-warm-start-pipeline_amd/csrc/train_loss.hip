@@ -23,6 +23,13 @@
 //     row order by a bitonic sort of (m_i, i) in LDS, the greedy with the used-column bitmap in LDS,
 //     primal_upper, the four terms and ret;
 //   * backward: one thread per (b, i), closed form in fp64 from cnt, R and the scattered K.
+//
+// The DualGNN loss (gnn/train.py:267-308 `compute_loss`) differs in its third term only:
+//   v_reg = sum_j (vh_j - v_j)^2 / n_b,  vh = the model's v_hint
+// which sends 2 d_j / n_b, d_j = vh_j - v_j, into vh_j and, through v_j = C_{a_j j} - u_{a_j}, 2 S_i / n_b into
+// u_i with S_i = sum_{a_j = i} d_j.  The column pass, the hinge pass and the greedy are shared; the workgroup of
+// an instance forms S_i without floating-point atomics: a bitonic sort of (a_j << 32 | j) in the LDS buffer the
+// row order uses afterwards, then one serial fp64 sum per run of equal a_j, which adds in ascending j.
 #include "device_utils.hpp"
 #include "dense_sweeps.hpp"  // colmin_chunks
 #include "train_loss.hpp"
@@ -190,12 +197,77 @@ __global__ void __launch_bounds__(kTlThreads) tl_hinge_kernel(TrainLossParams p)
     if (lane == 0) p.hpart[(size_t)b * p.hparts + slot] = hs;
 }
 
+// ascending bitonic sort of ord[0 .. p2), p2 a power of two, by the whole workgroup; ends on a barrier
+__device__ __forceinline__ void tl_bitonic_sort(unsigned long long *ord, int p2, int tid, int nt)
+{
+    for (int k = 2; k <= p2; k <<= 1) {
+        for (int s = k >> 1; s > 0; s >>= 1) {
+            for (int t = tid; t < p2 / 2; t += nt) {
+                const int lo = ((t & ~(s - 1)) << 1) | (t & (s - 1));
+                const int hi = lo + s;
+                const unsigned long long x = ord[lo], y = ord[hi];
+                if ((x > y) == ((lo & k) == 0)) {
+                    ord[lo] = y;
+                    ord[hi] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// S_i = sum_{j: a_j = i} d_j of the DualGNN loss into p.vsum, d_j = vh_j - v_j into p.dj.  ord[] is free here:
+// it takes the keys (a_j << 32 | j), sorted; then every slot trades its j for the bits of d_j, and the thread
+// at the head of a run of equal a_j adds the run in fp64, front to back: ascending j, whatever the run length.
+// Rows that own no column keep the 0 written first.
+__device__ __forceinline__ void tl_segment_sums(const TrainLossParams &p, unsigned long long *ord, int p2, size_t bn,
+                                                int nb, int tid, int nt)
+{
+    const float *vhb = p.vh + bn, *vb = p.v + bn;
+    for (int i = tid; i < nb; i += nt) p.vsum[bn + i] = 0.0;
+    for (int j = tid; j < p2; j += nt) {
+        unsigned long long key = ~0ull;
+        if (j < nb) {
+            p.dj[bn + j] = vhb[j] - vb[j];
+            const int a = p.arow[bn + j];
+            if ((unsigned)a < (unsigned)nb) key = ((unsigned long long)(unsigned)a << 32) | (unsigned)j;
+        }
+        ord[j] = key;
+    }
+    __syncthreads();  // the keys, and the zeros of vsum before any head stores its sum
+    tl_bitonic_sort(ord, p2, tid, nt);
+    for (int k = tid; k < nb; k += nt) {
+        const unsigned long long e = ord[k];
+        if (e != ~0ull) {
+            const int j = (int)(unsigned)e;
+            ord[k] = (e & 0xffffffff00000000ull) | __float_as_uint(vhb[j] - vb[j]);
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < nb; k += nt) {
+        const unsigned long long e = ord[k];
+        if (e == ~0ull) continue;
+        const unsigned row = (unsigned)(e >> 32);
+        if (k > 0 && (unsigned)(ord[k - 1] >> 32) == row) continue;  // not the head of its run
+        double s = 0.0;
+        for (int q = k; q < nb; ++q) {
+            const unsigned long long f = ord[q];
+            if ((unsigned)(f >> 32) != row) break;
+            s += (double)__uint_as_float((unsigned)f);
+        }
+        p.vsum[bn + row] = s;
+    }
+    __syncthreads();  // ord[] goes to the row order next
+}
+
 // ------------------------------------------------------------------------------------------
 // One workgroup per instance.  Dynamic LDS: ord[p2] 64-bit words (p2 = n rounded up to a power of two),
 // then the used-column bitmap.  ord holds the sort keys (f32_key(m_i) << 32 | i), then per position of
 // the row order (first column to try << 32 | row), then (column taken << 32 | row), and at the end the
 // matched costs by row.
 // ------------------------------------------------------------------------------------------
+// kDual: the third term is v_reg of the DualGNN loss, and S_i and d_j are left for its backward.
+template <bool kDual>
 __global__ void __launch_bounds__(kTlGreedyThreads) tl_greedy_kernel(TrainLossParams p, int p2)
 {
     extern __shared__ unsigned long long ord[];
@@ -231,7 +303,7 @@ __global__ void __launch_bounds__(kTlGreedyThreads) tl_greedy_kernel(TrainLossPa
     double su = 0.0, sv = 0.0, sr = 0.0, sh = 0.0;
     for (int i = tid; i < nb; i += nt) {
         const float ui = ub[i];
-        const float d = ui - p.ut[bn + i];
+        const float d = kDual ? p.vh[bn + i] - vb[i] : ui - p.ut[bn + i];
         const float q = d * d;
         su += (double)ui;
         sv += (double)vb[i];
@@ -242,26 +314,14 @@ __global__ void __launch_bounds__(kTlGreedyThreads) tl_greedy_kernel(TrainLossPa
     sv = bc.sum_f64(sv);
     sr = bc.sum_f64(sr);
     sh = bc.sum_f64(sh);
+    if constexpr (kDual) tl_segment_sums(p, ord, p2, bn, nb, tid, nt);
 
     // row order: ascending (m_i, i)
     for (int i = tid; i < p2; i += nt)
         ord[i] = (i < nb) ? (((unsigned long long)p.mkey[bn + i] << 32) | (unsigned)i) : ~0ull;
     for (int w = tid; w < (n + 31) / 32; w += nt) used[w] = 0u;
     __syncthreads();
-    for (int k = 2; k <= p2; k <<= 1) {
-        for (int s = k >> 1; s > 0; s >>= 1) {
-            for (int t = tid; t < p2 / 2; t += nt) {
-                const int lo = ((t & ~(s - 1)) << 1) | (t & (s - 1));
-                const int hi = lo + s;
-                const unsigned long long x = ord[lo], y = ord[hi];
-                if ((x > y) == ((lo & k) == 0)) {
-                    ord[lo] = y;
-                    ord[hi] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    tl_bitonic_sort(ord, p2, tid, nt);
     for (int k = tid; k < nb; k += nt) {
         const unsigned row = (unsigned)ord[k];
         ord[k] = ((unsigned long long)(unsigned)p.mj[bn + row] << 32) | row;
@@ -364,6 +424,31 @@ tl_backward_kernel(TrainLossParams p, const float *weights, float grad_scale, fl
     grad_u[o] = (float)g;
 }
 
+// DualGNN backward, one thread per (b, i) and, with the same index, per (b, j):
+//   grad_u_i  = grad_scale * [ w0 (cnt_i - 1) + w1 (R_i - sum_{a_j = i} K_j) / n_b^2 + w2 2 S_i / n_b ]
+//   grad_vh_j = grad_scale * w2 2 d_j / n_b
+// in fp64, rounded once; 0 on the padding.
+__global__ void __launch_bounds__(kTlThreads)
+tl_dual_backward_kernel(TrainLossParams p, const float *weights, float grad_scale, float *grad_u, float *grad_vh)
+{
+    const int b = blockIdx.y, n = p.n;
+    const int i = blockIdx.x * kTlThreads + threadIdx.x;
+    if (i >= n) return;
+    const int nb = tl_size(p.sizes[b], n);
+    const size_t o = (size_t)b * n + i;
+    double g = 0.0, gv = 0.0;
+    if (i < nb) {
+        const double dn = (double)nb;
+        const double gap = (double)(p.cnt[o] - 1);
+        const double feas = (double)(p.R[o] - p.ksum[o]) / (dn * dn);
+        const double reg = 2.0 * p.vsum[o] / dn;
+        g = (double)grad_scale * ((double)weights[0] * gap + (double)weights[1] * feas + (double)weights[2] * reg);
+        gv = (double)grad_scale * ((double)weights[2] * (2.0 * (double)p.dj[o] / dn));
+    }
+    grad_u[o] = (float)g;
+    grad_vh[o] = (float)gv;
+}
+
 int tl_pow2(int n)
 {
     int q = 1;
@@ -403,12 +488,13 @@ hipError_t launch_train_loss_forward(const TrainLossParams &p, hipStream_t strea
     // always the limit of the largest n, never this call's size: calls from several host threads with
     // different n then cannot lower it under each other's launches
     constexpr int kMaxLds = (int)(sizeof(unsigned long long) * kTrainLossMaxN + sizeof(unsigned) * (kTrainLossMaxN / 32));
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(tl_greedy_kernel),
+    const auto greedy = p.vh ? tl_greedy_kernel<true> : tl_greedy_kernel<false>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(greedy),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
     if (e != hipSuccess) return e;
     int threads = (n + kWave - 1) / kWave * kWave;
     if (threads > kTlGreedyThreads) threads = kTlGreedyThreads;
-    hipLaunchKernelGGL(tl_greedy_kernel, dim3(batch), dim3(threads), lds, stream, p, p2);
+    hipLaunchKernelGGL(greedy, dim3(batch), dim3(threads), lds, stream, p, p2);
     return hipGetLastError();
 }
 
@@ -417,6 +503,14 @@ hipError_t launch_train_loss_backward(const TrainLossParams &p, const float *wei
 {
     hipLaunchKernelGGL(tl_backward_kernel, dim3((p.n + kTlThreads - 1) / kTlThreads, p.batch), dim3(kTlThreads), 0,
                        stream, p, weights, grad_scale, grad_u);
+    return hipGetLastError();
+}
+
+hipError_t launch_dual_loss_backward(const TrainLossParams &p, const float *weights, float grad_scale, float *grad_u,
+                                     float *grad_vh, hipStream_t stream)
+{
+    hipLaunchKernelGGL(tl_dual_backward_kernel, dim3((p.n + kTlThreads - 1) / kTlThreads, p.batch), dim3(kTlThreads),
+                       0, stream, p, weights, grad_scale, grad_u, grad_vh);
     return hipGetLastError();
 }
 

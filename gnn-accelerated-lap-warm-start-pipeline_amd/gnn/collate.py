@@ -25,6 +25,21 @@ class DeviceBatch:
     sizes: torch.Tensor     # (B,) int32
 
 
+@dataclass
+class DualDeviceBatch:
+    """A padded DualGNN batch on the device; N = the largest size.  The fields of the reference's Batch
+    (gnn/train.py:33-41), as its `collate` (:64-95) pads them, plus the sizes the mask stands for.  Made by
+    DualWarmStartPipeline.dual_training_batch."""
+    cost: torch.Tensor       # (B, N, N) float32, 0 outside the prefix
+    u: torch.Tensor          # (B, N) float32, 0 on padded rows
+    v: torch.Tensor          # (B, N) float32
+    row_feat: torch.Tensor   # (B, N, 14) float32, 0 on padded rows
+    col_feat: torch.Tensor   # (B, N, 14) float32, 0 on padded columns
+    edge_feat: torch.Tensor  # (B, N, N, 10) float32, 0 outside the prefix
+    mask: torch.Tensor       # (B, N) bool, the prefix mask
+    sizes: torch.Tensor      # (B,) int32
+
+
 def _host_vector(x, n, name):
     x = np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x).reshape(-1)
     if x.shape[0] < n:

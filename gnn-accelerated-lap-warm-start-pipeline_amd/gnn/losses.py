@@ -1,6 +1,7 @@
-"""The OneGNN training loss on the MI355X: `compute_loss` of the reference's gnn/train_one_gnn.py:180-226
-with its greedy primal bound (`greedy_primal_upper`, :137-177; `greedy_primal_upper_np` of eval.py) as HIP
-kernels (csrc/train_loss.hip), forward and backward.
+"""The training losses on the MI355X as HIP kernels (csrc/train_loss.hip), forward and backward: OneGNN's,
+`compute_loss` of the reference's gnn/train_one_gnn.py:180-226 with its greedy primal bound (`greedy_primal_upper`,
+:137-177; `greedy_primal_upper_np` of eval.py), as `warmstart_loss`; and DualGNN's, `compute_loss` of
+gnn/train.py:267-308 (the same body in gnn/train_progressive.py:226-281), as `dual_warmstart_loss`.
 
 Per instance with n_b valid rows and columns:
 
@@ -10,6 +11,15 @@ Per instance with n_b valid rows and columns:
     u_reg        = sum_i (u_i - u_target_i)^2 / n_b
     primal_upper = cost of the greedy assignment on (C_ij - u_i) - v_j   (a constant for autograd)
     loss         = w0 mean_b(primal_upper - dual_lower) + w1 mean_b(feas) + w2 mean_b(u_reg)
+
+DualGNN's loss has another third term, on the model's second output v_hint:
+
+    v_reg        = sum_j (v_hint_j - v_j)^2 / n_b
+    loss         = w0 mean_b(primal_upper - dual_lower) + w1 mean_b(feas) + w2 mean_b(v_reg)
+
+It sends 2 (v_hint_j - v_j) / n_b into v_hint_j and, because v_j = C_{a_j j} - u_{a_j}, the sum of those over the
+columns with a_j = i into u_i: an fp64 sum in ascending j without floating-point atomics, so equal inputs give
+equal bits.
 
 The float32 terms are the reference's; every sum is accumulated in fp64 and rounded to float32 once, so the
 values differ from the reference's float32 sums by its summation error, not by more.
@@ -35,10 +45,13 @@ __all__ = ["warmstart_loss", "greedy_primal_upper_batch"]
 DEFAULT_WEIGHTS = (1.0, 1.0, 0.1)  # primal gap, feasibility, u regulariser (train_one_gnn.py:215-219)
 
 
-def _check_args(cost, u_pred, u_target, mask):
-    """Argument errors, raised before any device work: types and dtypes, then shapes, then devices."""
+def _check_args(cost, u_pred, u_target, mask, v_hint=None):
+    """Argument errors, raised before any device work: types and dtypes, then shapes, then devices.  v_hint: the
+    second prediction of the DualGNN loss, checked like u_pred, behind it."""
     half = (torch.float16, torch.bfloat16, torch.float32)
     args = [("cost", cost, (torch.float32,)), ("u_pred", u_pred, half)]
+    if v_hint is not None:
+        args.append(("v_hint", v_hint, half))
     if u_target is not None:
         args.append(("u_target", u_target, (torch.float32,)))
     if mask is not None:
@@ -158,6 +171,76 @@ def warmstart_loss(cost, u_pred, u_target, mask, weights=DEFAULT_WEIGHTS):
     loss, primal_gap, dual_lower, feas, u_reg, primal_upper, v_proj, argmin_row, assign, ret = _WarmstartLoss.apply(
         u_pred, cost, u_target.contiguous(), sizes, w)
     metrics = dict(primal_gap=primal_gap, feas=feas, dual_lower=dual_lower, primal_upper=primal_upper, u_reg=u_reg,
+                   v_proj=v_proj, assign=assign, argmin_row=argmin_row, ret=ret)
+    return loss, metrics
+
+
+class _DualWarmstartLoss(torch.autograd.Function):
+    """loss = w0 mean(primal_upper - dual_lower) + w1 mean(feas) + w2 mean(v_reg); differentiable in u_pred and
+    v_hint.  The backward is one call of lapwarm_dual_loss_backward with grad_scale = 1 / B and the weights
+    multiplied by the incoming gradient on the device: nothing is added to what the kernel returns."""
+
+    @staticmethod
+    def forward(ctx, u_pred, v_hint, cost, sizes, weights):
+        lib = _hip.require_device()
+        u = u_pred.detach().to(torch.float32).contiguous()
+        vh = v_hint.detach().to(torch.float32).contiguous()
+        B, n = u.shape
+        dev = cost.device
+        v_proj = torch.empty((B, n), dtype=torch.float32, device=dev)
+        argmin_row = torch.empty((B, n), dtype=torch.int32, device=dev)
+        assign = torch.empty((B, n), dtype=torch.int32, device=dev)
+        terms = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        ret = torch.empty((B,), dtype=torch.int32, device=dev)
+        nbytes = int(lib.lapwarm_dual_loss_workspace_bytes(B, n))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        hip_call("lapwarm_dual_loss_forward", "dual_loss_forward", dev, cost, B, n, sizes, u, vh, v_proj, argmin_row,
+                 assign, terms, ret, ws, nbytes)
+        dual_lower, feas, v_reg, primal_upper = terms.unbind(1)
+        primal_gap = primal_upper - dual_lower
+        loss = weights[0] * primal_gap.mean() + weights[1] * feas.mean() + weights[2] * v_reg.mean()
+        ctx.save_for_backward(u, vh, sizes, weights, ws)
+        ctx.in_dtypes = (u_pred.dtype, v_hint.dtype)
+        ctx.mark_non_differentiable(primal_gap, dual_lower, feas, v_reg, primal_upper, v_proj, argmin_row, assign, ret)
+        return loss, primal_gap, dual_lower, feas, v_reg, primal_upper, v_proj, argmin_row, assign, ret
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, *unused):
+        u, vh, sizes, weights, ws = ctx.saved_tensors
+        _hip.require_device()
+        B, n = u.shape
+        w = (weights * grad_loss.to(torch.float32)).contiguous()
+        grad_u = torch.empty_like(u)
+        grad_vh = torch.empty_like(vh)
+        hip_call("lapwarm_dual_loss_backward", "dual_loss_backward", u.device, B, n, sizes, u, vh, w, 1.0 / B, grad_u,
+                 grad_vh, ws, ws.numel())
+        return grad_u.to(ctx.in_dtypes[0]), grad_vh.to(ctx.in_dtypes[1]), None, None, None
+
+
+def dual_warmstart_loss(cost, u_pred, v_hint, mask, weights=DEFAULT_WEIGHTS):
+    """The reference's DualGNN training loss (gnn/train.py:267-308) of a padded batch: ``(loss, metrics)``.
+
+    cost (B, n, n) float32 on the GPU; u_pred and v_hint (B, n), the model's two outputs, float32 (or half
+    precision, upcast to float32; each gradient comes back in its input's dtype); mask (B, n) bool, a prefix mask
+    as in `warmstart_loss`.  `weights` = (primal gap, feas, v_reg), three numbers or a float32 tensor of shape (3,)
+    on the GPU.  u_pred and v_hint receive gradients, from one backward kernel.  `metrics` is that of
+    `warmstart_loss` with v_reg in place of u_reg.  Apart from the first upload of a weights triple nothing is
+    copied from or to the host and nothing synchronises.  Ties: see the module docstring."""
+    if v_hint is None or mask is None:
+        raise TypeError("v_hint and mask are required")
+    if isinstance(weights, torch.Tensor):
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (3,):
+            raise ValueError("a weights tensor must be float32 of shape (3,)")
+    elif len(weights) != 3:
+        raise ValueError("weights must be (primal gap, feas, v_reg)")
+    _check_args(cost, u_pred, None, mask, v_hint)
+    cost = cost.contiguous()
+    sizes = mask.sum(1, dtype=torch.int32)
+    w = _device_weights(weights, cost.device)
+    loss, primal_gap, dual_lower, feas, v_reg, primal_upper, v_proj, argmin_row, assign, ret = _DualWarmstartLoss.apply(
+        u_pred, v_hint, cost, sizes, w)
+    metrics = dict(primal_gap=primal_gap, feas=feas, dual_lower=dual_lower, primal_upper=primal_upper, v_reg=v_reg,
                    v_proj=v_proj, assign=assign, argmin_row=argmin_row, ret=ret)
     return loss, metrics
 

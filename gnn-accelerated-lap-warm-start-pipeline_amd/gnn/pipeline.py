@@ -641,16 +641,46 @@ class WarmStartPipeline:
                                                             ("dual_noise_std", "dual_noise_prob"))
         pack = ragged_pack(costs, self.device)
         r = row_features_packed(pack, return_topk=True, want_cost32=True)
+        u, v = self._labels_packed(pack, r, dual_noise_std, dual_noise_prob, generator, "training_batch")
+        return DeviceBatch(cost=r.cost32, u=u, v=v, row_feat=r.feat, topk=r.topk, mask=r.mask, sizes=r.sizes)
+
+    def _labels_packed(self, pack, r, dual_noise_std, dual_noise_prob, generator, who):
+        """The label half of training_batch and dual_training_batch: the float32 targets u, v (B, N) of a packed
+        batch, from the matching of the seeded solve and its ragged oracle duals, noisy where asked.  `r`: the row
+        features of the pack (a OneGNN prediction reads them); `who` names the caller in the error."""
         x = self._matching_packed(pack, r)
         u, v, ret, _ = self.oracle_duals_ragged(pack, x)
         bad = torch.nonzero(ret).reshape(-1).tolist()
         if bad:
-            raise RuntimeError(f"training_batch: oracle duals of instance {bad[0]} (n = {pack.host_sizes[bad[0]]}) "
+            raise RuntimeError(f"{who}: oracle duals of instance {bad[0]} (n = {pack.host_sizes[bad[0]]}) "
                                f"failed with code {int(ret[bad[0]])}")
         if dual_noise_prob > 0.0 and dual_noise_std > 0.0:
             u, v, _ = self.noisy_duals_ragged(pack, u, v, dual_noise_std, generator=generator, prob=dual_noise_prob)
-        return DeviceBatch(cost=r.cost32, u=u.to(torch.float32), v=v.to(torch.float32), row_feat=r.feat,
-                           topk=r.topk, mask=r.mask, sizes=r.sizes)
+        return u.to(torch.float32), v.to(torch.float32)
+
+    def dual_training_batch(self, costs, dual_noise_std: float = 0.0, dual_noise_prob: float = 0.0, generator=None):
+        """costs of different sizes -> a labelled DualDeviceBatch (gnn/collate.py), the reference's `collate`
+        (gnn/train.py:64-95) with the labels made on the device and no per-instance host work: one ragged_pack (the
+        only upload of the costs), the ragged graph features (edge, row and column features, mask), the float32
+        costs, then the label half of training_batch: the matching of the seeded solve from this pipeline's model,
+        the ragged oracle duals of that matching as the float32 targets u, v (0 on padded rows) and, with
+        dual_noise_prob > 0 and dual_noise_std > 0, its noisy-label recipe with `generator`.  u and v are bit for
+        bit those of training_batch for the same costs.  The graph features limit every size to n <= 4096: a
+        larger one raises the ValueError of graph_features_packed.  Raises RuntimeError naming the first instance
+        whose oracle duals fail, with its code.  The method of a DualWarmStartPipeline: like the prediction, it goes
+        by the model's type, and a pipeline around another model raises TypeError."""
+        from .collate import DualDeviceBatch
+        dual_noise_std, dual_noise_prob = _check_noise_args(dual_noise_std, dual_noise_prob, generator,
+                                                            ("dual_noise_std", "dual_noise_prob"))
+        if not isinstance(self.model, DualGNN):
+            raise TypeError(f"dual_training_batch needs a pipeline around a DualGNN (DualWarmStartPipeline), not "
+                            f"{type(self.model).__name__}")
+        pack = ragged_pack(costs, self.device)
+        f = graph_features_packed(pack)
+        r = row_features_packed(pack, return_topk=False, want_cost32=True)  # the float32 cast, padded with 0
+        u, v = self._labels_packed(pack, r, dual_noise_std, dual_noise_prob, generator, "dual_training_batch")
+        return DualDeviceBatch(cost=r.cost32, u=u, v=v, row_feat=f.row, col_feat=f.col, edge_feat=f.edge, mask=f.mask,
+                               sizes=f.sizes)
 
     # ---- dual utilities of a ragged batch (csrc/ragged_duals.hip): solvers/advanced_dual.py:14-63 and the
     # classical seeds of solvers/seed_baselines.py for every instance of a pack in one call each

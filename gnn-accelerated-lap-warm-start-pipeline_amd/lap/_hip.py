@@ -95,6 +95,11 @@ SIGNATURES = {
                                               c_vp, c_vp, ct.c_size_t, c_vp]),
     "lapwarm_train_loss_backward": (ct.c_int, [ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, ct.c_float, c_vp, c_vp,
                                                ct.c_size_t, c_vp]),
+    "lapwarm_dual_loss_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_dual_loss_forward": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                             c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_dual_loss_backward": (ct.c_int, [ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, ct.c_float, c_vp, c_vp,
+                                              c_vp, ct.c_size_t, c_vp]),
     "lapwarm_refine_aggregate_batched": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int, ct.c_int,
                                                     ct.c_int, c_vp]),
     "lapwarm_refine_aggregate_wsum": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_int, ct.c_int, c_vp]),

@@ -433,6 +433,35 @@ int lapwarm_train_loss_backward(int batch, int n, const int *sizes, const float 
                                 const float *weights, float grad_scale, float *grad_u, const void *workspace,
                                 size_t workspace_bytes, void *stream);
 
+/* The DualGNN training loss, gnn/train.py:267-308 `compute_loss` (the same body in gnn/train_progressive.py:226-281)
+ * with its host greedy (:224-264).  Everything is as in lapwarm_train_loss_forward but the third term: v_hint
+ * [batch][n], the model's second output, takes the place of u_target, and terms [batch][4] = dual_lower (:282),
+ * feas (:284-288), v_reg (:299), primal_upper (:295), with v_reg = sum_{j < n_b} (v_hint_j - v_proj_j)^2 / n_b: the
+ * float32 difference and square of the reference, summed in fp64 in a fixed order and rounded once.  v_proj,
+ * argmin_row, assign, ret, ties and NaN are bit for bit those of lapwarm_train_loss_forward on the same C, sizes and
+ * u_pred.  The workspace (lapwarm_dual_loss_workspace_bytes: 0 out of range, else the training-loss workspace and,
+ * behind it, d_j = v_hint_j - v_proj_j and S_i = sum_{j: a_j = i} d_j) keeps what the backward needs.  S_i is an
+ * fp64 sum in ascending j, without floating-point atomics: equal inputs give equal bits.
+ * Returns 0, -2 for n <= 0, batch <= 0 or batch > 65535, -5 for n > 16384, -1 workspace too small, <= -1000 HIP
+ * error.  Four kernels on the caller's stream, no memset, no allocation, no host synchronisation; every workspace
+ * word that is read is written inside the call. */
+size_t lapwarm_dual_loss_workspace_bytes(int batch, int n);
+int lapwarm_dual_loss_forward(const float *C, int batch, int n, const int *sizes, const float *u_pred,
+                              const float *v_hint, float *v_proj, int *argmin_row, int *assign, float *terms,
+                              int *ret, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Gradient of  w0 (primal_upper - dual_lower) + w1 feas + w2 v_reg  of every instance with respect to u_pred and
+ * v_hint, times grad_scale (1 / batch for the reference's batch means, :301; primal_upper is a constant):
+ *   grad_u[b][i]      = grad_scale [ w0 (cnt_i - 1) + w1 (R_i - sum_{j: a_j = i} K_j) / n_b^2 + w2 2 S_i / n_b ]
+ *   grad_v_hint[b][j] = grad_scale   w2 2 d_j / n_b
+ * with cnt, R, K as in lapwarm_train_loss_backward: v_j = C_{a_j j} - u_{a_j}, so v_reg reaches u_i through the
+ * columns whose minimum row i attains.  Evaluated in fp64, rounded once; both 0 on the padding and for instances
+ * with ret 2.  weights [3] float32 on the device (the reference: 1, 1, 0.1); workspace: the one the forward call of
+ * the same batch, n, sizes, u_pred and v_hint wrote; it is only read.  One kernel; returns as the forward. */
+int lapwarm_dual_loss_backward(int batch, int n, const int *sizes, const float *u_pred, const float *v_hint,
+                               const float *weights, float grad_scale, float *grad_u, float *grad_v_hint,
+                               const void *workspace, size_t workspace_bytes, void *stream);
+
 /* OneGNN top-k refinement, aggregation part (gnn/one_gnn.py:139-155), float32:
  *   val_k = topk16[row][k] - u_pre[row]   (== topk(cost - u_pre): x -> x - c is monotone)
  *   w     = softmax(-val) over the finite entries (0 elsewhere)

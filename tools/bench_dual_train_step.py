@@ -9,7 +9,11 @@ every round; medians and spreads (max - min) over the rounds, and torch.cuda.max
 relative to what was allocated before it.  A path that runs out of memory is recorded as such.  Per-kernel times come
 from a separate run of this file with --only fused under `rocprofv3 --kernel-trace --stats`.
 
-Usage:  python tools/bench_dual_train_step.py [--reps 5] [--inner 3] [--only fused|plain] [--cases a,b] [--out FILE]
+With --loss the scalar is the reference's DualGNN training loss on the device (gnn.losses.dual_warmstart_loss on the
+float32 costs of the case): the measured step is forward, loss with its greedy, backward.
+
+Usage:  python tools/bench_dual_train_step.py [--reps 5] [--inner 3] [--only fused|plain] [--cases a,b] [--loss]
+                                              [--out FILE]
 """
 import argparse
 import json
@@ -33,6 +37,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--only", choices=("fused", "plain"), default=None)
     ap.add_argument("--cases", default="8x256,1x512,1x1024,ragged")
+    ap.add_argument("--loss", action="store_true", help="the step's scalar is dual_warmstart_loss")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -41,7 +46,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_dual_train_step.py needs the MI355X: nothing here is measured on a CPU")
     from gnn.dual_gnn import DualGNN
-    from gnn.features import graph_features_device, graph_features_packed, ragged_pack
+    from gnn.features import graph_features_device, graph_features_packed, ragged_pack, row_features_packed
+    from gnn.losses import dual_warmstart_loss
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     model = DualGNN(hidden_dim=args.hidden, layers=args.layers, heads=args.heads).to(dev).train()
@@ -52,23 +58,29 @@ def main():
             sizes = [int(x) for x in np.linspace(384, 640, 32).round()]
             pack = ragged_pack([torch.from_numpy(rs.uniform(0.0, 1.0, (m, m))).to(dev) for m in sizes], dev)
             f = graph_features_packed(pack)
-            return f.edge, f.row, f.col, f.mask, pack.sizes
+            cost = row_features_packed(pack, return_topk=False, want_cost32=True).cost32 if args.loss else None
+            return f.edge, f.row, f.col, f.mask, pack.sizes, cost
         B, n = (int(x) for x in case.split("x"))
-        edge, row, col = graph_features_device(torch.from_numpy(rs.uniform(0.0, 1.0, (B, n, n))).to(dev))
-        return edge, row, col, None, None
+        C = torch.from_numpy(rs.uniform(0.0, 1.0, (B, n, n))).to(dev)
+        edge, row, col = graph_features_device(C)
+        return edge, row, col, None, None, C.to(torch.float32) if args.loss else None
 
     lines = []
     for case in args.cases.split(","):
-        edge, row, col, mask, sizes = inputs(case)
+        edge, row, col, mask, sizes, cost = inputs(case)
         g = torch.Generator(device=dev).manual_seed(1)
         tu, tv = (torch.randn(edge.shape[:2], device=dev, generator=g) for _ in range(2))
         keep = torch.ones_like(tu) if mask is None else mask.to(tu.dtype)
+        keep_bool = keep.to(torch.bool)
 
         def step(fused):
             model.fused_attention_training = fused
             model.zero_grad(set_to_none=True)
             out = model(edge, row, col, mask, sizes=sizes if fused else None)
-            loss = (((out["u"] - tu) ** 2 + (out["v_hint"] - tv) ** 2) * keep).sum() / keep.sum()
+            if args.loss:
+                loss, _ = dual_warmstart_loss(cost, out["u"], out["v_hint"], keep_bool)
+            else:
+                loss = (((out["u"] - tu) ** 2 + (out["v_hint"] - tv) ** 2) * keep).sum() / keep.sum()
             loss.backward()
 
         def measure(fused):
@@ -96,7 +108,7 @@ def main():
                 if not got[p] or not isinstance(got[p][-1], str):  # a path that ran out of memory is not tried again
                     got[p].append(measure(p == "fused"))
         line = dict(case=case, shape=list(edge.shape[:2]), hidden=args.hidden, layers=args.layers, heads=args.heads,
-                    reps=args.reps, inner=args.inner)
+                    reps=args.reps, inner=args.inner, scalar="dual_warmstart_loss" if args.loss else "mse")
         for p in paths:
             if isinstance(got[p][-1], str):
                 line[f"{p}_failed"] = got[p][-1]
@@ -108,7 +120,7 @@ def main():
             line[f"{p}_peak_mib"] = round(max(b for _, b in got[p]) / 2**20, 1)
         print(json.dumps(line), flush=True)
         lines.append(line)
-        del edge, row, col, tu, tv, keep
+        del edge, row, col, tu, tv, keep, cost
         model.zero_grad(set_to_none=True)
         torch.cuda.empty_cache()
     if args.out:

@@ -9,7 +9,11 @@ with a host clock around work that ends in a device synchronise, alternating, af
 device figure is the mean of 50 back-to-back steps, so it includes the step's allocations.  Prints one JSON line
 per size; `composed_host_greedy_ms` is the part of the composed time spent in the host greedy, copies included.
 
-Usage:  python tools/bench_train_loss.py [--reps 5] [--sizes 512 2048] [--out FILE]
+With --dual the loss is DualGNN's (gnn.losses.dual_warmstart_loss: v_reg on a v_hint, two gradients) and the
+composed formula has its third term; `onegnn_device_ms` is then the OneGNN device loss on the same costs in the
+same run, 50 back-to-back steps as well: the dual loss should cost that plus the per-row segment sum.
+
+Usage:  python tools/bench_train_loss.py [--reps 5] [--sizes 512 2048] [--dual] [--out FILE]
 """
 import argparse
 import json
@@ -43,11 +47,11 @@ def greedy_on_host(cost, reduced):
     return float(cost[np.arange(n), taken].sum(dtype=np.float64))
 
 
-def composed_loss(cost, u_pred, u_target, mask, clock, weights=(1.0, 1.0, 0.1)):
+def composed_loss(cost, u_pred, u_target, mask, clock, weights=(1.0, 1.0, 0.1), v_hint=None):
     """The loss of DESIGN.md's table (section "Training loss") in torch ops on the tensors' device, float32
     throughout, with (B, n, n) temporaries and autograd doing the backward; the greedy bound is computed on
     the host, one instance at a time, from copies of C and the reduced costs.  clock["greedy"] collects the
-    time of that host part, copies included."""
+    time of that host part, copies included.  With v_hint the third term is DualGNN's v_reg on it."""
     B, n = u_pred.shape
     sizes = mask.sum(dim=1)
     pair = mask[:, :, None] & mask[:, None, :]
@@ -59,7 +63,10 @@ def composed_loss(cost, u_pred, u_target, mask, clock, weights=(1.0, 1.0, 0.1)):
     dual_lower = torch.where(mask, u_pred, zero).sum(dim=1) + v.sum(dim=1)
     residue = ((u_pred[:, :, None] + v[:, None, :]) - cost).clamp_min(0.0)
     feas = torch.where(pair, residue, zero).sum(dim=(1, 2)) / (sizes * sizes).to(cost.dtype)
-    u_reg = torch.where(mask, (u_pred - u_target).square(), zero).sum(dim=1) / sizes.to(cost.dtype)
+    if v_hint is None:
+        u_reg = torch.where(mask, (u_pred - u_target).square(), zero).sum(dim=1) / sizes.to(cost.dtype)
+    else:
+        u_reg = torch.where(mask, (v_hint - v).square(), zero).sum(dim=1) / sizes.to(cost.dtype)
     reduced = (shifted - v[:, None, :]).detach()
     t0 = time.perf_counter()
     host_sizes = sizes.tolist()
@@ -84,9 +91,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--sizes", type=int, nargs="+", default=[512, 2048])
+    ap.add_argument("--dual", action="store_true", help="time dual_warmstart_loss, the OneGNN loss beside it")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    from gnn.losses import warmstart_loss
+    from gnn.losses import dual_warmstart_loss, warmstart_loss
     if not torch.cuda.is_available():
         raise SystemExit("bench_train_loss.py needs the MI355X: nothing here is measured on a CPU")
     dev = torch.device("cuda:0")
@@ -98,19 +106,31 @@ def main():
         u_target = cost.min(dim=2).values
         u0 = u_target + 0.05 * torch.randn((B, n), dtype=torch.float32, device=dev, generator=g)
         mask = torch.ones((B, n), dtype=torch.bool, device=dev)
+        # --dual: v_hint = a random perturbation of the min-trick of u_target
+        v0 = (cost - u_target[:, :, None]).amin(dim=1) + 0.05 * torch.randn((B, n), dtype=torch.float32, device=dev,
+                                                                            generator=g) if args.dual else None
         clock = {"greedy": 0.0}
 
-        def device_step():
+        def onegnn_step():
             u = u0.clone().requires_grad_()
             loss, metrics = warmstart_loss(cost, u, u_target, mask)
             loss.backward()
             return loss.detach(), u.grad, metrics["primal_upper"]
 
+        def dual_step():
+            u, vh = u0.clone().requires_grad_(), v0.clone().requires_grad_()
+            loss, metrics = dual_warmstart_loss(cost, u, vh, mask)
+            loss.backward()
+            return loss.detach(), (u.grad, vh.grad), metrics["primal_upper"]
+
         def composed_step():
             u = u0.clone().requires_grad_()
-            loss, primal = composed_loss(cost, u, u_target, mask, clock)
+            vh = v0.clone().requires_grad_() if args.dual else None
+            loss, primal = composed_loss(cost, u, u_target, mask, clock, v_hint=vh)
             loss.backward()
-            return loss.detach(), u.grad, primal
+            return loss.detach(), (u.grad, vh.grad) if args.dual else u.grad, primal
+
+        device_step = dual_step if args.dual else onegnn_step
 
         timed(device_step)
         timed(composed_step)
@@ -135,8 +155,20 @@ def main():
                     speedup=round(float(np.median(t_ref)) / dev_ms, 1),
                     loss_device=float(loss_d), loss_composed=float(loss_c),
                     primal_equal=int((primal_d == primal_c).sum()),
-                    grad_max_abs_diff=float((grad_d - grad_c).abs().max()),
                     C_GBps_two_reads=round(2 * B * n * n * 4 / (dev_ms * 1e-3) / 1e9, 1))
+        if args.dual:
+            line["loss"] = "dual"
+            line["grad_max_abs_diff"] = float((grad_d[0] - grad_c[0]).abs().max())
+            line["grad_v_hint_max_abs_diff"] = float((grad_d[1] - grad_c[1]).abs().max())
+            onegnn_step()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(inner):
+                onegnn_step()
+            torch.cuda.synchronize()
+            line["onegnn_device_ms"] = round((time.perf_counter() - t0) * 1e3 / inner, 4)
+        else:
+            line["grad_max_abs_diff"] = float((grad_d - grad_c).abs().max())
         print(json.dumps(line), flush=True)
         lines.append(line)
     if args.out:
