@@ -26,6 +26,12 @@
 //                                    of a chunk of edges and the way back through it, rows into the workspace
 //   dual_edge_wgrad_kernel           62 VGPRs, no LDS, 8 waves/SIMD: the five sums over edges as TN MFMA products
 //   dual_edge_wgrad_reduce_kernel    workgroups and chunks in order, fp64, rounded once
+//
+// Dropout inside the fused region (dual_dropout.hpp; DESIGN.md, "DualGNN backward"): every kernel that sees h1 or an
+// attention weight is a template <bool DROP>.  The figures above are those of DROP = false, whose code is unchanged;
+// DROP = true regenerates the mask from (seed, stream, element index) wherever it is needed, stores none, and takes
+// 227 (edge scores), 244 (ragged), 102 (attention), 101 / 108 (backward query / key) and 244 (edge backward) VGPRs
+// with the same LDS, no scratch and the same waves per SIMD (profiles/dual_gnn_dropout.md).
 #include "dual_gnn.hpp"
 
 #include <atomic>
@@ -93,10 +99,37 @@ __device__ __forceinline__ EsWeights es_stage_weights(const float *W1, const flo
     return EsWeights{W2s, Gs, W1s, b1s, b2s};
 }
 
+// The keep bits of a lane's edge (dual_dropout.hpp, stream 0): the lane holds the units 16 t + 4 g + r of its edge,
+// the group 4 t + g of four consecutive units, so one Philox call gives the four registers of a (t, g).  Bit 4 t + r
+// is the keep flag of h1[t][r].  `edge` is the edge's index (b N + i) N + j in the padded layout.
+__device__ __forceinline__ unsigned es_keep_bits(const DualDropout &d, unsigned long long edge, int g)
+{
+    unsigned bits = 0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        unsigned wd[4];
+        dual_dropout_words(d.k0, d.k1, kDropStreamEdge, edge * (kHid / 4) + 4 * t + g, wd);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bits |= (wd[r] >= d.threshold ? 1u : 0u) << (4 * t + r);
+    }
+    return bits;
+}
+
+// keep * scale * h1 for block t of a lane's h1
+__device__ __forceinline__ f32x4 es_drop4(f32x4 v, unsigned bits, int t, float scale)
+{
+    f32x4 o;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = ((bits >> (4 * t + r)) & 1u) ? v[r] * scale : 0.0f;
+    return o;
+}
+
 // The scores of one wave's 16 edges: f, the edge's features or null for a lane without an edge (read as zeros);
 // lane group g = lane >> 4 holds the outputs 4 g + r in register r.  An edge is one column of every product, so its
-// scores do not depend on which edges share its tile.
-__device__ __forceinline__ f32x4 es_wave_tile(const EsWeights &w, const float *f, int col, int g)
+// scores do not depend on which edges share its tile.  DROP: h1 is keep * scale * h1, `keep` from es_keep_bits.
+template <bool DROP>
+__device__ __forceinline__ f32x4 es_wave_tile(const EsWeights &w, const float *f, int col, int g, unsigned keep = 0,
+                                              float scale = 1.0f)
 {
     // B fragments of the first product: F^T, k = 4 s + g on the lane group, edge on lane & 15
     float fb[3];
@@ -113,6 +146,7 @@ __device__ __forceinline__ f32x4 es_wave_tile(const EsWeights &w, const float *f
         for (int s = 0; s < 3; ++s)
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.W1s[(16 * m + col) * kKPad + 4 * s + g], fb[s], acc, 0, 0, 0);
         h1[m] = gelu4(acc);
+        if constexpr (DROP) h1[m] = es_drop4(h1[m], keep, m, scale);
     }
     // second and third product together: block m of h2 is the k-steps (t = m, r) of the third product, so it
     // is used as soon as it exists.  The loop over m stays rolled (two blocks per trip: two independent
@@ -135,9 +169,11 @@ __device__ __forceinline__ f32x4 es_wave_tile(const EsWeights &w, const float *f
     return sc;
 }
 
+template <bool DROP>
 __global__ void __launch_bounds__(kEsThreads)
 dual_edge_scores_kernel(const float *F, const float *W1, const float *b1, const float *W2, const float *b2,
-                        const float *G, float *scores, long long E, long long NN, int heads, long long tiles)
+                        const float *G, float *scores, long long E, long long NN, int heads, long long tiles,
+                        DualDropout drop)
 {
     const int outs = 2 * heads;
     const EsWeights w = es_stage_weights(W1, b1, W2, b2, G, outs);
@@ -146,7 +182,9 @@ dual_edge_scores_kernel(const float *F, const float *W1, const float *b1, const 
     const int col = lane & 15, g = lane >> 4;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const long long e = tile * kEsTile + (long long)wave * kEsEdgesPerWave + col;
-        const f32x4 sc = es_wave_tile(w, e < E ? F + e * kDualEdgeIn : nullptr, col, g);
+        // the keep bits before the MFMA chain, while few registers are live
+        const unsigned keep = DROP ? es_keep_bits(drop, (unsigned long long)e, g) : 0u;
+        const f32x4 sc = es_wave_tile<DROP>(w, e < E ? F + e * kDualEdgeIn : nullptr, col, g, keep, drop.scale);
         // the tail tile: an edge past the end was read as zeros and is not written
         if (e < E) {
             const long long b = e / NN, rem = e - b * NN;
@@ -165,9 +203,11 @@ dual_edge_scores_kernel(const float *F, const float *W1, const float *b1, const 
 // the other, row by row, and wave w of workgroup g takes the numbers 8 g + w, + 8 gridDim.x, ...  A wave walks the
 // instances in order with the running first number of each, so no prefix sum is stored anywhere, and the waves of
 // a workgroup share no barrier after the weights are staged.
+template <bool DROP>
 __global__ void __launch_bounds__(kEsThreads)
 dual_edge_scores_ragged_kernel(const float *F, const float *W1, const float *b1, const float *W2, const float *b2,
-                               const float *G, float *scores, const int *sizes, int batch, int N, int heads)
+                               const float *G, float *scores, const int *sizes, int batch, int N, int heads,
+                               DualDropout drop)
 {
     const int outs = 2 * heads;
     const EsWeights w = es_stage_weights(W1, b1, W2, b2, G, outs);
@@ -186,7 +226,9 @@ dual_edge_scores_ragged_kernel(const float *F, const float *W1, const float *b1,
             const int t = (int)(next - first);
             const int i = t / groups, j = (t - i * groups) * kEsEdgesPerWave + col;
             const size_t at = (size_t)i * N + j;
-            const f32x4 sc = es_wave_tile(w, j < n ? F + ((size_t)b * NN + at) * kDualEdgeIn : nullptr, col, g);
+            const unsigned keep = DROP ? es_keep_bits(drop, (unsigned long long)b * NN + at, g) : 0u;
+            const f32x4 sc = es_wave_tile<DROP>(w, j < n ? F + ((size_t)b * NN + at) * kDualEdgeIn : nullptr, col, g,
+                                                keep, drop.scale);
             if (j < n) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -206,6 +248,17 @@ constexpr int kDChunk = 128;   // head_dim columns per pass over the keys: 8 per
 
 __device__ __forceinline__ float at_neg_inf() { return __int_as_float(0xff800000); }
 
+// The index of (b, dir, h, query 0, key 0) in the logical tensor of the attention weights (dual_dropout.hpp, stream 1)
+__device__ __forceinline__ unsigned long long at_drop_base(int b, int dir, int h, int heads, int N)
+{
+    return (unsigned long long)(((size_t)b * 2 + dir) * heads + h) * N * N;
+}
+
+// DROP: the tile of exp(score - max) carries the keep flag of its (query, key) in the sign bit (an exp is never
+// negative): -e is a dropped weight.  The sum takes |e|, the weighted values e * scale or 0, so the statistics are
+// those of the undropped softmax and LDS holds what it held.  The flag is a function of (q, k) alone: every pass over
+// the keys (head_dim > 128) sees the same mask.
+template <bool DROP>
 __global__ void __launch_bounds__(kAtThreads) dual_attention_kernel(DualAttnParams p)
 {
     __shared__ float s_e[kTQ][kTK + 1];
@@ -240,6 +293,7 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_kernel(DualAttnPara
         return;
     }
     const float kb = p.kbias[dir * p.heads + h];
+    const unsigned long long drop_base = DROP ? at_drop_base(b, dir, h, p.heads, N) : 0;
 
     // the tile s_e[q][k] of leaky_relu scores (pass 0) or of exp(score - max) (pass 1).  Loads run along the
     // contiguous index of scores: the key for the row direction, the query for the column direction.
@@ -256,6 +310,9 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_kernel(DualAttnPara
                 s = s >= 0.0f ? s : 0.2f * s;
             }
             if (exps) s = (s == at_neg_inf()) ? 0.0f : expf(s - s_max[lq]);
+            if constexpr (DROP) {
+                if (exps && !dual_dropout_keep(p.drop, kDropStreamAttn, drop_base + (size_t)q * N + k)) s = -s;
+            }
             s_e[lq][lk] = s;
         }
     };
@@ -287,8 +344,13 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_kernel(DualAttnPara
             }
             __syncthreads();
             for (int k = 0; k < kTK; ++k) {
-                const float e = s_e[cq][k];
-                sum += e;
+                float e = s_e[cq][k];
+                if constexpr (DROP) {
+                    sum += fabsf(e);
+                    e = (__float_as_uint(e) >> 31) ? 0.0f : e * p.drop.scale;
+                } else {
+                    sum += e;
+                }
 #pragma unroll
                 for (int r = 0; r < kDChunk / 16; ++r) {
                     const int d = slot + 16 * r;
@@ -353,6 +415,9 @@ constexpr int kBwVStride = kDChunk + 1;  // a thread reads the rows slot + 16 r 
 // Query-major: one workgroup per (16 queries, head, direction, instance) walks the key tiles; dS, da and the
 // workgroup's part of dkb.  The tile of z is loaded, and the tile of dz stored, along the contiguous index of the
 // scores as the forward's load_tile does; thread (cq, slot) owns the keys slot + 16 r of query cq in between.
+// DROP: dw[q,k] = keep * scale * (dmsg[q] . val[k]), the mask of the forward regenerated; delta = sum_k w dw is then
+// dmsg[q] . msg[q] with msg the dropped message, and dz = w (dw - delta) slope as without dropout.
+template <bool DROP>
 __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_query_kernel(DualAttnBwdParams p)
 {
     __shared__ float s_z[kTQ][kTK + 1];
@@ -376,6 +441,7 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_query_kernel(Du
         return;
     }
     const int q = q0 + cq;
+    const unsigned long long drop_base = DROP ? at_drop_base(b, dir, h, heads, N) : 0;
     const bool live = q < nb && (!v.mask || v.mask[q]);
     float mq = 0.0f, sq = 1.0f;
     if (live) {
@@ -441,6 +507,8 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_query_kernel(Du
         for (int r = 0; r < kTK / 16; ++r) {
             const int k = slot + 16 * r;
             const float z = s_z[cq][k];
+            if constexpr (DROP)
+                dw[r] *= dual_dropout_factor(p.fwd.drop, kDropStreamAttn, drop_base + (size_t)q * N + (k0 + k));
             if (z != at_neg_inf()) {
                 const float s = z >= 0.0f ? z : 0.2f * z;
                 delta += (expf(s - mq) / sq) * dw[r];
@@ -497,6 +565,8 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_query_kernel(Du
 
 // Key-major: one workgroup per (16 keys, head, direction, instance) walks the query tiles, the forward with the
 // roles swapped: dc[k] = sum_q dS[q,k] (read back) and dval[k] = sum_q w[q,k] dmsg[q] with w recomputed.
+// DROP: dval[k] = sum_q w keep scale dmsg[q] with the element index of the query-major kernel.
+template <bool DROP>
 __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_key_kernel(DualAttnBwdParams p)
 {
     __shared__ float s_w[kTQ][kTK + 1];   // [key][query]
@@ -512,6 +582,7 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_key_kernel(Dual
     float *dc = (dir ? p.dc_col : p.dc_row) + ((size_t)b * heads + h) * N;
     float *dval = (dir ? p.d_row_val : p.d_col_val) + (size_t)b * N * hidden + (size_t)h * D;
     const int ck = tid >> 4, slot = tid & 15;
+    const unsigned long long drop_base = DROP ? at_drop_base(b, dir, h, heads, N) : 0;
     if (kk0 >= nb) {  // padded keys
         for (int idx = tid; idx < kTQ * D; idx += kAtThreads) {
             const int k = kk0 + idx / D;
@@ -538,6 +609,8 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_key_kernel(Dual
                     const float z = ((v.a[q] + v.c[k]) + v.sc[at]) + v.kb;
                     const float s = z >= 0.0f ? z : 0.2f * z;
                     w = expf(s - v.stats[(size_t)q * 2]) / v.stats[(size_t)q * 2 + 1];
+                    if constexpr (DROP)
+                        w *= dual_dropout_factor(p.fwd.drop, kDropStreamAttn, drop_base + (size_t)q * N + k);
                     g = dS[at];
                 }
                 s_w[lk][lq] = w;
@@ -624,9 +697,12 @@ __device__ __forceinline__ float gelu_grad(float x)
 }
 
 // One wave tile.  f: the features of the lane's edge or null; ds: dS of the lane's edge for the outputs 4 s + g
-// (zeros for a lane without an edge and past 2 * heads); row: the lane's workspace row.
+// (zeros for a lane without an edge and past 2 * heads); row: the lane's workspace row.  DROP: the recompute applies
+// the forward's mask (`keep` from es_keep_bits), the row's h1 is the dropped one, which dW2 needs, and
+// dx1 = dh1 * keep * scale * GELU'(x1).
+template <bool DROP>
 __device__ __forceinline__ void eb_wave_tile(const EsWeights &w, const float *f, const float (&ds)[4], float *row,
-                                             int col, int g)
+                                             int col, int g, unsigned keep = 0, float scale = 1.0f)
 {
     float fb[3];
 #pragma unroll
@@ -642,6 +718,7 @@ __device__ __forceinline__ void eb_wave_tile(const EsWeights &w, const float *f,
         for (int s = 0; s < 3; ++s)
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.W1s[(16 * m + col) * kKPad + 4 * s + g], fb[s], acc, 0, 0, 0);
         h1[m] = gelu4(acc);
+        if constexpr (DROP) h1[m] = es_drop4(h1[m], keep, m, scale);
         *reinterpret_cast<f32x4 *>(&row[kRowH1 + 16 * m + 4 * g]) = h1[m];
     }
     f32x4 dh1[8];
@@ -680,6 +757,7 @@ __device__ __forceinline__ void eb_wave_tile(const EsWeights &w, const float *f,
         f32x4 d;
 #pragma unroll
         for (int r = 0; r < 4; ++r) d[r] = dh1[t][r] * gelu_grad(acc[r]);
+        if constexpr (DROP) d = es_drop4(d, keep, t, scale);
         *reinterpret_cast<f32x4 *>(&row[kRowDh1 + 16 * t + 4 * g]) = d;
     }
 #pragma unroll
@@ -692,10 +770,11 @@ __device__ __forceinline__ void eb_wave_tile(const EsWeights &w, const float *f,
 
 // The wave tiles [t0, t1) of the batch: numbered 16 edges at a time in the linear edge order (sizes null) or as
 // dual_edge_scores_ragged_kernel numbers them.  Wave tile t writes the rows 16 (t - t0) .. + 15.
+template <bool DROP>
 __global__ void __launch_bounds__(kEsThreads)
 dual_edge_backward_kernel(const float *F, const float *W1, const float *b1, const float *W2, const float *b2,
                           const float *G, const float *dS, const int *sizes, int batch, int N, int heads,
-                          long long t0, long long t1, float *rows)
+                          long long t0, long long t1, float *rows, DualDropout drop)
 {
     const int outs = 2 * heads;
     const EsWeights w = es_stage_weights(W1, b1, W2, b2, G, outs);
@@ -714,7 +793,10 @@ dual_edge_backward_kernel(const float *F, const float *W1, const float *b1, cons
             ds[s] = (at >= 0 && o < outs) ? dS[((size_t)b * outs + o) * NN + (size_t)at] : 0.0f;
         }
         float *row = rows + ((size_t)(t - t0) * kEsEdgesPerWave + col) * kRowFloats;
-        eb_wave_tile(w, at >= 0 ? F + ((size_t)b * NN + (size_t)at) * kDualEdgeIn : nullptr, ds, row, col, g);
+        // a lane without an edge has dS = 0, hence dx2 = dx1 = 0 whatever its bits are
+        const unsigned keep = DROP ? es_keep_bits(drop, (unsigned long long)b * NN + (at >= 0 ? at : 0), g) : 0u;
+        eb_wave_tile<DROP>(w, at >= 0 ? F + ((size_t)b * NN + (size_t)at) * kDualEdgeIn : nullptr, ds, row, col, g,
+                           keep, drop.scale);
     };
     if (!sizes) {
         const long long E = (long long)NN * batch;
@@ -838,39 +920,93 @@ size_t dual_gnn_workspace_bytes(int batch, int n, int heads)
     return (bytes + 255) & ~(size_t)255;
 }
 
-hipError_t launch_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                   const float *b2, const float *G, float *scores, int batch, int n, int heads,
-                                   hipStream_t stream)
+namespace {
+
+template <bool DROP>
+hipError_t edge_scores_uniform(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                               const float *b2, const float *G, float *scores, int batch, int n, int heads,
+                               const DualDropout &drop, hipStream_t stream)
 {
     const long long NN = (long long)n * n, E = NN * batch;
     const long long tiles = (E + kEsTile - 1) / kEsTile;
     const int blocks = (int)(tiles < kEsMaxBlocks ? tiles : kEsMaxBlocks);
     static std::atomic<bool> raised{false};
-    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(dual_edge_scores_kernel), raised)) return e;
-    hipLaunchKernelGGL(dual_edge_scores_kernel, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream, edge_feat, W1,
-                       b1, W2, b2, G, scores, E, NN, heads, tiles);
+    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(dual_edge_scores_kernel<DROP>), raised)) return e;
+    hipLaunchKernelGGL(dual_edge_scores_kernel<DROP>, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream, edge_feat,
+                       W1, b1, W2, b2, G, scores, E, NN, heads, tiles, drop);
     return hipGetLastError();
 }
 
-hipError_t launch_dual_edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                          const float *b2, const float *G, float *scores, const int *sizes, int batch,
-                                          int n, int heads, hipStream_t stream)
+template <bool DROP>
+hipError_t edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                              const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
+                              int heads, const DualDropout &drop, hipStream_t stream)
 {
     // the sizes are on the device: the grid is sized for the padded batch, and a workgroup without a tile leaves
     const long long wave_tiles = (long long)batch * n * ((n + kEsEdgesPerWave - 1) / kEsEdgesPerWave);
     const long long tiles = (wave_tiles + kEsWaves - 1) / kEsWaves;
     const int blocks = (int)(tiles < kEsMaxBlocks ? tiles : kEsMaxBlocks);
     static std::atomic<bool> raised{false};
-    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(dual_edge_scores_ragged_kernel), raised)) return e;
-    hipLaunchKernelGGL(dual_edge_scores_ragged_kernel, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream, edge_feat,
-                       W1, b1, W2, b2, G, scores, sizes, batch, n, heads);
+    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(dual_edge_scores_ragged_kernel<DROP>), raised))
+        return e;
+    hipLaunchKernelGGL(dual_edge_scores_ragged_kernel<DROP>, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream,
+                       edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                   const float *b2, const float *G, float *scores, int batch, int n, int heads,
+                                   hipStream_t stream)
+{
+    return edge_scores_uniform<false>(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, DualDropout{}, stream);
+}
+
+hipError_t launch_dual_edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                          const float *b2, const float *G, float *scores, const int *sizes, int batch,
+                                          int n, int heads, hipStream_t stream)
+{
+    return edge_scores_ragged<false>(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, DualDropout{},
+                                     stream);
+}
+
+hipError_t launch_dual_edge_scores_dropout(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                           const float *b2, const float *G, float *scores, const int *sizes, int batch,
+                                           int n, int heads, const DualDropout &drop, hipStream_t stream)
+{
+    if (!drop.on) {
+        return sizes ? launch_dual_edge_scores_ragged(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, stream)
+                     : launch_dual_edge_scores(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, stream);
+    }
+    return sizes ? edge_scores_ragged<true>(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop, stream)
+                 : edge_scores_uniform<true>(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, drop, stream);
 }
 
 hipError_t launch_dual_attention(const DualAttnParams &p, hipStream_t stream)
 {
     const dim3 grid((p.n + kTQ - 1) / kTQ, p.heads, 2 * p.batch);
-    hipLaunchKernelGGL(dual_attention_kernel, grid, dim3(kAtThreads), 0, stream, p);
+    if (p.drop.on)
+        hipLaunchKernelGGL(dual_attention_kernel<true>, grid, dim3(kAtThreads), 0, stream, p);
+    else
+        hipLaunchKernelGGL(dual_attention_kernel<false>, grid, dim3(kAtThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256)
+dual_dropout_keep_kernel(DualDropout drop, unsigned stream_id, unsigned long long first, unsigned long long count,
+                         unsigned char *keep)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < count) keep[i] = dual_dropout_keep(drop, stream_id, first + i) ? 1 : 0;
+}
+
+hipError_t launch_dual_dropout_keep(const DualDropout &drop, unsigned stream_id, unsigned long long first,
+                                    unsigned long long count, unsigned char *keep, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(dual_dropout_keep_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, drop,
+                       stream_id, first, count, keep);
     return hipGetLastError();
 }
 
@@ -917,9 +1053,15 @@ hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_
     const DualAttnParams &f = p.fwd;
     const int tiles = (f.n + kTQ - 1) / kTQ;
     const dim3 grid(tiles, f.heads, 2 * f.batch);
-    hipLaunchKernelGGL(dual_attention_bwd_query_kernel, grid, dim3(kAtThreads), 0, stream, p);
+    if (f.drop.on)
+        hipLaunchKernelGGL(dual_attention_bwd_query_kernel<true>, grid, dim3(kAtThreads), 0, stream, p);
+    else
+        hipLaunchKernelGGL(dual_attention_bwd_query_kernel<false>, grid, dim3(kAtThreads), 0, stream, p);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(dual_attention_bwd_key_kernel, grid, dim3(kAtThreads), 0, stream, p);
+    if (f.drop.on)
+        hipLaunchKernelGGL(dual_attention_bwd_key_kernel<true>, grid, dim3(kAtThreads), 0, stream, p);
+    else
+        hipLaunchKernelGGL(dual_attention_bwd_key_kernel<false>, grid, dim3(kAtThreads), 0, stream, p);
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(dual_attention_bwd_kbias_kernel, dim3(2 * f.heads), dim3(kAtThreads), 0, stream, p.partials,
                        p.dkb, f.batch, f.heads, tiles);
@@ -929,7 +1071,8 @@ hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_
 hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
                                             const float *b2, const float *G, const float *dS, const int *sizes,
                                             float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch,
-                                            int n, int heads, void *workspace, hipStream_t stream)
+                                            int n, int heads, void *workspace, hipStream_t stream,
+                                            const DualDropout &drop)
 {
     const EdgeBwdLayout l = edge_bwd_layout(batch, n);
     const long long E = (long long)batch * n * n;
@@ -938,14 +1081,20 @@ hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float 
     float *rows = static_cast<float *>(workspace);
     float *partials = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + l.partials_at);
     double *sums = reinterpret_cast<double *>(static_cast<unsigned char *>(workspace) + l.sums_at);
-    static std::atomic<bool> raised{false};
-    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(dual_edge_backward_kernel), raised)) return e;
+    static std::atomic<bool> raised{false}, raised_drop{false};
+    if (hipError_t e = drop.on ? es_raise_lds(reinterpret_cast<const void *>(dual_edge_backward_kernel<true>), raised_drop)
+                               : es_raise_lds(reinterpret_cast<const void *>(dual_edge_backward_kernel<false>), raised))
+        return e;
     for (long long t0 = 0; t0 < tiles; t0 += chunk) {
         const long long t1 = t0 + chunk < tiles ? t0 + chunk : tiles;
         const long long wgs = (t1 - t0 + kEsWaves - 1) / kEsWaves;
         const int blocks = (int)(wgs < kEsMaxBlocks ? wgs : kEsMaxBlocks);
-        hipLaunchKernelGGL(dual_edge_backward_kernel, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream, edge_feat,
-                           W1, b1, W2, b2, G, dS, sizes, batch, n, heads, t0, t1, rows);
+        if (drop.on)
+            hipLaunchKernelGGL(dual_edge_backward_kernel<true>, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream,
+                               edge_feat, W1, b1, W2, b2, G, dS, sizes, batch, n, heads, t0, t1, rows, drop);
+        else
+            hipLaunchKernelGGL(dual_edge_backward_kernel<false>, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream,
+                               edge_feat, W1, b1, W2, b2, G, dS, sizes, batch, n, heads, t0, t1, rows, drop);
         if (hipError_t e = hipGetLastError()) return e;
         const int wg = (int)(((t1 - t0) * kEsEdgesPerWave + l.per - 1) / l.per);
         hipLaunchKernelGGL(dual_edge_wgrad_kernel, dim3(wg), dim3(kEsThreads), 0, stream, rows, sizes, batch, n, t0, t1,

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "dual_dropout.hpp"
+
 namespace lapwarm {
 
 constexpr int kDualMaxHeads = 8;      // 2 * heads outputs fit the 16-wide MFMA tile
@@ -33,6 +35,9 @@ struct DualAttnParams {
     // [batch][heads][n][2] or null: the maximum and the sum of exp(s - max) of every query's softmax, for the
     // backward.  Null pointers leave the kernel's arithmetic and every message bit as they are.
     float *row_stats = nullptr, *col_stats = nullptr;
+    // The dropout of the attention weights (stream 1 of dual_dropout.hpp), off by default: the weighted values use
+    // w * keep * scale, the statistics stay those of the undropped softmax, and the backward regenerates the mask.
+    DualDropout drop{};
 };
 
 // The backward of the attention (dual_gnn.hip): fwd holds the forward's inputs, its messages and its statistics
@@ -55,6 +60,11 @@ size_t dual_gnn_workspace_bytes(int batch, int n, int heads);  // the scores ten
 hipError_t launch_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2,
                                    const float *b2, const float *G, float *scores, int batch, int n, int heads,
                                    hipStream_t stream);
+// With drop.on, h1 = GELU(W1 f + b1) is replaced by keep * scale * h1 (stream 0 of dual_dropout.hpp) before the second
+// product; sizes null: the uniform batch.  With drop.on false: the launch above or the ragged one below.
+hipError_t launch_dual_edge_scores_dropout(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                           const float *b2, const float *G, float *scores, const int *sizes, int batch,
+                                           int n, int heads, const DualDropout &drop, hipStream_t stream);
 // The same scores for a padded batch of instances of sizes[b] (device, [batch]; a size outside 1..n: no edge): only
 // the edges (i, j < sizes[b]) are computed, a row's tail rounded up to 16 edges, and written; scores outside the
 // prefixes are left as they are.  On the prefixes the bits are launch_dual_edge_scores's on the same input.
@@ -73,6 +83,10 @@ hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_
 hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
                                             const float *b2, const float *G, const float *dS, const int *sizes,
                                             float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch,
-                                            int n, int heads, void *workspace, hipStream_t stream);
+                                            int n, int heads, void *workspace, hipStream_t stream,
+                                            const DualDropout &drop = DualDropout{});
+// keep[i] = 1 if element first + i of the stream is kept, else 0, for i < count: the keep rule itself, for tests
+hipError_t launch_dual_dropout_keep(const DualDropout &drop, unsigned stream_id, unsigned long long first,
+                                    unsigned long long count, unsigned char *keep, hipStream_t stream);
 
 }  // namespace lapwarm

@@ -646,14 +646,14 @@ size_t lapwarm_dual_backward_workspace_bytes(int batch, int n, int heads)
 
 int lapwarm_dual_backward_chunk(void) { return kDualBwdChunk; }
 
-int lapwarm_dual_attention_backward(const float *scores, const float *a_row, const float *c_row, const float *a_col,
-                                    const float *c_col, const float *kbias, const unsigned char *mask,
-                                    const int *sizes, const float *row_val, const float *col_val,
-                                    const float *row_msg, const float *col_msg, const float *row_stats,
-                                    const float *col_stats, const float *d_row_msg, const float *d_col_msg, float *dS,
-                                    float *da_row, float *dc_row, float *da_col, float *dc_col, float *dkb,
-                                    float *d_row_val, float *d_col_val, int batch, int n, int heads, int head_dim,
-                                    void *workspace, size_t workspace_bytes, void *stream_)
+static int dual_attention_backward(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                                   const float *c_col, const float *kbias, const unsigned char *mask,
+                                   const int *sizes, const float *row_val, const float *col_val,
+                                   const float *row_msg, const float *col_msg, const float *row_stats,
+                                   const float *col_stats, const float *d_row_msg, const float *d_col_msg, float *dS,
+                                   float *da_row, float *dc_row, float *da_col, float *dc_col, float *dkb,
+                                   float *d_row_val, float *d_col_val, int batch, int n, int heads, int head_dim,
+                                   void *workspace, size_t workspace_bytes, const DualDropout &drop, void *stream_)
 {
     if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads || head_dim < 1) return -2;
     if (n > kMaxN) return -5;
@@ -665,7 +665,7 @@ int lapwarm_dual_attention_backward(const float *scores, const float *a_row, con
     DualAttnBwdParams p{};
     p.fwd = DualAttnParams{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val,
                            const_cast<float *>(row_msg), const_cast<float *>(col_msg), batch, n, heads, head_dim,
-                           sizes, const_cast<float *>(row_stats), const_cast<float *>(col_stats)};
+                           sizes, const_cast<float *>(row_stats), const_cast<float *>(col_stats), drop};
     p.d_row_msg = d_row_msg;
     p.d_col_msg = d_col_msg;
     p.dS = dS;
@@ -681,10 +681,25 @@ int lapwarm_dual_attention_backward(const float *scores, const float *a_row, con
     return 0;
 }
 
-int lapwarm_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                      const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
-                                      float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
-                                      void *workspace, size_t workspace_bytes, void *stream_)
+int lapwarm_dual_attention_backward(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                                    const float *c_col, const float *kbias, const unsigned char *mask,
+                                    const int *sizes, const float *row_val, const float *col_val,
+                                    const float *row_msg, const float *col_msg, const float *row_stats,
+                                    const float *col_stats, const float *d_row_msg, const float *d_col_msg, float *dS,
+                                    float *da_row, float *dc_row, float *da_col, float *dc_col, float *dkb,
+                                    float *d_row_val, float *d_col_val, int batch, int n, int heads, int head_dim,
+                                    void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return dual_attention_backward(scores, a_row, c_row, a_col, c_col, kbias, mask, sizes, row_val, col_val, row_msg,
+                                   col_msg, row_stats, col_stats, d_row_msg, d_col_msg, dS, da_row, dc_row, da_col,
+                                   dc_col, dkb, d_row_val, d_col_val, batch, n, heads, head_dim, workspace,
+                                   workspace_bytes, DualDropout{}, stream_);
+}
+
+static int dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                     const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
+                                     float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
+                                     void *workspace, size_t workspace_bytes, const DualDropout &drop, void *stream_)
 {
     if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
     if (n > kMaxN) return -5;
@@ -692,7 +707,98 @@ int lapwarm_dual_edge_scores_backward(const float *edge_feat, const float *W1, c
         return -2;
     if (int rc = check_workspace(workspace_bytes, dual_backward_workspace_bytes(batch, n, heads))) return rc;
     HIP_TRY(launch_dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n,
-                                             heads, workspace, as_stream(stream_)));
+                                             heads, workspace, as_stream(stream_), drop));
+    return 0;
+}
+
+int lapwarm_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                      const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
+                                      float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
+                                      void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n, heads,
+                                     workspace, workspace_bytes, DualDropout{}, stream_);
+}
+
+// ---- DualGNN training with the two dropouts of the fused region (dual_dropout.hpp) ----
+// p in [0, 1), before any HIP call; p == 0 leaves `on` false, which selects the kernels without the generator
+static int dual_dropout_of(unsigned long long seed, double p, DualDropout *d)
+{
+    if (!(p >= 0.0 && p < 1.0)) return -2;  // NaN included
+    d->k0 = (unsigned)seed;
+    d->k1 = (unsigned)(seed >> 32);
+    d->threshold = (unsigned)(p * 4294967296.0);  // floor(p 2^32) <= 2^32 - 1
+    d->scale = (float)(1.0 / (1.0 - p));
+    d->on = p > 0.0;
+    return 0;
+}
+
+int lapwarm_dual_edge_scores_dropout(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                     const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
+                                     int heads, unsigned long long seed, double p, void *stream_)
+{
+    DualDropout drop;
+    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
+    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
+    if (n > kMaxN) return -5;
+    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !scores) return -2;
+    HIP_TRY(launch_dual_edge_scores_dropout(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop,
+                                            as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_dual_attention_stats_dropout(const float *scores, const float *a_row, const float *c_row,
+                                         const float *a_col, const float *c_col, const float *kbias,
+                                         const unsigned char *mask, const int *sizes, const float *row_val,
+                                         const float *col_val, float *row_msg, float *col_msg, float *row_stats,
+                                         float *col_stats, int batch, int n, int heads, int head_dim,
+                                         unsigned long long seed, double p, void *stream_)
+{
+    DualAttnParams q{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val, row_msg, col_msg,
+                     batch, n, heads, head_dim, sizes, row_stats, col_stats};
+    if (int rc = dual_dropout_of(seed, p, &q.drop)) return rc;
+    return dual_attention_stats(q, stream_);
+}
+
+int lapwarm_dual_attention_backward_dropout(const float *scores, const float *a_row, const float *c_row,
+                                            const float *a_col, const float *c_col, const float *kbias,
+                                            const unsigned char *mask, const int *sizes, const float *row_val,
+                                            const float *col_val, const float *row_msg, const float *col_msg,
+                                            const float *row_stats, const float *col_stats, const float *d_row_msg,
+                                            const float *d_col_msg, float *dS, float *da_row, float *dc_row,
+                                            float *da_col, float *dc_col, float *dkb, float *d_row_val,
+                                            float *d_col_val, int batch, int n, int heads, int head_dim,
+                                            void *workspace, size_t workspace_bytes, unsigned long long seed, double p,
+                                            void *stream_)
+{
+    DualDropout drop;
+    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
+    return dual_attention_backward(scores, a_row, c_row, a_col, c_col, kbias, mask, sizes, row_val, col_val, row_msg,
+                                   col_msg, row_stats, col_stats, d_row_msg, d_col_msg, dS, da_row, dc_row, da_col,
+                                   dc_col, dkb, d_row_val, d_col_val, batch, n, heads, head_dim, workspace,
+                                   workspace_bytes, drop, stream_);
+}
+
+int lapwarm_dual_edge_scores_backward_dropout(const float *edge_feat, const float *W1, const float *b1,
+                                              const float *W2, const float *b2, const float *G, const float *dS,
+                                              const int *sizes, float *dW1, float *db1, float *dW2, float *db2,
+                                              float *dG, int batch, int n, int heads, void *workspace,
+                                              size_t workspace_bytes, unsigned long long seed, double p, void *stream_)
+{
+    DualDropout drop;
+    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
+    return dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n, heads,
+                                     workspace, workspace_bytes, drop, stream_);
+}
+
+int lapwarm_dual_dropout_keep(unsigned long long seed, unsigned int stream_id, unsigned long long first,
+                              unsigned long long count, double p, unsigned char *keep, void *stream_)
+{
+    DualDropout drop;
+    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
+    if (count == 0) return 0;
+    if (!keep || count >= (1ull << 39)) return -2;  // the grid's x dimension: 2^31 blocks of 256
+    HIP_TRY(launch_dual_dropout_keep(drop, stream_id, first, count, keep, as_stream(stream_)));
     return 0;
 }
 

@@ -33,8 +33,19 @@ Two forwards:
     and dkb on to attn_*_weight, attn_*_bias, edge_mlp[5], row_proj and col_proj.  No (B, N, N, hidden) tensor is
     saved: per layer the scores, two messages and 4 B H N statistics.  DROPOUT on this path: the dropouts of the
     two update MLPs are applied as always; the two inside the fused region (in the edge MLP, on the attention
-    weights) are NOT applied, in training mode too (there is no device RNG in the kernels).  The default, False,
-    routes exactly as before.
+    weights) are applied only with `fused_dropout` (below).  The default, False, routes exactly as before.
+
+  * with `fused_dropout = True` as well (DualGNN: all layers; DualLayer: that layer; default False, and off it changes
+    neither routing nor bits) the fused training path applies those two dropouts in training mode when their p is in
+    (0, 1): the reference's training regime.  The kernels hold a counter-based generator (csrc/dual_dropout.hpp:
+    Philox4x32-10 keyed by a 64-bit seed; an element is kept iff its word >= floor(p 2^32) and then scaled by
+    float(1 / (1 - p)); the element index is that of the PADDED (B, N, N, 128) tensor of the edge MLP, stream 0, or of
+    the (B, 2, H, N, N) attention weights, stream 1, so tiling, chunking and `sizes` cannot change a mask).  Each
+    such layer call draws ONE seed, torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64, generator=g) on the CPU
+    with g = `dropout_generator` (None: torch's default CPU generator), the layers in forward order, without any
+    device synchronisation.  The seed and p ride on the autograd contexts and the backward REGENERATES the mask:
+    no (B, N, N, 128) mask is stored.  A captured graph (torch.cuda.graph) holds the seeds as kernel arguments:
+    every replay applies the one mask of the capture.  p == 1 takes the plain path; eval mode never applies them.
 
 A padded batch of instances of different sizes passes `sizes` (B,) int32 on the device: `mask` is then the prefix
 mask of the sizes (built here when it is None).  The fused path hands the sizes to lapwarm_dual_edge_scores_ragged
@@ -92,7 +103,7 @@ class _EdgeScores(torch.autograd.Function):
     scores outside the prefixes are never written and their gradient is never read."""
 
     @staticmethod
-    def forward(ctx, edge_feat, W1, b1, W2, b2, G, sizes):
+    def forward(ctx, edge_feat, W1, b1, W2, b2, G, sizes, seed=0, p=0.0):
         from lap import _hip
         from ._call import hip_call
         _hip.require_device()
@@ -100,12 +111,15 @@ class _EdgeScores(torch.autograd.Function):
         H = G.shape[0] // 2
         args = [t.detach().contiguous() for t in (edge_feat, W1, b1, W2, b2, G)]
         scores = torch.empty((B, 2, H, N, N), dtype=torch.float32, device=edge_feat.device)
-        if sizes is not None:
+        if p > 0.0:  # the dropout after the edge MLP's first GELU, stream 0 of the seed
+            hip_call("lapwarm_dual_edge_scores_dropout", "dual_edge_scores", scores.device, *args, scores, sizes, B, N, H,
+                     seed, p)
+        elif sizes is not None:
             hip_call("lapwarm_dual_edge_scores_ragged", "dual_edge_scores", scores.device, *args, scores, sizes, B, N, H)
         else:
             hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", scores.device, *args, scores, B, N, H)
         ctx.save_for_backward(*args)
-        ctx.sizes = sizes
+        ctx.sizes, ctx.seed, ctx.p = sizes, seed, p
         return scores
 
     @staticmethod
@@ -118,9 +132,13 @@ class _EdgeScores(torch.autograd.Function):
         dev = edge_feat.device
         ws = _backward_workspace(_hip.load(), B, N, H, dev)
         grads = [torch.empty_like(t) for t in (W1, b1, W2, b2, G)]
-        hip_call("lapwarm_dual_edge_scores_backward", "dual_edge_scores_backward", dev, edge_feat, W1, b1, W2, b2, G,
-                 d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel())
-        return (None, *grads, None)
+        if ctx.p > 0.0:  # the forward's mask again, from its seed
+            hip_call("lapwarm_dual_edge_scores_backward_dropout", "dual_edge_scores_backward", dev, edge_feat, W1, b1,
+                     W2, b2, G, d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel(), ctx.seed, ctx.p)
+        else:
+            hip_call("lapwarm_dual_edge_scores_backward", "dual_edge_scores_backward", dev, edge_feat, W1, b1, W2, b2,
+                     G, d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel())
+        return (None, *grads, None, None, None)
 
 
 class _EdgeAttention(torch.autograd.Function):
@@ -128,7 +146,7 @@ class _EdgeAttention(torch.autograd.Function):
     statistics and the messages.  The backward is lapwarm_dual_attention_backward."""
 
     @staticmethod
-    def forward(ctx, scores, a_row, c_row, a_col, c_col, kbias, row_val, col_val, mask8, sizes):
+    def forward(ctx, scores, a_row, c_row, a_col, c_col, kbias, row_val, col_val, mask8, sizes, seed=0, p=0.0):
         from lap import _hip
         from ._call import hip_call
         _hip.require_device()
@@ -139,14 +157,17 @@ class _EdgeAttention(torch.autograd.Function):
         vals = [t.detach().contiguous() for t in (row_val, col_val)]
         row_msg, col_msg = (torch.empty((B, N, H * D), dtype=torch.float32, device=dev) for _ in range(2))
         row_stats, col_stats = (torch.empty((B, H, N, 2), dtype=torch.float32, device=dev) for _ in range(2))
-        if sizes is not None:
+        if p > 0.0:  # the dropout of the attention weights, stream 1 of the seed
+            hip_call("lapwarm_dual_attention_stats_dropout", "dual_attention", dev, *args, mask8, sizes, *vals, row_msg,
+                     col_msg, row_stats, col_stats, B, N, H, D, seed, p)
+        elif sizes is not None:
             hip_call("lapwarm_dual_attention_stats_ragged", "dual_attention", dev, *args, sizes, *vals, row_msg, col_msg,
                      row_stats, col_stats, B, N, H, D)
         else:
             hip_call("lapwarm_dual_attention_stats", "dual_attention", dev, *args, mask8, *vals, row_msg, col_msg,
                      row_stats, col_stats, B, N, H, D)
         ctx.save_for_backward(*args, *vals, row_msg, col_msg, row_stats, col_stats)
-        ctx.mask8, ctx.sizes = mask8, sizes
+        ctx.mask8, ctx.sizes, ctx.seed, ctx.p = mask8, sizes, seed, p
         return row_msg, col_msg
 
     @staticmethod
@@ -164,19 +185,26 @@ class _EdgeAttention(torch.autograd.Function):
         da_row, dc_row, da_col, dc_col = (torch.empty_like(a_row) for _ in range(4))
         dkb = torch.empty_like(kbias)
         d_row_val, d_col_val = torch.empty_like(row_val), torch.empty_like(col_val)
-        hip_call("lapwarm_dual_attention_backward", "dual_attention_backward", dev, scores, a_row, c_row, a_col, c_col,
-                 kbias, ctx.mask8, ctx.sizes, row_val, col_val, row_msg, col_msg, row_stats, col_stats,
-                 d_row_msg.contiguous(), d_col_msg.contiguous(), dS, da_row, dc_row, da_col, dc_col, dkb, d_row_val,
-                 d_col_val, B, N, H, D, ws, ws.numel())
-        return dS, da_row, dc_row, da_col, dc_col, dkb, d_row_val, d_col_val, None, None
+        tail = (ctx.seed, ctx.p) if ctx.p > 0.0 else ()
+        hip_call("lapwarm_dual_attention_backward" + ("_dropout" if tail else ""), "dual_attention_backward", dev,
+                 scores, a_row, c_row, a_col, c_col, kbias, ctx.mask8, ctx.sizes, row_val, col_val, row_msg, col_msg,
+                 row_stats, col_stats, d_row_msg.contiguous(), d_col_msg.contiguous(), dS, da_row, dc_row, da_col,
+                 dc_col, dkb, d_row_val, d_col_val, B, N, H, D, ws, ws.numel(), *tail)
+        return dS, da_row, dc_row, da_col, dc_col, dkb, d_row_val, d_col_val, None, None, None, None
 
 
 class DualLayer(nn.Module):
     # With True, CUDA float32 tensors with heads <= 8 and an edge_feat that needs no gradient take the fused path
     # also in training mode and while a gradient is recorded (HIP forward and backward).  The two dropouts inside
-    # the fused region (in the edge MLP, on the attention weights) are then not applied; those of the update MLPs
-    # are.  DualGNN.fused_attention_training sets it on every layer of a model.
+    # the fused region (in the edge MLP, on the attention weights) are then not applied unless fused_dropout is set
+    # too; those of the update MLPs are.  DualGNN.fused_attention_training sets it on every layer of a model.
     fused_attention_training = False
+    # With True as well, the fused training path applies the two dropouts of the fused region in training mode
+    # (module docstring): one seed per layer call from `dropout_generator` (a CPU torch.Generator, or None for torch's
+    # default one), the masks regenerated in the backward.  DualGNN.fused_dropout / .dropout_generator set both on
+    # every layer of a model.
+    fused_dropout = False
+    dropout_generator = None
 
     def __init__(self, hidden_dim: int, heads: int = 4, dropout: float = 0.1) -> None:
         super().__init__()
@@ -243,6 +271,14 @@ class DualLayer(nn.Module):
         if nbytes == 0:
             raise ValueError(f"DualLayer: batch {B}, n {N} or heads {H} outside the fused kernels' range")
         lin1, lin2 = self.edge_mlp[0], self.edge_mlp[3]
+        p_edge, p_attn = self._fused_dropout_rates()
+        if p_edge > 0.0 or p_attn > 0.0:  # one seed per layer call, on the CPU: no device synchronisation
+            seed = int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64, generator=self.dropout_generator))
+            scores = _EdgeScores.apply(edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], sizes,
+                                       seed, p_edge)
+            mask8 = None if mask is None or sizes is not None else mask.to(torch.uint8).contiguous()
+            return _EdgeAttention.apply(scores, fold["a_row"], fold["c_row"], fold["a_col"], fold["c_col"],
+                                        fold["kbias"], row_val, col_val, mask8, sizes, seed, p_attn)
         if _records_grad(self, row_embed, col_embed):  # the trainable route: HIP forward and backward
             scores = _EdgeScores.apply(edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], sizes)
             mask8 = None if mask is None or sizes is not None else mask.to(torch.uint8).contiguous()
@@ -295,9 +331,18 @@ class DualLayer(nn.Module):
         col_msg = self._attend(cols, rows, edge, self.attn_col_weight, self.attn_col_bias, keep, rv, True)
         return row_msg, col_msg
 
+    def _fused_dropout_rates(self) -> tuple[float, float]:
+        """(p of the edge MLP's dropout, p of the attention weights' dropout) as the fused path applies them: 0 where
+        fused_dropout is off, in eval mode, or for a p outside (0, 1)."""
+        if not (self.fused_dropout and self.fused_attention_training and self.training):
+            return 0.0, 0.0
+        return tuple(float(m.p) if 0.0 < m.p < 1.0 else 0.0 for m in (self.edge_mlp[2], self.dropout))
+
     def takes_fused_path(self, edge_feat, row_embed, col_embed) -> bool:
         fits = (edge_feat.is_cuda and self.heads <= FUSED_MAX_HEADS
                 and self.attn_row_weight.dtype == torch.float32)  # (a .double() copy is a plain-path model)
+        if self.fused_dropout and self.training and max(self.edge_mlp[2].p, self.dropout.p) >= 1.0:
+            return False  # p == 1 drops everything: the plain path
         if self.fused_attention_training:  # training mode and recorded gradients too; none for edge_feat
             return fits and not (torch.is_grad_enabled() and edge_feat.requires_grad)
         return fits and not self.training and not _records_grad(self, edge_feat, row_embed, col_embed)
@@ -343,6 +388,26 @@ class DualGNN(nn.Module):
     def fused_attention_training(self, on: bool) -> None:
         for layer in self.layers:
             layer.fused_attention_training = bool(on)
+
+    @property
+    def fused_dropout(self) -> bool:
+        """The switch of every layer (DualLayer.fused_dropout); False unless set."""
+        return all(layer.fused_dropout for layer in self.layers)
+
+    @fused_dropout.setter
+    def fused_dropout(self, on: bool) -> None:
+        for layer in self.layers:
+            layer.fused_dropout = bool(on)
+
+    @property
+    def dropout_generator(self) -> Optional[torch.Generator]:
+        """The CPU generator the layers draw their dropout seeds from, in forward order; None: torch's default."""
+        return self.layers[0].dropout_generator
+
+    @dropout_generator.setter
+    def dropout_generator(self, generator: Optional[torch.Generator]) -> None:
+        for layer in self.layers:
+            layer.dropout_generator = generator
 
     def _forward(self, edge_feat, row_feat, col_feat, mask, sizes=None):
         nodes = (self.row_encoder(row_feat), self.col_encoder(col_feat))

@@ -127,6 +127,15 @@ SIGNATURES = {
     "lapwarm_dual_backward_chunk": (ct.c_int, []),
     "lapwarm_dual_attention_backward": (ct.c_int, [c_vp] * 24 + [ct.c_int] * 4 + [c_vp, ct.c_size_t, c_vp]),
     "lapwarm_dual_edge_scores_backward": (ct.c_int, [c_vp] * 13 + [ct.c_int] * 3 + [c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_dual_edge_scores_dropout": (ct.c_int, [c_vp] * 8 + [ct.c_int] * 3 + [ct.c_ulonglong, ct.c_double, c_vp]),
+    "lapwarm_dual_attention_stats_dropout": (ct.c_int, [c_vp] * 14 + [ct.c_int] * 4 + [ct.c_ulonglong, ct.c_double,
+                                                                                       c_vp]),
+    "lapwarm_dual_attention_backward_dropout": (ct.c_int, [c_vp] * 24 + [ct.c_int] * 4 + [
+        c_vp, ct.c_size_t, ct.c_ulonglong, ct.c_double, c_vp]),
+    "lapwarm_dual_edge_scores_backward_dropout": (ct.c_int, [c_vp] * 13 + [ct.c_int] * 3 + [
+        c_vp, ct.c_size_t, ct.c_ulonglong, ct.c_double, c_vp]),
+    "lapwarm_dual_dropout_keep": (ct.c_int, [ct.c_ulonglong, ct.c_uint, ct.c_ulonglong, ct.c_ulonglong, ct.c_double,
+                                             c_vp, c_vp]),
     "lapwarm_profile_enable": (None, [ct.c_int]),
     "lapwarm_profile_last_solver_ms": (ct.c_double, []),
     "lapwarm_solver_uses_helpers": (ct.c_int, [ct.c_int]),

@@ -622,6 +622,58 @@ int lapwarm_dual_edge_scores_backward(const float *edge_feat, const float *W1, c
                                       float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
                                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* DualGNN training with the reference's two dropouts inside the fused region: in the edge MLP after its first GELU and
+ * on the attention weights.  No mask is stored; the backward regenerates the forward's.  The keep rule is a pure
+ * function of (seed, stream, element index e), Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, key increments
+ * 0x9E3779B9, 0xBB67AE85):
+ *     key (lo32(seed), hi32(seed)),  counter (lo32(e >> 2), hi32(e >> 2), stream, 0),  word = output number e & 3;
+ *     e is kept iff word >= T, T = floor(p 2^32) formed in double;  a kept value is multiplied by float(1 / (1 - p)).
+ *   The logical tensors are indexed in the PADDED layout, so tiling, chunking and sizes cannot change a mask:
+ *     stream 0, edge MLP:           e = ((b n + i) n + j) 128 + unit,  applied to h1 = GELU(W1 f + b1);
+ *     stream 1, attention weights:  e = (((b 2 + dir) heads + h) n + q) n + k,  q the query and k the key of the
+ *                                   direction (dir = 1: the query is the column j), applied to the softmax weights
+ *                                   after the masked pairs are zeroed.
+ * lapwarm_dual_edge_scores_dropout: lapwarm_dual_edge_scores (sizes NULL) or _ragged with h1 replaced by
+ *   keep scale h1 before the second product.
+ * lapwarm_dual_attention_stats_dropout: lapwarm_dual_attention_stats (mask nullable; sizes nullable, taking precedence)
+ *   whose messages are sum_k w[q,k] keep scale val[k]; the statistics are those of the undropped softmax.
+ * lapwarm_dual_attention_backward_dropout: lapwarm_dual_attention_backward with
+ *     dw[q,k] = keep scale (dmsg[q] . val[k]),  delta[q] = sum_k w dw (= dmsg[q] . msg[q], msg the dropped message),
+ *     dz = w (dw - delta) slope,  dval[k] = sum_q w keep scale dmsg[q].
+ * lapwarm_dual_edge_scores_backward_dropout: lapwarm_dual_edge_scores_backward whose recompute applies the mask:
+ *     h1 is the dropped one (in dW2 too) and dx1 = dh1 keep scale GELU'(x1).
+ *   The four take the argument lists of the entries without dropout plus seed and p, the same seed and p in the forward
+ *   and its backward.  p outside [0, 1) or NaN: -2 before any HIP call.  With p == 0 they give the bits of the entries
+ *   without dropout.  No scratch, no atomics: equal inputs and an equal seed give equal bits.
+ * lapwarm_dual_dropout_keep: keep[i] = 1 if element first + i of stream stream_id is kept, else 0, i < count, by the
+ *   device function the kernels use (keep on the device; count < 2^39). */
+int lapwarm_dual_edge_scores_dropout(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                     const float *b2, const float *G, float *scores, const int *sizes_or_null, int batch,
+                                     int n, int heads, unsigned long long seed, double p, void *stream);
+int lapwarm_dual_attention_stats_dropout(const float *scores, const float *a_row, const float *c_row,
+                                         const float *a_col, const float *c_col, const float *kbias,
+                                         const unsigned char *mask_or_null, const int *sizes_or_null,
+                                         const float *row_val, const float *col_val, float *row_msg, float *col_msg,
+                                         float *row_stats, float *col_stats, int batch, int n, int heads, int head_dim,
+                                         unsigned long long seed, double p, void *stream);
+int lapwarm_dual_attention_backward_dropout(const float *scores, const float *a_row, const float *c_row,
+                                            const float *a_col, const float *c_col, const float *kbias,
+                                            const unsigned char *mask, const int *sizes, const float *row_val,
+                                            const float *col_val, const float *row_msg, const float *col_msg,
+                                            const float *row_stats, const float *col_stats, const float *d_row_msg,
+                                            const float *d_col_msg, float *dS, float *da_row, float *dc_row,
+                                            float *da_col, float *dc_col, float *dkb, float *d_row_val,
+                                            float *d_col_val, int batch, int n, int heads, int head_dim,
+                                            void *workspace, size_t workspace_bytes, unsigned long long seed, double p,
+                                            void *stream);
+int lapwarm_dual_edge_scores_backward_dropout(const float *edge_feat, const float *W1, const float *b1,
+                                              const float *W2, const float *b2, const float *G, const float *dS,
+                                              const int *sizes, float *dW1, float *db1, float *dW2, float *db2,
+                                              float *dG, int batch, int n, int heads, void *workspace,
+                                              size_t workspace_bytes, unsigned long long seed, double p, void *stream);
+int lapwarm_dual_dropout_keep(unsigned long long seed, unsigned int stream_id, unsigned long long first,
+                              unsigned long long count, double p, unsigned char *keep, void *stream);
+
 /* Profiling hook for bench.py: when enabled, lapwarm_seeded_batched / lapwarm_lapjv_batched /
  * lapwarm_seeded_ragged / lapwarm_lapjv_ragged / lapwarm_lapjv_extended_ragged bracket their solver launches
  * with HIP events on the caller's stream;

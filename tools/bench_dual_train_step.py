@@ -12,8 +12,12 @@ from a separate run of this file with --only fused under `rocprofv3 --kernel-tra
 With --loss the scalar is the reference's DualGNN training loss on the device (gnn.losses.dual_warmstart_loss on the
 float32 costs of the case): the measured step is forward, loss with its greedy, backward.
 
+With --fused-dropout P a third path, fused_dropout, alternates with the other two: the fused path with
+DualGNN.fused_dropout on and p = P in the edge MLP and on the attention weights (the reference's training regime at
+P = 0.1); `fused` stays the fused path with the switch off.
+
 Usage:  python tools/bench_dual_train_step.py [--reps 5] [--inner 3] [--only fused|plain] [--cases a,b] [--loss]
-                                              [--out FILE]
+                                              [--fused-dropout P] [--out FILE]
 """
 import argparse
 import json
@@ -38,6 +42,8 @@ def main():
     ap.add_argument("--only", choices=("fused", "plain"), default=None)
     ap.add_argument("--cases", default="8x256,1x512,1x1024,ragged")
     ap.add_argument("--loss", action="store_true", help="the step's scalar is dual_warmstart_loss")
+    ap.add_argument("--fused-dropout", type=float, default=None, metavar="P",
+                    help="also measure the fused path with fused_dropout at this p")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -51,6 +57,9 @@ def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     model = DualGNN(hidden_dim=args.hidden, layers=args.layers, heads=args.heads).to(dev).train()
+    if args.fused_dropout is not None:  # the two dropouts of the fused region; fused_dropout switches them per step
+        for layer in model.layers:
+            layer.edge_mlp[2].p = layer.dropout.p = args.fused_dropout
 
     def inputs(case):
         rs = np.random.RandomState(len(case))
@@ -73,8 +82,9 @@ def main():
         keep = torch.ones_like(tu) if mask is None else mask.to(tu.dtype)
         keep_bool = keep.to(torch.bool)
 
-        def step(fused):
+        def step(fused, dropout=False):
             model.fused_attention_training = fused
+            model.fused_dropout = dropout
             model.zero_grad(set_to_none=True)
             out = model(edge, row, col, mask, sizes=sizes if fused else None)
             if args.loss:
@@ -83,17 +93,17 @@ def main():
                 loss = (((out["u"] - tu) ** 2 + (out["v_hint"] - tv) ** 2) * keep).sum() / keep.sum()
             loss.backward()
 
-        def measure(fused):
+        def measure(fused, dropout=False):
             """(ms per step, peak bytes over a step) or the text of the failure"""
             try:
                 for _ in range(args.warmup):
-                    step(fused)
+                    step(fused, dropout)
                 torch.cuda.synchronize()
                 torch.cuda.reset_peak_memory_stats()
                 before = torch.cuda.memory_allocated()
                 t0 = time.perf_counter()
                 for _ in range(args.inner):
-                    step(fused)
+                    step(fused, dropout)
                 torch.cuda.synchronize()
                 return (time.perf_counter() - t0) * 1e3 / args.inner, torch.cuda.max_memory_allocated() - before
             except torch.OutOfMemoryError as e:
@@ -102,13 +112,17 @@ def main():
                 return str(e).splitlines()[0]
 
         paths = [p for p in ("fused", "plain") if args.only in (None, p)]
+        if args.fused_dropout is not None and "fused" in paths:
+            paths.insert(1, "fused_dropout")
         got = {p: [] for p in paths}
         for _ in range(args.reps):
             for p in paths:
                 if not got[p] or not isinstance(got[p][-1], str):  # a path that ran out of memory is not tried again
-                    got[p].append(measure(p == "fused"))
+                    got[p].append(measure(p != "plain", p == "fused_dropout"))
         line = dict(case=case, shape=list(edge.shape[:2]), hidden=args.hidden, layers=args.layers, heads=args.heads,
                     reps=args.reps, inner=args.inner, scalar="dual_warmstart_loss" if args.loss else "mse")
+        if args.fused_dropout is not None:
+            line["fused_dropout_p"] = args.fused_dropout
         for p in paths:
             if isinstance(got[p][-1], str):
                 line[f"{p}_failed"] = got[p][-1]
