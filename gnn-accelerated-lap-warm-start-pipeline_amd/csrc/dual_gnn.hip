@@ -32,9 +32,20 @@
 // DROP = true regenerates the mask from (seed, stream, element index) wherever it is needed, stores none, and takes
 // 227 (edge scores), 244 (ragged), 102 (attention), 101 / 108 (backward query / key) and 244 (edge backward) VGPRs
 // with the same LDS, no scratch and the same waves per SIMD (profiles/dual_gnn_dropout.md).
+//
+// The bf16 edge MLP (second template parameter BF16 of the tile functions and edge kernels; contract and layout below,
+// DESIGN.md "DualGNN bf16 edge MLP").  BF16 = false is the code and the figures above.  BF16 = true, no scratch anywhere:
+//   dual_edge_scores_kernel          152 VGPRs (DROP: 202), 44 288 B LDS, one workgroup of 8 waves per CU: 2 waves/SIMD
+//   dual_edge_scores_ragged_kernel   161 VGPRs (DROP: 212), 44 288 B LDS, 2 waves/SIMD
+//   dual_edge_backward_kernel        187 VGPRs (DROP: 235), 91 392 B LDS (W2 and W2^T staged, 8 KB of flush buffers),
+//                                    2 waves/SIMD
+//   dual_edge_wgrad_bf16_kernel      94 VGPRs, no LDS, 5 waves/SIMD
+// Staged in bf16 the forward's weights would let two workgroups share a CU's LDS, but not at 152 VGPRs; that and
+// 16-edge tiles at higher occupancy are not measured yet (profiles/dual_gnn_bf16.md).
 #include "dual_gnn.hpp"
 
 #include <atomic>
+#include <type_traits>
 
 namespace lapwarm {
 namespace {
@@ -99,6 +110,158 @@ __device__ __forceinline__ EsWeights es_stage_weights(const float *W1, const flo
     return EsWeights{W2s, Gs, W1s, b1s, b2s};
 }
 
+// ---- the bf16 edge MLP (BF16 = true; DESIGN.md, "DualGNN bf16 edge MLP") ------------------------------------------
+// The contract: round-to-nearest-even from fp32 to bf16 (v_cvt_pk_bf16_f32, which the compiler emits for a cast) of
+// edge_feat when a lane loads it, of W1, W2 and G when they are staged, of h1 after GELU and dropout, of h2 after
+// GELU, and in the backward of dS, dh2pre, dh1pre and the column of ones where they become MFMA operands.  b1, b2,
+// the pre-activations (fp32 accumulators of v_mfma_f32_16x16x32_bf16), GELU, GELU', the score and every gradient sum
+// stay fp32 (fp64 across workgroups and chunks).  The transposed arrangement of the fp32 form carries over: a result
+// tile has its edge on the lane and the units 4 g + r of a 16-unit block in register r, and one k-step of 32 covers
+// the blocks 2 s and 2 s + 1, lane group g supplying its own eight values 32 s + 4 g + r and 32 s + 16 + 4 g + r.
+// The weights are staged with their k index permuted to match (es_kpos), so an A fragment is one 16-byte LDS read;
+// a permutation of k applied to both operands changes no product.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kBfStride = kHid + 8;        // LDS row stride of W2, W2^T and G in bf16: 272 B, conflict-free b128 reads
+constexpr int kBfK1 = 16;                  // K = 10 (and the 2 * heads of G^T) padded to 16; k 16..31 are zero lanes
+constexpr int kBfFlushUnits = 32;          // the backward's transpose buffer: 32 units x 16 edges per wave
+constexpr size_t kEsBfFwdBytes = (size_t)(kHid * kBfStride + kOutPad * kBfStride + kHid * kBfK1) * 2 + 2 * kHid * 4;
+constexpr size_t kEsBfBwdBytes =
+    kEsBfFwdBytes + (size_t)(kHid * kBfStride + kHid * kBfK1 + kEsWaves * kBfFlushUnits * kEsEdgesPerWave) * 2;
+
+// where unit u of a 128-wide k index lies in a staged row: k-step u >> 5, then lane group, block parity, register
+__device__ __forceinline__ int es_kpos(int u) { return (u & ~31) | (((u >> 2) & 3) << 3) | (((u >> 4) & 1) << 2) | (u & 3); }
+
+struct EsWeightsBf {
+    const __bf16 *W2s;   // [128][136], k permuted by es_kpos
+    const __bf16 *Gs;    // [16][136], k permuted, rows >= 2 * heads are 0
+    const __bf16 *W1s;   // [128][16], columns >= 10 are 0
+    const float *b1s;    // [128]
+    const float *b2s;    // [128]
+    // the backward only
+    const __bf16 *W2Ts;  // [128][136]: W2Ts[k][es_kpos(o)] = W2[o][k]
+    const __bf16 *GTs;   // [128][16]: GTs[k][o] = G[o][k], columns >= 2 * heads are 0
+    __bf16 *flush;       // [8 waves][32 units][16 edges]
+};
+
+// All threads of the workgroup; ends with a barrier.  BWD: the transposes and the flush buffers as well.
+template <bool BWD>
+__device__ __forceinline__ EsWeightsBf es_stage_weights_bf16(const float *W1, const float *b1, const float *W2,
+                                                             const float *b2, const float *G, int outs)
+{
+    extern __shared__ __align__(16) float es_lds[];
+    __bf16 *W2s = reinterpret_cast<__bf16 *>(es_lds);
+    __bf16 *Gs = W2s + kHid * kBfStride;
+    __bf16 *W1s = Gs + kOutPad * kBfStride;
+    float *b1s = reinterpret_cast<float *>(W1s + kHid * kBfK1);
+    float *b2s = b1s + kHid;
+    __bf16 *W2Ts = reinterpret_cast<__bf16 *>(b2s + kHid);
+    __bf16 *GTs = W2Ts + kHid * kBfStride;
+    __bf16 *flush = GTs + kHid * kBfK1;
+    const int tid = threadIdx.x;
+    for (int idx = tid; idx < kHid * kHid; idx += kEsThreads) {
+        const int o = idx >> 7, k = idx & 127;
+        const __bf16 v = (__bf16)W2[idx];
+        W2s[o * kBfStride + es_kpos(k)] = v;
+        if constexpr (BWD) W2Ts[k * kBfStride + es_kpos(o)] = v;
+    }
+    for (int idx = tid; idx < kOutPad * kHid; idx += kEsThreads) {
+        const int o = idx >> 7, k = idx & 127;
+        const __bf16 v = (__bf16)(o < outs ? G[idx] : 0.0f);
+        Gs[o * kBfStride + es_kpos(k)] = v;
+        if constexpr (BWD) GTs[k * kBfK1 + o] = v;
+    }
+    for (int idx = tid; idx < kHid * kBfK1; idx += kEsThreads) {
+        const int r = idx >> 4, c = idx & 15;
+        W1s[idx] = (__bf16)(c < kDualEdgeIn ? W1[r * kDualEdgeIn + c] : 0.0f);
+    }
+    if (tid < kHid) {
+        b1s[tid] = b1[tid];
+        b2s[tid] = b2[tid];
+    }
+    __syncthreads();
+    return EsWeightsBf{W2s, Gs, W1s, b1s, b2s, W2Ts, GTs, flush + (tid >> 6) * kBfFlushUnits * kEsEdgesPerWave};
+}
+
+template <bool BF16> struct EsStaged { typedef EsWeights type; };
+template <> struct EsStaged<true> { typedef EsWeightsBf type; };
+
+template <bool BF16, bool BWD>
+__device__ __forceinline__ typename EsStaged<BF16>::type es_stage(const float *W1, const float *b1, const float *W2,
+                                                                  const float *b2, const float *G, int outs)
+{
+    if constexpr (BF16)
+        return es_stage_weights_bf16<BWD>(W1, b1, W2, b2, G, outs);
+    else
+        return es_stage_weights(W1, b1, W2, b2, G, outs);
+}
+
+__device__ __forceinline__ bf16x8 bf_zero8()
+{
+    const __bf16 z = (__bf16)0.0f;
+    return bf16x8{z, z, z, z, z, z, z, z};
+}
+
+// two accumulator blocks, 2 s and 2 s + 1, as the fragment of k-step s
+__device__ __forceinline__ bf16x8 bf_pack(f32x4 lo, f32x4 hi)
+{
+    return bf16x8{(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3],
+                  (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
+}
+
+// 16 k values of a [rows][16] image for the lane groups 0 and 1; the groups 2 and 3 hold the zero half of the k-step
+__device__ __forceinline__ bf16x8 bf_k16_fragment(const __bf16 *row16, int g)
+{
+    return g < 2 ? *reinterpret_cast<const bf16x8 *>(row16 + 8 * g) : bf_zero8();
+}
+
+// B fragment of the first product: the lane's features k = 8 g + j, rounded as they are loaded
+__device__ __forceinline__ bf16x8 bf_feature_fragment(const float *f, int g)
+{
+    bf16x8 fb = bf_zero8();
+    if (f && g < 2) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (8 * g + j < kDualEdgeIn) fb[j] = (__bf16)f[8 * g + j];
+    }
+    return fb;
+}
+
+__device__ __forceinline__ f32x4 es_drop4(f32x4 v, unsigned bits, int t, float scale);
+
+// h1 of the lane's edge as the four k-step fragments of the second product (rounded after GELU and dropout)
+template <bool DROP>
+__device__ __forceinline__ void bf_first_layer(const EsWeightsBf &w, bf16x8 fb, int col, int g, unsigned keep,
+                                               float scale, bf16x8 (&h1)[4])
+{
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        f32x4 blk[2];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int m = 2 * s + half;
+            f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * m + 4 * g]);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_k16_fragment(&w.W1s[(16 * m + col) * kBfK1], g), fb, acc, 0,
+                                                          0, 0);
+            blk[half] = gelu4(acc);
+            if constexpr (DROP) blk[half] = es_drop4(blk[half], keep, m, scale);
+        }
+        h1[s] = bf_pack(blk[0], blk[1]);
+    }
+}
+
+// x2 of block m: four k-steps over h1
+__device__ __forceinline__ f32x4 bf_second_layer(const EsWeightsBf &w, const bf16x8 (&h1)[4], int m, int col, int g)
+{
+    f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b2s[16 * m + 4 * g]);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            *reinterpret_cast<const bf16x8 *>(&w.W2s[(16 * m + col) * kBfStride + 32 * s + 8 * g]), h1[s], acc, 0, 0, 0);
+    return acc;
+}
+
 // The keep bits of a lane's edge (dual_dropout.hpp, stream 0): the lane holds the units 16 t + 4 g + r of its edge,
 // the group 4 t + g of four consecutive units, so one Philox call gives the four registers of a (t, g).  Bit 4 t + r
 // is the keep flag of h1[t][r].  `edge` is the edge's index (b N + i) N + j in the padded layout.
@@ -127,10 +290,24 @@ __device__ __forceinline__ f32x4 es_drop4(f32x4 v, unsigned bits, int t, float s
 // The scores of one wave's 16 edges: f, the edge's features or null for a lane without an edge (read as zeros);
 // lane group g = lane >> 4 holds the outputs 4 g + r in register r.  An edge is one column of every product, so its
 // scores do not depend on which edges share its tile.  DROP: h1 is keep * scale * h1, `keep` from es_keep_bits.
-template <bool DROP>
-__device__ __forceinline__ f32x4 es_wave_tile(const EsWeights &w, const float *f, int col, int g, unsigned keep = 0,
-                                              float scale = 1.0f)
+// BF16: the same tile on v_mfma_f32_16x16x32_bf16 (the contract above): 8 + 32 + 4 MFMAs for 16 edges.
+template <bool DROP, bool BF16>
+__device__ __forceinline__ f32x4 es_wave_tile(const typename EsStaged<BF16>::type &w, const float *f, int col, int g,
+                                              unsigned keep = 0, float scale = 1.0f)
 {
+    if constexpr (BF16) {
+        bf16x8 h1[4];
+        bf_first_layer<DROP>(w, bf_feature_fragment(f, g), col, g, keep, scale, h1);
+        f32x4 sc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+        for (int s = 0; s < 4; ++s) {  // two blocks of h2 are k-step s of the third product
+            const f32x4 lo = gelu4(bf_second_layer(w, h1, 2 * s, col, g));
+            const f32x4 hi = gelu4(bf_second_layer(w, h1, 2 * s + 1, col, g));
+            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                *reinterpret_cast<const bf16x8 *>(&w.Gs[col * kBfStride + 32 * s + 8 * g]), bf_pack(lo, hi), sc, 0, 0, 0);
+        }
+        return sc;
+    } else {
     // B fragments of the first product: F^T, k = 4 s + g on the lane group, edge on lane & 15
     float fb[3];
 #pragma unroll
@@ -167,16 +344,17 @@ __device__ __forceinline__ f32x4 es_wave_tile(const EsWeights &w, const float *f
         for (int r = 0; r < 4; ++r) sc = __builtin_amdgcn_mfma_f32_16x16x4f32(gm[r], h2[r], sc, 0, 0, 0);
     }
     return sc;
+    }
 }
 
-template <bool DROP>
+template <bool DROP, bool BF16>
 __global__ void __launch_bounds__(kEsThreads)
 dual_edge_scores_kernel(const float *F, const float *W1, const float *b1, const float *W2, const float *b2,
                         const float *G, float *scores, long long E, long long NN, int heads, long long tiles,
                         DualDropout drop)
 {
     const int outs = 2 * heads;
-    const EsWeights w = es_stage_weights(W1, b1, W2, b2, G, outs);
+    const auto w = es_stage<BF16, false>(W1, b1, W2, b2, G, outs);
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int col = lane & 15, g = lane >> 4;
@@ -184,7 +362,7 @@ dual_edge_scores_kernel(const float *F, const float *W1, const float *b1, const 
         const long long e = tile * kEsTile + (long long)wave * kEsEdgesPerWave + col;
         // the keep bits before the MFMA chain, while few registers are live
         const unsigned keep = DROP ? es_keep_bits(drop, (unsigned long long)e, g) : 0u;
-        const f32x4 sc = es_wave_tile<DROP>(w, e < E ? F + e * kDualEdgeIn : nullptr, col, g, keep, drop.scale);
+        const f32x4 sc = es_wave_tile<DROP, BF16>(w, e < E ? F + e * kDualEdgeIn : nullptr, col, g, keep, drop.scale);
         // the tail tile: an edge past the end was read as zeros and is not written
         if (e < E) {
             const long long b = e / NN, rem = e - b * NN;
@@ -203,14 +381,14 @@ dual_edge_scores_kernel(const float *F, const float *W1, const float *b1, const 
 // the other, row by row, and wave w of workgroup g takes the numbers 8 g + w, + 8 gridDim.x, ...  A wave walks the
 // instances in order with the running first number of each, so no prefix sum is stored anywhere, and the waves of
 // a workgroup share no barrier after the weights are staged.
-template <bool DROP>
+template <bool DROP, bool BF16>
 __global__ void __launch_bounds__(kEsThreads)
 dual_edge_scores_ragged_kernel(const float *F, const float *W1, const float *b1, const float *W2, const float *b2,
                                const float *G, float *scores, const int *sizes, int batch, int N, int heads,
                                DualDropout drop)
 {
     const int outs = 2 * heads;
-    const EsWeights w = es_stage_weights(W1, b1, W2, b2, G, outs);
+    const auto w = es_stage<BF16, false>(W1, b1, W2, b2, G, outs);
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, g = lane >> 4;
@@ -227,7 +405,7 @@ dual_edge_scores_ragged_kernel(const float *F, const float *W1, const float *b1,
             const int i = t / groups, j = (t - i * groups) * kEsEdgesPerWave + col;
             const size_t at = (size_t)i * N + j;
             const unsigned keep = DROP ? es_keep_bits(drop, (unsigned long long)b * NN + at, g) : 0u;
-            const f32x4 sc = es_wave_tile<DROP>(w, j < n ? F + ((size_t)b * NN + at) * kDualEdgeIn : nullptr, col, g,
+            const f32x4 sc = es_wave_tile<DROP, BF16>(w, j < n ? F + ((size_t)b * NN + at) * kDualEdgeIn : nullptr, col, g,
                                                 keep, drop.scale);
             if (j < n) {
 #pragma unroll
@@ -700,10 +878,103 @@ __device__ __forceinline__ float gelu_grad(float x)
 // (zeros for a lane without an edge and past 2 * heads); row: the lane's workspace row.  DROP: the recompute applies
 // the forward's mask (`keep` from es_keep_bits), the row's h1 is the dropped one, which dW2 needs, and
 // dx1 = dh1 * keep * scale * GELU'(x1).
-template <bool DROP>
-__device__ __forceinline__ void eb_wave_tile(const EsWeights &w, const float *f, const float (&ds)[4], float *row,
-                                             int col, int g, unsigned keep = 0, float scale = 1.0f)
+//
+// BF16 (the contract at the top of this file): the workspace holds, per wave tile, an image [544 units][16 edges] of
+// bf16 in the unit order of the fp32 row (kRowH1 .. kRowF), so that a fragment of stage 2, eight consecutive edges of
+// one unit, is one 16-byte load.  `ds` is then dS of the lane's edge for the outputs 8 g + j (g < 2) and `row` the
+// wave tile's image.  32 units at a time go through the wave's LDS buffer (eb_flush32): 2-byte LDS writes, one 16-byte
+// read and one 16-byte global store per lane.  dh2 = G^T dS takes G^T and dh1 = W2^T dh2pre takes W2^T from their own
+// staged images, so every A fragment is one LDS read; the loop walks two blocks of h2 at a time, one k-step of dh1.
+
+// 32 units x 16 edges of a wave tile: v[4 half + r] is unit 16 half + 4 g + r of the lane's edge; dst is the image's
+// first unit of the 32.  The LDS unit serves a wave's accesses in order; the fences keep the compiler from moving them.
+__device__ __forceinline__ void eb_flush_copy(__bf16 *buf, __bf16 *dst, int lane)
 {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const bf16x8 out = *reinterpret_cast<const bf16x8 *>(buf + 8 * lane);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    *reinterpret_cast<bf16x8 *>(dst + 8 * lane) = out;
+}
+
+__device__ __forceinline__ void eb_flush32(__bf16 *buf, bf16x8 v, __bf16 *dst, int lane)
+{
+    const int col = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) buf[(16 * (j >> 2) + 4 * g + (j & 3)) * kEsEdgesPerWave + col] = v[j];
+    eb_flush_copy(buf, dst, lane);
+}
+
+template <bool DROP, bool BF16>
+__device__ __forceinline__ void eb_wave_tile(const typename EsStaged<BF16>::type &w, const float *f,
+                                             const float (&ds)[BF16 ? 8 : 4],
+                                             typename std::conditional<BF16, __bf16, float>::type *row, int col, int g,
+                                             unsigned keep = 0, float scale = 1.0f)
+{
+    if constexpr (BF16) {
+        const int lane = 16 * g + col;
+        const bf16x8 fb = bf_feature_fragment(f, g);
+        bf16x8 dsb;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dsb[j] = (__bf16)ds[j];
+        bf16x8 h1[4];
+        bf_first_layer<DROP>(w, fb, col, g, keep, scale, h1);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) eb_flush32(w.flush, h1[s], row + (kRowH1 + 32 * s) * kEsEdgesPerWave, lane);
+        f32x4 dh1[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) dh1[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+        for (int s = 0; s < 4; ++s) {
+            f32x4 x2[2], d[2];
+#pragma unroll
+            for (int half = 0; half < 2; ++half) x2[half] = bf_second_layer(w, h1, 2 * s + half, col, g);
+            eb_flush32(w.flush, bf_pack(gelu4(x2[0]), gelu4(x2[1])), row + (kRowH2 + 32 * s) * kEsEdgesPerWave, lane);
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const int m = 2 * s + half;
+                d[half] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_k16_fragment(&w.GTs[(16 * m + col) * kBfK1], g), dsb,
+                                                                  f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) d[half][r] = d[half][r] * gelu_grad(x2[half][r]);
+            }
+            const bf16x8 dp = bf_pack(d[0], d[1]);
+            eb_flush32(w.flush, dp, row + (kRowDh2 + 32 * s) * kEsEdgesPerWave, lane);
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                dh1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    *reinterpret_cast<const bf16x8 *>(&w.W2Ts[(16 * t + col) * kBfStride + 32 * s + 8 * g]), dp, dh1[t], 0,
+                    0, 0);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {  // the first layer's pre-activation once more
+            f32x4 d[2];
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const int t = 2 * s + half;
+                f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * t + 4 * g]);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_k16_fragment(&w.W1s[(16 * t + col) * kBfK1], g), fb, acc,
+                                                              0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) d[half][r] = dh1[t][r] * gelu_grad(acc[r]);
+                if constexpr (DROP) d[half] = es_drop4(d[half], keep, t, scale);
+            }
+            eb_flush32(w.flush, bf_pack(d[0], d[1]), row + (kRowDh1 + 32 * s) * kEsEdgesPerWave, lane);
+        }
+        // dS (16 units) and the features with their column of ones (16 units): the lane groups 0 and 1 hold them
+        if (g < 2) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = 8 * g + j;
+                w.flush[k * kEsEdgesPerWave + col] = dsb[j];
+                w.flush[(kOutPad + k) * kEsEdgesPerWave + col] = k == kOnesCol ? (__bf16)(f ? 1.0f : 0.0f) : fb[j];
+            }
+        }
+        eb_flush_copy(w.flush, row + kRowDs * kEsEdgesPerWave, lane);
+    } else {
     float fb[3];
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
@@ -766,18 +1037,21 @@ __device__ __forceinline__ void eb_wave_tile(const EsWeights &w, const float *f,
         row[kRowDs + k] = ds[s];
         row[kRowF + k] = s < 3 ? (k == kOnesCol ? (f ? 1.0f : 0.0f) : fb[s]) : 0.0f;
     }
+    }
 }
 
 // The wave tiles [t0, t1) of the batch: numbered 16 edges at a time in the linear edge order (sizes null) or as
 // dual_edge_scores_ragged_kernel numbers them.  Wave tile t writes the rows 16 (t - t0) .. + 15.
-template <bool DROP>
+// BF16: rows holds bf16 images of 16 edges (eb_wave_tile), half the bytes.
+template <bool DROP, bool BF16>
 __global__ void __launch_bounds__(kEsThreads)
 dual_edge_backward_kernel(const float *F, const float *W1, const float *b1, const float *W2, const float *b2,
                           const float *G, const float *dS, const int *sizes, int batch, int N, int heads,
-                          long long t0, long long t1, float *rows, DualDropout drop)
+                          long long t0, long long t1, typename std::conditional<BF16, __bf16, float>::type *rows,
+                          DualDropout drop)
 {
     const int outs = 2 * heads;
-    const EsWeights w = es_stage_weights(W1, b1, W2, b2, G, outs);
+    const auto w = es_stage<BF16, true>(W1, b1, W2, b2, G, outs);
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, g = lane >> 4;
@@ -786,17 +1060,18 @@ dual_edge_backward_kernel(const float *F, const float *W1, const float *b1, cons
     long long next = t0 + (long long)blockIdx.x * kEsWaves + wave;
     // at: the edge's offset inside its instance's [n][n] plane, or -1
     auto tile = [&](long long t, int b, long long at) {
-        float ds[4];
+        float ds[BF16 ? 8 : 4];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int o = 4 * s + g;
+        for (int s = 0; s < (BF16 ? 8 : 4); ++s) {
+            const int o = BF16 ? 8 * g + s : 4 * s + g;  // the k index of dS as the lane's fragment holds it
             ds[s] = (at >= 0 && o < outs) ? dS[((size_t)b * outs + o) * NN + (size_t)at] : 0.0f;
         }
-        float *row = rows + ((size_t)(t - t0) * kEsEdgesPerWave + col) * kRowFloats;
+        // the lane's row, or with BF16 the wave tile's image
+        auto *row = rows + ((size_t)(t - t0) * kEsEdgesPerWave + (BF16 ? 0 : col)) * kRowFloats;
         // a lane without an edge has dS = 0, hence dx2 = dx1 = 0 whatever its bits are
         const unsigned keep = DROP ? es_keep_bits(drop, (unsigned long long)b * NN + (at >= 0 ? at : 0), g) : 0u;
-        eb_wave_tile<DROP>(w, at >= 0 ? F + ((size_t)b * NN + (size_t)at) * kDualEdgeIn : nullptr, ds, row, col, g,
-                           keep, drop.scale);
+        eb_wave_tile<DROP, BF16>(w, at >= 0 ? F + ((size_t)b * NN + (size_t)at) * kDualEdgeIn : nullptr, ds, row, col, g,
+                                 keep, drop.scale);
     };
     if (!sizes) {
         const long long E = (long long)NN * batch;
@@ -871,6 +1146,48 @@ dual_edge_wgrad_kernel(const float *rows, const int *sizes, int batch, int N, lo
     }
 }
 
+// The same five products on v_mfma_f32_16x16x32_bf16 from the bf16 images of stage 1: the edge is k, one k-step takes
+// two wave tiles (lane groups 0, 1: edges 0..7, 8..15 of the first, groups 2, 3 of the second; a slice with an odd
+// number of tiles ends with zero fragments there).  Every fragment is one 16-byte load; the partials keep their layout.
+__global__ void __launch_bounds__(kEsThreads)
+dual_edge_wgrad_bf16_kernel(const __bf16 *rows, const int *sizes, int batch, int N, long long t0, long long t1, int per,
+                            float *partials)
+{
+    const long long nrows = eb_chunk_rows(sizes, batch, N, t0, t1);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15, g = lane >> 4;
+    const long long begin = (long long)blockIdx.x * per;
+    const long long end = begin + per < nrows ? begin + per : nrows;  // per and nrows are multiples of 16
+    const long long tile_end = end / kEsEdgesPerWave;
+    f32x4 acc[11];
+#pragma unroll
+    for (int j = 0; j < 11; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (long long pair = begin / kEsEdgesPerWave; pair < tile_end; pair += 2) {  // wave-uniform
+        const long long tile = pair + (g >> 1);
+        const bool has = tile < tile_end;
+        const __bf16 *image = rows + (size_t)(has ? tile : 0) * kEsEdgesPerWave * kRowFloats + 8 * (g & 1);
+        auto frag = [&](int unit) {
+            return has ? *reinterpret_cast<const bf16x8 *>(image + (size_t)unit * kEsEdgesPerWave) : bf_zero8();
+        };
+        const bf16x8 a2 = frag(kRowDh2 + 16 * wave + col), a1 = frag(kRowDh1 + 16 * wave + col);
+        const bf16x8 as = frag(kRowDs + col), bf = frag(kRowF + col), bh = frag(kRowH2 + 16 * wave + col);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, frag(kRowH1 + 16 * j + col), acc[j], 0, 0, 0);
+        acc[8] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as, bh, acc[8], 0, 0, 0);
+        acc[9] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bf, acc[9], 0, 0, 0);
+        acc[10] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, bf, acc[10], 0, 0, 0);
+    }
+    float *out = partials + (size_t)blockIdx.x * kWgOut;
+#pragma unroll
+    for (int j = 0; j < 11; ++j) {
+        const int tile = j < 8 ? 8 * wave + j : 64 + 8 * (j - 8) + wave;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[tile * 256 + (4 * g + r) * 16 + col] = acc[j][r];
+    }
+}
+
 // output idx of the partials = tile * 256 + row * 16 + column of the tile
 __global__ void __launch_bounds__(256)
 dual_edge_wgrad_reduce_kernel(const float *partials, int blocks, double *sums, int first, int last, float *dW1,
@@ -901,10 +1218,10 @@ constexpr size_t kEsLdsBytes = (size_t)kEsLdsFloats * sizeof(float);
 
 // more dynamic LDS than the 64 KB default is allowed once per process and kernel, not on each of a forward's
 // launches (and not inside a capture: the first launch is the uncaptured warm-up every captured call has)
-hipError_t es_raise_lds(const void *kernel, std::atomic<bool> &raised)
+hipError_t es_raise_lds(const void *kernel, std::atomic<bool> &raised, size_t bytes = kEsLdsBytes)
 {
     if (!raised.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEsLdsBytes);
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return e;
         raised.store(true, std::memory_order_release);
     }
@@ -922,7 +1239,7 @@ size_t dual_gnn_workspace_bytes(int batch, int n, int heads)
 
 namespace {
 
-template <bool DROP>
+template <bool DROP, bool BF16 = false>
 hipError_t edge_scores_uniform(const float *edge_feat, const float *W1, const float *b1, const float *W2,
                                const float *b2, const float *G, float *scores, int batch, int n, int heads,
                                const DualDropout &drop, hipStream_t stream)
@@ -931,13 +1248,15 @@ hipError_t edge_scores_uniform(const float *edge_feat, const float *W1, const fl
     const long long tiles = (E + kEsTile - 1) / kEsTile;
     const int blocks = (int)(tiles < kEsMaxBlocks ? tiles : kEsMaxBlocks);
     static std::atomic<bool> raised{false};
-    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(dual_edge_scores_kernel<DROP>), raised)) return e;
-    hipLaunchKernelGGL(dual_edge_scores_kernel<DROP>, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream, edge_feat,
-                       W1, b1, W2, b2, G, scores, E, NN, heads, tiles, drop);
+    constexpr size_t lds = BF16 ? kEsBfFwdBytes : kEsLdsBytes;
+    const auto kernel = dual_edge_scores_kernel<DROP, BF16>;
+    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(kernel), raised, lds)) return e;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kEsThreads), lds, stream, edge_feat, W1, b1, W2, b2, G, scores, E, NN,
+                       heads, tiles, drop);
     return hipGetLastError();
 }
 
-template <bool DROP>
+template <bool DROP, bool BF16 = false>
 hipError_t edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
                               const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
                               int heads, const DualDropout &drop, hipStream_t stream)
@@ -947,10 +1266,11 @@ hipError_t edge_scores_ragged(const float *edge_feat, const float *W1, const flo
     const long long tiles = (wave_tiles + kEsWaves - 1) / kEsWaves;
     const int blocks = (int)(tiles < kEsMaxBlocks ? tiles : kEsMaxBlocks);
     static std::atomic<bool> raised{false};
-    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(dual_edge_scores_ragged_kernel<DROP>), raised))
-        return e;
-    hipLaunchKernelGGL(dual_edge_scores_ragged_kernel<DROP>, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream,
-                       edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop);
+    constexpr size_t lds = BF16 ? kEsBfFwdBytes : kEsLdsBytes;
+    const auto kernel = dual_edge_scores_ragged_kernel<DROP, BF16>;
+    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(kernel), raised, lds)) return e;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kEsThreads), lds, stream, edge_feat, W1, b1, W2, b2, G, scores, sizes,
+                       batch, n, heads, drop);
     return hipGetLastError();
 }
 
@@ -981,6 +1301,20 @@ hipError_t launch_dual_edge_scores_dropout(const float *edge_feat, const float *
     }
     return sizes ? edge_scores_ragged<true>(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop, stream)
                  : edge_scores_uniform<true>(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, drop, stream);
+}
+
+hipError_t launch_dual_edge_scores_bf16(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                        const float *b2, const float *G, float *scores, const int *sizes, int batch,
+                                        int n, int heads, const DualDropout &drop, hipStream_t stream)
+{
+    if (drop.on)
+        return sizes ? edge_scores_ragged<true, true>(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop,
+                                                      stream)
+                     : edge_scores_uniform<true, true>(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, drop,
+                                                       stream);
+    return sizes ? edge_scores_ragged<false, true>(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop,
+                                                   stream)
+                 : edge_scores_uniform<false, true>(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, drop, stream);
 }
 
 hipError_t launch_dual_attention(const DualAttnParams &p, hipStream_t stream)
@@ -1068,43 +1402,60 @@ hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                            const float *b2, const float *G, const float *dS, const int *sizes,
-                                            float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch,
-                                            int n, int heads, void *workspace, hipStream_t stream,
-                                            const DualDropout &drop)
+namespace {
+
+template <bool DROP, bool BF16>
+hipError_t edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
+                                float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
+                                void *workspace, hipStream_t stream, const DualDropout &drop)
 {
     const EdgeBwdLayout l = edge_bwd_layout(batch, n);
     const long long E = (long long)batch * n * n;
     const long long tiles = sizes ? l.tiles : (E + kEsEdgesPerWave - 1) / kEsEdgesPerWave;
     const long long chunk = kDualBwdChunk / kEsEdgesPerWave;
-    float *rows = static_cast<float *>(workspace);
+    // BF16: the chunk's rows are bf16 images in the first half of the fp32 rows' room
+    auto *rows = static_cast<typename std::conditional<BF16, __bf16, float>::type *>(workspace);
     float *partials = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + l.partials_at);
     double *sums = reinterpret_cast<double *>(static_cast<unsigned char *>(workspace) + l.sums_at);
-    static std::atomic<bool> raised{false}, raised_drop{false};
-    if (hipError_t e = drop.on ? es_raise_lds(reinterpret_cast<const void *>(dual_edge_backward_kernel<true>), raised_drop)
-                               : es_raise_lds(reinterpret_cast<const void *>(dual_edge_backward_kernel<false>), raised))
-        return e;
+    constexpr size_t lds = BF16 ? kEsBfBwdBytes : kEsLdsBytes;
+    const auto kernel = dual_edge_backward_kernel<DROP, BF16>;
+    static std::atomic<bool> raised{false};
+    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(kernel), raised, lds)) return e;
     for (long long t0 = 0; t0 < tiles; t0 += chunk) {
         const long long t1 = t0 + chunk < tiles ? t0 + chunk : tiles;
         const long long wgs = (t1 - t0 + kEsWaves - 1) / kEsWaves;
         const int blocks = (int)(wgs < kEsMaxBlocks ? wgs : kEsMaxBlocks);
-        if (drop.on)
-            hipLaunchKernelGGL(dual_edge_backward_kernel<true>, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream,
-                               edge_feat, W1, b1, W2, b2, G, dS, sizes, batch, n, heads, t0, t1, rows, drop);
-        else
-            hipLaunchKernelGGL(dual_edge_backward_kernel<false>, dim3(blocks), dim3(kEsThreads), kEsLdsBytes, stream,
-                               edge_feat, W1, b1, W2, b2, G, dS, sizes, batch, n, heads, t0, t1, rows, drop);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kEsThreads), lds, stream, edge_feat, W1, b1, W2, b2, G, dS, sizes,
+                           batch, n, heads, t0, t1, rows, drop);
         if (hipError_t e = hipGetLastError()) return e;
         const int wg = (int)(((t1 - t0) * kEsEdgesPerWave + l.per - 1) / l.per);
-        hipLaunchKernelGGL(dual_edge_wgrad_kernel, dim3(wg), dim3(kEsThreads), 0, stream, rows, sizes, batch, n, t0, t1,
-                           l.per, partials);
+        if constexpr (BF16)
+            hipLaunchKernelGGL(dual_edge_wgrad_bf16_kernel, dim3(wg), dim3(kEsThreads), 0, stream, rows, sizes, batch, n,
+                               t0, t1, l.per, partials);
+        else
+            hipLaunchKernelGGL(dual_edge_wgrad_kernel, dim3(wg), dim3(kEsThreads), 0, stream, rows, sizes, batch, n, t0,
+                               t1, l.per, partials);
         if (hipError_t e = hipGetLastError()) return e;
         hipLaunchKernelGGL(dual_edge_wgrad_reduce_kernel, dim3(kWgOut / 256), dim3(256), 0, stream, partials, wg, sums,
                            t0 == 0 ? 1 : 0, t1 == tiles ? 1 : 0, dW1, db1, dW2, db2, dG, 2 * heads);
         if (hipError_t e = hipGetLastError()) return e;
     }
     return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                            const float *b2, const float *G, const float *dS, const int *sizes,
+                                            float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch,
+                                            int n, int heads, void *workspace, hipStream_t stream,
+                                            const DualDropout &drop, bool bf16)
+{
+    const auto launch = bf16 ? (drop.on ? edge_scores_backward<true, true> : edge_scores_backward<false, true>)
+                             : (drop.on ? edge_scores_backward<true, false> : edge_scores_backward<false, false>);
+    return launch(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n, heads, workspace, stream,
+                  drop);
 }
 
 }  // namespace lapwarm

@@ -71,6 +71,11 @@ hipError_t launch_dual_edge_scores_dropout(const float *edge_feat, const float *
 hipError_t launch_dual_edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
                                           const float *b2, const float *G, float *scores, const int *sizes, int batch,
                                           int n, int heads, hipStream_t stream);
+// The edge MLP on the bf16 MFMA units (the contract in dual_gnn.hip): sizes null for the uniform batch, drop.on false
+// for no dropout.  The scores stay fp32; the mask of a seed is the mask of the fp32 launches.
+hipError_t launch_dual_edge_scores_bf16(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                        const float *b2, const float *G, float *scores, const int *sizes, int batch,
+                                        int n, int heads, const DualDropout &drop, hipStream_t stream);
 // heads <= 65535 here (the grid's y dimension): kDualMaxHeads limits the edge-scores kernel and the workspace only
 hipError_t launch_dual_attention(const DualAttnParams &p, hipStream_t stream);
 
@@ -79,12 +84,13 @@ size_t dual_backward_workspace_bytes(int batch, int n, int heads);
 // Three kernels: query-major (dS, da, per-workgroup partials of dkb), key-major (dc, dval), the reduce of dkb.
 hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_t stream);
 // Per chunk of kDualBwdChunk edges three kernels: the recompute (rows into the workspace), the TN products per
-// workgroup slice, the fp64 reduce over workgroups and chunks.  sizes null: the uniform batch.
+// workgroup slice, the fp64 reduce over workgroups and chunks.  sizes null: the uniform batch.  bf16: the backward of
+// launch_dual_edge_scores_bf16, whose rows are bf16 and fit the same workspace.
 hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
                                             const float *b2, const float *G, const float *dS, const int *sizes,
                                             float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch,
                                             int n, int heads, void *workspace, hipStream_t stream,
-                                            const DualDropout &drop = DualDropout{});
+                                            const DualDropout &drop = DualDropout{}, bool bf16 = false);
 // keep[i] = 1 if element first + i of the stream is kept, else 0, for i < count: the keep rule itself, for tests
 hipError_t launch_dual_dropout_keep(const DualDropout &drop, unsigned stream_id, unsigned long long first,
                                     unsigned long long count, unsigned char *keep, hipStream_t stream);

@@ -699,7 +699,8 @@ int lapwarm_dual_attention_backward(const float *scores, const float *a_row, con
 static int dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
                                      const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
                                      float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
-                                     void *workspace, size_t workspace_bytes, const DualDropout &drop, void *stream_)
+                                     void *workspace, size_t workspace_bytes, const DualDropout &drop, void *stream_,
+                                     bool bf16 = false)
 {
     if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
     if (n > kMaxN) return -5;
@@ -707,7 +708,7 @@ static int dual_edge_scores_backward(const float *edge_feat, const float *W1, co
         return -2;
     if (int rc = check_workspace(workspace_bytes, dual_backward_workspace_bytes(batch, n, heads))) return rc;
     HIP_TRY(launch_dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n,
-                                             heads, workspace, as_stream(stream_), drop));
+                                             heads, workspace, as_stream(stream_), drop, bf16));
     return 0;
 }
 
@@ -789,6 +790,33 @@ int lapwarm_dual_edge_scores_backward_dropout(const float *edge_feat, const floa
     if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
     return dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n, heads,
                                      workspace, workspace_bytes, drop, stream_);
+}
+
+// ---- the edge MLP on the bf16 MFMA units (dual_gnn.hip); sizes nullable, p == 0: no dropout ----
+int lapwarm_dual_edge_scores_bf16(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                  const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
+                                  int heads, unsigned long long seed, double p, void *stream_)
+{
+    DualDropout drop;
+    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
+    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
+    if (n > kMaxN) return -5;
+    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !scores) return -2;
+    HIP_TRY(launch_dual_edge_scores_bf16(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop,
+                                         as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_dual_edge_scores_backward_bf16(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                           const float *b2, const float *G, const float *dS, const int *sizes,
+                                           float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch, int n,
+                                           int heads, void *workspace, size_t workspace_bytes, unsigned long long seed,
+                                           double p, void *stream_)
+{
+    DualDropout drop;
+    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
+    return dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n, heads,
+                                     workspace, workspace_bytes, drop, stream_, true);
 }
 
 int lapwarm_dual_dropout_keep(unsigned long long seed, unsigned int stream_id, unsigned long long first,

@@ -17,8 +17,8 @@ Two forwards:
     lapwarm_dual_edge_scores (10 -> 128 -> 128 -> 2 heads per edge on the fp32 MFMA units) and
     lapwarm_dual_attention (masked softmax and the weighted sum of the values, both directions).  The four
     projections, the update MLPs and the LayerNorms stay with PyTorch-ROCm.  The path runs in float32 with
-    autocast DISABLED around it: a caller's `torch.autocast("cuda")` is ignored (exact f32 MFMA has no
-    reduced-precision variant to switch to, and the outputs seed an fp64 solver).
+    autocast DISABLED around it: a caller's `torch.autocast("cuda")` is ignored.  Reduced precision is chosen by a
+    switch of its own, `fused_edge_precision` (below), never by the autocast context.
 
   * the plain torch path otherwise (training mode, CPU tensors, a gradient being recorded, heads > 8), in the
     reference's op order with its dropout placements: inside the edge MLP, on both attention-weight tensors and
@@ -46,6 +46,18 @@ Two forwards:
     device synchronisation.  The seed and p ride on the autograd contexts and the backward REGENERATES the mask:
     no (B, N, N, 128) mask is stored.  A captured graph (torch.cuda.graph) holds the seeds as kernel arguments:
     every replay applies the one mask of the capture.  p == 1 takes the plain path; eval mode never applies them.
+
+  * `fused_edge_precision = "bf16"` (DualGNN: all layers; DualLayer: that layer; default "fp32", which changes neither
+    routing nor kernels nor bits) runs the edge MLP, and only it, on the bf16 MFMA units wherever the fused path is
+    taken: the eval forward, uniform and with `sizes`, and _EdgeScores with and without `fused_dropout`
+    (lapwarm_dual_edge_scores_bf16 and its backward).  Round-to-nearest-even conversions from fp32 to bf16 are applied
+    to edge_feat as it is loaded, to W1, W2 and G as they are staged, to h1 after GELU and dropout, to h2 after GELU,
+    and in the backward to dS, dh2pre, dh1pre and the column of ones where they become MFMA operands; biases,
+    pre-activations, GELU, GELU', the scores and every gradient sum stay fp32 (fp64 across workgroups and chunks).
+    The backward recomputes the forward's rounded activations and returns the gradient of the fp32 function at them
+    (straight-through rounding); the switch rides on the autograd context.  The attention kernels, the folded a, c
+    and kbias and everything torch does stay fp32; the dropout mask of a seed is the mask under "fp32".  The seeds
+    feed an exact fp64 solver: a less precise u changes the number of augmenting paths, never the optimal cost.
 
 A padded batch of instances of different sizes passes `sizes` (B,) int32 on the device: `mask` is then the prefix
 mask of the sizes (built here when it is None).  The fused path hands the sizes to lapwarm_dual_edge_scores_ragged
@@ -90,6 +102,12 @@ def _prefix_mask(sizes, mask, edge_feat) -> torch.Tensor:
     return prefix
 
 
+def _edge_precision(value) -> str:
+    if value not in ("fp32", "bf16"):
+        raise ValueError(f'fused_edge_precision must be "fp32" or "bf16", not {value!r}')
+    return value
+
+
 def _backward_workspace(lib, B, N, H, dev) -> torch.Tensor:
     nbytes = int(lib.lapwarm_dual_backward_workspace_bytes(B, N, H))
     if nbytes == 0:
@@ -103,7 +121,7 @@ class _EdgeScores(torch.autograd.Function):
     scores outside the prefixes are never written and their gradient is never read."""
 
     @staticmethod
-    def forward(ctx, edge_feat, W1, b1, W2, b2, G, sizes, seed=0, p=0.0):
+    def forward(ctx, edge_feat, W1, b1, W2, b2, G, sizes, seed=0, p=0.0, precision="fp32"):
         from lap import _hip
         from ._call import hip_call
         _hip.require_device()
@@ -111,7 +129,10 @@ class _EdgeScores(torch.autograd.Function):
         H = G.shape[0] // 2
         args = [t.detach().contiguous() for t in (edge_feat, W1, b1, W2, b2, G)]
         scores = torch.empty((B, 2, H, N, N), dtype=torch.float32, device=edge_feat.device)
-        if p > 0.0:  # the dropout after the edge MLP's first GELU, stream 0 of the seed
+        if precision == "bf16":  # sizes may be None, p == 0 is no dropout
+            hip_call("lapwarm_dual_edge_scores_bf16", "dual_edge_scores", scores.device, *args, scores, sizes, B, N, H,
+                     seed, p)
+        elif p > 0.0:  # the dropout after the edge MLP's first GELU, stream 0 of the seed
             hip_call("lapwarm_dual_edge_scores_dropout", "dual_edge_scores", scores.device, *args, scores, sizes, B, N, H,
                      seed, p)
         elif sizes is not None:
@@ -119,7 +140,7 @@ class _EdgeScores(torch.autograd.Function):
         else:
             hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", scores.device, *args, scores, B, N, H)
         ctx.save_for_backward(*args)
-        ctx.sizes, ctx.seed, ctx.p = sizes, seed, p
+        ctx.sizes, ctx.seed, ctx.p, ctx.precision = sizes, seed, p, precision
         return scores
 
     @staticmethod
@@ -132,13 +153,16 @@ class _EdgeScores(torch.autograd.Function):
         dev = edge_feat.device
         ws = _backward_workspace(_hip.load(), B, N, H, dev)
         grads = [torch.empty_like(t) for t in (W1, b1, W2, b2, G)]
-        if ctx.p > 0.0:  # the forward's mask again, from its seed
+        if ctx.precision == "bf16":  # the forward's precision, and its mask again from its seed
+            hip_call("lapwarm_dual_edge_scores_backward_bf16", "dual_edge_scores_backward", dev, edge_feat, W1, b1,
+                     W2, b2, G, d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel(), ctx.seed, ctx.p)
+        elif ctx.p > 0.0:  # the forward's mask again, from its seed
             hip_call("lapwarm_dual_edge_scores_backward_dropout", "dual_edge_scores_backward", dev, edge_feat, W1, b1,
                      W2, b2, G, d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel(), ctx.seed, ctx.p)
         else:
             hip_call("lapwarm_dual_edge_scores_backward", "dual_edge_scores_backward", dev, edge_feat, W1, b1, W2, b2,
                      G, d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel())
-        return (None, *grads, None, None, None)
+        return (None, *grads, None, None, None, None)
 
 
 class _EdgeAttention(torch.autograd.Function):
@@ -205,6 +229,9 @@ class DualLayer(nn.Module):
     # every layer of a model.
     fused_dropout = False
     dropout_generator = None
+    # "fp32" or "bf16": the arithmetic of the edge MLP wherever the fused path is taken (module docstring).  Checked
+    # when a fused call reads it; DualGNN.fused_edge_precision checks it when it is set.
+    fused_edge_precision = "fp32"
 
     def __init__(self, hidden_dim: int, heads: int = 4, dropout: float = 0.1) -> None:
         super().__init__()
@@ -271,30 +298,35 @@ class DualLayer(nn.Module):
         if nbytes == 0:
             raise ValueError(f"DualLayer: batch {B}, n {N} or heads {H} outside the fused kernels' range")
         lin1, lin2 = self.edge_mlp[0], self.edge_mlp[3]
+        precision = _edge_precision(self.fused_edge_precision)
         p_edge, p_attn = self._fused_dropout_rates()
         if p_edge > 0.0 or p_attn > 0.0:  # one seed per layer call, on the CPU: no device synchronisation
             seed = int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64, generator=self.dropout_generator))
             scores = _EdgeScores.apply(edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], sizes,
-                                       seed, p_edge)
+                                       seed, p_edge, precision)
             mask8 = None if mask is None or sizes is not None else mask.to(torch.uint8).contiguous()
             return _EdgeAttention.apply(scores, fold["a_row"], fold["c_row"], fold["a_col"], fold["c_col"],
                                         fold["kbias"], row_val, col_val, mask8, sizes, seed, p_attn)
         if _records_grad(self, row_embed, col_embed):  # the trainable route: HIP forward and backward
-            scores = _EdgeScores.apply(edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], sizes)
+            scores = _EdgeScores.apply(edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], sizes,
+                                       0, 0.0, precision)
             mask8 = None if mask is None or sizes is not None else mask.to(torch.uint8).contiguous()
             return _EdgeAttention.apply(scores, fold["a_row"], fold["c_row"], fold["a_col"], fold["c_col"],
                                         fold["kbias"], row_val, col_val, mask8, sizes)
         row_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
         col_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
         scores = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        edge = (edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], scores)
+        if precision == "bf16":  # one entry for both batches: sizes may be None; seed 0, p 0: no dropout
+            hip_call("lapwarm_dual_edge_scores_bf16", "dual_edge_scores", dev, *edge, sizes, B, N, H, 0, 0.0)
+        elif sizes is not None:
+            hip_call("lapwarm_dual_edge_scores_ragged", "dual_edge_scores", dev, *edge, sizes, B, N, H)
+        else:
+            hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", dev, *edge, B, N, H)
         if sizes is not None:  # scores outside the prefixes are neither written nor read
-            hip_call("lapwarm_dual_edge_scores_ragged", "dual_edge_scores", dev, edge_feat, lin1.weight, lin1.bias,
-                     lin2.weight, lin2.bias, fold["G"], scores, sizes, B, N, H)
             hip_call("lapwarm_dual_attention_ragged", "dual_attention", dev, scores, fold["a_row"], fold["c_row"],
                      fold["a_col"], fold["c_col"], fold["kbias"], sizes, row_val, col_val, row_msg, col_msg, B, N, H, D)
             return row_msg, col_msg
-        hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", dev, edge_feat, lin1.weight, lin1.bias, lin2.weight,
-                 lin2.bias, fold["G"], scores, B, N, H)
         mask8 = None if mask is None else mask.to(torch.uint8).contiguous()
         hip_call("lapwarm_dual_attention", "dual_attention", dev, scores, fold["a_row"], fold["c_row"], fold["a_col"],
                  fold["c_col"], fold["kbias"], mask8, row_val, col_val, row_msg, col_msg, B, N, H, D)
@@ -398,6 +430,17 @@ class DualGNN(nn.Module):
     def fused_dropout(self, on: bool) -> None:
         for layer in self.layers:
             layer.fused_dropout = bool(on)
+
+    @property
+    def fused_edge_precision(self) -> str:
+        """The switch of every layer (DualLayer.fused_edge_precision): "fp32" unless set; "bf16" when all layers are."""
+        return "bf16" if all(layer.fused_edge_precision == "bf16" for layer in self.layers) else "fp32"
+
+    @fused_edge_precision.setter
+    def fused_edge_precision(self, precision: str) -> None:
+        precision = _edge_precision(precision)
+        for layer in self.layers:
+            layer.fused_edge_precision = precision
 
     @property
     def dropout_generator(self) -> Optional[torch.Generator]:

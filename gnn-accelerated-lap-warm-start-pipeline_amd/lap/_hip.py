@@ -134,6 +134,9 @@ SIGNATURES = {
         c_vp, ct.c_size_t, ct.c_ulonglong, ct.c_double, c_vp]),
     "lapwarm_dual_edge_scores_backward_dropout": (ct.c_int, [c_vp] * 13 + [ct.c_int] * 3 + [
         c_vp, ct.c_size_t, ct.c_ulonglong, ct.c_double, c_vp]),
+    "lapwarm_dual_edge_scores_bf16": (ct.c_int, [c_vp] * 8 + [ct.c_int] * 3 + [ct.c_ulonglong, ct.c_double, c_vp]),
+    "lapwarm_dual_edge_scores_backward_bf16": (ct.c_int, [c_vp] * 13 + [ct.c_int] * 3 + [
+        c_vp, ct.c_size_t, ct.c_ulonglong, ct.c_double, c_vp]),
     "lapwarm_dual_dropout_keep": (ct.c_int, [ct.c_ulonglong, ct.c_uint, ct.c_ulonglong, ct.c_ulonglong, ct.c_double,
                                              c_vp, c_vp]),
     "lapwarm_profile_enable": (None, [ct.c_int]),

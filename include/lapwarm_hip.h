@@ -674,6 +674,27 @@ int lapwarm_dual_edge_scores_backward_dropout(const float *edge_feat, const floa
 int lapwarm_dual_dropout_keep(unsigned long long seed, unsigned int stream_id, unsigned long long first,
                               unsigned long long count, double p, unsigned char *keep, void *stream);
 
+/* The edge MLP of DualGNN on the bf16 MFMA units (v_mfma_f32_16x16x32_bf16), forward and backward.  Conversions are
+ * round-to-nearest-even from fp32 to bf16, at exactly these points: edge_feat when it is loaded; W1, W2 and G when they
+ * are staged; h1 after GELU and dropout (keep scale gelu(x1)); h2 after GELU; in the backward dS, dh2pre = dh2 GELU'(x2),
+ * dh1pre and the column of ones where they become MFMA operands.  b1, b2, both pre-activations, GELU, GELU', the scores
+ * and the sums of the weight gradients (fp32 per workgroup slice, fp64 across slices and chunks, rounded once) are as
+ * in the fp32 entries.  The backward recomputes h1 and h2 as the forward does and returns the gradient of the fp32
+ * function at the rounded values (straight-through rounding).  No atomics: equal inputs and an equal seed give equal
+ * bits; the dropout mask of a seed is the mask of the fp32 entries.
+ * lapwarm_dual_edge_scores_bf16: the argument list of lapwarm_dual_edge_scores_dropout; sizes NULL for the uniform
+ *   batch, p == 0 for no dropout.
+ * lapwarm_dual_edge_scores_backward_bf16: the argument list of lapwarm_dual_edge_scores_backward_dropout with the seed
+ *   and p of the forward; the workspace is lapwarm_dual_backward_workspace_bytes, unchanged. */
+int lapwarm_dual_edge_scores_bf16(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                  const float *b2, const float *G, float *scores, const int *sizes_or_null, int batch,
+                                  int n, int heads, unsigned long long seed, double p, void *stream);
+int lapwarm_dual_edge_scores_backward_bf16(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                           const float *b2, const float *G, const float *dS, const int *sizes,
+                                           float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch, int n,
+                                           int heads, void *workspace, size_t workspace_bytes, unsigned long long seed,
+                                           double p, void *stream);
+
 /* Profiling hook for bench.py: when enabled, lapwarm_seeded_batched / lapwarm_lapjv_batched /
  * lapwarm_seeded_ragged / lapwarm_lapjv_ragged / lapwarm_lapjv_extended_ragged bracket their solver launches
  * with HIP events on the caller's stream;
