@@ -24,7 +24,7 @@
 //   dual_attention_bwd_kbias_kernel  the partials in order, fp64
 //   dual_edge_backward_kernel        224 VGPRs, 83 200 B LDS (through es_raise_lds), 2 waves/SIMD: the recompute
 //                                    of a chunk of edges and the way back through it, rows into the workspace
-//   dual_edge_wgrad_kernel           62 VGPRs, no LDS, 8 waves/SIMD: the five sums over edges as TN MFMA products
+//   dual_edge_wgrad_kernel           61 VGPRs, no LDS, 8 waves/SIMD: the five sums over edges as TN MFMA products
 //   dual_edge_wgrad_reduce_kernel    workgroups and chunks in order, fp64, rounded once
 //
 // Dropout inside the fused region (dual_dropout.hpp; DESIGN.md, "DualGNN backward"): every kernel that sees h1 or an
@@ -33,8 +33,11 @@
 // 227 (edge scores), 244 (ragged), 102 (attention), 101 / 108 (backward query / key) and 244 (edge backward) VGPRs
 // with the same LDS, no scratch and the same waves per SIMD (profiles/dual_gnn_dropout.md).
 //
-// The bf16 edge MLP (second template parameter BF16 of the tile functions and edge kernels; contract and layout below,
-// DESIGN.md "DualGNN bf16 edge MLP").  BF16 = false is the code and the figures above.  BF16 = true, no scratch anywhere:
+// The bf16 edge MLP (second template parameter BF16 of the edge kernels; contract and layout below, DESIGN.md "DualGNN
+// bf16 edge MLP").  A kernel stages EsWeights or EsWeightsBf (es_stage_weights, picked by std::bool_constant<BF16>), and
+// the staged type picks the tile: es_wave_tile and eb_wave_tile are two overloads each, sharing es_first_pre /
+// es_first_layer / es_second_layer (fp32) and es_first_pre / bf_first_layer / bf_second_layer (bf16) between forward
+// and backward.  BF16 = false is the code and the figures above.  BF16 = true, no scratch anywhere:
 //   dual_edge_scores_kernel          152 VGPRs (DROP: 202), 44 288 B LDS, one workgroup of 8 waves per CU: 2 waves/SIMD
 //   dual_edge_scores_ragged_kernel   161 VGPRs (DROP: 212), 44 288 B LDS, 2 waves/SIMD
 //   dual_edge_backward_kernel        187 VGPRs (DROP: 235), 91 392 B LDS (W2 and W2^T staged, 8 KB of flush buffers),
@@ -42,6 +45,12 @@
 //   dual_edge_wgrad_bf16_kernel      94 VGPRs, no LDS, 5 waves/SIMD
 // Staged in bf16 the forward's weights would let two workgroups share a CU's LDS, but not at 152 VGPRs; that and
 // 16-edge tiles at higher occupancy are not measured yet (profiles/dual_gnn_bf16.md).
+//
+// Written once and shared: the wave tiles of an instance (es_instance_tiles, host and device), the clamped prefix
+// (dual_prefix_len), the attention kernels' tile slot (at_tile_slot) and their (b, dir, h) view (AtView, AtBwdView), the
+// slice and store of stage 2 (wg_begin, wg_store).  The host takes one record per call (DualEdgeParams, DualEdgeGrads,
+// DualAttnParams), picks an instantiation with dispatch_bools, and keeps the raised-LDS flag per kernel
+// (es_raise_lds<Kernel>).  Figures of this build beside its parent's: profiles/dual_gnn_refactor.md.
 #include "dual_gnn.hpp"
 
 #include <atomic>
@@ -75,8 +84,27 @@ __device__ __forceinline__ f32x4 gelu4(f32x4 v)
     return o;
 }
 
-// The staged weights of one workgroup (dynamic LDS, kEsLdsFloats floats).
+// The wave tiles of one instance of a padded batch: 16 consecutive j of one row i, a row's tail rounded up to a tile.
+// A size outside 1..N is an empty instance.  The kernels and the host's workspace layout number the tiles from here.
+__host__ __device__ __forceinline__ int dual_prefix_len(int size, int N) { return (size >= 1 && size <= N) ? size : 0; }
+
+struct EsInstanceTiles {
+    int n, groups;    // the clamped size; tiles per row
+    long long count;  // at most 16384 * 1024
+};
+
+__host__ __device__ __forceinline__ EsInstanceTiles es_instance_tiles(int size, int N)
+{
+    const int n = dual_prefix_len(size, N);
+    const int groups = (n + kEsEdgesPerWave - 1) / kEsEdgesPerWave;
+    return EsInstanceTiles{n, groups, (long long)n * groups};
+}
+
+// The staged weights of one workgroup (dynamic LDS, kEsLdsFloats floats).  Row and kDsRegs: what the backward's tile
+// writes per edge and how many dS values of its edge a lane holds.
 struct EsWeights {
+    typedef float Row;
+    static constexpr int kDsRegs = 4;
     const float *W2s;  // [128][132]
     const float *Gs;   // [16][132], rows >= 2 * heads are 0
     const float *W1s;  // [128][12], columns 10, 11 are 0
@@ -84,8 +112,10 @@ struct EsWeights {
     const float *b2s;  // [128]
 };
 
-// All threads of the workgroup; ends with a barrier.
-__device__ __forceinline__ EsWeights es_stage_weights(const float *W1, const float *b1, const float *W2,
+// All threads of the workgroup; ends with a barrier.  The tag picks the fp32 images (here) or the bf16 ones (below);
+// BWD: the fp32 backward reads the forward's images.
+template <bool BWD>
+__device__ __forceinline__ EsWeights es_stage_weights(std::false_type, const float *W1, const float *b1, const float *W2,
                                                       const float *b2, const float *G, int outs)
 {
     extern __shared__ __align__(16) float es_lds[];
@@ -108,6 +138,51 @@ __device__ __forceinline__ EsWeights es_stage_weights(const float *W1, const flo
     }
     __syncthreads();
     return EsWeights{W2s, Gs, W1s, b1s, b2s};
+}
+
+__device__ __forceinline__ f32x4 es_drop4(f32x4 v, unsigned bits, int t, float scale);
+
+// B fragments of the first product: F^T, k = 4 s + g on the lane group, edge on lane & 15; f null: zeros
+__device__ __forceinline__ void es_feature_fragment(const float *f, int g, float (&fb)[3])
+{
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int k = 4 * s + g;
+        fb[s] = (f && k < kDualEdgeIn) ? f[k] : 0.0f;
+    }
+}
+
+// x1 = W1 f + b1 of block m: three k-steps
+__device__ __forceinline__ f32x4 es_first_pre(const EsWeights &w, const float (&fb)[3], int m, int col, int g)
+{
+    f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * m + 4 * g]);
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.W1s[(16 * m + col) * kKPad + 4 * s + g], fb[s], acc, 0, 0, 0);
+    return acc;
+}
+
+// block m of h1 = GELU(x1), dropped with DROP
+template <bool DROP>
+__device__ __forceinline__ f32x4 es_first_layer(const EsWeights &w, const float (&fb)[3], int m, int col, int g,
+                                                unsigned keep, float scale)
+{
+    const f32x4 h1 = gelu4(es_first_pre(w, fb, m, col, g));
+    if constexpr (DROP) return es_drop4(h1, keep, m, scale);
+    return h1;
+}
+
+// x2 of block m: the k-steps (t, r) over h1
+__device__ __forceinline__ f32x4 es_second_layer(const EsWeights &w, const f32x4 (&h1)[8], int m, int col, int g)
+{
+    f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b2s[16 * m + 4 * g]);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(&w.W2s[(16 * m + col) * kWStride + 16 * t + 4 * g]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], h1[t][r], acc, 0, 0, 0);
+    }
+    return acc;
 }
 
 // ---- the bf16 edge MLP (BF16 = true; DESIGN.md, "DualGNN bf16 edge MLP") ------------------------------------------
@@ -134,6 +209,8 @@ constexpr size_t kEsBfBwdBytes =
 __device__ __forceinline__ int es_kpos(int u) { return (u & ~31) | (((u >> 2) & 3) << 3) | (((u >> 4) & 1) << 2) | (u & 3); }
 
 struct EsWeightsBf {
+    typedef __bf16 Row;  // per wave tile an image [544 units][16 edges]
+    static constexpr int kDsRegs = 8;
     const __bf16 *W2s;   // [128][136], k permuted by es_kpos
     const __bf16 *Gs;    // [16][136], k permuted, rows >= 2 * heads are 0
     const __bf16 *W1s;   // [128][16], columns >= 10 are 0
@@ -147,8 +224,8 @@ struct EsWeightsBf {
 
 // All threads of the workgroup; ends with a barrier.  BWD: the transposes and the flush buffers as well.
 template <bool BWD>
-__device__ __forceinline__ EsWeightsBf es_stage_weights_bf16(const float *W1, const float *b1, const float *W2,
-                                                             const float *b2, const float *G, int outs)
+__device__ __forceinline__ EsWeightsBf es_stage_weights(std::true_type, const float *W1, const float *b1, const float *W2,
+                                                        const float *b2, const float *G, int outs)
 {
     extern __shared__ __align__(16) float es_lds[];
     __bf16 *W2s = reinterpret_cast<__bf16 *>(es_lds);
@@ -184,19 +261,6 @@ __device__ __forceinline__ EsWeightsBf es_stage_weights_bf16(const float *W1, co
     return EsWeightsBf{W2s, Gs, W1s, b1s, b2s, W2Ts, GTs, flush + (tid >> 6) * kBfFlushUnits * kEsEdgesPerWave};
 }
 
-template <bool BF16> struct EsStaged { typedef EsWeights type; };
-template <> struct EsStaged<true> { typedef EsWeightsBf type; };
-
-template <bool BF16, bool BWD>
-__device__ __forceinline__ typename EsStaged<BF16>::type es_stage(const float *W1, const float *b1, const float *W2,
-                                                                  const float *b2, const float *G, int outs)
-{
-    if constexpr (BF16)
-        return es_stage_weights_bf16<BWD>(W1, b1, W2, b2, G, outs);
-    else
-        return es_stage_weights(W1, b1, W2, b2, G, outs);
-}
-
 __device__ __forceinline__ bf16x8 bf_zero8()
 {
     const __bf16 z = (__bf16)0.0f;
@@ -228,7 +292,12 @@ __device__ __forceinline__ bf16x8 bf_feature_fragment(const float *f, int g)
     return fb;
 }
 
-__device__ __forceinline__ f32x4 es_drop4(f32x4 v, unsigned bits, int t, float scale);
+// x1 = W1 f + b1 of block m: one k-step
+__device__ __forceinline__ f32x4 es_first_pre(const EsWeightsBf &w, bf16x8 fb, int m, int col, int g)
+{
+    const f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * m + 4 * g]);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_k16_fragment(&w.W1s[(16 * m + col) * kBfK1], g), fb, acc, 0, 0, 0);
+}
 
 // h1 of the lane's edge as the four k-step fragments of the second product (rounded after GELU and dropout)
 template <bool DROP>
@@ -241,10 +310,7 @@ __device__ __forceinline__ void bf_first_layer(const EsWeightsBf &w, bf16x8 fb, 
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int m = 2 * s + half;
-            f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * m + 4 * g]);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_k16_fragment(&w.W1s[(16 * m + col) * kBfK1], g), fb, acc, 0,
-                                                          0, 0);
-            blk[half] = gelu4(acc);
+            blk[half] = gelu4(es_first_pre(w, fb, m, col, g));
             if constexpr (DROP) blk[half] = es_drop4(blk[half], keep, m, scale);
         }
         h1[s] = bf_pack(blk[0], blk[1]);
@@ -290,61 +356,46 @@ __device__ __forceinline__ f32x4 es_drop4(f32x4 v, unsigned bits, int t, float s
 // The scores of one wave's 16 edges: f, the edge's features or null for a lane without an edge (read as zeros);
 // lane group g = lane >> 4 holds the outputs 4 g + r in register r.  An edge is one column of every product, so its
 // scores do not depend on which edges share its tile.  DROP: h1 is keep * scale * h1, `keep` from es_keep_bits.
-// BF16: the same tile on v_mfma_f32_16x16x32_bf16 (the contract above): 8 + 32 + 4 MFMAs for 16 edges.
-template <bool DROP, bool BF16>
-__device__ __forceinline__ f32x4 es_wave_tile(const typename EsStaged<BF16>::type &w, const float *f, int col, int g,
-                                              unsigned keep = 0, float scale = 1.0f)
+// The staged weights' type picks the tile: fp32 here, bf16 below.
+template <bool DROP>
+__device__ __forceinline__ f32x4 es_wave_tile(const EsWeights &w, const float *f, int col, int g, unsigned keep = 0,
+                                              float scale = 1.0f)
 {
-    if constexpr (BF16) {
-        bf16x8 h1[4];
-        bf_first_layer<DROP>(w, bf_feature_fragment(f, g), col, g, keep, scale, h1);
-        f32x4 sc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 1
-        for (int s = 0; s < 4; ++s) {  // two blocks of h2 are k-step s of the third product
-            const f32x4 lo = gelu4(bf_second_layer(w, h1, 2 * s, col, g));
-            const f32x4 hi = gelu4(bf_second_layer(w, h1, 2 * s + 1, col, g));
-            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                *reinterpret_cast<const bf16x8 *>(&w.Gs[col * kBfStride + 32 * s + 8 * g]), bf_pack(lo, hi), sc, 0, 0, 0);
-        }
-        return sc;
-    } else {
-    // B fragments of the first product: F^T, k = 4 s + g on the lane group, edge on lane & 15
     float fb[3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        const int k = 4 * s + g;
-        fb[s] = (f && k < kDualEdgeIn) ? f[k] : 0.0f;
-    }
+    es_feature_fragment(f, g, fb);
     f32x4 h1[8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * m + 4 * g]);
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.W1s[(16 * m + col) * kKPad + 4 * s + g], fb[s], acc, 0, 0, 0);
-        h1[m] = gelu4(acc);
-        if constexpr (DROP) h1[m] = es_drop4(h1[m], keep, m, scale);
-    }
+    for (int m = 0; m < 8; ++m) h1[m] = es_first_layer<DROP>(w, fb, m, col, g, keep, scale);
     // second and third product together: block m of h2 is the k-steps (t = m, r) of the third product, so it
     // is used as soon as it exists.  The loop over m stays rolled (two blocks per trip: two independent
     // accumulator chains); unrolled, the scheduler hoists every LDS read of W2 and spills.
     f32x4 sc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 2
     for (int m = 0; m < 8; ++m) {
-        f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b2s[16 * m + 4 * g]);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(&w.W2s[(16 * m + col) * kWStride + 16 * t + 4 * g]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], h1[t][r], acc, 0, 0, 0);
-        }
-        const f32x4 h2 = gelu4(acc);
+        const f32x4 h2 = gelu4(es_second_layer(w, h1, m, col, g));
         const f32x4 gm = *reinterpret_cast<const f32x4 *>(&w.Gs[col * kWStride + 16 * m + 4 * g]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) sc = __builtin_amdgcn_mfma_f32_16x16x4f32(gm[r], h2[r], sc, 0, 0, 0);
     }
     return sc;
+}
+
+// The same tile on v_mfma_f32_16x16x32_bf16 (the contract above): 8 + 32 + 4 MFMAs for 16 edges.
+template <bool DROP>
+__device__ __forceinline__ f32x4 es_wave_tile(const EsWeightsBf &w, const float *f, int col, int g, unsigned keep = 0,
+                                              float scale = 1.0f)
+{
+    bf16x8 h1[4];
+    bf_first_layer<DROP>(w, bf_feature_fragment(f, g), col, g, keep, scale, h1);
+    f32x4 sc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+    for (int s = 0; s < 4; ++s) {  // two blocks of h2 are k-step s of the third product
+        const f32x4 lo = gelu4(bf_second_layer(w, h1, 2 * s, col, g));
+        const f32x4 hi = gelu4(bf_second_layer(w, h1, 2 * s + 1, col, g));
+        sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            *reinterpret_cast<const bf16x8 *>(&w.Gs[col * kBfStride + 32 * s + 8 * g]), bf_pack(lo, hi), sc, 0, 0, 0);
     }
+    return sc;
 }
 
 template <bool DROP, bool BF16>
@@ -354,7 +405,7 @@ dual_edge_scores_kernel(const float *F, const float *W1, const float *b1, const 
                         DualDropout drop)
 {
     const int outs = 2 * heads;
-    const auto w = es_stage<BF16, false>(W1, b1, W2, b2, G, outs);
+    const auto w = es_stage_weights<false>(std::bool_constant<BF16>{}, W1, b1, W2, b2, G, outs);
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int col = lane & 15, g = lane >> 4;
@@ -362,7 +413,7 @@ dual_edge_scores_kernel(const float *F, const float *W1, const float *b1, const 
         const long long e = tile * kEsTile + (long long)wave * kEsEdgesPerWave + col;
         // the keep bits before the MFMA chain, while few registers are live
         const unsigned keep = DROP ? es_keep_bits(drop, (unsigned long long)e, g) : 0u;
-        const f32x4 sc = es_wave_tile<DROP, BF16>(w, e < E ? F + e * kDualEdgeIn : nullptr, col, g, keep, drop.scale);
+        const f32x4 sc = es_wave_tile<DROP>(w, e < E ? F + e * kDualEdgeIn : nullptr, col, g, keep, drop.scale);
         // the tail tile: an edge past the end was read as zeros and is not written
         if (e < E) {
             const long long b = e / NN, rem = e - b * NN;
@@ -388,7 +439,7 @@ dual_edge_scores_ragged_kernel(const float *F, const float *W1, const float *b1,
                                DualDropout drop)
 {
     const int outs = 2 * heads;
-    const auto w = es_stage<BF16, false>(W1, b1, W2, b2, G, outs);
+    const auto w = es_stage_weights<false>(std::bool_constant<BF16>{}, W1, b1, W2, b2, G, outs);
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, g = lane >> 4;
@@ -396,18 +447,15 @@ dual_edge_scores_ragged_kernel(const float *F, const float *W1, const float *b1,
     const size_t NN = (size_t)N * N;
     long long next = (long long)blockIdx.x * kEsWaves + wave, first = 0;
     for (int b = 0; b < batch; ++b) {
-        int n = sizes[b];
-        n = (n >= 1 && n <= N) ? n : 0;
-        const int groups = (n + kEsEdgesPerWave - 1) / kEsEdgesPerWave;
-        const long long count = (long long)n * groups;  // at most 16384 * 1024
-        for (; next < first + count; next += stride) {
+        const EsInstanceTiles it = es_instance_tiles(sizes[b], N);
+        for (; next < first + it.count; next += stride) {
             const int t = (int)(next - first);
-            const int i = t / groups, j = (t - i * groups) * kEsEdgesPerWave + col;
+            const int i = t / it.groups, j = (t - i * it.groups) * kEsEdgesPerWave + col;
             const size_t at = (size_t)i * N + j;
             const unsigned keep = DROP ? es_keep_bits(drop, (unsigned long long)b * NN + at, g) : 0u;
-            const f32x4 sc = es_wave_tile<DROP, BF16>(w, j < n ? F + ((size_t)b * NN + at) * kDualEdgeIn : nullptr, col, g,
+            const f32x4 sc = es_wave_tile<DROP>(w, j < it.n ? F + ((size_t)b * NN + at) * kDualEdgeIn : nullptr, col, g,
                                                 keep, drop.scale);
-            if (j < n) {
+            if (j < it.n) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int o = 4 * g + r;  // dir * heads + h
@@ -415,7 +463,7 @@ dual_edge_scores_ragged_kernel(const float *F, const float *W1, const float *b1,
                 }
             }
         }
-        first += count;
+        first += it.count;
     }
 }
 
@@ -432,6 +480,42 @@ __device__ __forceinline__ unsigned long long at_drop_base(int b, int dir, int h
     return (unsigned long long)(((size_t)b * 2 + dir) * heads + h) * N * N;
 }
 
+// The slot (lq, lk) of a 16 x 64 tile that thread tid moves in round r.  Consecutive threads run along the contiguous
+// index of the scores: the key for the row direction, the query for the column direction.  The key-major kernel, whose
+// tiles are 16 keys x 64 queries, asks with !dir and swaps the two.
+struct AtSlot {
+    int lq, lk;
+};
+
+__device__ __forceinline__ AtSlot at_tile_slot(int tid, int dir, int r)
+{
+    return AtSlot{dir ? (tid & 15) : ((tid >> 6) + 4 * r), dir ? ((tid >> 4) + 16 * r) : (tid & 63)};
+}
+
+// What the forward and both backward kernels take from the forward's parameters for their (b, dir, h).  bh and node:
+// where (b, h) lies in a [batch][heads] tensor and (b, node 0, h, 0) in a [batch][n][heads * head_dim] one.
+struct AtView {
+    const float *sc, *a, *c, *val;
+    const unsigned char *mask;  // null with sizes: the mask is then the prefix [0, nb)
+    int nb;                     // bounds the queries and the keys
+    size_t bh, node;
+};
+
+__device__ __forceinline__ AtView at_view(const DualAttnParams &f, int b, int dir, int h)
+{
+    const int N = f.n, D = f.head_dim, hidden = f.heads * D;
+    AtView v;
+    v.bh = (size_t)b * f.heads + h;
+    v.node = (size_t)b * N * hidden + (size_t)h * D;
+    v.sc = f.scores + (((size_t)b * 2 + dir) * f.heads + h) * ((size_t)N * N);
+    v.a = (dir ? f.a_col : f.a_row) + v.bh * N;
+    v.c = (dir ? f.c_col : f.c_row) + v.bh * N;
+    v.val = (dir ? f.row_val : f.col_val) + v.node;
+    v.nb = f.sizes ? dual_prefix_len(f.sizes[b], N) : N;
+    v.mask = (f.mask && !f.sizes) ? f.mask + (size_t)b * N : nullptr;
+    return v;
+}
+
 // DROP: the tile of exp(score - max) carries the keep flag of its (query, key) in the sign bit (an exp is never
 // negative): -e is a dropped weight.  The sum takes |e|, the weighted values e * scale or 0, so the statistics are
 // those of the undropped softmax and LDS holds what it held.  The flag is a function of (q, k) alone: every pass over
@@ -446,22 +530,14 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_kernel(DualAttnPara
     const int dir = blockIdx.z & 1, b = blockIdx.z >> 1, h = blockIdx.y;
     const int q0 = blockIdx.x * kTQ;
     const int N = p.n, D = p.head_dim, hidden = p.heads * p.head_dim;
-    const size_t NN = (size_t)N * N;
-    const float *sc = p.scores + (((size_t)b * 2 + dir) * p.heads + h) * NN;
-    const float *a = (dir ? p.a_col : p.a_row) + ((size_t)b * p.heads + h) * N;
-    const float *c = (dir ? p.c_col : p.c_row) + ((size_t)b * p.heads + h) * N;
-    const float *val = (dir ? p.row_val : p.col_val) + (size_t)b * N * hidden + (size_t)h * D;
-    float *msg = (dir ? p.col_msg : p.row_msg) + (size_t)b * N * hidden + (size_t)h * D;
-    // with sizes the mask is the prefix: nb bounds the queries and the keys, and `mask` is not read
-    int nb = N;
-    if (p.sizes) {
-        nb = p.sizes[b];
-        nb = (nb >= 1 && nb <= N) ? nb : 0;
-    }
-    const unsigned char *mask = (p.mask && !p.sizes) ? p.mask + (size_t)b * N : nullptr;
+    const AtView v = at_view(p, b, dir, h);
+    const float *sc = v.sc, *a = v.a, *c = v.c, *val = v.val;
+    const unsigned char *mask = v.mask;
+    const int nb = v.nb;
+    float *msg = (dir ? p.col_msg : p.row_msg) + v.node;
     const int cq = tid >> 4, slot = tid & 15;
     float *stats = dir ? p.col_stats : p.row_stats;  // the training forward keeps every query's maximum and sum
-    if (stats) stats += ((size_t)b * p.heads + h) * N * 2;
+    if (stats) stats += v.bh * N * 2;
     if (q0 >= nb) {  // a block of padded queries (workgroup-uniform): zero messages, no key is read
         for (int idx = tid; idx < kTQ * D; idx += kAtThreads) {
             const int q = q0 + idx / D;
@@ -478,8 +554,7 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_kernel(DualAttnPara
     auto load_tile = [&](int k0, bool exps) {
 #pragma unroll
         for (int r = 0; r < (kTQ * kTK) / kAtThreads; ++r) {
-            const int lq = dir ? (tid & 15) : ((tid >> 6) + 4 * r);
-            const int lk = dir ? ((tid >> 4) + 16 * r) : (tid & 63);
+            const auto [lq, lk] = at_tile_slot(tid, dir, r);
             const int q = q0 + lq, k = k0 + lk;
             float s = at_neg_inf();
             if (q < nb && k < nb && (!mask || (mask[q] && mask[k]))) {
@@ -558,32 +633,17 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_kernel(DualAttnPara
 //   sum_k w dw (a first pass over the keys that also parks dw in dS); exactly 0 on a masked pair.
 // Every sum runs in a fixed order in fp32 (the parts of dkb in fp64); there is no atomic.
 
-struct AtBwdView {  // what both passes take from the parameters for their (b, dir, h)
-    const float *sc, *a, *c, *val, *msg, *dmsg, *stats;
-    const unsigned char *mask;
+struct AtBwdView : AtView {  // and what both backward passes add for their (b, dir, h)
+    const float *dmsg, *stats;
     float kb;
-    int nb;
 };
 
 __device__ __forceinline__ AtBwdView at_bwd_view(const DualAttnBwdParams &p, int b, int dir, int h)
 {
     const DualAttnParams &f = p.fwd;
-    const int N = f.n, D = f.head_dim, hidden = f.heads * D;
-    const size_t NN = (size_t)N * N, bh = (size_t)b * f.heads + h, node = (size_t)b * N * hidden + (size_t)h * D;
-    AtBwdView v;
-    v.sc = f.scores + (((size_t)b * 2 + dir) * f.heads + h) * NN;
-    v.a = (dir ? f.a_col : f.a_row) + bh * N;
-    v.c = (dir ? f.c_col : f.c_row) + bh * N;
-    v.val = (dir ? f.row_val : f.col_val) + node;
-    v.msg = (dir ? f.col_msg : f.row_msg) + node;
-    v.dmsg = (dir ? p.d_col_msg : p.d_row_msg) + node;
-    v.stats = (dir ? f.col_stats : f.row_stats) + bh * N * 2;
-    v.nb = N;
-    if (f.sizes) {
-        const int nb = f.sizes[b];
-        v.nb = (nb >= 1 && nb <= N) ? nb : 0;
-    }
-    v.mask = (f.mask && !f.sizes) ? f.mask + (size_t)b * N : nullptr;
+    AtBwdView v{at_view(f, b, dir, h)};
+    v.dmsg = (dir ? p.d_col_msg : p.d_row_msg) + v.node;
+    v.stats = (dir ? f.col_stats : f.row_stats) + v.bh * f.n * 2;
     v.kb = f.kbias[dir * f.heads + h];
     return v;
 }
@@ -610,7 +670,7 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_query_kernel(Du
     const AtBwdView v = at_bwd_view(p, b, dir, h);
     const int nb = v.nb;
     float *dS = p.dS + (((size_t)b * 2 + dir) * heads + h) * (size_t)N * N;
-    float *da = (dir ? p.da_col : p.da_row) + ((size_t)b * heads + h) * N;
+    float *da = (dir ? p.da_col : p.da_row) + v.bh * N;
     double *part = p.partials + ((size_t)blockIdx.z * heads + h) * gridDim.x + blockIdx.x;
     const int cq = tid >> 4, slot = tid & 15;
     if (q0 >= nb) {  // padded queries: zero gradients, no score and no dS entry is touched
@@ -631,8 +691,7 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_query_kernel(Du
     auto load_z = [&](int k0, bool with_dw) {
 #pragma unroll
         for (int r = 0; r < (kTQ * kTK) / kAtThreads; ++r) {
-            const int lq = dir ? (tid & 15) : ((tid >> 6) + 4 * r);
-            const int lk = dir ? ((tid >> 4) + 16 * r) : (tid & 63);
+            const auto [lq, lk] = at_tile_slot(tid, dir, r);
             const int qq = q0 + lq, k = k0 + lk;
             float z = at_neg_inf(), g = 0.0f;
             if (qq < nb && k < nb && (!v.mask || (v.mask[qq] && v.mask[k]))) {
@@ -647,8 +706,7 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_query_kernel(Du
     auto store_tile = [&](int k0) {  // s_z -> dS, inside the prefix (the whole matrix without sizes)
 #pragma unroll
         for (int r = 0; r < (kTQ * kTK) / kAtThreads; ++r) {
-            const int lq = dir ? (tid & 15) : ((tid >> 6) + 4 * r);
-            const int lk = dir ? ((tid >> 4) + 16 * r) : (tid & 63);
+            const auto [lq, lk] = at_tile_slot(tid, dir, r);
             const int qq = q0 + lq, k = k0 + lk;
             if (qq < nb && k < nb) dS[dir ? (size_t)k * N + qq : (size_t)qq * N + k] = s_z[lq][lk];
         }
@@ -757,8 +815,8 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_key_kernel(Dual
     const AtBwdView v = at_bwd_view(p, b, dir, h);
     const int nb = v.nb;
     const float *dS = p.dS + (((size_t)b * 2 + dir) * heads + h) * (size_t)N * N;
-    float *dc = (dir ? p.dc_col : p.dc_row) + ((size_t)b * heads + h) * N;
-    float *dval = (dir ? p.d_row_val : p.d_col_val) + (size_t)b * N * hidden + (size_t)h * D;
+    float *dc = (dir ? p.dc_col : p.dc_row) + v.bh * N;
+    float *dval = (dir ? p.d_row_val : p.d_col_val) + v.node;
     const int ck = tid >> 4, slot = tid & 15;
     const unsigned long long drop_base = DROP ? at_drop_base(b, dir, h, heads, N) : 0;
     if (kk0 >= nb) {  // padded keys
@@ -778,8 +836,7 @@ __global__ void __launch_bounds__(kAtThreads) dual_attention_bwd_key_kernel(Dual
         for (int q0 = 0; q0 < nb; q0 += kTK) {
 #pragma unroll
             for (int r = 0; r < (kTQ * kTK) / kAtThreads; ++r) {
-                const int lk = dir ? ((tid >> 6) + 4 * r) : (tid & 15);
-                const int lq = dir ? (tid & 63) : ((tid >> 4) + 16 * r);
+                const auto [lk, lq] = at_tile_slot(tid, !dir, r);  // the roles swapped
                 const int q = q0 + lq, k = kk0 + lk;
                 float w = 0.0f, g = 0.0f;
                 if (q < nb && k < nb && (!v.mask || (v.mask[q] && v.mask[k]))) {
@@ -874,15 +931,14 @@ __device__ __forceinline__ float gelu_grad(float x)
     return cdf + x * pdf;
 }
 
-// One wave tile.  f: the features of the lane's edge or null; ds: dS of the lane's edge for the outputs 4 s + g
-// (zeros for a lane without an edge and past 2 * heads); row: the lane's workspace row.  DROP: the recompute applies
-// the forward's mask (`keep` from es_keep_bits), the row's h1 is the dropped one, which dW2 needs, and
-// dx1 = dh1 * keep * scale * GELU'(x1).
+// One wave tile, eb_wave_tile: two overloads picked by the staged weights' type, as es_wave_tile's.  f: the features of
+// the lane's edge or null; ds: dS of the lane's edge (zeros for a lane without an edge and past 2 * heads); row: where
+// the tile's rows go.  DROP: the recompute applies the forward's mask (`keep` from es_keep_bits), the row's h1 is the
+// dropped one, which dW2 needs, and dx1 = dh1 * keep * scale * GELU'(x1).
 //
-// BF16 (the contract at the top of this file): the workspace holds, per wave tile, an image [544 units][16 edges] of
+// bf16 (the contract at the top of this file): the workspace holds, per wave tile, an image [544 units][16 edges] of
 // bf16 in the unit order of the fp32 row (kRowH1 .. kRowF), so that a fragment of stage 2, eight consecutive edges of
-// one unit, is one 16-byte load.  `ds` is then dS of the lane's edge for the outputs 8 g + j (g < 2) and `row` the
-// wave tile's image.  32 units at a time go through the wave's LDS buffer (eb_flush32): 2-byte LDS writes, one 16-byte
+// one unit, is one 16-byte load.  32 units at a time go through the wave's LDS buffer (eb_flush32): 2-byte LDS writes, one 16-byte
 // read and one 16-byte global store per lane.  dh2 = G^T dS takes G^T and dh1 = W2^T dh2pre takes W2^T from their own
 // staged images, so every A fragment is one LDS read; the loop walks two blocks of h2 at a time, one k-step of dh1.
 
@@ -908,88 +964,17 @@ __device__ __forceinline__ void eb_flush32(__bf16 *buf, bf16x8 v, __bf16 *dst, i
     eb_flush_copy(buf, dst, lane);
 }
 
-template <bool DROP, bool BF16>
-__device__ __forceinline__ void eb_wave_tile(const typename EsStaged<BF16>::type &w, const float *f,
-                                             const float (&ds)[BF16 ? 8 : 4],
-                                             typename std::conditional<BF16, __bf16, float>::type *row, int col, int g,
-                                             unsigned keep = 0, float scale = 1.0f)
+// fp32: ds is dS of the lane's edge for the outputs 4 s + g, row the lane's workspace row.
+template <bool DROP>
+__device__ __forceinline__ void eb_wave_tile(const EsWeights &w, const float *f, const float (&ds)[4], float *row, int col,
+                                             int g, unsigned keep = 0, float scale = 1.0f)
 {
-    if constexpr (BF16) {
-        const int lane = 16 * g + col;
-        const bf16x8 fb = bf_feature_fragment(f, g);
-        bf16x8 dsb;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dsb[j] = (__bf16)ds[j];
-        bf16x8 h1[4];
-        bf_first_layer<DROP>(w, fb, col, g, keep, scale, h1);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) eb_flush32(w.flush, h1[s], row + (kRowH1 + 32 * s) * kEsEdgesPerWave, lane);
-        f32x4 dh1[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) dh1[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 1
-        for (int s = 0; s < 4; ++s) {
-            f32x4 x2[2], d[2];
-#pragma unroll
-            for (int half = 0; half < 2; ++half) x2[half] = bf_second_layer(w, h1, 2 * s + half, col, g);
-            eb_flush32(w.flush, bf_pack(gelu4(x2[0]), gelu4(x2[1])), row + (kRowH2 + 32 * s) * kEsEdgesPerWave, lane);
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int m = 2 * s + half;
-                d[half] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_k16_fragment(&w.GTs[(16 * m + col) * kBfK1], g), dsb,
-                                                                  f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) d[half][r] = d[half][r] * gelu_grad(x2[half][r]);
-            }
-            const bf16x8 dp = bf_pack(d[0], d[1]);
-            eb_flush32(w.flush, dp, row + (kRowDh2 + 32 * s) * kEsEdgesPerWave, lane);
-#pragma unroll
-            for (int t = 0; t < 8; ++t)
-                dh1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    *reinterpret_cast<const bf16x8 *>(&w.W2Ts[(16 * t + col) * kBfStride + 32 * s + 8 * g]), dp, dh1[t], 0,
-                    0, 0);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {  // the first layer's pre-activation once more
-            f32x4 d[2];
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int t = 2 * s + half;
-                f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * t + 4 * g]);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_k16_fragment(&w.W1s[(16 * t + col) * kBfK1], g), fb, acc,
-                                                              0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) d[half][r] = dh1[t][r] * gelu_grad(acc[r]);
-                if constexpr (DROP) d[half] = es_drop4(d[half], keep, t, scale);
-            }
-            eb_flush32(w.flush, bf_pack(d[0], d[1]), row + (kRowDh1 + 32 * s) * kEsEdgesPerWave, lane);
-        }
-        // dS (16 units) and the features with their column of ones (16 units): the lane groups 0 and 1 hold them
-        if (g < 2) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int k = 8 * g + j;
-                w.flush[k * kEsEdgesPerWave + col] = dsb[j];
-                w.flush[(kOutPad + k) * kEsEdgesPerWave + col] = k == kOnesCol ? (__bf16)(f ? 1.0f : 0.0f) : fb[j];
-            }
-        }
-        eb_flush_copy(w.flush, row + kRowDs * kEsEdgesPerWave, lane);
-    } else {
     float fb[3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        const int k = 4 * s + g;
-        fb[s] = (f && k < kDualEdgeIn) ? f[k] : 0.0f;
-    }
+    es_feature_fragment(f, g, fb);
     f32x4 h1[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
-        f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * m + 4 * g]);
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.W1s[(16 * m + col) * kKPad + 4 * s + g], fb[s], acc, 0, 0, 0);
-        h1[m] = gelu4(acc);
-        if constexpr (DROP) h1[m] = es_drop4(h1[m], keep, m, scale);
+        h1[m] = es_first_layer<DROP>(w, fb, m, col, g, keep, scale);
         *reinterpret_cast<f32x4 *>(&row[kRowH1 + 16 * m + 4 * g]) = h1[m];
     }
     f32x4 dh1[8];
@@ -997,13 +982,7 @@ __device__ __forceinline__ void eb_wave_tile(const typename EsStaged<BF16>::type
     for (int t = 0; t < 8; ++t) dh1[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 1
     for (int m = 0; m < 8; ++m) {
-        f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b2s[16 * m + 4 * g]);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(&w.W2s[(16 * m + col) * kWStride + 16 * t + 4 * g]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], h1[t][r], acc, 0, 0, 0);
-        }
+        const f32x4 acc = es_second_layer(w, h1, m, col, g);
         *reinterpret_cast<f32x4 *>(&row[kRowH2 + 16 * m + 4 * g]) = gelu4(acc);
         f32x4 d = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -1021,10 +1000,7 @@ __device__ __forceinline__ void eb_wave_tile(const typename EsStaged<BF16>::type
     }
 #pragma unroll
     for (int t = 0; t < 8; ++t) {  // the first layer's pre-activation once more: three products, no register kept
-        f32x4 acc = *reinterpret_cast<const f32x4 *>(&w.b1s[16 * t + 4 * g]);
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.W1s[(16 * t + col) * kKPad + 4 * s + g], fb[s], acc, 0, 0, 0);
+        const f32x4 acc = es_first_pre(w, fb, t, col, g);
         f32x4 d;
 #pragma unroll
         for (int r = 0; r < 4; ++r) d[r] = dh1[t][r] * gelu_grad(acc[r]);
@@ -1037,21 +1013,84 @@ __device__ __forceinline__ void eb_wave_tile(const typename EsStaged<BF16>::type
         row[kRowDs + k] = ds[s];
         row[kRowF + k] = s < 3 ? (k == kOnesCol ? (f ? 1.0f : 0.0f) : fb[s]) : 0.0f;
     }
+}
+
+// bf16: ds is dS of the lane's edge for the outputs 8 g + j (g < 2), row the wave tile's image.
+template <bool DROP>
+__device__ __forceinline__ void eb_wave_tile(const EsWeightsBf &w, const float *f, const float (&ds)[8], __bf16 *row,
+                                             int col, int g, unsigned keep = 0, float scale = 1.0f)
+{
+    const int lane = 16 * g + col;
+    const bf16x8 fb = bf_feature_fragment(f, g);
+    bf16x8 dsb;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dsb[j] = (__bf16)ds[j];
+    bf16x8 h1[4];
+    bf_first_layer<DROP>(w, fb, col, g, keep, scale, h1);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) eb_flush32(w.flush, h1[s], row + (kRowH1 + 32 * s) * kEsEdgesPerWave, lane);
+    f32x4 dh1[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) dh1[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+    for (int s = 0; s < 4; ++s) {
+        f32x4 x2[2], d[2];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) x2[half] = bf_second_layer(w, h1, 2 * s + half, col, g);
+        eb_flush32(w.flush, bf_pack(gelu4(x2[0]), gelu4(x2[1])), row + (kRowH2 + 32 * s) * kEsEdgesPerWave, lane);
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int m = 2 * s + half;
+            d[half] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf_k16_fragment(&w.GTs[(16 * m + col) * kBfK1], g), dsb,
+                                                              f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) d[half][r] = d[half][r] * gelu_grad(x2[half][r]);
+        }
+        const bf16x8 dp = bf_pack(d[0], d[1]);
+        eb_flush32(w.flush, dp, row + (kRowDh2 + 32 * s) * kEsEdgesPerWave, lane);
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+            dh1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                *reinterpret_cast<const bf16x8 *>(&w.W2Ts[(16 * t + col) * kBfStride + 32 * s + 8 * g]), dp, dh1[t], 0, 0,
+                0);
     }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {  // the first layer's pre-activation once more
+        f32x4 d[2];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int t = 2 * s + half;
+            const f32x4 acc = es_first_pre(w, fb, t, col, g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) d[half][r] = dh1[t][r] * gelu_grad(acc[r]);
+            if constexpr (DROP) d[half] = es_drop4(d[half], keep, t, scale);
+        }
+        eb_flush32(w.flush, bf_pack(d[0], d[1]), row + (kRowDh1 + 32 * s) * kEsEdgesPerWave, lane);
+    }
+    // dS (16 units) and the features with their column of ones (16 units): the lane groups 0 and 1 hold them
+    if (g < 2) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = 8 * g + j;
+            w.flush[k * kEsEdgesPerWave + col] = dsb[j];
+            w.flush[(kOutPad + k) * kEsEdgesPerWave + col] = k == kOnesCol ? (__bf16)(f ? 1.0f : 0.0f) : fb[j];
+        }
+    }
+    eb_flush_copy(w.flush, row + kRowDs * kEsEdgesPerWave, lane);
 }
 
 // The wave tiles [t0, t1) of the batch: numbered 16 edges at a time in the linear edge order (sizes null) or as
-// dual_edge_scores_ragged_kernel numbers them.  Wave tile t writes the rows 16 (t - t0) .. + 15.
-// BF16: rows holds bf16 images of 16 edges (eb_wave_tile), half the bytes.
+// dual_edge_scores_ragged_kernel numbers them.  Wave tile t writes the rows 16 (t - t0) .. + 15 of `rows`: floats, or
+// with BF16 the bf16 images of 16 edges (eb_wave_tile), half the bytes.
 template <bool DROP, bool BF16>
 __global__ void __launch_bounds__(kEsThreads)
 dual_edge_backward_kernel(const float *F, const float *W1, const float *b1, const float *W2, const float *b2,
                           const float *G, const float *dS, const int *sizes, int batch, int N, int heads,
-                          long long t0, long long t1, typename std::conditional<BF16, __bf16, float>::type *rows,
-                          DualDropout drop)
+                          long long t0, long long t1, void *rows, DualDropout drop)
 {
     const int outs = 2 * heads;
-    const auto w = es_stage<BF16, true>(W1, b1, W2, b2, G, outs);
+    const auto w = es_stage_weights<true>(std::bool_constant<BF16>{}, W1, b1, W2, b2, G, outs);
+    typedef decltype(w) Staged;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, g = lane >> 4;
@@ -1060,18 +1099,19 @@ dual_edge_backward_kernel(const float *F, const float *W1, const float *b1, cons
     long long next = t0 + (long long)blockIdx.x * kEsWaves + wave;
     // at: the edge's offset inside its instance's [n][n] plane, or -1
     auto tile = [&](long long t, int b, long long at) {
-        float ds[BF16 ? 8 : 4];
+        float ds[Staged::kDsRegs];
 #pragma unroll
-        for (int s = 0; s < (BF16 ? 8 : 4); ++s) {
+        for (int s = 0; s < Staged::kDsRegs; ++s) {
             const int o = BF16 ? 8 * g + s : 4 * s + g;  // the k index of dS as the lane's fragment holds it
             ds[s] = (at >= 0 && o < outs) ? dS[((size_t)b * outs + o) * NN + (size_t)at] : 0.0f;
         }
         // the lane's row, or with BF16 the wave tile's image
-        auto *row = rows + ((size_t)(t - t0) * kEsEdgesPerWave + (BF16 ? 0 : col)) * kRowFloats;
+        auto *row = static_cast<typename Staged::Row *>(rows) +
+                    ((size_t)(t - t0) * kEsEdgesPerWave + (BF16 ? 0 : col)) * kRowFloats;
         // a lane without an edge has dS = 0, hence dx2 = dx1 = 0 whatever its bits are
         const unsigned keep = DROP ? es_keep_bits(drop, (unsigned long long)b * NN + (at >= 0 ? at : 0), g) : 0u;
-        eb_wave_tile<DROP, BF16>(w, at >= 0 ? F + ((size_t)b * NN + (size_t)at) * kDualEdgeIn : nullptr, ds, row, col, g,
-                                 keep, drop.scale);
+        eb_wave_tile<DROP>(w, at >= 0 ? F + ((size_t)b * NN + (size_t)at) * kDualEdgeIn : nullptr, ds, row, col, g, keep,
+                           drop.scale);
     };
     if (!sizes) {
         const long long E = (long long)NN * batch;
@@ -1084,17 +1124,14 @@ dual_edge_backward_kernel(const float *F, const float *W1, const float *b1, cons
     }
     long long first = 0;
     for (int b = 0; b < batch && first < t1; ++b) {
-        int n = sizes[b];
-        n = (n >= 1 && n <= N) ? n : 0;
-        const int groups = (n + kEsEdgesPerWave - 1) / kEsEdgesPerWave;
-        const long long count = (long long)n * groups;
-        const long long end = first + count < t1 ? first + count : t1;
+        const EsInstanceTiles it = es_instance_tiles(sizes[b], N);
+        const long long end = first + it.count < t1 ? first + it.count : t1;
         for (; next < end; next += stride) {
             const int t = (int)(next - first);
-            const int i = t / groups, j = (t - i * groups) * kEsEdgesPerWave + col;
-            tile(next, b, j < n ? (long long)i * N + j : -1);
+            const int i = t / it.groups, j = (t - i * it.groups) * kEsEdgesPerWave + col;
+            tile(next, b, j < it.n ? (long long)i * N + j : -1);
         }
-        first += count;
+        first += it.count;
     }
 }
 
@@ -1103,30 +1140,52 @@ __device__ __forceinline__ long long eb_chunk_rows(const int *sizes, int batch, 
 {
     if (sizes) {
         long long total = 0;
-        for (int b = 0; b < batch; ++b) {
-            int n = sizes[b];
-            n = (n >= 1 && n <= N) ? n : 0;
-            total += (long long)n * ((n + kEsEdgesPerWave - 1) / kEsEdgesPerWave);
-        }
+        for (int b = 0; b < batch; ++b) total += es_instance_tiles(sizes[b], N).count;
         t1 = total < t1 ? total : t1;
     }
     return t1 > t0 ? (t1 - t0) * kEsEdgesPerWave : 0;
+}
+
+// Stage 2, both precisions: a workgroup's slice [begin, end) of the chunk's rows (per and the chunk's row count are
+// multiples of 16), the lane's place in its wave's tiles, and the eleven accumulators zeroed.
+struct WgSlice {
+    int wave, col, g;
+    long long begin, end;
+};
+
+__device__ __forceinline__ WgSlice wg_begin(const int *sizes, int batch, int N, long long t0, long long t1, int per,
+                                            f32x4 (&acc)[11])
+{
+    const long long nrows = eb_chunk_rows(sizes, batch, N, t0, t1);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long long begin = (long long)blockIdx.x * per;
+    const WgSlice s{wave, lane & 15, lane >> 4, begin, begin + per < nrows ? begin + per : nrows};
+#pragma unroll
+    for (int j = 0; j < 11; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    return s;
+}
+
+// the workgroup's partials: wave w owns the tiles 8 w + j of dW2 and the tile w of dG, dW1 | db1 and db2
+__device__ __forceinline__ void wg_store(float *partials, const f32x4 (&acc)[11], const WgSlice &s)
+{
+    float *out = partials + (size_t)blockIdx.x * kWgOut;
+#pragma unroll
+    for (int j = 0; j < 11; ++j) {
+        const int tile = j < 8 ? 8 * s.wave + j : 64 + 8 * (j - 8) + s.wave;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[tile * 256 + (4 * s.g + r) * 16 + s.col] = acc[j][r];
+    }
 }
 
 __global__ void __launch_bounds__(kEsThreads)
 dual_edge_wgrad_kernel(const float *rows, const int *sizes, int batch, int N, long long t0, long long t1, int per,
                        float *partials)
 {
-    const long long nrows = eb_chunk_rows(sizes, batch, N, t0, t1);
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int col = lane & 15, g = lane >> 4;
-    const long long begin = (long long)blockIdx.x * per;
-    const long long end = begin + per < nrows ? begin + per : nrows;  // per and nrows are multiples of 16
     f32x4 acc[11];
-#pragma unroll
-    for (int j = 0; j < 11; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    for (long long e = begin; e < end; e += 4) {
+    const WgSlice s = wg_begin(sizes, batch, N, t0, t1, per, acc);
+    const int wave = s.wave, col = s.col, g = s.g;
+    for (long long e = s.begin; e < s.end; e += 4) {
         const float *row = rows + (size_t)(e + g) * kRowFloats;
         const float a2 = row[kRowDh2 + 16 * wave + col], a1 = row[kRowDh1 + 16 * wave + col];
         const float as = row[kRowDs + col], bf = row[kRowF + col], bh = row[kRowH2 + 16 * wave + col];
@@ -1137,13 +1196,7 @@ dual_edge_wgrad_kernel(const float *rows, const int *sizes, int batch, int N, lo
         acc[9] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bf, acc[9], 0, 0, 0);
         acc[10] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, bf, acc[10], 0, 0, 0);
     }
-    float *out = partials + (size_t)blockIdx.x * kWgOut;
-#pragma unroll
-    for (int j = 0; j < 11; ++j) {
-        const int tile = j < 8 ? 8 * wave + j : 64 + 8 * (j - 8) + wave;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) out[tile * 256 + (4 * g + r) * 16 + col] = acc[j][r];
-    }
+    wg_store(partials, acc, s);
 }
 
 // The same five products on v_mfma_f32_16x16x32_bf16 from the bf16 images of stage 1: the edge is k, one k-step takes
@@ -1153,17 +1206,11 @@ __global__ void __launch_bounds__(kEsThreads)
 dual_edge_wgrad_bf16_kernel(const __bf16 *rows, const int *sizes, int batch, int N, long long t0, long long t1, int per,
                             float *partials)
 {
-    const long long nrows = eb_chunk_rows(sizes, batch, N, t0, t1);
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int col = lane & 15, g = lane >> 4;
-    const long long begin = (long long)blockIdx.x * per;
-    const long long end = begin + per < nrows ? begin + per : nrows;  // per and nrows are multiples of 16
-    const long long tile_end = end / kEsEdgesPerWave;
     f32x4 acc[11];
-#pragma unroll
-    for (int j = 0; j < 11; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    for (long long pair = begin / kEsEdgesPerWave; pair < tile_end; pair += 2) {  // wave-uniform
+    const WgSlice s = wg_begin(sizes, batch, N, t0, t1, per, acc);
+    const int wave = s.wave, col = s.col, g = s.g;
+    const long long tile_end = s.end / kEsEdgesPerWave;
+    for (long long pair = s.begin / kEsEdgesPerWave; pair < tile_end; pair += 2) {  // wave-uniform
         const long long tile = pair + (g >> 1);
         const bool has = tile < tile_end;
         const __bf16 *image = rows + (size_t)(has ? tile : 0) * kEsEdgesPerWave * kRowFloats + 8 * (g & 1);
@@ -1179,13 +1226,7 @@ dual_edge_wgrad_bf16_kernel(const __bf16 *rows, const int *sizes, int batch, int
         acc[9] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bf, acc[9], 0, 0, 0);
         acc[10] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, bf, acc[10], 0, 0, 0);
     }
-    float *out = partials + (size_t)blockIdx.x * kWgOut;
-#pragma unroll
-    for (int j = 0; j < 11; ++j) {
-        const int tile = j < 8 ? 8 * wave + j : 64 + 8 * (j - 8) + wave;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) out[tile * 256 + (4 * g + r) * 16 + col] = acc[j][r];
-    }
+    wg_store(partials, acc, s);
 }
 
 // output idx of the partials = tile * 256 + row * 16 + column of the tile
@@ -1217,16 +1258,37 @@ dual_edge_wgrad_reduce_kernel(const float *partials, int blocks, double *sums, i
 constexpr size_t kEsLdsBytes = (size_t)kEsLdsFloats * sizeof(float);
 
 // more dynamic LDS than the 64 KB default is allowed once per process and kernel, not on each of a forward's
-// launches (and not inside a capture: the first launch is the uncaptured warm-up every captured call has)
-hipError_t es_raise_lds(const void *kernel, std::atomic<bool> &raised, size_t bytes = kEsLdsBytes)
+// launches (and not inside a capture: the first launch is the uncaptured warm-up every captured call has).  The flag
+// belongs to the kernel instantiation: one shared by two would leave the second without its attribute.
+template <auto Kernel>
+hipError_t es_raise_lds(size_t bytes)
 {
+    static std::atomic<bool> raised{false};
     if (!raised.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return e;
         raised.store(true, std::memory_order_release);
     }
     return hipSuccess;
 }
+
+// f(std::bool_constant...) of the runtime flags: where a launch picks its <DROP> or <DROP, BF16> instantiation
+template <class F>
+hipError_t dispatch_bools(bool a, F &&f)
+{
+    return a ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <class F>
+hipError_t dispatch_bools(bool a, bool b, F &&f)
+{
+    return dispatch_bools(a, [&](auto A) { return dispatch_bools(b, [&](auto B) { return f(A, B); }); });
+}
+
+// the padded batch's wave tiles in the ragged numbering: the sizes are on the device, so grids and workspaces are
+// sized for every instance at n
+long long es_padded_tiles(int batch, int n) { return batch * es_instance_tiles(n, n).count; }
 
 }  // namespace
 
@@ -1239,92 +1301,45 @@ size_t dual_gnn_workspace_bytes(int batch, int n, int heads)
 
 namespace {
 
-template <bool DROP, bool BF16 = false>
-hipError_t edge_scores_uniform(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                               const float *b2, const float *G, float *scores, int batch, int n, int heads,
-                               const DualDropout &drop, hipStream_t stream)
+template <bool DROP, bool BF16>
+hipError_t edge_scores(const DualEdgeParams &p, float *scores, hipStream_t stream)
 {
-    const long long NN = (long long)n * n, E = NN * batch;
-    const long long tiles = (E + kEsTile - 1) / kEsTile;
-    const int blocks = (int)(tiles < kEsMaxBlocks ? tiles : kEsMaxBlocks);
-    static std::atomic<bool> raised{false};
     constexpr size_t lds = BF16 ? kEsBfFwdBytes : kEsLdsBytes;
-    const auto kernel = dual_edge_scores_kernel<DROP, BF16>;
-    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(kernel), raised, lds)) return e;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kEsThreads), lds, stream, edge_feat, W1, b1, W2, b2, G, scores, E, NN,
-                       heads, tiles, drop);
-    return hipGetLastError();
-}
-
-template <bool DROP, bool BF16 = false>
-hipError_t edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                              const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
-                              int heads, const DualDropout &drop, hipStream_t stream)
-{
-    // the sizes are on the device: the grid is sized for the padded batch, and a workgroup without a tile leaves
-    const long long wave_tiles = (long long)batch * n * ((n + kEsEdgesPerWave - 1) / kEsEdgesPerWave);
-    const long long tiles = (wave_tiles + kEsWaves - 1) / kEsWaves;
-    const int blocks = (int)(tiles < kEsMaxBlocks ? tiles : kEsMaxBlocks);
-    static std::atomic<bool> raised{false};
-    constexpr size_t lds = BF16 ? kEsBfFwdBytes : kEsLdsBytes;
-    const auto kernel = dual_edge_scores_ragged_kernel<DROP, BF16>;
-    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(kernel), raised, lds)) return e;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kEsThreads), lds, stream, edge_feat, W1, b1, W2, b2, G, scores, sizes,
-                       batch, n, heads, drop);
+    const long long NN = (long long)p.n * p.n, E = NN * p.batch;
+    // a workgroup takes 8 wave tiles at a time; with sizes the grid is sized for the padded batch, and a workgroup
+    // without a tile leaves
+    const long long tiles = p.sizes ? (es_padded_tiles(p.batch, p.n) + kEsWaves - 1) / kEsWaves : (E + kEsTile - 1) / kEsTile;
+    const dim3 grid((unsigned)(tiles < kEsMaxBlocks ? tiles : kEsMaxBlocks));
+    if (p.sizes) {
+        constexpr auto kernel = dual_edge_scores_ragged_kernel<DROP, BF16>;
+        if (hipError_t e = es_raise_lds<kernel>(lds)) return e;
+        hipLaunchKernelGGL(kernel, grid, dim3(kEsThreads), lds, stream, p.edge_feat, p.W1, p.b1, p.W2, p.b2, p.G, scores,
+                           p.sizes, p.batch, p.n, p.heads, p.drop);
+    } else {
+        constexpr auto kernel = dual_edge_scores_kernel<DROP, BF16>;
+        if (hipError_t e = es_raise_lds<kernel>(lds)) return e;
+        hipLaunchKernelGGL(kernel, grid, dim3(kEsThreads), lds, stream, p.edge_feat, p.W1, p.b1, p.W2, p.b2, p.G, scores,
+                           E, NN, p.heads, tiles, p.drop);
+    }
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                   const float *b2, const float *G, float *scores, int batch, int n, int heads,
-                                   hipStream_t stream)
+hipError_t launch_dual_edge_scores(const DualEdgeParams &p, float *scores, hipStream_t stream)
 {
-    return edge_scores_uniform<false>(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, DualDropout{}, stream);
-}
-
-hipError_t launch_dual_edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                          const float *b2, const float *G, float *scores, const int *sizes, int batch,
-                                          int n, int heads, hipStream_t stream)
-{
-    return edge_scores_ragged<false>(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, DualDropout{},
-                                     stream);
-}
-
-hipError_t launch_dual_edge_scores_dropout(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                           const float *b2, const float *G, float *scores, const int *sizes, int batch,
-                                           int n, int heads, const DualDropout &drop, hipStream_t stream)
-{
-    if (!drop.on) {
-        return sizes ? launch_dual_edge_scores_ragged(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, stream)
-                     : launch_dual_edge_scores(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, stream);
-    }
-    return sizes ? edge_scores_ragged<true>(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop, stream)
-                 : edge_scores_uniform<true>(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, drop, stream);
-}
-
-hipError_t launch_dual_edge_scores_bf16(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                        const float *b2, const float *G, float *scores, const int *sizes, int batch,
-                                        int n, int heads, const DualDropout &drop, hipStream_t stream)
-{
-    if (drop.on)
-        return sizes ? edge_scores_ragged<true, true>(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop,
-                                                      stream)
-                     : edge_scores_uniform<true, true>(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, drop,
-                                                       stream);
-    return sizes ? edge_scores_ragged<false, true>(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop,
-                                                   stream)
-                 : edge_scores_uniform<false, true>(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, drop, stream);
+    return dispatch_bools(p.drop.on, p.bf16, [&](auto drop, auto bf16) {
+        return edge_scores<decltype(drop)::value, decltype(bf16)::value>(p, scores, stream);
+    });
 }
 
 hipError_t launch_dual_attention(const DualAttnParams &p, hipStream_t stream)
 {
     const dim3 grid((p.n + kTQ - 1) / kTQ, p.heads, 2 * p.batch);
-    if (p.drop.on)
-        hipLaunchKernelGGL(dual_attention_kernel<true>, grid, dim3(kAtThreads), 0, stream, p);
-    else
-        hipLaunchKernelGGL(dual_attention_kernel<false>, grid, dim3(kAtThreads), 0, stream, p);
-    return hipGetLastError();
+    return dispatch_bools(p.drop.on, [&](auto drop) {
+        hipLaunchKernelGGL(dual_attention_kernel<decltype(drop)::value>, grid, dim3(kAtThreads), 0, stream, p);
+        return hipGetLastError();
+    });
 }
 
 __global__ void __launch_bounds__(256)
@@ -1358,7 +1373,7 @@ struct EdgeBwdLayout {
 EdgeBwdLayout edge_bwd_layout(int batch, int n)
 {
     EdgeBwdLayout l;
-    l.tiles = (long long)batch * n * ((n + kEsEdgesPerWave - 1) / kEsEdgesPerWave);
+    l.tiles = es_padded_tiles(batch, n);
     const long long all = l.tiles * kEsEdgesPerWave;
     l.rows = all < kDualBwdChunk ? all : kDualBwdChunk;
     long long per = (l.rows + kWgMaxBlocks - 1) / kWgMaxBlocks;
@@ -1387,16 +1402,14 @@ hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_
     const DualAttnParams &f = p.fwd;
     const int tiles = (f.n + kTQ - 1) / kTQ;
     const dim3 grid(tiles, f.heads, 2 * f.batch);
-    if (f.drop.on)
-        hipLaunchKernelGGL(dual_attention_bwd_query_kernel<true>, grid, dim3(kAtThreads), 0, stream, p);
-    else
-        hipLaunchKernelGGL(dual_attention_bwd_query_kernel<false>, grid, dim3(kAtThreads), 0, stream, p);
-    if (hipError_t e = hipGetLastError()) return e;
-    if (f.drop.on)
-        hipLaunchKernelGGL(dual_attention_bwd_key_kernel<true>, grid, dim3(kAtThreads), 0, stream, p);
-    else
-        hipLaunchKernelGGL(dual_attention_bwd_key_kernel<false>, grid, dim3(kAtThreads), 0, stream, p);
-    if (hipError_t e = hipGetLastError()) return e;
+    const hipError_t e = dispatch_bools(f.drop.on, [&](auto drop) {
+        constexpr bool DROP = decltype(drop)::value;
+        hipLaunchKernelGGL(dual_attention_bwd_query_kernel<DROP>, grid, dim3(kAtThreads), 0, stream, p);
+        if (hipError_t e = hipGetLastError()) return e;
+        hipLaunchKernelGGL(dual_attention_bwd_key_kernel<DROP>, grid, dim3(kAtThreads), 0, stream, p);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(dual_attention_bwd_kbias_kernel, dim3(2 * f.heads), dim3(kAtThreads), 0, stream, p.partials,
                        p.dkb, f.batch, f.heads, tiles);
     return hipGetLastError();
@@ -1405,40 +1418,37 @@ hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_
 namespace {
 
 template <bool DROP, bool BF16>
-hipError_t edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
-                                float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
-                                void *workspace, hipStream_t stream, const DualDropout &drop)
+hipError_t edge_scores_backward(const DualEdgeParams &p, const float *dS, const DualEdgeGrads &grads, void *workspace,
+                                hipStream_t stream)
 {
-    const EdgeBwdLayout l = edge_bwd_layout(batch, n);
-    const long long E = (long long)batch * n * n;
-    const long long tiles = sizes ? l.tiles : (E + kEsEdgesPerWave - 1) / kEsEdgesPerWave;
+    const EdgeBwdLayout l = edge_bwd_layout(p.batch, p.n);
+    const long long E = (long long)p.batch * p.n * p.n;
+    const long long tiles = p.sizes ? l.tiles : (E + kEsEdgesPerWave - 1) / kEsEdgesPerWave;
     const long long chunk = kDualBwdChunk / kEsEdgesPerWave;
-    // BF16: the chunk's rows are bf16 images in the first half of the fp32 rows' room
-    auto *rows = static_cast<typename std::conditional<BF16, __bf16, float>::type *>(workspace);
+    // the chunk's rows first; BF16: bf16 images in the first half of the fp32 rows' room
     float *partials = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + l.partials_at);
     double *sums = reinterpret_cast<double *>(static_cast<unsigned char *>(workspace) + l.sums_at);
     constexpr size_t lds = BF16 ? kEsBfBwdBytes : kEsLdsBytes;
-    const auto kernel = dual_edge_backward_kernel<DROP, BF16>;
-    static std::atomic<bool> raised{false};
-    if (hipError_t e = es_raise_lds(reinterpret_cast<const void *>(kernel), raised, lds)) return e;
+    constexpr auto kernel = dual_edge_backward_kernel<DROP, BF16>;
+    if (hipError_t e = es_raise_lds<kernel>(lds)) return e;
     for (long long t0 = 0; t0 < tiles; t0 += chunk) {
         const long long t1 = t0 + chunk < tiles ? t0 + chunk : tiles;
         const long long wgs = (t1 - t0 + kEsWaves - 1) / kEsWaves;
         const int blocks = (int)(wgs < kEsMaxBlocks ? wgs : kEsMaxBlocks);
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kEsThreads), lds, stream, edge_feat, W1, b1, W2, b2, G, dS, sizes,
-                           batch, n, heads, t0, t1, rows, drop);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kEsThreads), lds, stream, p.edge_feat, p.W1, p.b1, p.W2, p.b2, p.G,
+                           dS, p.sizes, p.batch, p.n, p.heads, t0, t1, workspace, p.drop);
         if (hipError_t e = hipGetLastError()) return e;
         const int wg = (int)(((t1 - t0) * kEsEdgesPerWave + l.per - 1) / l.per);
         if constexpr (BF16)
-            hipLaunchKernelGGL(dual_edge_wgrad_bf16_kernel, dim3(wg), dim3(kEsThreads), 0, stream, rows, sizes, batch, n,
-                               t0, t1, l.per, partials);
+            hipLaunchKernelGGL(dual_edge_wgrad_bf16_kernel, dim3(wg), dim3(kEsThreads), 0, stream,
+                               static_cast<const __bf16 *>(workspace), p.sizes, p.batch, p.n, t0, t1, l.per, partials);
         else
-            hipLaunchKernelGGL(dual_edge_wgrad_kernel, dim3(wg), dim3(kEsThreads), 0, stream, rows, sizes, batch, n, t0,
-                               t1, l.per, partials);
+            hipLaunchKernelGGL(dual_edge_wgrad_kernel, dim3(wg), dim3(kEsThreads), 0, stream,
+                               static_cast<const float *>(workspace), p.sizes, p.batch, p.n, t0, t1, l.per, partials);
         if (hipError_t e = hipGetLastError()) return e;
         hipLaunchKernelGGL(dual_edge_wgrad_reduce_kernel, dim3(kWgOut / 256), dim3(256), 0, stream, partials, wg, sums,
-                           t0 == 0 ? 1 : 0, t1 == tiles ? 1 : 0, dW1, db1, dW2, db2, dG, 2 * heads);
+                           t0 == 0 ? 1 : 0, t1 == tiles ? 1 : 0, grads.dW1, grads.db1, grads.dW2, grads.db2, grads.dG,
+                           2 * p.heads);
         if (hipError_t e = hipGetLastError()) return e;
     }
     return hipSuccess;
@@ -1446,16 +1456,12 @@ hipError_t edge_scores_backward(const float *edge_feat, const float *W1, const f
 
 }  // namespace
 
-hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                            const float *b2, const float *G, const float *dS, const int *sizes,
-                                            float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch,
-                                            int n, int heads, void *workspace, hipStream_t stream,
-                                            const DualDropout &drop, bool bf16)
+hipError_t launch_dual_edge_scores_backward(const DualEdgeParams &p, const float *dS, const DualEdgeGrads &grads,
+                                            void *workspace, hipStream_t stream)
 {
-    const auto launch = bf16 ? (drop.on ? edge_scores_backward<true, true> : edge_scores_backward<false, true>)
-                             : (drop.on ? edge_scores_backward<true, false> : edge_scores_backward<false, false>);
-    return launch(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n, heads, workspace, stream,
-                  drop);
+    return dispatch_bools(p.drop.on, p.bf16, [&](auto drop, auto bf16) {
+        return edge_scores_backward<decltype(drop)::value, decltype(bf16)::value>(p, dS, grads, workspace, stream);
+    });
 }
 
 }  // namespace lapwarm

@@ -56,26 +56,30 @@ struct DualAttnBwdParams {
 // of 128 each, dS and the features padded to 16) take 30720 * 2176 B = 63.75 MiB.
 constexpr int kDualBwdChunk = 30720;
 
+// The edge MLP's call (dual_gnn.hip): scores[b][dir][h][i][j] from the features, both directions.
+struct DualEdgeParams {
+    const float *edge_feat;           // [batch][n][n][10]
+    const float *W1, *b1, *W2, *b2;   // Linear(10, 128), Linear(128, 128)
+    const float *G;                   // [2 * heads][128], the folded score weights
+    // [batch] on the device, or null for the uniform batch.  A padded batch of instances of sizes[b] (a size outside
+    // 1..n: no edge): only the edges (i, j < sizes[b]) are computed, a row's tail rounded up to 16 edges, and written;
+    // scores outside the prefixes are left as they are.  On the prefixes the bits are the uniform batch's.
+    const int *sizes;
+    int batch, n, heads;
+    // With drop.on, h1 = GELU(W1 f + b1) is replaced by keep * scale * h1 (stream 0 of dual_dropout.hpp) before the
+    // second product.  drop.on false selects the kernels without the generator: their bits, whatever else drop holds.
+    DualDropout drop{};
+    // The edge MLP on the bf16 MFMA units (the contract in dual_gnn.hip).  The scores stay fp32; the mask of a seed is
+    // the mask of the fp32 kernels.
+    bool bf16 = false;
+};
+
+struct DualEdgeGrads {
+    float *dW1, *db1, *dW2, *db2, *dG;  // the shapes of W1, b1, W2, b2, G
+};
+
 size_t dual_gnn_workspace_bytes(int batch, int n, int heads);  // the scores tensor; 0 for arguments out of range
-hipError_t launch_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                   const float *b2, const float *G, float *scores, int batch, int n, int heads,
-                                   hipStream_t stream);
-// With drop.on, h1 = GELU(W1 f + b1) is replaced by keep * scale * h1 (stream 0 of dual_dropout.hpp) before the second
-// product; sizes null: the uniform batch.  With drop.on false: the launch above or the ragged one below.
-hipError_t launch_dual_edge_scores_dropout(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                           const float *b2, const float *G, float *scores, const int *sizes, int batch,
-                                           int n, int heads, const DualDropout &drop, hipStream_t stream);
-// The same scores for a padded batch of instances of sizes[b] (device, [batch]; a size outside 1..n: no edge): only
-// the edges (i, j < sizes[b]) are computed, a row's tail rounded up to 16 edges, and written; scores outside the
-// prefixes are left as they are.  On the prefixes the bits are launch_dual_edge_scores's on the same input.
-hipError_t launch_dual_edge_scores_ragged(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                          const float *b2, const float *G, float *scores, const int *sizes, int batch,
-                                          int n, int heads, hipStream_t stream);
-// The edge MLP on the bf16 MFMA units (the contract in dual_gnn.hip): sizes null for the uniform batch, drop.on false
-// for no dropout.  The scores stay fp32; the mask of a seed is the mask of the fp32 launches.
-hipError_t launch_dual_edge_scores_bf16(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                        const float *b2, const float *G, float *scores, const int *sizes, int batch,
-                                        int n, int heads, const DualDropout &drop, hipStream_t stream);
+hipError_t launch_dual_edge_scores(const DualEdgeParams &p, float *scores, hipStream_t stream);
 // heads <= 65535 here (the grid's y dimension): kDualMaxHeads limits the edge-scores kernel and the workspace only
 hipError_t launch_dual_attention(const DualAttnParams &p, hipStream_t stream);
 
@@ -84,13 +88,10 @@ size_t dual_backward_workspace_bytes(int batch, int n, int heads);
 // Three kernels: query-major (dS, da, per-workgroup partials of dkb), key-major (dc, dval), the reduce of dkb.
 hipError_t launch_dual_attention_backward(const DualAttnBwdParams &p, hipStream_t stream);
 // Per chunk of kDualBwdChunk edges three kernels: the recompute (rows into the workspace), the TN products per
-// workgroup slice, the fp64 reduce over workgroups and chunks.  sizes null: the uniform batch.  bf16: the backward of
-// launch_dual_edge_scores_bf16, whose rows are bf16 and fit the same workspace.
-hipError_t launch_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                            const float *b2, const float *G, const float *dS, const int *sizes,
-                                            float *dW1, float *db1, float *dW2, float *db2, float *dG, int batch,
-                                            int n, int heads, void *workspace, hipStream_t stream,
-                                            const DualDropout &drop = DualDropout{}, bool bf16 = false);
+// workgroup slice, the fp64 reduce over workgroups and chunks.  dS: the gradient of the scores, in their layout.
+// p.bf16: the backward of the bf16 forward, whose rows are bf16 and fit the same workspace.
+hipError_t launch_dual_edge_scores_backward(const DualEdgeParams &p, const float *dS, const DualEdgeGrads &grads,
+                                            void *workspace, hipStream_t stream);
 // keep[i] = 1 if element first + i of the stream is kept, else 0, for i < count: the keep rule itself, for tests
 hipError_t launch_dual_dropout_keep(const DualDropout &drop, unsigned stream_id, unsigned long long first,
                                     unsigned long long count, unsigned char *keep, hipStream_t stream);

@@ -527,13 +527,38 @@ int lapwarm_graph_features_batched(const double *C, int batch, int n, const doub
 
 size_t lapwarm_dual_gnn_workspace_bytes(int batch, int n, int heads) { return dual_gnn_workspace_bytes(batch, n, heads); }
 
+// The checks of the four edge-score forwards, in the order the ABI keeps: dimensions (heads by kDualMaxHeads, the
+// kernel's tile limit), n, pointers.  An entry that takes p checks it before it comes here.
+static bool dual_edge_null(const DualEdgeParams &p)
+{
+    return !p.edge_feat || !p.W1 || !p.b1 || !p.W2 || !p.b2 || !p.G;
+}
+
+static int dual_edge_scores(const DualEdgeParams &p, float *scores, bool need_sizes, void *stream_)
+{
+    if (p.batch < 1 || p.batch > kDualMaxBatch || p.n < 1 || p.heads < 1 || p.heads > kDualMaxHeads) return -2;
+    if (p.n > kMaxN) return -5;
+    if (dual_edge_null(p) || !scores || (need_sizes && !p.sizes)) return -2;
+    HIP_TRY(launch_dual_edge_scores(p, scores, as_stream(stream_)));
+    return 0;
+}
+
 int lapwarm_dual_edge_scores(const float *edge_feat, const float *W1, const float *b1, const float *W2, const float *b2,
                              const float *G, float *scores, int batch, int n, int heads, void *stream_)
 {
-    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
-    if (n > kMaxN) return -5;
-    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !scores) return -2;
-    HIP_TRY(launch_dual_edge_scores(edge_feat, W1, b1, W2, b2, G, scores, batch, n, heads, as_stream(stream_)));
+    return dual_edge_scores({edge_feat, W1, b1, W2, b2, G, nullptr, batch, n, heads}, scores, false, stream_);
+}
+
+// The checks of the five attention forwards.  heads: the grid's y dimension, not kDualMaxHeads.
+static int dual_attention(const DualAttnParams &p, bool need_stats, bool need_sizes, void *stream_)
+{
+    if (p.batch < 1 || p.batch > kDualMaxBatch || p.n < 1 || p.heads < 1 || p.heads > kMaxGridY || p.head_dim < 1)
+        return -2;
+    if (p.n > kMaxN) return -5;
+    if (!p.scores || !p.a_row || !p.c_row || !p.a_col || !p.c_col || !p.kbias || !p.row_val || !p.col_val ||
+        !p.row_msg || !p.col_msg || (need_stats && (!p.row_stats || !p.col_stats)) || (need_sizes && !p.sizes))
+        return -2;
+    HIP_TRY(launch_dual_attention(p, as_stream(stream_)));
     return 0;
 }
 
@@ -542,15 +567,9 @@ int lapwarm_dual_attention(const float *scores, const float *a_row, const float 
                            const float *col_val, float *row_msg, float *col_msg, int batch, int n, int heads,
                            int head_dim, void *stream_)
 {
-    // heads: the grid's y dimension, not kDualMaxHeads, which is the edge-scores kernel's tile limit
-    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kMaxGridY || head_dim < 1) return -2;
-    if (n > kMaxN) return -5;
-    if (!scores || !a_row || !c_row || !a_col || !c_col || !kbias || !row_val || !col_val || !row_msg || !col_msg)
-        return -2;
     DualAttnParams p{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val, row_msg, col_msg,
                      batch, n, heads, head_dim};
-    HIP_TRY(launch_dual_attention(p, as_stream(stream_)));
-    return 0;
+    return dual_attention(p, false, false, stream_);
 }
 
 // ---- DualGNN on a ragged batch: the features (graph_features.hip) and the size-aware attention (dual_gnn.hip) ----
@@ -579,12 +598,7 @@ int lapwarm_dual_edge_scores_ragged(const float *edge_feat, const float *W1, con
                                     const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
                                     int heads, void *stream_)
 {
-    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
-    if (n > kMaxN) return -5;
-    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !scores || !sizes) return -2;
-    HIP_TRY(launch_dual_edge_scores_ragged(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads,
-                                           as_stream(stream_)));
-    return 0;
+    return dual_edge_scores({edge_feat, W1, b1, W2, b2, G, sizes, batch, n, heads}, scores, true, stream_);
 }
 
 int lapwarm_dual_attention_ragged(const float *scores, const float *a_row, const float *c_row, const float *a_col,
@@ -592,30 +606,12 @@ int lapwarm_dual_attention_ragged(const float *scores, const float *a_row, const
                                   const float *col_val, float *row_msg, float *col_msg, int batch, int n, int heads,
                                   int head_dim, void *stream_)
 {
-    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kMaxGridY || head_dim < 1) return -2;
-    if (n > kMaxN) return -5;
-    if (!scores || !a_row || !c_row || !a_col || !c_col || !kbias || !sizes || !row_val || !col_val || !row_msg ||
-        !col_msg)
-        return -2;
     DualAttnParams p{scores, a_row, c_row, a_col, c_col, kbias, nullptr, row_val, col_val, row_msg, col_msg,
                      batch, n, heads, head_dim, sizes};
-    HIP_TRY(launch_dual_attention(p, as_stream(stream_)));
-    return 0;
+    return dual_attention(p, false, true, stream_);
 }
 
 // ---- DualGNN training: the forward with its softmax statistics, and the two backwards (dual_gnn.hip) ----
-static int dual_attention_stats(const DualAttnParams &p, void *stream_)
-{
-    if (p.batch < 1 || p.batch > kDualMaxBatch || p.n < 1 || p.heads < 1 || p.heads > kMaxGridY || p.head_dim < 1)
-        return -2;
-    if (p.n > kMaxN) return -5;
-    if (!p.scores || !p.a_row || !p.c_row || !p.a_col || !p.c_col || !p.kbias || !p.row_val || !p.col_val ||
-        !p.row_msg || !p.col_msg || !p.row_stats || !p.col_stats)
-        return -2;
-    HIP_TRY(launch_dual_attention(p, as_stream(stream_)));
-    return 0;
-}
-
 int lapwarm_dual_attention_stats(const float *scores, const float *a_row, const float *c_row, const float *a_col,
                                  const float *c_col, const float *kbias, const unsigned char *mask,
                                  const float *row_val, const float *col_val, float *row_msg, float *col_msg,
@@ -624,7 +620,7 @@ int lapwarm_dual_attention_stats(const float *scores, const float *a_row, const 
 {
     DualAttnParams p{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val, row_msg, col_msg,
                      batch, n, heads, head_dim, nullptr, row_stats, col_stats};
-    return dual_attention_stats(p, stream_);
+    return dual_attention(p, true, false, stream_);
 }
 
 int lapwarm_dual_attention_stats_ragged(const float *scores, const float *a_row, const float *c_row,
@@ -633,10 +629,10 @@ int lapwarm_dual_attention_stats_ragged(const float *scores, const float *a_row,
                                         float *row_stats, float *col_stats, int batch, int n, int heads, int head_dim,
                                         void *stream_)
 {
-    if (!sizes) return -2;
+    if (!sizes) return -2;  // before the dimensions here: n > kMaxN with null sizes is -2
     DualAttnParams p{scores, a_row, c_row, a_col, c_col, kbias, nullptr, row_val, col_val, row_msg, col_msg,
                      batch, n, heads, head_dim, sizes, row_stats, col_stats};
-    return dual_attention_stats(p, stream_);
+    return dual_attention(p, true, true, stream_);
 }
 
 size_t lapwarm_dual_backward_workspace_bytes(int batch, int n, int heads)
@@ -646,83 +642,8 @@ size_t lapwarm_dual_backward_workspace_bytes(int batch, int n, int heads)
 
 int lapwarm_dual_backward_chunk(void) { return kDualBwdChunk; }
 
-static int dual_attention_backward(const float *scores, const float *a_row, const float *c_row, const float *a_col,
-                                   const float *c_col, const float *kbias, const unsigned char *mask,
-                                   const int *sizes, const float *row_val, const float *col_val,
-                                   const float *row_msg, const float *col_msg, const float *row_stats,
-                                   const float *col_stats, const float *d_row_msg, const float *d_col_msg, float *dS,
-                                   float *da_row, float *dc_row, float *da_col, float *dc_col, float *dkb,
-                                   float *d_row_val, float *d_col_val, int batch, int n, int heads, int head_dim,
-                                   void *workspace, size_t workspace_bytes, const DualDropout &drop, void *stream_)
-{
-    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads || head_dim < 1) return -2;
-    if (n > kMaxN) return -5;
-    if (!scores || !a_row || !c_row || !a_col || !c_col || !kbias || !row_val || !col_val || !row_msg || !col_msg ||
-        !row_stats || !col_stats || !d_row_msg || !d_col_msg || !dS || !da_row || !dc_row || !da_col || !dc_col ||
-        !dkb || !d_row_val || !d_col_val || !workspace)
-        return -2;
-    if (int rc = check_workspace(workspace_bytes, dual_backward_workspace_bytes(batch, n, heads))) return rc;
-    DualAttnBwdParams p{};
-    p.fwd = DualAttnParams{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val,
-                           const_cast<float *>(row_msg), const_cast<float *>(col_msg), batch, n, heads, head_dim,
-                           sizes, const_cast<float *>(row_stats), const_cast<float *>(col_stats), drop};
-    p.d_row_msg = d_row_msg;
-    p.d_col_msg = d_col_msg;
-    p.dS = dS;
-    p.da_row = da_row;
-    p.dc_row = dc_row;
-    p.da_col = da_col;
-    p.dc_col = dc_col;
-    p.dkb = dkb;
-    p.d_row_val = d_row_val;
-    p.d_col_val = d_col_val;
-    p.partials = static_cast<double *>(workspace);
-    HIP_TRY(launch_dual_attention_backward(p, as_stream(stream_)));
-    return 0;
-}
-
-int lapwarm_dual_attention_backward(const float *scores, const float *a_row, const float *c_row, const float *a_col,
-                                    const float *c_col, const float *kbias, const unsigned char *mask,
-                                    const int *sizes, const float *row_val, const float *col_val,
-                                    const float *row_msg, const float *col_msg, const float *row_stats,
-                                    const float *col_stats, const float *d_row_msg, const float *d_col_msg, float *dS,
-                                    float *da_row, float *dc_row, float *da_col, float *dc_col, float *dkb,
-                                    float *d_row_val, float *d_col_val, int batch, int n, int heads, int head_dim,
-                                    void *workspace, size_t workspace_bytes, void *stream_)
-{
-    return dual_attention_backward(scores, a_row, c_row, a_col, c_col, kbias, mask, sizes, row_val, col_val, row_msg,
-                                   col_msg, row_stats, col_stats, d_row_msg, d_col_msg, dS, da_row, dc_row, da_col,
-                                   dc_col, dkb, d_row_val, d_col_val, batch, n, heads, head_dim, workspace,
-                                   workspace_bytes, DualDropout{}, stream_);
-}
-
-static int dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                     const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
-                                     float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
-                                     void *workspace, size_t workspace_bytes, const DualDropout &drop, void *stream_,
-                                     bool bf16 = false)
-{
-    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
-    if (n > kMaxN) return -5;
-    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !dS || !dW1 || !db1 || !dW2 || !db2 || !dG || !workspace)
-        return -2;
-    if (int rc = check_workspace(workspace_bytes, dual_backward_workspace_bytes(batch, n, heads))) return rc;
-    HIP_TRY(launch_dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n,
-                                             heads, workspace, as_stream(stream_), drop, bf16));
-    return 0;
-}
-
-int lapwarm_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                      const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
-                                      float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
-                                      void *workspace, size_t workspace_bytes, void *stream_)
-{
-    return dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n, heads,
-                                     workspace, workspace_bytes, DualDropout{}, stream_);
-}
-
-// ---- DualGNN training with the two dropouts of the fused region (dual_dropout.hpp) ----
-// p in [0, 1), before any HIP call; p == 0 leaves `on` false, which selects the kernels without the generator
+// p in [0, 1), before any HIP call and before every other check of an entry that takes p; p == 0 leaves `on` false,
+// which selects the kernels without the generator, and the record DualDropout{}
 static int dual_dropout_of(unsigned long long seed, double p, DualDropout *d)
 {
     if (!(p >= 0.0 && p < 1.0)) return -2;  // NaN included
@@ -734,31 +655,21 @@ static int dual_dropout_of(unsigned long long seed, double p, DualDropout *d)
     return 0;
 }
 
-int lapwarm_dual_edge_scores_dropout(const float *edge_feat, const float *W1, const float *b1, const float *W2,
-                                     const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
-                                     int heads, unsigned long long seed, double p, void *stream_)
+// Both backwards bound heads by kDualMaxHeads (the workspace's limit) and check the workspace last.
+static int dual_attention_backward(DualAttnBwdParams p, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    DualDropout drop;
-    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
-    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
-    if (n > kMaxN) return -5;
-    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !scores) return -2;
-    HIP_TRY(launch_dual_edge_scores_dropout(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop,
-                                            as_stream(stream_)));
+    const DualAttnParams &f = p.fwd;
+    if (f.batch < 1 || f.batch > kDualMaxBatch || f.n < 1 || f.heads < 1 || f.heads > kDualMaxHeads || f.head_dim < 1)
+        return -2;
+    if (f.n > kMaxN) return -5;
+    if (!f.scores || !f.a_row || !f.c_row || !f.a_col || !f.c_col || !f.kbias || !f.row_val || !f.col_val ||
+        !f.row_msg || !f.col_msg || !f.row_stats || !f.col_stats || !p.d_row_msg || !p.d_col_msg || !p.dS ||
+        !p.da_row || !p.dc_row || !p.da_col || !p.dc_col || !p.dkb || !p.d_row_val || !p.d_col_val || !workspace)
+        return -2;
+    if (int rc = check_workspace(workspace_bytes, dual_backward_workspace_bytes(f.batch, f.n, f.heads))) return rc;
+    p.partials = static_cast<double *>(workspace);
+    HIP_TRY(launch_dual_attention_backward(p, as_stream(stream_)));
     return 0;
-}
-
-int lapwarm_dual_attention_stats_dropout(const float *scores, const float *a_row, const float *c_row,
-                                         const float *a_col, const float *c_col, const float *kbias,
-                                         const unsigned char *mask, const int *sizes, const float *row_val,
-                                         const float *col_val, float *row_msg, float *col_msg, float *row_stats,
-                                         float *col_stats, int batch, int n, int heads, int head_dim,
-                                         unsigned long long seed, double p, void *stream_)
-{
-    DualAttnParams q{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val, row_msg, col_msg,
-                     batch, n, heads, head_dim, sizes, row_stats, col_stats};
-    if (int rc = dual_dropout_of(seed, p, &q.drop)) return rc;
-    return dual_attention_stats(q, stream_);
 }
 
 int lapwarm_dual_attention_backward_dropout(const float *scores, const float *a_row, const float *c_row,
@@ -772,12 +683,72 @@ int lapwarm_dual_attention_backward_dropout(const float *scores, const float *a_
                                             void *workspace, size_t workspace_bytes, unsigned long long seed, double p,
                                             void *stream_)
 {
-    DualDropout drop;
-    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
-    return dual_attention_backward(scores, a_row, c_row, a_col, c_col, kbias, mask, sizes, row_val, col_val, row_msg,
-                                   col_msg, row_stats, col_stats, d_row_msg, d_col_msg, dS, da_row, dc_row, da_col,
-                                   dc_col, dkb, d_row_val, d_col_val, batch, n, heads, head_dim, workspace,
-                                   workspace_bytes, drop, stream_);
+    DualAttnBwdParams q{{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val,
+                         const_cast<float *>(row_msg), const_cast<float *>(col_msg), batch, n, heads, head_dim, sizes,
+                         const_cast<float *>(row_stats), const_cast<float *>(col_stats)},
+                        d_row_msg, d_col_msg, dS, da_row, dc_row, da_col, dc_col, dkb, d_row_val, d_col_val, nullptr};
+    if (int rc = dual_dropout_of(seed, p, &q.fwd.drop)) return rc;
+    return dual_attention_backward(q, workspace, workspace_bytes, stream_);
+}
+
+int lapwarm_dual_attention_backward(const float *scores, const float *a_row, const float *c_row, const float *a_col,
+                                    const float *c_col, const float *kbias, const unsigned char *mask,
+                                    const int *sizes, const float *row_val, const float *col_val,
+                                    const float *row_msg, const float *col_msg, const float *row_stats,
+                                    const float *col_stats, const float *d_row_msg, const float *d_col_msg, float *dS,
+                                    float *da_row, float *dc_row, float *da_col, float *dc_col, float *dkb,
+                                    float *d_row_val, float *d_col_val, int batch, int n, int heads, int head_dim,
+                                    void *workspace, size_t workspace_bytes, void *stream_)
+{
+    // seed 0, p 0: no dropout
+    return lapwarm_dual_attention_backward_dropout(scores, a_row, c_row, a_col, c_col, kbias, mask, sizes, row_val,
+                                                   col_val, row_msg, col_msg, row_stats, col_stats, d_row_msg,
+                                                   d_col_msg, dS, da_row, dc_row, da_col, dc_col, dkb, d_row_val,
+                                                   d_col_val, batch, n, heads, head_dim, workspace, workspace_bytes, 0,
+                                                   0.0, stream_);
+}
+
+static int dual_edge_scores_backward(const DualEdgeParams &p, const float *dS, const DualEdgeGrads &g, void *workspace,
+                                     size_t workspace_bytes, void *stream_)
+{
+    if (p.batch < 1 || p.batch > kDualMaxBatch || p.n < 1 || p.heads < 1 || p.heads > kDualMaxHeads) return -2;
+    if (p.n > kMaxN) return -5;
+    if (dual_edge_null(p) || !dS || !g.dW1 || !g.db1 || !g.dW2 || !g.db2 || !g.dG || !workspace) return -2;
+    if (int rc = check_workspace(workspace_bytes, dual_backward_workspace_bytes(p.batch, p.n, p.heads))) return rc;
+    HIP_TRY(launch_dual_edge_scores_backward(p, dS, g, workspace, as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_dual_edge_scores_backward(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                      const float *b2, const float *G, const float *dS, const int *sizes, float *dW1,
+                                      float *db1, float *dW2, float *db2, float *dG, int batch, int n, int heads,
+                                      void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return dual_edge_scores_backward({edge_feat, W1, b1, W2, b2, G, sizes, batch, n, heads}, dS,
+                                     {dW1, db1, dW2, db2, dG}, workspace, workspace_bytes, stream_);
+}
+
+// ---- DualGNN training with the two dropouts of the fused region (dual_dropout.hpp); sizes nullable ----
+int lapwarm_dual_edge_scores_dropout(const float *edge_feat, const float *W1, const float *b1, const float *W2,
+                                     const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
+                                     int heads, unsigned long long seed, double p, void *stream_)
+{
+    DualEdgeParams q{edge_feat, W1, b1, W2, b2, G, sizes, batch, n, heads};
+    if (int rc = dual_dropout_of(seed, p, &q.drop)) return rc;
+    return dual_edge_scores(q, scores, false, stream_);
+}
+
+int lapwarm_dual_attention_stats_dropout(const float *scores, const float *a_row, const float *c_row,
+                                         const float *a_col, const float *c_col, const float *kbias,
+                                         const unsigned char *mask, const int *sizes, const float *row_val,
+                                         const float *col_val, float *row_msg, float *col_msg, float *row_stats,
+                                         float *col_stats, int batch, int n, int heads, int head_dim,
+                                         unsigned long long seed, double p, void *stream_)
+{
+    DualAttnParams q{scores, a_row, c_row, a_col, c_col, kbias, mask, row_val, col_val, row_msg, col_msg,
+                     batch, n, heads, head_dim, sizes, row_stats, col_stats};
+    if (int rc = dual_dropout_of(seed, p, &q.drop)) return rc;
+    return dual_attention(q, true, false, stream_);
 }
 
 int lapwarm_dual_edge_scores_backward_dropout(const float *edge_feat, const float *W1, const float *b1,
@@ -786,10 +757,9 @@ int lapwarm_dual_edge_scores_backward_dropout(const float *edge_feat, const floa
                                               float *dG, int batch, int n, int heads, void *workspace,
                                               size_t workspace_bytes, unsigned long long seed, double p, void *stream_)
 {
-    DualDropout drop;
-    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
-    return dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n, heads,
-                                     workspace, workspace_bytes, drop, stream_);
+    DualEdgeParams q{edge_feat, W1, b1, W2, b2, G, sizes, batch, n, heads};
+    if (int rc = dual_dropout_of(seed, p, &q.drop)) return rc;
+    return dual_edge_scores_backward(q, dS, {dW1, db1, dW2, db2, dG}, workspace, workspace_bytes, stream_);
 }
 
 // ---- the edge MLP on the bf16 MFMA units (dual_gnn.hip); sizes nullable, p == 0: no dropout ----
@@ -797,14 +767,10 @@ int lapwarm_dual_edge_scores_bf16(const float *edge_feat, const float *W1, const
                                   const float *b2, const float *G, float *scores, const int *sizes, int batch, int n,
                                   int heads, unsigned long long seed, double p, void *stream_)
 {
-    DualDropout drop;
-    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
-    if (batch < 1 || batch > kDualMaxBatch || n < 1 || heads < 1 || heads > kDualMaxHeads) return -2;
-    if (n > kMaxN) return -5;
-    if (!edge_feat || !W1 || !b1 || !W2 || !b2 || !G || !scores) return -2;
-    HIP_TRY(launch_dual_edge_scores_bf16(edge_feat, W1, b1, W2, b2, G, scores, sizes, batch, n, heads, drop,
-                                         as_stream(stream_)));
-    return 0;
+    DualEdgeParams q{edge_feat, W1, b1, W2, b2, G, sizes, batch, n, heads};
+    if (int rc = dual_dropout_of(seed, p, &q.drop)) return rc;
+    q.bf16 = true;
+    return dual_edge_scores(q, scores, false, stream_);
 }
 
 int lapwarm_dual_edge_scores_backward_bf16(const float *edge_feat, const float *W1, const float *b1, const float *W2,
@@ -813,11 +779,12 @@ int lapwarm_dual_edge_scores_backward_bf16(const float *edge_feat, const float *
                                            int heads, void *workspace, size_t workspace_bytes, unsigned long long seed,
                                            double p, void *stream_)
 {
-    DualDropout drop;
-    if (int rc = dual_dropout_of(seed, p, &drop)) return rc;
-    return dual_edge_scores_backward(edge_feat, W1, b1, W2, b2, G, dS, sizes, dW1, db1, dW2, db2, dG, batch, n, heads,
-                                     workspace, workspace_bytes, drop, stream_, true);
+    DualEdgeParams q{edge_feat, W1, b1, W2, b2, G, sizes, batch, n, heads};
+    if (int rc = dual_dropout_of(seed, p, &q.drop)) return rc;
+    q.bf16 = true;
+    return dual_edge_scores_backward(q, dS, {dW1, db1, dW2, db2, dG}, workspace, workspace_bytes, stream_);
 }
+
 
 int lapwarm_dual_dropout_keep(unsigned long long seed, unsigned int stream_id, unsigned long long first,
                               unsigned long long count, double p, unsigned char *keep, void *stream_)

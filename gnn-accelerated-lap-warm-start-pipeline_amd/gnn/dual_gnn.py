@@ -115,6 +115,43 @@ def _backward_workspace(lib, B, N, H, dev) -> torch.Tensor:
     return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
 
 
+# ---- which C entry a fused call reaches: each choice is made here and nowhere else ------------------------------
+def _edge_scores_entry(sizes, seed, p, precision, dims):
+    """The entry that computes the edge scores of (sizes, p, precision) and its arguments after `scores`; dims is
+    (B, N, H).  fp32 without dropout keeps the plain and the _ragged entry: timings and profiles name them."""
+    if precision == "bf16":  # one entry for both batches: sizes may be None, p == 0 is no dropout
+        return "lapwarm_dual_edge_scores_bf16", (sizes, *dims, seed, p)
+    if p > 0.0:  # the dropout after the edge MLP's first GELU, stream 0 of the seed
+        return "lapwarm_dual_edge_scores_dropout", (sizes, *dims, seed, p)
+    if sizes is not None:
+        return "lapwarm_dual_edge_scores_ragged", (sizes, *dims)
+    return "lapwarm_dual_edge_scores", tuple(dims)
+
+
+def _edge_backward_entry(seed, p, precision):
+    """The backward of _edge_scores_entry's entry and its arguments after the workspace: the forward's precision, and
+    its mask again from its seed."""
+    suffix = "_bf16" if precision == "bf16" else "_dropout" if p > 0.0 else ""
+    return "lapwarm_dual_edge_scores_backward" + suffix, ((seed, p) if suffix else ())
+
+
+def _attention_entry(mask8, sizes, seed, p, stats):
+    """The attention forward of (sizes, p): the entry, its arguments between kbias and the values, and those after
+    (B, N, H, D).  stats: the training forward, which keeps the softmax statistics; only it has a dropout."""
+    if p > 0.0:  # the dropout of the attention weights, stream 1 of the seed
+        assert stats
+        return "lapwarm_dual_attention_stats_dropout", (mask8, sizes), (seed, p)
+    name = "lapwarm_dual_attention_stats" if stats else "lapwarm_dual_attention"
+    if sizes is not None:  # scores outside the prefixes are neither written nor read
+        return name + "_ragged", (sizes,), ()
+    return name, (mask8,), ()
+
+
+def _attention_backward_entry(seed, p):
+    """The backward of _attention_entry's entry (it takes mask8 and sizes always) and its arguments after the workspace."""
+    return ("lapwarm_dual_attention_backward_dropout", (seed, p)) if p > 0.0 else ("lapwarm_dual_attention_backward", ())
+
+
 class _EdgeScores(torch.autograd.Function):
     """scores (B, 2, H, N, N) of lapwarm_dual_edge_scores[_ragged]; saves only its inputs.  The backward is
     lapwarm_dual_edge_scores_backward: gradients for W1, b1, W2, b2 and G, none for edge_feat.  With `sizes` the
@@ -129,16 +166,8 @@ class _EdgeScores(torch.autograd.Function):
         H = G.shape[0] // 2
         args = [t.detach().contiguous() for t in (edge_feat, W1, b1, W2, b2, G)]
         scores = torch.empty((B, 2, H, N, N), dtype=torch.float32, device=edge_feat.device)
-        if precision == "bf16":  # sizes may be None, p == 0 is no dropout
-            hip_call("lapwarm_dual_edge_scores_bf16", "dual_edge_scores", scores.device, *args, scores, sizes, B, N, H,
-                     seed, p)
-        elif p > 0.0:  # the dropout after the edge MLP's first GELU, stream 0 of the seed
-            hip_call("lapwarm_dual_edge_scores_dropout", "dual_edge_scores", scores.device, *args, scores, sizes, B, N, H,
-                     seed, p)
-        elif sizes is not None:
-            hip_call("lapwarm_dual_edge_scores_ragged", "dual_edge_scores", scores.device, *args, scores, sizes, B, N, H)
-        else:
-            hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", scores.device, *args, scores, B, N, H)
+        entry, tail = _edge_scores_entry(sizes, seed, p, precision, (B, N, H))
+        hip_call(entry, "dual_edge_scores", scores.device, *args, scores, *tail)
         ctx.save_for_backward(*args)
         ctx.sizes, ctx.seed, ctx.p, ctx.precision = sizes, seed, p, precision
         return scores
@@ -153,15 +182,9 @@ class _EdgeScores(torch.autograd.Function):
         dev = edge_feat.device
         ws = _backward_workspace(_hip.load(), B, N, H, dev)
         grads = [torch.empty_like(t) for t in (W1, b1, W2, b2, G)]
-        if ctx.precision == "bf16":  # the forward's precision, and its mask again from its seed
-            hip_call("lapwarm_dual_edge_scores_backward_bf16", "dual_edge_scores_backward", dev, edge_feat, W1, b1,
-                     W2, b2, G, d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel(), ctx.seed, ctx.p)
-        elif ctx.p > 0.0:  # the forward's mask again, from its seed
-            hip_call("lapwarm_dual_edge_scores_backward_dropout", "dual_edge_scores_backward", dev, edge_feat, W1, b1,
-                     W2, b2, G, d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel(), ctx.seed, ctx.p)
-        else:
-            hip_call("lapwarm_dual_edge_scores_backward", "dual_edge_scores_backward", dev, edge_feat, W1, b1, W2, b2,
-                     G, d_scores.contiguous(), ctx.sizes, *grads, B, N, H, ws, ws.numel())
+        entry, tail = _edge_backward_entry(ctx.seed, ctx.p, ctx.precision)
+        hip_call(entry, "dual_edge_scores_backward", dev, edge_feat, W1, b1, W2, b2, G, d_scores.contiguous(), ctx.sizes,
+                 *grads, B, N, H, ws, ws.numel(), *tail)
         return (None, *grads, None, None, None, None)
 
 
@@ -181,15 +204,9 @@ class _EdgeAttention(torch.autograd.Function):
         vals = [t.detach().contiguous() for t in (row_val, col_val)]
         row_msg, col_msg = (torch.empty((B, N, H * D), dtype=torch.float32, device=dev) for _ in range(2))
         row_stats, col_stats = (torch.empty((B, H, N, 2), dtype=torch.float32, device=dev) for _ in range(2))
-        if p > 0.0:  # the dropout of the attention weights, stream 1 of the seed
-            hip_call("lapwarm_dual_attention_stats_dropout", "dual_attention", dev, *args, mask8, sizes, *vals, row_msg,
-                     col_msg, row_stats, col_stats, B, N, H, D, seed, p)
-        elif sizes is not None:
-            hip_call("lapwarm_dual_attention_stats_ragged", "dual_attention", dev, *args, sizes, *vals, row_msg, col_msg,
-                     row_stats, col_stats, B, N, H, D)
-        else:
-            hip_call("lapwarm_dual_attention_stats", "dual_attention", dev, *args, mask8, *vals, row_msg, col_msg,
-                     row_stats, col_stats, B, N, H, D)
+        entry, masks, tail = _attention_entry(mask8, sizes, seed, p, stats=True)
+        hip_call(entry, "dual_attention", dev, *args, *masks, *vals, row_msg, col_msg, row_stats, col_stats, B, N, H, D,
+                 *tail)
         ctx.save_for_backward(*args, *vals, row_msg, col_msg, row_stats, col_stats)
         ctx.mask8, ctx.sizes, ctx.seed, ctx.p = mask8, sizes, seed, p
         return row_msg, col_msg
@@ -209,9 +226,8 @@ class _EdgeAttention(torch.autograd.Function):
         da_row, dc_row, da_col, dc_col = (torch.empty_like(a_row) for _ in range(4))
         dkb = torch.empty_like(kbias)
         d_row_val, d_col_val = torch.empty_like(row_val), torch.empty_like(col_val)
-        tail = (ctx.seed, ctx.p) if ctx.p > 0.0 else ()
-        hip_call("lapwarm_dual_attention_backward" + ("_dropout" if tail else ""), "dual_attention_backward", dev,
-                 scores, a_row, c_row, a_col, c_col, kbias, ctx.mask8, ctx.sizes, row_val, col_val, row_msg, col_msg,
+        entry, tail = _attention_backward_entry(ctx.seed, ctx.p)
+        hip_call(entry, "dual_attention_backward", dev, scores, a_row, c_row, a_col, c_col, kbias, ctx.mask8, ctx.sizes, row_val, col_val, row_msg, col_msg,
                  row_stats, col_stats, d_row_msg.contiguous(), d_col_msg.contiguous(), dS, da_row, dc_row, da_col,
                  dc_col, dkb, d_row_val, d_col_val, B, N, H, D, ws, ws.numel(), *tail)
         return dS, da_row, dc_row, da_col, dc_col, dkb, d_row_val, d_col_val, None, None, None, None
@@ -300,36 +316,23 @@ class DualLayer(nn.Module):
         lin1, lin2 = self.edge_mlp[0], self.edge_mlp[3]
         precision = _edge_precision(self.fused_edge_precision)
         p_edge, p_attn = self._fused_dropout_rates()
-        if p_edge > 0.0 or p_attn > 0.0:  # one seed per layer call, on the CPU: no device synchronisation
-            seed = int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64, generator=self.dropout_generator))
-            scores = _EdgeScores.apply(edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], sizes,
-                                       seed, p_edge, precision)
-            mask8 = None if mask is None or sizes is not None else mask.to(torch.uint8).contiguous()
-            return _EdgeAttention.apply(scores, fold["a_row"], fold["c_row"], fold["a_col"], fold["c_col"],
-                                        fold["kbias"], row_val, col_val, mask8, sizes, seed, p_attn)
-        if _records_grad(self, row_embed, col_embed):  # the trainable route: HIP forward and backward
-            scores = _EdgeScores.apply(edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], sizes,
-                                       0, 0.0, precision)
-            mask8 = None if mask is None or sizes is not None else mask.to(torch.uint8).contiguous()
-            return _EdgeAttention.apply(scores, fold["a_row"], fold["c_row"], fold["a_col"], fold["c_col"],
-                                        fold["kbias"], row_val, col_val, mask8, sizes)
+        dropout = p_edge > 0.0 or p_attn > 0.0
+        edge = (edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"])
+        attn = (fold["a_row"], fold["c_row"], fold["a_col"], fold["c_col"], fold["kbias"])
+        mask8 = None if mask is None or sizes is not None else mask.to(torch.uint8).contiguous()
+        if dropout or _records_grad(self, row_embed, col_embed):  # the trainable route: HIP forward and backward
+            seed = 0
+            if dropout:  # one seed per layer call, on the CPU: no device synchronisation
+                seed = int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64, generator=self.dropout_generator))
+            scores = _EdgeScores.apply(*edge, sizes, seed, p_edge, precision)
+            return _EdgeAttention.apply(scores, *attn, row_val, col_val, mask8, sizes, seed, p_attn)
         row_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
         col_msg = torch.empty((B, N, H * D), dtype=torch.float32, device=dev)
         scores = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-        edge = (edge_feat, lin1.weight, lin1.bias, lin2.weight, lin2.bias, fold["G"], scores)
-        if precision == "bf16":  # one entry for both batches: sizes may be None; seed 0, p 0: no dropout
-            hip_call("lapwarm_dual_edge_scores_bf16", "dual_edge_scores", dev, *edge, sizes, B, N, H, 0, 0.0)
-        elif sizes is not None:
-            hip_call("lapwarm_dual_edge_scores_ragged", "dual_edge_scores", dev, *edge, sizes, B, N, H)
-        else:
-            hip_call("lapwarm_dual_edge_scores", "dual_edge_scores", dev, *edge, B, N, H)
-        if sizes is not None:  # scores outside the prefixes are neither written nor read
-            hip_call("lapwarm_dual_attention_ragged", "dual_attention", dev, scores, fold["a_row"], fold["c_row"],
-                     fold["a_col"], fold["c_col"], fold["kbias"], sizes, row_val, col_val, row_msg, col_msg, B, N, H, D)
-            return row_msg, col_msg
-        mask8 = None if mask is None else mask.to(torch.uint8).contiguous()
-        hip_call("lapwarm_dual_attention", "dual_attention", dev, scores, fold["a_row"], fold["c_row"], fold["a_col"],
-                 fold["c_col"], fold["kbias"], mask8, row_val, col_val, row_msg, col_msg, B, N, H, D)
+        entry, tail = _edge_scores_entry(sizes, 0, 0.0, precision, (B, N, H))  # seed 0, p 0: no dropout
+        hip_call(entry, "dual_edge_scores", dev, *edge, scores, *tail)
+        entry, masks, tail = _attention_entry(mask8, sizes, 0, 0.0, stats=False)
+        hip_call(entry, "dual_attention", dev, scores, *attn, *masks, row_val, col_val, row_msg, col_msg, B, N, H, D, *tail)
         return row_msg, col_msg
 
     # ---- the plain path ------------------------------------------------------------------------------------

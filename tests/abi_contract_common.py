@@ -3,7 +3,8 @@ lapwarm_*_workspace_bytes entry returns over a grid that straddles the branches 
 codes of calls that an entry point rejects before its first HIP call (argument checks, their order, the workspace
 check).  The command line prints the record of the environment it runs in as JSON; tests/golden/abi_contract.json
 holds "sizes" and "codes" of what it printed for the library of commit 8a46a51, before the ABI's repeated steps
-were gathered into helpers.  "short_text" (the error text after each too-small workspace) is asserted, not
+were gathered into helpers; the twelve lapwarm_dual_* entries of _dual() and "dual_backward" were recorded from the
+library of commit 1970bca, before the DualGNN launchers were gathered into DualEdgeParams.  "short_text" (the error text after each too-small workspace) is asserted, not
 recorded: that commit left it unset at ten entry points."""
 import ctypes as ct
 import itertools
@@ -35,8 +36,9 @@ def sizes(lib):
         out[name] = [f(b, n) for b, n in points]
     out["refine_backward"] = [lib.lapwarm_refine_backward_workspace_bytes(r, h)
                               for r, h in itertools.product((0, 1, 33, 1024), (0, 1, 64, 128))]
-    out["dual_gnn"] = [lib.lapwarm_dual_gnn_workspace_bytes(b, n, h)
-                       for b, n, h in itertools.product((0, 1, 2, 32768), (0, 1, 33, 512, 16385), (0, 1, 8, 9))]
+    dual_grid = list(itertools.product((0, 1, 2, 32768), (0, 1, 33, 512, 16385), (0, 1, 8, 9)))
+    out["dual_gnn"] = [lib.lapwarm_dual_gnn_workspace_bytes(b, n, h) for b, n, h in dual_grid]
+    out["dual_backward"] = [lib.lapwarm_dual_backward_workspace_bytes(b, n, h) for b, n, h in dual_grid]
     out["lapjv_extended"] = [lib.lapwarm_lapjv_extended_workspace_bytes(b, r, c, e, t)
                              for b, (r, c), e, t in itertools.product((0, 1, 2, 65535, 65536), ((3, 3), (3, 5), (5, 3)),
                                                                       (0, 1), (INF, 10.0))]
@@ -63,6 +65,70 @@ def _uniform(lib, symbol, query, args, ws_at, limits_batch=False, smaller=None):
         cases["n=16385,ws=0"] = f(*args(B, 16385, P, 0))
         cases["ws short"] = ws_at(lambda: f(*args(B, N, P, need - 1)))
     return cases
+
+
+def _dual(lib, ws_at):
+    """The other twelve lapwarm_dual_* compute entries.  `sizes`, `p` and the workspace are keyword arguments of
+    every call; an entry takes the ones it has."""
+    H, NAN = 4, float("nan")
+    need = lib.lapwarm_dual_backward_workspace_bytes(B, N, H)
+
+    def cases(symbol, call, heads, sizes=None, takes_p=False, stats=False, backward=False):
+        """`sizes`: None (no such argument), "required" or "nullable"."""
+        c = {"n=0": call(n=0), "batch=0": call(b=0), "batch=32768": call(b=32768), "n=16385": call(n=16385),
+             "null": call(first=None), "n=16385,null": call(n=16385, first=None), f"heads={heads}": call(h=heads)}
+        if sizes == "required":
+            c["null sizes"] = call(sizes=None)
+            c["n=16385,null sizes"] = call(n=16385, sizes=None)
+        if sizes == "nullable":  # accepted up to the next check
+            c["null sizes,n=16385"] = call(n=16385, sizes=None)
+        if stats:
+            c["head_dim=0"] = call(d=0)
+            c["null stats"] = call(stats=None)
+        if takes_p:
+            c.update({"p=1": call(p=1.0), "p=-0.1": call(p=-0.1), "p=nan": call(p=NAN), "p=1,n=16385": call(p=1.0, n=16385)})
+        if backward:
+            c.update({"null ws": call(ws=None), "n=16385,ws=0": call(n=16385, s=0), "null,ws short": call(first=None, s=need - 1),
+                      "null sizes,ws short": call(sizes=None, s=need - 1),
+                      "ws short": ws_at(symbol)(lambda: call(s=need - 1))})
+        return c
+
+    out = {}
+    for suffix, takes_p in (("_ragged", False), ("_dropout", True), ("_bf16", True)):
+        symbol = "lapwarm_dual_edge_scores" + suffix
+        f = getattr(lib, symbol)
+        g = lambda b=B, n=N, h=H, first=P, sizes=P, p=0.5, f=f, takes_p=takes_p: f(  # noqa: E731
+            first, P, P, P, P, P, P, sizes, b, n, h, *((7, p) if takes_p else ()), None)
+        out[symbol] = cases(symbol, g, 9, sizes="nullable" if takes_p else "required", takes_p=takes_p)
+    for suffix, takes_p in (("", False), ("_dropout", True), ("_bf16", True)):
+        symbol = "lapwarm_dual_edge_scores_backward" + suffix
+        f = getattr(lib, symbol)
+        g = lambda b=B, n=N, h=H, first=P, sizes=P, p=0.5, ws=P, s=need, f=f, takes_p=takes_p: f(  # noqa: E731
+            first, P, P, P, P, P, P, sizes, P, P, P, P, P, b, n, h, ws, s, *((7, p) if takes_p else ()), None)
+        out[symbol] = cases(symbol, g, 9, sizes="nullable", takes_p=takes_p, backward=True)
+    for suffix, takes_p in (("", False), ("_dropout", True)):
+        symbol = "lapwarm_dual_attention_backward" + suffix
+        f = getattr(lib, symbol)
+        g = lambda b=B, n=N, h=H, d=16, first=P, sizes=P, p=0.5, ws=P, s=need, f=f, takes_p=takes_p: f(  # noqa: E731
+            first, P, P, P, P, P, None, sizes, *([P] * 16), b, n, h, d, ws, s, *((7, p) if takes_p else ()), None)
+        out[symbol] = cases(symbol, g, 9, sizes="nullable", takes_p=takes_p, backward=True)
+    f = lib.lapwarm_dual_attention_ragged
+    g = lambda b=B, n=N, h=H, first=P, sizes=P: f(first, P, P, P, P, P, sizes, P, P, P, P, b, n, h, 16, None)  # noqa: E731
+    out["lapwarm_dual_attention_ragged"] = cases("lapwarm_dual_attention_ragged", g, 65536, sizes="required")
+    f = lib.lapwarm_dual_attention_stats
+    g = lambda b=B, n=N, h=H, d=16, first=P, stats=P: f(first, P, P, P, P, P, None, P, P, P, P, stats, P, b, n, h, d, None)  # noqa: E731
+    out["lapwarm_dual_attention_stats"] = cases("lapwarm_dual_attention_stats", g, 65536, stats=True)
+    f = lib.lapwarm_dual_attention_stats_ragged
+    g = lambda b=B, n=N, h=H, d=16, first=P, sizes=P, stats=P: f(  # noqa: E731
+        first, P, P, P, P, P, sizes, P, P, P, P, stats, P, b, n, h, d, None)
+    out["lapwarm_dual_attention_stats_ragged"] = cases("lapwarm_dual_attention_stats_ragged", g, 65536,
+                                                       sizes="required", stats=True)
+    f = lib.lapwarm_dual_attention_stats_dropout
+    g = lambda b=B, n=N, h=H, d=16, first=P, sizes=P, stats=P, p=0.5: f(  # noqa: E731
+        first, P, P, P, P, P, None, sizes, P, P, P, P, stats, P, b, n, h, d, 7, p, None)
+    out["lapwarm_dual_attention_stats_dropout"] = cases("lapwarm_dual_attention_stats_dropout", g, 65536,
+                                                        sizes="nullable", takes_p=True, stats=True)
+    return out
 
 
 def codes(lib):
@@ -116,6 +182,7 @@ def codes(lib):
     g = lambda b=B, n=N, h=4, s=P: f(s, P, P, P, P, P, None, P, P, P, P, b, n, h, 16, None)  # noqa: E731
     out["lapwarm_dual_attention"] = {"n=0": g(n=0), "batch=0": g(b=0), "heads=65536": g(h=65536), "n=16385": g(n=16385),
                                      "null": g(s=None), "n=16385,null": g(n=16385, s=None)}
+    out.update(_dual(lib, ws_at))
     f = lib.lapwarm_refine_backward
     need = lib.lapwarm_refine_backward_workspace_bytes(N, 64)
     g = lambda r=N, h=64, t=P, s=need: f(t, P, P, P, P, None, P, P, P, r, h, P, s, None)  # noqa: E731

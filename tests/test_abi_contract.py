@@ -76,6 +76,6 @@ def test_return_codes_and_check_order_are_unchanged(contract):
 def test_a_short_workspace_sets_the_error_text(contract):
     got, want = contract
     short = {symbol for symbol, cases in want["codes"].items() if cases.get("ws short") == -1}
-    assert set(got["short_text"]) == short and len(short) == 24
+    assert set(got["short_text"]) == short and len(short) == 29
     for symbol, text in got["short_text"].items():
         assert text.startswith("workspace too small"), (symbol, text)
