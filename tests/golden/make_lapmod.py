@@ -1,5 +1,8 @@
-"""Writes tests/golden/lapmod_cases.npz: sparse LAPMOD inputs and what the reference's lapmod_internal returns for
-them with FP_1, FP_2 and FP_DYNAMIC.
+"""Writes tests/golden/lapmod_cases.npz and lapmod_long_rows.npz: sparse LAPMOD inputs and what the reference's
+lapmod_internal returns for them with FP_1, FP_2 and FP_DYNAMIC.  The second file holds the cases of
+long_row_cases(), drawn from a generator of their own, and for dec_single193 the two counts of arr_first_values();
+every condition those cases are there for is asserted and printed.  A committed file is loaded first and every key
+of it must equal what is about to be written: stored cases never move.
 
     python tests/golden/make_lapmod.py [LDS_MAX_N]          (from the repo root)
 
@@ -100,9 +103,70 @@ def certain_ret1(n, cc, ii, kk):
     return not empty[claim0.max()] if claim0.size else True
 
 
-def main():
-    lib = lapmod_lib()
-    lds_max = int(sys.argv[1]) if len(sys.argv) > 1 else 3395
+def arr_first_values(n, cc, ii, kk):
+    """The column reduction, the reduction transfer and the two ARR passes, serially and in plain Python, after
+    DESIGN.md, "Sparse LAPMOD".  Returns (above, far, free): the ARR rows whose first reduced value exceeds LARGE,
+    those of them whose first entry below LARGE lies at position >= 64 of the row (the serial scan ignores every
+    entry before it), and the rows still free after the second pass."""
+    LARGE = 1e6
+    v, x, y = np.full(n, LARGE), np.full(n, -1), np.zeros(n, dtype=np.int64)
+    for i in range(n):
+        for k in range(ii[i], ii[i + 1]):
+            if cc[k] < v[kk[k]]:
+                v[kk[k]], y[kk[k]] = cc[k], i
+    shared = np.zeros(n, dtype=bool)  # rows that claimed more than one column
+    for j in reversed(range(n)):
+        if x[y[j]] < 0:
+            x[y[j]] = j
+        else:
+            shared[y[j]] = True
+            y[j] = -1
+    free = []
+    for i in range(n):
+        if x[i] < 0:
+            free.append(i)
+        elif not shared[i] and ii[i + 1] - ii[i] > 1:
+            others = [cc[k] - v[kk[k]] for k in range(ii[i], ii[i + 1]) if kk[k] != x[i]]
+            v[x[i]] -= min([LARGE] + others)
+    above = far = 0
+    for _ in range(2):
+        todo, free, current, visits = free, [], 0, 0
+        while current < len(todo):
+            visits += 1
+            row = todo[current]
+            current += 1
+            red = [cc[k] - v[kk[k]] for k in range(ii[row], ii[row + 1])]
+            j1, v1, j2, v2 = (kk[ii[row]], red[0], -1, LARGE) if red else (0, LARGE, -1, LARGE)
+            if red and red[0] > LARGE:
+                above += 1
+                below = [p for p in range(1, len(red)) if red[p] < LARGE]
+                far += bool(below) and below[0] >= 64
+            for p in range(1, len(red)):
+                if red[p] < v2:
+                    if red[p] >= v1:
+                        j2, v2 = kk[ii[row] + p], red[p]
+                    else:
+                        j2, v2, j1, v1 = j1, v1, kk[ii[row] + p], red[p]
+            owner, lowered = y[j1], v[j1] - (v2 - v1)
+            lowers = lowered < v[j1]
+            if visits < current * n:
+                if lowers:
+                    v[j1] = lowered
+                elif owner >= 0 and j2 >= 0:
+                    j1, owner = j2, y[j2]
+                if owner >= 0 and lowers:
+                    current -= 1
+                    todo[current] = owner
+                elif owner >= 0:
+                    free.append(owner)
+            elif owner >= 0:
+                free.append(owner)
+            x[row], y[j1] = j1, row
+    return above, far, len(free)
+
+
+def stored_cases(lds_max):
+    """The 45 cases of lapmod_cases.npz, from their own generator: they keep their draws whatever follows."""
     rng = np.random.default_rng(20240611)
     cases = []  # (label, n, cc, ii, kk, kind)
 
@@ -186,8 +250,63 @@ def main():
     add(f"n{lds_max + 1}_above_lds", random_sparse(rng, lds_max + 1, 4, mostly_fine), "tie")
     add("n4096_k16", random_sparse(rng, 4096, 16, mostly_fine), "tie")
 
-    out = {"labels": np.array([c[0] for c in cases]), "lds_max_n": np.int64(lds_max)}
-    tie_aug, disagree = {}, 0
+    return cases
+
+
+def long_row_cases():
+    """The cases of lapmod_long_rows.npz, from a generator of their own: rows of 64, 65, 128, 129 and 193 entries
+    (the device loops take a row in chunks of 64), costs that are inexact in fp64 and reach the path search, and
+    unsolvable instances above n = 64."""
+    rng = np.random.default_rng(20261021)
+    cases = []
+
+    def add(label, cost, kind="long"):
+        cases.append((label,) + from_masked(cost) + (kind,))
+
+    def dec(m):  # decimal ties: tenths are no dyadic fractions
+        return rng.integers(1, 8, size=m) / 10.0
+
+    add("dec_full129", random_sparse(rng, 129, 129, dec))
+    add("dec_full193", random_sparse(rng, 193, 193, dec))
+    add("dec_rows64_n130", random_sparse(rng, 130, 63, dec))
+    add("dec_rows65_n130", random_sparse(rng, 130, 64, dec))
+    add("dec_rows128_n200", random_sparse(rng, 200, 127, dec))
+    add("dec_rows129_n200", random_sparse(rng, 200, 128, dec))
+    add("dec_sparse130", random_sparse(rng, 130, 4, dec))
+    add("lowrank129", np.outer(rng.random(129) * 10.0, rng.random(129) * 10.0) + 0.01 * rng.random((129, 129)))
+    # Single-entry rows, built by hand.  A single-entry row that ARR visits lowers its column's v by about 1e6, and
+    # the full row it displaces then starts with a reduced value above LARGE where its entry of column 0 costs more
+    # than the single one.  Its first entry below LARGE lies behind every lowered column, so position >= 64 needs
+    # columns 0..63 lowered: more single-entry rows than `single_rows = 0.2` of 193 gives, in the order of their
+    # columns, each at the column's smallest cost (1/10) and below a full row that claims the column first.
+    n, first, count = 193, 120, 66
+    sr = np.full((n, n), INF)
+    for i in range(n):
+        if first <= i < first + count:
+            sr[i, i - first] = 1 / 10.0
+        else:
+            sr[i] = dec(n)
+    add("dec_single193", sr)
+    # an empty column, with row 0 holding the strict minimum of a later column (as `empty_column`)
+    ec = random_sparse(rng, 130, 64, dec)
+    ec[:, 3] = INF
+    ec[0, 129] = 0.0
+    assert np.isfinite(ec).any(axis=1).all()  # (the row whose permutation entry was in column 3 keeps its others)
+    add("dec_empty_col130", ec, "unsolvable")
+    # Hall's condition: two rows hold the same single column, and no column is empty
+    hc = random_sparse(rng, 130, 64, dec)
+    for i in (41, 97):
+        hc[i] = INF
+        hc[i, 70] = dec(1)[0]
+    assert np.isfinite(hc).any(axis=0).all()
+    add("dec_hall130", hc, "unsolvable")
+    return cases
+
+
+def records(lib, cases, times):
+    """label__key -> array for every case, and what the assertions of main() need: kind -> [(label, n, aug)], the
+    number of solvable cases whose FP_1 and FP_2 assignments differ."""
+    out, by_kind, disagree = {}, {}, 0
     for label, n, cc, ii, kk, kind in cases:
         solvable = kind != "unsolvable"
         if n <= 300:  # (the larger ones hold a permutation by construction)
@@ -197,8 +316,11 @@ def main():
         small = n < 32768
         out[f"{label}__n"] = np.int64(n)
         scale = next((q for q in (1, 64) if np.all(cc * q == np.floor(cc * q)) and cc.max() * q < 65536), 0)
+        if not scale and np.array_equal(np.rint(cc * 10) / 10.0, cc) and cc.max() * 10 < 65536:
+            scale = 10  # tenths: drawn as integers over 10.0, so stored / 10.0 gives their bits back
         if scale:
-            out[f"{label}__cc"] = (cc * scale).astype(np.uint16)  # cc = stored / ccscale, exactly
+            out[f"{label}__cc"] = np.rint(cc * scale).astype(np.uint16)  # cc = stored / ccscale, exactly
+            assert np.array_equal(out[f"{label}__cc"].astype(np.float64) / float(scale), cc), label
         else:
             out[f"{label}__cc"] = cc.astype(np.float32) if np.all(cc == cc.astype(np.float32)) else cc
         out[f"{label}__ccscale"] = np.int64(max(scale, 1))
@@ -225,18 +347,76 @@ def main():
             out[f"{label}__ret_{fp}"] = np.int64(ret)
             out[f"{label}__x_{fp}"] = x.astype(np.int16 if small else np.int32)
             out[f"{label}__y_{fp}"] = y.astype(np.int16 if small else np.int32)
-            if n >= 257:
+            if times or n >= 257:
                 print(f"{label} fp={fp} aug={aug} reference {secs * 1e3:.2f} ms")
         if 1 in xs and 2 in xs and not np.array_equal(xs[1], xs[2]):
             disagree += 1
-        if kind == "tie" and n >= 63:
+        by_kind.setdefault(kind, []).append((label, n, aug))
+    return out, by_kind, disagree
+
+
+def same_as_committed(path, out):
+    """Every key of the committed file equals what is about to be written (bits and dtype): stored cases never
+    move.  True when the file holds nothing else either, so that it need not be rewritten."""
+    if not path.exists():
+        return False
+    old = np.load(path, allow_pickle=False)
+    for key in old.files:
+        assert key in out and old[key].dtype == out[key].dtype and old[key].shape == np.shape(out[key]), key
+        assert np.array_equal(old[key], out[key], equal_nan=old[key].dtype.kind == "f"), key
+    print(f"{path.name}: {len(old.files)} committed keys equal to the regenerated ones")
+    return set(old.files) == set(out)
+
+
+def main():
+    lib = lapmod_lib()
+    lds_max = int(sys.argv[1]) if len(sys.argv) > 1 else 3395
+    cases = stored_cases(lds_max)
+    out, by_kind, disagree = records(lib, cases, times=False)
+    out.update(labels=np.array([c[0] for c in cases]), lds_max_n=np.int64(lds_max))
+    tie_aug = {}
+    for _, n, aug in by_kind["tie"]:
+        if n >= 63:
             tie_aug.setdefault(n, []).append(aug)
     for n, flags in tie_aug.items():
         assert 2 * sum(flags) >= len(flags), (n, flags)
     assert disagree >= 1
     assert out["empty_column__strict"] and out["infs_unsolvable0__strict"] and out["inf_col__strict"]
     path = HERE / "lapmod_cases.npz"
-    np.savez_compressed(path, **out)
+    if not same_as_committed(path, out):
+        np.savez_compressed(path, **out)
+    print(f"{len(cases)} cases, {disagree} with FP_1 != FP_2, {path.stat().st_size} bytes")
+
+    # the long-row cases: a file of their own (both together would pass 1 MiB), read by the same loader
+    cases = long_row_cases()
+    assert not {c[0] for c in cases} & set(out["labels"].tolist())
+    out, by_kind, disagree = records(lib, cases, times=True)
+    out["labels"] = np.array([c[0] for c in cases])
+    assert all(aug for _, _, aug in by_kind["long"]), by_kind["long"]
+    print("augmentation reached by every solvable case:", [label for label, _, _ in by_kind["long"]])
+    lengths = set()
+    for label, n, cc, ii, kk, kind in cases:
+        lengths |= set(np.diff(ii).tolist())
+        assert not np.all(cc * 64 == np.floor(cc * 64)), label
+    assert {64, 65, 128, 129, 193} <= lengths, sorted(lengths)
+    print("row lengths include 64, 65, 128, 129, 193; no case has dyadic costs")
+    picked = {label: int(out[f"{label}__dyn"]) for label, _, _ in by_kind["long"]}
+    assert set(picked.values()) == {1, 2}, picked
+    print("FP_DYNAMIC picks", picked)
+    label, n, cc, ii, kk, _ = next(c for c in cases if c[0] == "dec_single193")
+    above, far, free = arr_first_values(n, cc, ii, kk)
+    assert (free > 0) == bool(out[f"{label}__aug"]), free  # the transcription ends ARR as the reference does
+    assert above >= 1 and far >= 1, (above, far)
+    out[f"{label}__arr_first_above"], out[f"{label}__arr_first_far"] = np.int64(above), np.int64(far)
+    print(f"{label}: {above} ARR rows start above LARGE, {far} of them with the first entry below it at "
+          f"position >= 64; {free} rows free after ARR")
+    for label, _, _ in by_kind["unsolvable"]:
+        assert out[f"{label}__strict"], label
+        assert int(out[f"{label}__dyn"]) == 1 and f"{label}__ret_2" not in out, label
+    print("unsolvable and strict:", [label for label, _, _ in by_kind["unsolvable"]])
+    path = HERE / "lapmod_long_rows.npz"
+    if not same_as_committed(path, out):
+        np.savez_compressed(path, **out)
     print(f"{len(cases)} cases, {disagree} with FP_1 != FP_2, {path.stat().st_size} bytes")
 
 

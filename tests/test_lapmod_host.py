@@ -8,7 +8,7 @@ import pytest
 
 from conftest import ROOT
 from host_common import lib  # noqa: F401
-from lapmod_common import densify, load_cases, problem
+from lapmod_common import densify, load_cases, long_row_labels, problem
 
 ENTRIES = {"lapwarm_lapmod_workspace_bytes": 3, "lapwarm_lapmod_lds_max_n": 0, "lapwarm_lapmod_ragged": 18}
 
@@ -146,6 +146,45 @@ def test_sparse_helpers_match_the_fixtures():
             n, cc, ii, kk = lap.sparse_from_masked(*args)
             assert n == c["n"] and np.array_equal(cc, c["cc"]) and np.array_equal(ii, c["ii"])
             assert np.array_equal(kk, c["kk"])
+
+
+def test_long_row_cases_keep_what_they_are_there_for():
+    """What tests/golden/make_lapmod.py asserts of lapmod_long_rows.npz when it writes it, read back from the file:
+    a regeneration cannot lose the long rows, the inexact costs in the search or the rows that start above LARGE."""
+    cases, _ = load_cases()
+    labels = long_row_labels()
+    assert labels == ("dec_full129", "dec_full193", "dec_rows64_n130", "dec_rows65_n130", "dec_rows128_n200",
+                      "dec_rows129_n200", "dec_sparse130", "lowrank129", "dec_single193", "dec_empty_col130",
+                      "dec_hall130")
+    assert list(cases)[-len(labels):] == list(labels) and len(cases) == 45 + len(labels)
+    lengths, picked = set(), set()
+    for label in labels:
+        c = cases[label]
+        lengths |= set(np.diff(c["ii"]).tolist())
+        assert not np.all(c["cc"] * 64 == np.floor(c["cc"] * 64)), label  # no dyadic costs: fp64 rounds
+        assert np.all(c["cc"] >= 0.0) and np.all(c["cc"] < 1e6), label
+        assert c["solvable"] == (label not in ("dec_empty_col130", "dec_hall130")), label
+        if c["solvable"]:
+            assert c["aug"], label  # the path search runs
+            assert set(c["ref"]) == {1, 2, 3} and set(c["v"]) == {1, 2, 3}, label
+            picked.add(c["dyn"])
+        else:
+            assert c["strict"] and c["n"] > 64 and c["dyn"] == 1 and set(c["ref"]) == {1, 3}, label
+    assert {64, 65, 128, 129, 193} <= lengths
+    assert picked == {1, 2}
+    assert cases["dec_sparse130"]["dyn"] == 2 and cases["dec_full129"]["dyn"] == 1
+    tenths = cases["dec_full193"]["cc"]
+    assert np.array_equal(tenths, np.rint(tenths * 10) / 10.0) and set(np.rint(tenths * 10)) == set(range(1, 8))
+    single = cases["dec_single193"]
+    assert single["arr_first_above"] >= 1 and single["arr_first_far"] >= 1
+    assert single["arr_first_far"] <= single["arr_first_above"]
+    assert 1 in np.diff(single["ii"]) and 193 in np.diff(single["ii"])
+    hall = cases["dec_hall130"]
+    assert np.unique(hall["kk"]).size == hall["n"] and np.sum(np.diff(hall["ii"]) == 1) == 2
+    empty = cases["dec_empty_col130"]
+    assert np.unique(empty["kk"]).size == empty["n"] - 1 and np.all(np.diff(empty["ii"]) > 0)
+    # the 45 earlier cases reach none of this: rows of at most 103 entries
+    assert max(np.diff(c["ii"]).max() for label, c in cases.items() if label not in labels) == 103
 
 
 def test_get_cost_matches_the_fixtures():
