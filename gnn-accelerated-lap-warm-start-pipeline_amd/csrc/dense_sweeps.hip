@@ -859,7 +859,7 @@ hipError_t launch_seed_prepare_ragged(const RaggedBatch &g, const double *u_seed
                                       double *v_work, int *flags, long long *x, long long *y, int *ret,
                                       long long *stats, hipStream_t stream)
 {
-    if (g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(seed_prepare_ragged_kernel, dim3((g.N + kSweepThreads - 1) / kSweepThreads, g.batch),
                        dim3(kSweepThreads), 0, stream, g, u_seed, v_seed, u_work, v_work, flags, x, y, ret, stats);
     return hipGetLastError();
@@ -889,7 +889,7 @@ hipError_t launch_projection(const double *C, int n, int batch, double *u, doubl
 // p.n == g.N, p.batch == g.batch; p.C is not read.  The register-resident variant is chosen by N.
 hipError_t launch_prelude_ragged(const PreludeParams &p, const RaggedBatch &g, hipStream_t stream)
 {
-    if (g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535 || p.n != g.N) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N) || p.n != g.N) return hipErrorInvalidValue;
     const dim3 grid(g.N, g.batch), block(kSweepThreads);
     if (g.N <= 8 * kSweepThreads)
         hipLaunchKernelGGL(prelude_ragged_kernel<8>, grid, block, 0, stream, p, g);
@@ -903,7 +903,7 @@ hipError_t launch_prelude_ragged(const PreludeParams &p, const RaggedBatch &g, h
 hipError_t launch_projection_ragged(const RaggedBatch &g, double *u, double *v, const int *viol_cnt, int *inst_flags,
                                     double eps, hipStream_t stream)
 {
-    if (g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(projection_ragged_kernel, dim3(g.batch), dim3(kSweepThreads), 0, stream, g, u, v, viol_cnt,
                        inst_flags, eps);
     return hipGetLastError();
@@ -1006,7 +1006,7 @@ hipError_t launch_row_features(const FeatureParams &p, hipStream_t stream)
 // LDS is sized for N: the rows of one launch share one size, whatever their instance's n_b.
 hipError_t launch_row_features_ragged(const RaggedBatch &g, const RaggedFeatureOut &o, hipStream_t stream)
 {
-    if (g.N > 16384 || g.N < 1 || g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+    if (check_ragged_dims(g.batch, g.N)) return hipErrorInvalidValue;
     const int npad = (g.N + 1) & ~1;
     const size_t lds = row_features_lds(npad);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(row_features_ragged_kernel),

@@ -1285,7 +1285,7 @@ int lapwarm_reduce_costs_batched(const double *C, int batch, int n, const double
     return 0;
 }
 
-// ---- dual utilities of a ragged batch (ragged_duals.hip) ----
+// ---- dual utilities of a ragged batch (ragged_duals.hpp, ragged_batch.hip) ----
 static RaggedDualsWs ragged_duals_layout(void *workspace, int batch, int N)
 {
     Carver c{reinterpret_cast<unsigned char *>(workspace), 0};

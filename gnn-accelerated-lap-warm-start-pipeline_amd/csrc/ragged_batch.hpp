@@ -42,8 +42,9 @@ __device__ __forceinline__ int ragged_size(const RaggedBatch &g, int b)
 // u, out [batch][N].  One kernel.
 hipError_t launch_colmin_ragged(const RaggedBatch &g, const double *u, double *out, hipStream_t stream);
 
-// gmin[b] = min_{i, j < n_b} ((C_b[i][j] - u[b][i]) - v[b][j]), NaN as np.min, +inf for an instance treated as
-// empty: launch_reduced_min per instance.  u, v, rowpart [batch][N]; gmin [batch].  Two kernels.
+// gmin[b] = min_{i, j < n_b} ((C_b[i][j] - u[b][i]) - v[b][j]), NaN as np.min, 0 for an instance treated as
+// empty: launch_reduced_min per instance.  u, v, rowpart [batch][N]; gmin [batch].  Two kernels, the first two of
+// launch_reduce_costs_ragged (ragged_duals.hpp).
 hipError_t launch_reduced_min_ragged(const RaggedBatch &g, const double *u, const double *v, double *rowpart,
                                      double *gmin, hipStream_t stream);
 

@@ -1,5 +1,5 @@
 // ragged_duals.hpp -- the dual utilities (row minima, feasibility projection, reduced costs) of a batch of cost
-// matrices of different sizes (ragged_duals.hip).
+// matrices of different sizes (ragged_batch.hip).
 #pragma once
 
 #include "ragged_batch.hpp"

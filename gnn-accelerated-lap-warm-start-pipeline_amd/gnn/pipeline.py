@@ -682,7 +682,7 @@ class WarmStartPipeline:
         return DualDeviceBatch(cost=r.cost32, u=u, v=v, row_feat=f.row, col_feat=f.col, edge_feat=f.edge, mask=f.mask,
                                sizes=f.sizes)
 
-    # ---- dual utilities of a ragged batch (csrc/ragged_duals.hip): solvers/advanced_dual.py:14-63 and the
+    # ---- dual utilities of a ragged batch (csrc/ragged_batch.hip): solvers/advanced_dual.py:14-63 and the
     # classical seeds of solvers/seed_baselines.py for every instance of a pack in one call each
     def _check_duals_args(self, pack, u, v):
         """Argument errors, raised before any device work: types and dtypes, then shapes, then devices."""

@@ -1,5 +1,5 @@
 """The ragged dual utilities on the MI355X: lapwarm_rowmin_ragged, lapwarm_project_feasible_ragged and
-lapwarm_reduce_costs_ragged (csrc/ragged_duals.hip) through ctypes, WarmStartPipeline, gnn.row_min_ragged and the
+lapwarm_reduce_costs_ragged (csrc/ragged_batch.hip) through ctypes, WarmStartPipeline, gnn.row_min_ragged and the
 *_many functions of `solvers`.
 
 Every value the kernels produce is a minimum or a difference of two doubles, so results are compared for
@@ -190,7 +190,7 @@ def test_fixture_cases_reduce_costs_and_feasibility(layout, shift):
 
 # --------------------------------------------------------------------------- against the uniform entries
 def row_width():
-    src = (PKG / "csrc" / "ragged_duals.hip").read_text()
+    src = (PKG / "csrc" / "ragged_batch.hip").read_text()
     return int(re.search(r"constexpr int kRowThreads = (\d+);", src).group(1))
 
 
