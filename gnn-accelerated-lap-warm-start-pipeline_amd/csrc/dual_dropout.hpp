@@ -3,7 +3,7 @@
 // A mask is never stored: whether element e of a logical tensor is kept is a pure function of (seed, stream, e), so
 // the backward regenerates what the forward used, and tiling, chunking and `sizes` cannot change a mask.
 //
-//   Philox4x32-10 (Salmon et al., SC'11): key (lo32(seed), hi32(seed)), counter (lo32(e >> 2), hi32(e >> 2), stream, 0);
+//   Philox4x32-10 (philox.hpp): key (lo32(seed), hi32(seed)), counter (lo32(e >> 2), hi32(e >> 2), stream, 0);
 //   the random word of e is output e & 3; e is kept iff word >= T, T = floor(p * 2^32) formed in double on the host;
 //   a kept value is multiplied by float(1 / (1 - p)).
 //
@@ -14,6 +14,8 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include "philox.hpp"
 
 namespace lapwarm {
 
@@ -30,22 +32,7 @@ struct DualDropout {
 __host__ __device__ __forceinline__ void dual_dropout_words(unsigned k0, unsigned k1, unsigned stream,
                                                             unsigned long long group, unsigned (&out)[4])
 {
-    unsigned c0 = (unsigned)group, c1 = (unsigned)(group >> 32), c2 = stream, c3 = 0u;
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned)p1;
-        c3 = (unsigned)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0;
-    out[1] = c1;
-    out[2] = c2;
-    out[3] = c3;
+    philox4x32_10(k0, k1, stream, group, out);
 }
 
 // Element e alone (the attention kernels: one call per key that uses one word).

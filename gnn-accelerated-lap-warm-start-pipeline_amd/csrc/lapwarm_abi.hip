@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/lapwarm_hip.h"
+#include "cost_families.hpp"
 #include "dense_sweeps.hpp"
 #include "dual_gnn.hpp"
 #include "extend_costs.hpp"
@@ -1360,6 +1361,48 @@ int lapwarm_reduce_costs_ragged(const double *C, const long long *offsets, const
     const RaggedBatch g{C, offsets, sizes, ld, batch, N};
     const RaggedDualsWs w = ragged_duals_layout(workspace, batch, N);
     HIP_TRY(launch_reduce_costs_ragged(g, w, u, v, shift_nonneg, out, gmin, ret, as_stream(stream_)));
+    return 0;
+}
+
+// ---- synthetic cost families drawn into a ragged batch (cost_families.hpp) ----
+static CostFamiliesWs cost_families_layout(void *workspace, int batch, int N)
+{
+    Carver c{reinterpret_cast<unsigned char *>(workspace), 0};
+    CostFamiliesWs w;
+    w.fa = c.take<double>((size_t)batch * N * kMaxRank);
+    w.fb = c.take<double>((size_t)batch * N * kMaxRank);
+    w.part = c.take<double>((size_t)batch * cost_tiles(N));
+    w.colany = c.take<unsigned char>((size_t)batch * N);
+    w.bytes = c.off;
+    return w;
+}
+
+size_t lapwarm_cost_families_workspace_bytes(int batch, int N)
+{
+    if (check_ragged_dims(batch, N)) return 0;
+    return cost_families_layout(nullptr, batch, N).bytes;
+}
+
+int lapwarm_generate_costs_ragged(double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                  const int *family, const unsigned long long *seeds, const double *params, int *ret,
+                                  void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!family || !seeds || !params || !ret || !workspace) return -2;
+    if (int rc = check_workspace(workspace_bytes, lapwarm_cost_families_workspace_bytes(batch, N))) return rc;
+    const CostFamiliesArgs a{C,      offsets, sizes, ld,  batch, N,
+                             family, seeds,   params, ret, cost_families_layout(workspace, batch, N)};
+    HIP_TRY(launch_generate_costs_ragged(a, as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_cost_family_draws(unsigned long long seed, unsigned int stream_id, int kind, unsigned long long first,
+                              unsigned long long count, unsigned int m, void *out, void *stream_)
+{
+    if (kind < 0 || kind > 2 || (kind == 2 && (m < 1 || m > 0x7fffffffu))) return -2;
+    if (count == 0) return 0;
+    if (!out || count >= (1ull << 39)) return -2;  // the grid's x dimension: 2^31 blocks of 256
+    HIP_TRY(launch_cost_family_draws(seed, stream_id, kind, first, count, (int)m, out, as_stream(stream_)));
     return 0;
 }
 

@@ -20,6 +20,7 @@ from .features import (compute_row_features, compute_row_features_torch, positio
                        RaggedPack, ROW_FEATURE_DIM, row_min_ragged)
 from .one_gnn import OneGNN, ResidualBlock
 from .pipeline import GNNPredictor, WarmStartPipeline, load_checkpoint, load_dual_checkpoint
+from .synthetic import DEFAULT_PARAMS, FAMILY_IDS, SyntheticStream, synthetic_pack
 
 _OUT_OF_SCOPE = ("{} is a placeholder that keeps the reference harness' import line working; the O(n^2)-edge DualGNN "
                  "path runs on the MI355X as {} (see the `gnn` docstring for the routing)")
@@ -37,4 +38,4 @@ def compute_features(*args, **kwargs):
 __all__ = ["OneGNN", "ResidualBlock", "DualGNN", "compute_features", "compute_row_features",
            "compute_row_features_torch", "positional_encodings", "ROW_FEATURE_DIM", "GNNPredictor",
            "WarmStartPipeline", "load_checkpoint", "collate_device", "DeviceBatch", "ragged_pack", "RaggedPack",
-           "row_min_ragged"]
+           "row_min_ragged", "FAMILY_IDS", "DEFAULT_PARAMS", "synthetic_pack", "SyntheticStream"]

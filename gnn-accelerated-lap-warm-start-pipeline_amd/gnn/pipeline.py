@@ -636,13 +636,29 @@ class WarmStartPipeline:
         (data/generators.py:131-135) on the device: with that probability an instance's fp64 duals get N(0,
         dual_noise_std) noise and are projected back to feasibility in 75 rounds at most (noisy_duals_ragged, with
         `generator`); only u and v of the batch differ.  With the defaults nothing is added to the clean path."""
-        from .collate import DeviceBatch
         dual_noise_std, dual_noise_prob = _check_noise_args(dual_noise_std, dual_noise_prob, generator,
                                                             ("dual_noise_std", "dual_noise_prob"))
-        pack = ragged_pack(costs, self.device)
+        return self._training_batch_packed(ragged_pack(costs, self.device), dual_noise_std, dual_noise_prob, generator,
+                                           "training_batch")
+
+    def _training_batch_packed(self, pack, dual_noise_std, dual_noise_prob, generator, who):
+        """training_batch of a batch that is packed already, its noise arguments checked."""
+        from .collate import DeviceBatch
         r = row_features_packed(pack, return_topk=True, want_cost32=True)
-        u, v = self._labels_packed(pack, r, dual_noise_std, dual_noise_prob, generator, "training_batch")
+        u, v = self._labels_packed(pack, r, dual_noise_std, dual_noise_prob, generator, who)
         return DeviceBatch(cost=r.cost32, u=u, v=v, row_feat=r.feat, topk=r.topk, mask=r.mask, sizes=r.sizes)
+
+    def synthetic_training_batch(self, families, sizes, seeds, params=None, dual_noise_std: float = 0.0,
+                                 dual_noise_prob: float = 0.0, generator=None):
+        """training_batch of costs that are made on the device: gnn.synthetic.synthetic_pack(families, sizes, seeds,
+        params=params) in place of ragged_pack, so no cost matrix exists on the host and none is uploaded.  Every
+        field is bit for bit training_batch of those matrices."""
+        from .synthetic import synthetic_pack
+        dual_noise_std, dual_noise_prob = _check_noise_args(dual_noise_std, dual_noise_prob, generator,
+                                                            ("dual_noise_std", "dual_noise_prob"))
+        pack = synthetic_pack(families, sizes, seeds, self.device, params)
+        return self._training_batch_packed(pack, dual_noise_std, dual_noise_prob, generator,
+                                           "synthetic_training_batch")
 
     def _labels_packed(self, pack, r, dual_noise_std, dual_noise_prob, generator, who):
         """The label half of training_batch and dual_training_batch: the float32 targets u, v (B, N) of a packed
@@ -669,16 +685,36 @@ class WarmStartPipeline:
         larger one raises the ValueError of graph_features_packed.  Raises RuntimeError naming the first instance
         whose oracle duals fail, with its code.  The method of a DualWarmStartPipeline: like the prediction, it goes
         by the model's type, and a pipeline around another model raises TypeError."""
-        from .collate import DualDeviceBatch
+        dual_noise_std, dual_noise_prob = self._check_dual_training_args(dual_noise_std, dual_noise_prob, generator,
+                                                                         "dual_training_batch")
+        return self._dual_training_batch_packed(ragged_pack(costs, self.device), dual_noise_std, dual_noise_prob,
+                                                generator, "dual_training_batch")
+
+    def _check_dual_training_args(self, dual_noise_std, dual_noise_prob, generator, who):
         dual_noise_std, dual_noise_prob = _check_noise_args(dual_noise_std, dual_noise_prob, generator,
                                                             ("dual_noise_std", "dual_noise_prob"))
         if not isinstance(self.model, DualGNN):
-            raise TypeError(f"dual_training_batch needs a pipeline around a DualGNN (DualWarmStartPipeline), not "
+            raise TypeError(f"{who} needs a pipeline around a DualGNN (DualWarmStartPipeline), not "
                             f"{type(self.model).__name__}")
-        pack = ragged_pack(costs, self.device)
+        return dual_noise_std, dual_noise_prob
+
+    def synthetic_dual_training_batch(self, families, sizes, seeds, params=None, dual_noise_std: float = 0.0,
+                                      dual_noise_prob: float = 0.0, generator=None):
+        """dual_training_batch of costs that are made on the device (gnn.synthetic.synthetic_pack in place of
+        ragged_pack): bit for bit dual_training_batch of those matrices, with no matrix on the host."""
+        from .synthetic import synthetic_pack
+        dual_noise_std, dual_noise_prob = self._check_dual_training_args(dual_noise_std, dual_noise_prob, generator,
+                                                                         "synthetic_dual_training_batch")
+        pack = synthetic_pack(families, sizes, seeds, self.device, params)
+        return self._dual_training_batch_packed(pack, dual_noise_std, dual_noise_prob, generator,
+                                                "synthetic_dual_training_batch")
+
+    def _dual_training_batch_packed(self, pack, dual_noise_std, dual_noise_prob, generator, who):
+        """dual_training_batch of a batch that is packed already, its other arguments checked."""
+        from .collate import DualDeviceBatch
         f = graph_features_packed(pack)
         r = row_features_packed(pack, return_topk=False, want_cost32=True)  # the float32 cast, padded with 0
-        u, v = self._labels_packed(pack, r, dual_noise_std, dual_noise_prob, generator, "dual_training_batch")
+        u, v = self._labels_packed(pack, r, dual_noise_std, dual_noise_prob, generator, who)
         return DualDeviceBatch(cost=r.cost32, u=u, v=v, row_feat=f.row, col_feat=f.col, edge_feat=f.edge, mask=f.mask,
                                sizes=f.sizes)
 

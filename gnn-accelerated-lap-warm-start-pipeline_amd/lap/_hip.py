@@ -90,6 +90,11 @@ SIGNATURES = {
                                                    c_vp]),
     "lapwarm_reduce_costs_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, ct.c_int,
                                                c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_cost_families_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_generate_costs_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int, c_vp, c_vp, c_vp,
+                                                 c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_cost_family_draws": (ct.c_int, [ct.c_ulonglong, ct.c_uint, ct.c_int, ct.c_ulonglong, ct.c_ulonglong,
+                                             ct.c_uint, c_vp, c_vp]),
     "lapwarm_train_loss_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
     "lapwarm_train_loss_forward": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                               c_vp, c_vp, ct.c_size_t, c_vp]),

@@ -141,6 +141,17 @@ def generate_family(family: str, n: int, seed: int) -> np.ndarray:
     return FAMILIES[family](n, seed=seed)
 
 
+def generate_family_device(family: str, n: int, seed: int, device="cuda:0", **params) -> np.ndarray:
+    """One n x n matrix of `family` made on the device (gnn.synthetic.synthetic_pack) and downloaded: the NumPy-facing
+    convenience of the device generator.  `params` are the family's named parameters (gnn.synthetic.DEFAULT_PARAMS).
+    Same families and defaults as generate_family, but NOT the same matrices: the host generators above draw from
+    NumPy's streams, the device from Philox4x32-10 counters keyed by the 64-bit `seed` (csrc/cost_families.hpp), so
+    the two differ for equal seeds.  Raises KeyError for an unknown family, ValueError for a bad n, seed or parameter."""
+    from gnn.synthetic import synthetic_pack
+    pack = synthetic_pack([family], [n], [seed], device, params=[params or None])
+    return pack.C.cpu().numpy().reshape(n, n)
+
+
 def mixed_batch(batch: int, n: int, families=("uniform", "sparse", "metric", "clustered"),
                 seed: int = 1234) -> Tuple[np.ndarray, list]:
     """K3-style batch: `batch` matrices cycling through `families`, per-instance seeds

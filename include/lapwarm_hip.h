@@ -400,6 +400,30 @@ int lapwarm_reduce_costs_ragged(const double *C, const long long *offsets, const
                                 const double *u, const double *v, int shift_nonneg, double *out, double *gmin,
                                 int *ret, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The synthetic cost families of the reference's dataset generator (data/generators.py, SYNTHETIC_FAMILIES), drawn
+ * on the device straight into a ragged batch: C, offsets, sizes, ld, batch, N as above, C written instead of read.
+ * Every value is a pure function of (seed, stream, element) under Philox4x32-10 with key (lo32(seed), hi32(seed))
+ * and counter (lo32(group), hi32(group), stream, 0); csrc/cost_families.hpp states the draw rules, the streams and
+ * the seven families (0 uniform, 1 metric, 2 low_rank, 3 clustered, 4 noisy_linear, 5 tie, 6 sparse).  An
+ * instance's bits depend on its own (family, n, seed, params) only: not on the batch around it, its offset or ld.
+ * family [batch] int32, seeds [batch] uint64, params [batch][4] fp64 = (rank | blocks | bins, sigma | noise | jitter
+ * | sparsity, 0, 0), ret [batch] int32: all device arrays.  ret[b] = 0, 2 (size outside 1..N or wider than ld > 0:
+ * no work) or 3 (family outside 0..6, or a rank outside 1..64 for low_rank and noisy_linear: nothing of the
+ * instance is written).  Nothing outside the prefix [:n_b, :n_b] of an instance is written.  Three kernels on the
+ * caller's stream, each one grid over all instances; no host synchronisation: graph-capturable.  No atomics: equal
+ * arguments give equal bits.  Returns 0, -2 (N <= 0, batch outside 1..65535, ld < 0, a NULL pointer), -5
+ * (N > 16384), -1 (workspace below lapwarm_cost_families_workspace_bytes, which is 0 out of range), <= -1000 HIP
+ * error.
+ * lapwarm_cost_family_draws: out[i], i < count, = U (kind 0, fp64), Z (kind 1, fp64) or I(., m) (kind 2, int32) of
+ *   element first + i of stream stream_id, by the device functions the kernels use (out on the device; count < 2^39;
+ *   kind outside 0..2, or kind 2 with m outside 1..2^31-1: -2). */
+size_t lapwarm_cost_families_workspace_bytes(int batch, int N);
+int lapwarm_generate_costs_ragged(double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                  const int *family, const unsigned long long *seeds, const double *params, int *ret,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int lapwarm_cost_family_draws(unsigned long long seed, unsigned int stream_id, int kind, unsigned long long first,
+                              unsigned long long count, unsigned int m, void *out, void *stream);
+
 /* The OneGNN training loss, gnn/train_one_gnn.py:180-226 `compute_loss` with its host greedy
  * `greedy_primal_upper` (:137-177), float32 terms and fp64 sums.  C [batch][n][n] float32, padded to the batch
  * maximum n; sizes [batch] int32 = n_b, the valid rows and columns of instance b are the prefix 0..n_b-1
