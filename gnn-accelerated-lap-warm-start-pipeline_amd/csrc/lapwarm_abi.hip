@@ -23,6 +23,7 @@
 #include "lapmod_sparse.hpp"
 #include "onegnn_refine.hpp"
 #include "oracle_duals.hpp"
+#include "prune_price.hpp"
 #include "ragged_batch.hpp"
 #include "ragged_duals.hpp"
 #include "solve_plan.hpp"
@@ -1258,6 +1259,59 @@ int lapwarm_lapmod_ragged(const double *cc, const int *kk, const int *ii, const 
     p.ws_state_bytes = w.state_bytes;
     if (w.any_global) HIP_TRY(launch_lapmod_plan(p, stream));
     HIP_TRY(launch_lapmod(p, stream));
+    return 0;
+}
+
+// ---- pruning and pricing of dense rows into CSR (prune_price.hip) ----
+static PruneWs prune_layout(void *workspace, int batch, int N)
+{
+    Carver c{reinterpret_cast<unsigned char *>(workspace), 0};
+    const size_t bn = (size_t)batch * N;
+    PruneWs w;
+    w.thr = c.take<unsigned long long>(bn);
+    w.ties = c.take<int>(bn);
+    w.len = c.take<int>(bn);
+    w.nelig = c.take<int>(bn);
+    w.bad = c.take<int>(bn);
+    w.bytes = c.off;
+    return w;
+}
+
+size_t lapwarm_prune_workspace_bytes(int batch, int N)
+{
+    if (check_ragged_dims(batch, N)) return 0;
+    return prune_layout(nullptr, batch, N).bytes;
+}
+
+int lapwarm_prune_grow_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                              const double *key, const int *x, const int *kk_in, const int *ii_in,
+                              const long long *nnz_offsets_in, const long long *row_offsets_in, int m, double *cc_out,
+                              int *kk_out, int *ii_out, const long long *nnz_offsets_out,
+                              const long long *row_offsets_out, const long long *cap_out, long long *added,
+                              long long *viol, int *ret, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (m < 1 || m > kPruneMaxM || !added || !viol || !ret || !workspace) return -2;
+    if (x && !key) return -2;
+    if (kk_in ? (!ii_in || !nnz_offsets_in || !row_offsets_in) : (ii_in || nnz_offsets_in || row_offsets_in)) return -2;
+    if (cc_out ? (!kk_out || !ii_out || !nnz_offsets_out || !row_offsets_out || !cap_out)
+               : (kk_out || ii_out || nnz_offsets_out || row_offsets_out || cap_out))
+        return -2;
+    if (int rc = check_workspace(workspace_bytes, lapwarm_prune_workspace_bytes(batch, N))) return rc;
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    const PruneGrow p{key,    x,      kk_in,  ii_in,           nnz_offsets_in,  row_offsets_in, m,     cc_out,
+                      kk_out, ii_out, nnz_offsets_out, row_offsets_out, cap_out, added,          viol,  ret};
+    HIP_TRY(launch_prune_grow(g, p, prune_layout(workspace, batch, N), as_stream(stream_)));
+    return 0;
+}
+
+int lapwarm_prune_finish_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                const int *x, double *v, const int *ret, double *u, double *cost, void *stream_)
+{
+    if (int rc = check_ragged(C, offsets, sizes, ld, batch, N)) return rc;
+    if (!x || !v || !ret || !u || !cost) return -2;
+    const RaggedBatch g{C, offsets, sizes, ld, batch, N};
+    HIP_TRY(launch_prune_finish(g, x, v, ret, u, cost, as_stream(stream_)));
     return 0;
 }
 

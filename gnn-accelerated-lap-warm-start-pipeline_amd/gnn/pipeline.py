@@ -444,6 +444,175 @@ class WarmStartPipeline:
                  pack.row_offsets, pack.sizes, host_sizes, B, N, int(fp_version), x, y, v, ret, stats, ws, cap)
         return {"x": x, "y": y, "v": v, "ret": ret, "stats": stats}
 
+    # ---- exact dense solve through sparse LAPMOD (csrc/prune_price.hip; DESIGN.md, "Exact dense LAP through sparse
+    # LAPMOD"): prune the dense rows to CSR, solve, price the absent entries with the duals, grow, repeat
+    def prune_grow(self, pack: RaggedPack, m: int, key=None, x=None, csr: Optional[SparsePack] = None,
+                   write: bool = True):
+        """One grow step (lapwarm_prune_grow_ragged).  key (B, N) fp64 or None, x (B, N) int32 or None, csr the
+        current CSR (a SparsePack over the same instances) or None for the diagonal.  Returns (next, counts): next
+        a SparsePack without host_nnz (None without `write`: a pricing step), counts an int64 device block with
+        added [:B], viol [B:2B] and, as int32, ret [2B:]; `prune_counts` reads it back."""
+        B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
+        sizes = pack.host_sizes
+        counts = torch.empty((2 * B + (B + 1) // 2,), dtype=torch.int64, device=dev)
+        added, viol, ret = counts[:B], counts[B:2 * B], counts[2 * B:].view(torch.int32)
+        need = int(self.lib.lapwarm_prune_workspace_bytes(B, N))
+        if need == 0:
+            raise ValueError("prune_grow: a batch of 1..65535 instances with 1 <= n <= 16384 expected")
+        # (one block per power of two of the size: the live set shrinks from round to round)
+        bucket = max(1 << 16, 1 << (need - 1).bit_length())
+        ws, nbytes = self._cached_workspace(("prune", bucket), lambda: bucket)
+        nxt = None
+        out = [None] * 6
+        if write:
+            # what an instance can hold after the step: known without a read-back
+            if csr is None:
+                cap = [n * min(m + 1, n) for n in sizes]
+            else:
+                cap = [min(nz + n * m, n * n) for n, nz in zip(sizes, csr.host_nnz)]
+            meta = np.empty((3, B), dtype=np.int64)
+            meta[0] = np.concatenate(([0], np.cumsum(cap)[:-1]))
+            meta[1] = np.concatenate(([0], np.cumsum([n + 1 for n in sizes])[:-1]))
+            meta[2] = cap
+            meta_d = torch.from_numpy(meta).to(dev)
+            total, rows = int(sum(cap)), int(sum(sizes)) + B
+            nxt = SparsePack(torch.empty((total,), dtype=torch.float64, device=dev),
+                             torch.empty((total,), dtype=torch.int32, device=dev),
+                             torch.empty((rows,), dtype=torch.int32, device=dev), meta_d[0], meta_d[1], pack.sizes,
+                             sizes, None)
+            out = [nxt.cc, nxt.kk, nxt.ii, meta_d[0], meta_d[1], meta_d[2]]
+        cur = [None] * 4 if csr is None else [csr.kk, csr.ii, csr.nnz_offsets, csr.row_offsets]
+        hip_call("lapwarm_prune_grow_ragged", "prune_grow", dev, pack.C, pack.offsets, pack.sizes, pack.ld, B, N, key,
+                 x, *cur, int(m), *out, added, viol, ret, ws, nbytes)
+        return nxt, counts
+
+    @staticmethod
+    def prune_counts(counts, B, *more):
+        """[added, viol, ret] of a grow step over B instances as host lists, and every (B,) int32 tensor of `more`
+        likewise: one copy, one synchronisation."""
+        host = torch.cat([counts] + [t.to(torch.int64) for t in more]).cpu().numpy()
+        res = [host[:B].tolist(), host[B:2 * B].tolist(), host[2 * B:counts.numel()].view(np.int32)[:B].tolist()]
+        for q in range(len(more)):
+            res.append(host[counts.numel() + q * B:counts.numel() + (q + 1) * B].tolist())
+        return res
+
+    def lapjv_pruned_ragged(self, pack: RaggedPack, k: int = 16, seed=None, max_rounds: int = 32) -> dict:
+        """Exact lapjv of every instance of a ragged batch through sparse LAPMOD.  Round 0 keeps, per row, the
+        diagonal and the k columns with the smallest C_ij - seed_j (ties to the lower column); lapmod_ragged
+        (FP_DYNAMIC) solves the CSR; the pricing step adds to row i the at most k absent columns with the smallest
+        C_ij - v_j among those below u_i = C[i][x_i] - v[x_i]; an instance without such a column is certified
+        optimal and leaves the loop (the live instances are compacted on the host, so a certified one costs nothing
+        afterwards).  seed (B, N) fp64 on the device or None.  Returns device tensors: x, y (B, N) int32 (-1 beyond
+        n_b), u, v (B, N) fp64 (0 beyond n_b), cost (B,) fp64 (the sum of C[i][x_i] in ascending i), ret (B,) int32
+        (0 certified; 2 not certified after max_rounds solves: x, y are the last solve's; 3 not admissible -- a cost
+        outside [0, 1e6), NaN, or a seed that is not finite: x, y -1 and cost inf, nothing solved; 4 treated as
+        empty), rounds (B,) int32 the solves run, nnz (B,) int64 the size of the last CSR solved and viol_last (B,)
+        int64 (0 exactly when certified).  One small read-back per round: not graph-capturable."""
+        if not isinstance(pack, RaggedPack):
+            raise TypeError(f"Argument 'pack' must be a RaggedPack, not {type(pack).__name__}")
+        if pack.C.dtype != torch.float64:
+            raise TypeError(f"the packed costs must be torch.float64, not {pack.C.dtype}")
+        k, max_rounds = _check_rounds(k, "k"), _check_rounds(max_rounds, "max_rounds")
+        if not 1 <= k <= 256:
+            raise ValueError(f"k must be in 1..256, not {k}")
+        if max_rounds < 1:
+            raise ValueError(f"max_rounds must be at least 1, not {max_rounds}")
+        _check_pack_vector(pack, "seed", seed, optional=True)
+        B, N, dev = len(pack.host_sizes), pack.N, pack.C.device
+        x = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+        y = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+        v = torch.zeros((B, N), dtype=torch.float64, device=dev)
+        ret, rounds, nnz, viol_last = [0] * B, [0] * B, [0] * B, [-1] * B
+
+        csr, counts = self.prune_grow(pack, k, key=seed)
+        added, _, gret = self.prune_counts(counts, B)
+        csr.host_nnz = added
+        ids = list(range(B))  # the instances behind `sub` and `csr`, in their order
+        sub, r = pack, 0
+        while True:
+            keep = [q for q, b in enumerate(ids) if gret[q] == 0 and ret[b] == 0 and viol_last[b] != 0]
+            for q, b in enumerate(ids):
+                if gret[q] == 5 or (gret[q] != 0 and r > 0):  # (an admissible instance never gets there)
+                    raise RuntimeError(f"lapjv_pruned_ragged: grow step {r} returned {gret[q]} for instance {b}")
+                if gret[q] != 0:
+                    ret[b] = gret[q]
+            if r >= max_rounds:
+                for q in keep:
+                    ret[ids[q]] = 2
+                keep = []
+            if not keep:
+                break
+            # the live instances only: their offsets and sizes, the buffers as they are (N: lapmod_ragged's width)
+            if len(keep) < len(ids) or sub.N != max(sub.host_sizes):
+                idx = torch.tensor(keep, device=dev)
+                hs = [sub.host_sizes[q] for q in keep]
+                sub = RaggedPack(pack.C, sub.offsets[idx], sub.sizes[idx], None, None, pack.ld, max(hs), hs)
+                csr = SparsePack(csr.cc, csr.kk, csr.ii, csr.nnz_offsets[idx], csr.row_offsets[idx], sub.sizes, hs,
+                                 [csr.host_nnz[q] for q in keep])
+                ids = [ids[q] for q in keep]
+            sol = self.lapmod_ragged(csr, 3, want_stats=False)
+            r += 1
+            nxt, counts = self.prune_grow(sub, k, key=sol["v"], x=sol["x"], csr=csr, write=r < max_rounds)
+            where = torch.tensor(ids, device=dev)
+            x[where, :sub.N], y[where, :sub.N], v[where, :sub.N] = sol["x"], sol["y"], sol["v"]
+            added, viol, gret, sret = self.prune_counts(counts, len(ids), sol["ret"])
+            for q, b in enumerate(ids):
+                if sret[q] != 0:
+                    raise RuntimeError(f"lapjv_pruned_ragged: lapmod_ragged returned {sret[q]} for instance {b}")
+                rounds[b], nnz[b], viol_last[b] = r, csr.host_nnz[q], viol[q]
+            if nxt is not None:
+                nxt.host_nnz = [nz + a for nz, a in zip(csr.host_nnz, added)]
+                csr = nxt
+        ret_d = torch.tensor(ret, dtype=torch.int32, device=dev)
+        u = torch.empty((B, N), dtype=torch.float64, device=dev)
+        cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        hip_call("lapwarm_prune_finish_ragged", "lapjv_pruned_ragged", dev, pack.C, pack.offsets, pack.sizes, pack.ld,
+                 B, N, x, v, ret_d, u, cost)
+        return {"x": x, "y": y, "u": u, "v": v, "cost": cost, "ret": ret_d,
+                "rounds": torch.tensor(rounds, dtype=torch.int32, device=dev),
+                "nnz": torch.tensor(nnz, dtype=torch.int64, device=dev),
+                "viol_last": torch.tensor(viol_last, dtype=torch.int64, device=dev)}
+
+    def _pruned_packed(self, pack, k, seed, max_rounds=32):
+        """lapjv_pruned_ragged, and the dense route (lapjv_batch, one call per size) for the instances it leaves
+        with ret 2 or 3: one dict per instance with x, y (n_b,) int32, cost, ret and fallback (bool) on the host
+        side of the result, rounds and nnz."""
+        out = self.lapjv_pruned_ragged(pack, k, seed, max_rounds)
+        ret = out["ret"].tolist()
+        x, y, cost = out["x"], out["y"], out["cost"].clone()
+        redo = {}
+        for b, n in enumerate(pack.host_sizes):
+            if ret[b] in (2, 3):
+                redo.setdefault(n, []).append(b)
+        if redo:
+            off = pack.offsets.tolist()
+            stride = pack.ld or None
+            for n, members in redo.items():
+                ld = stride or n
+                C = torch.stack([pack.C[off[b]:off[b] + (n - 1) * ld + n].as_strided((n, n), (ld, 1))
+                                 for b in members]).contiguous()
+                xd, yd, _, _ = self.lapjv_batch(C, want_stats=False)
+                idx = torch.tensor(members, device=self.device)
+                x[idx, :n], y[idx, :n] = xd, yd
+                cost[idx] = torch.stack([C[q, torch.arange(n, device=self.device), xd[q].long()].sum()
+                                         for q in range(len(members))])
+        rounds, nnz = out["rounds"].tolist(), out["nnz"].tolist()
+        return [{"x": x[b, :n], "y": y[b, :n], "cost": cost[b], "ret": ret[b], "fallback": ret[b] in (2, 3),
+                 "rounds": rounds[b], "nnz": nnz[b]} for b, n in enumerate(pack.host_sizes)]
+
+    @torch.inference_mode()
+    def solve_pruned_many(self, costs, k: int = 16, use_model: bool = True, max_rounds: int = 32):
+        """Optimal assignments of square fp64 matrices of different sizes through the pruned route: the seed of
+        round 0 is predict_ragged's v_hat (the min-trick of the model's u_hat) with `use_model`, none without; an
+        instance that is not certified within max_rounds or is not admissible (ret 2 or 3) is solved again by the
+        dense lapjv_batch, so every instance comes back with an optimum.  One dict per instance, in input order:
+        x, y (n_b,) int32, cost, ret (of the pruned solve), fallback, rounds, nnz."""
+        if use_model:
+            pack, _, v_hat = self._predict_ragged(costs)
+        else:
+            pack, v_hat = ragged_pack(costs, self.device), None
+        return self._pruned_packed(pack, k, v_hat, max_rounds)
+
     def _extended_many_parts(self, costs, extend_cost=True, cost_limit=float("inf"), want_stats=True):
         """lapjv_extended_many before the results are cut up: a list of (indices, rows, cols, padded dict), one
         entry for the ragged call and one per lapjv_extended_batch call.  Argument errors come first."""

@@ -34,10 +34,18 @@ FP_2 and FP_DYNAMIC; `lapmod_many` solves a sequence of problems with one upload
 keeps raising NotImplementedError and the new names are importable without being listed in `__all__`, because
 tests/test_host_logic.py asserts both.  Once that assertion is retired, routing is three lines here: import
 `lapmod_sparse as lapmod` from ._lapmod, delete the raising `lapmod` below, and leave "lapmod" in `__all__`.
+
+    lapjv_pruned(cost, k=16, v=None, return_cost=True)        -> (opt, x, y)   int32
+    lapjv_pruned_many(costs, k=16, v=None, return_cost=True)  -> [(opt, x, y), ...]
+
+`lapjv_pruned` is the exact dense optimum through sparse LAPMOD: rows pruned to their k cheapest entries on the
+device, solved sparsely, and grown by dual pricing until no absent entry prices in (lap/_pruned.py).  Importable
+without being listed in `__all__`, like the names above.
 """
 from ._lapjv import lapjv, lapjv_extended, lapjv_many, LARGE_ as LARGE, FP_1_ as FP_1, FP_2_ as FP_2, FP_DYNAMIC_ as FP_DYNAMIC
 from ._seeded_jv import lapjv_seeded
 from ._lapmod import lapmod_sparse, lapmod_many, get_cost, sparse_from_dense, sparse_from_masked
+from ._pruned import lapjv_pruned, lapjv_pruned_many
 
 __version__ = "0.5.12+mi355x"
 

@@ -72,6 +72,10 @@ SIGNATURES = {
     "lapwarm_lapmod_lds_max_n": (ct.c_int, []),
     "lapwarm_lapmod_ragged": (ct.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ip, ct.c_int, ct.c_int, ct.c_int, c_vp,
                                          c_vp, c_vp, c_vp, c_vp, c_vp, ct.c_size_t, c_vp]),
+    "lapwarm_prune_workspace_bytes": (ct.c_size_t, [ct.c_int, ct.c_int]),
+    "lapwarm_prune_grow_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int] + [c_vp] * 6
+                                  + [ct.c_int] + [c_vp] * 10 + [ct.c_size_t, c_vp]),
+    "lapwarm_prune_finish_ragged": (ct.c_int, [c_vp, c_vp, c_vp, ct.c_int, ct.c_int, ct.c_int] + [c_vp] * 6),
     "lapwarm_project_round_batched":(ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, c_vp, c_vp,
                                                  ct.c_size_t, c_vp]),
     "lapwarm_reduce_costs_batched": (ct.c_int, [c_vp, ct.c_int, ct.c_int, c_vp, c_vp, ct.c_int, c_vp, c_vp,

@@ -309,6 +309,47 @@ int lapwarm_lapmod_ragged(const double *cc, const int *kk, const int *ii, const 
                           int fp_version, int *x, int *y, double *v, int *ret, long long *stats, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* Pruning and pricing of a ragged batch of dense cost matrices into CSR: the device steps of the exact dense solve
+ * through lapwarm_lapmod_ragged ("Exact dense LAP through sparse LAPMOD").  C, offsets, sizes, ld, batch
+ * and N as in the other ragged entries.  The round loop (grow, solve, price and grow, ... finish) lives in the
+ * caller, which reads viol and ret back once per round: the loop is NOT graph-capturable; each entry here is kernels
+ * on the caller's stream only, one grid over all instances each, without host synchronisation.
+ *
+ * lapwarm_prune_grow_ragged, one grow step.  key [batch][N] fp64 or NULL: key_ij = C_ij - key[b][j] (C_ij without).
+ * x [batch][N] int32 or NULL: the bound of row i is C[i][x_i] - key[b][x_i] with x, +inf without (x needs key).
+ * kk_in, ii_in, nnz_offsets_in, row_offsets_in: the current CSR in the layout of lapwarm_lapmod_ragged (columns
+ * sorted and unique per row; it is the output of an earlier call), or all four NULL: every row holds its diagonal
+ * only.  E_i is the set of columns absent from row i whose key is below the bound (fp64, as written).  The next
+ * row holds the current columns and the min(m, |E_i|) members of E_i with the smallest key, ties to the lower
+ * column, ascending in column; its values are read from C.  m in 1..256.  cc_out, kk_out, ii_out with
+ * nnz_offsets_out, row_offsets_out and cap_out (DEVICE arrays [batch]; cap_out the entries instance b may write
+ * from nnz_offsets_out[b]) receive the next CSR: ii_out holds n_b + 1 local row starts and the entries up to
+ * ii_out[n_b] are written, the rest of the capacity is not touched; all six NULL: a pricing step that writes no
+ * CSR.  added [batch] int64: entries of the next CSR minus those of the current one (of an absent one: 0), viol
+ * [batch] int64: the sum of |E_i|, ret [batch] int32: 0; 3 the instance is not admissible (a cost outside [0, 1e6)
+ * or NaN, a key that is not finite, an x_i or a current column outside 0..n_b-1, current row starts that do not
+ * ascend), decided in the pass over C: no CSR entries are written; 4 the instance is treated as empty (size outside
+ * 1..N or wider than ld > 0; lapwarm_rowmin_ragged reports 2 there, which is taken here by the caller's "not
+ * certified"): no work; 5 the next CSR exceeds cap_out[b]: no CSR entries are written.  Three kernels (two for a
+ * pricing step), two reads of C; nothing of size n x n is allocated; integer atomics in LDS only, so equal inputs
+ * give equal bits.  Returns 0, -2 (N <= 0, batch outside 1..65535, ld < 0, m outside 1..256, x without key, a CSR
+ * given in part, another NULL pointer), -5 (N > 16384), -1 (workspace below lapwarm_prune_workspace_bytes, which
+ * is 0 out of range), <= -1000 HIP error; only the last follows device work.
+ *
+ * lapwarm_prune_finish_ragged: for the instances with ret[b] 0 or 2, u[b][i] = C[i][x_i] - v[b][x_i], cost[b] the
+ * sum of C[i][x_i] taken serially in ascending i, and u, v set to 0 beyond n_b; for any other ret (and an instance
+ * treated as empty or holding an x_i outside 0..n_b-1) u, v all 0 and cost inf.  x [batch][N] int32, v [batch][N]
+ * fp64 in and out, ret [batch] in.  One kernel.  Returns 0, -2, -5 or <= -1000 as above. */
+size_t lapwarm_prune_workspace_bytes(int batch, int N);
+int lapwarm_prune_grow_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                              const double *key, const int *x, const int *kk_in, const int *ii_in,
+                              const long long *nnz_offsets_in, const long long *row_offsets_in, int m, double *cc_out,
+                              int *kk_out, int *ii_out, const long long *nnz_offsets_out,
+                              const long long *row_offsets_out, const long long *cap_out, long long *added,
+                              long long *viol, int *ret, void *workspace, size_t workspace_bytes, void *stream);
+int lapwarm_prune_finish_ragged(const double *C, const long long *offsets, const int *sizes, int ld, int batch, int N,
+                                const int *x, double *v, const int *ret, double *u, double *cost, void *stream);
+
 /* One round of project_feasible: u = min(u, rowmin(C-v)); v = min(v, colmin(C-u));
  * gmin[b] = min((C-u)-v).  The host loop decides when to stop. */
 int lapwarm_project_round_batched(const double *C, int batch, int n, double *u, double *v,
